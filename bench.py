@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: depth-maps/sec of the A-TVSNet multi-view inference path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
 
 A step = one depth map through the whole example.py pipeline (towers -> 2x stacked 3-D U-Net per source ->
 AAM1 -> refinement per source -> AAM2 -> x4 upsample + soft-argmin), inputs resident in HBM, synthetic
@@ -54,6 +54,10 @@ committed PMC passes; `roofline_hbm` = the plane-sweep warp
 rocprofv3 kernel trace of this command; `parity` = the output of the timed path against the oracle-generated
 fixture of this workload (tests/golden/fullsize_*.npz) and graph replay == eager bit for bit;
 `cpu_baseline` = the CPU oracle on the host cores.
+
+--dump-outputs DIR (e.g. bench_outputs/, git-ignored): rank 0 writes what the timed path returned in its LAST timed step --
+the depth map (1,H,W,1) -- as DIR/depth.npy (float32; beyond 64 MB a fixed seeded sample of its elements, their flat indices in
+DIR/depth_index.npy).  Inputs and weights are seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -127,6 +131,8 @@ def parse(argv=None):
                    help='with >= 2 ranks per source: one siamese direction per rank instead of further depth-map groups')
     p.add_argument('--dry', action='store_true',
                    help='no GPU: the ranks rendezvous over gloo, agree on the plan and print the line (launcher test)')
+    p.add_argument('--dump-outputs', metavar='DIR', default=None,
+                   help="write the timed path's output of its last timed step as DIR/<name>.npy (rank 0)")
     a = p.parse_args(argv)
     v, w, h, d = WORKLOADS[a.workload]
     a.custom = any(x is not None for x in (a.width, a.height, a.depths, a.views))
@@ -232,6 +238,7 @@ def launch(args, argv):
         #                      per GPU), next to the same depth map on ONE rank measured in the same invocation
         def secondary(nranks, extra, timeout_s):
             try:
+                extra = _without_option(extra, '--dump-outputs')       # other workloads: the dump is the primary run's
                 t2, rc2 = _run_ranks(nranks, extra + ['--no-cpu-baseline'], timeout_s)
                 l2 = _last_json(t2)
                 if l2 is not None and all(rc == 0 for rc in rc2):
@@ -263,6 +270,42 @@ def launch(args, argv):
     print(json.dumps(line))
     sys.stdout.flush()
     return 0
+
+
+def _without_option(argv, name):
+    """argv without `name VALUE` / `name=VALUE`."""
+    out, skip = [], False
+    for a in argv:
+        if skip:
+            skip = False
+        elif a == name:
+            skip = True
+        elif not a.startswith(name + '='):
+            out.append(a)
+    return out
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(directory, outputs):
+    """{name: tensor} -> directory/<name>.npy as float32; -> {name: shape}.  Beyond DUMP_LIMIT_BYTES in all, every output keeps
+    a fixed seeded sample of its elements (its share of the limit) and their flat indices go to <name>_index.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {name: t.detach().float().cpu().numpy() for name, t in outputs.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    shapes = {}
+    for name, a in arrays.items():
+        shapes[name] = list(a.shape)
+        if total > DUMP_LIMIT_BYTES:
+            # this output's share of the limit (less the .npy headers), 12 bytes per kept element: float32 value + float64 index
+            keep = max(1, (DUMP_LIMIT_BYTES - 4096 * len(arrays)) * a.nbytes // total // 12)
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=min(keep, a.size), replace=False))
+            np.save(os.path.join(directory, name + '_index.npy'), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + '.npy'), a)
+    return shapes
 
 
 def promote_view_sharded(line):
@@ -753,6 +796,8 @@ def rank_main(args):
         out = step()
     barrier()
     dt = time.perf_counter() - t0
+    # the graph's output buffer is written again by the regions below: keep the timed path's last result as it was
+    last_out = out.clone() if args.dump_outputs else None
     pipelined = None
     if pipe is not None and pipe.slots > 1:
         pipe.run(args.warmup)
@@ -1064,6 +1109,8 @@ def rank_main(args):
             problems.append('parity: rel-L1 above the bar')
         if isinstance(line.get('parity'), dict) and line['parity'].get('graph_equals_eager_bitwise') is False:
             problems.append('parity: graph replay differs from eager launch')
+        if args.dump_outputs:
+            line['dumped_outputs'] = {'dir': args.dump_outputs, 'shapes': dump_outputs(args.dump_outputs, {'depth': last_out})}
         line['ok'] = not problems
         if problems:
             line['problems'] = problems
@@ -1080,6 +1127,9 @@ def main(argv=None):
     args = parse(argv)
     if args.gpus < 1:
         sys.stderr.write('bench.py: --gpus must be >= 1\n')
+        return 2
+    if args.steps < 1:
+        sys.stderr.write('bench.py: --steps must be >= 1\n')
         return 2
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         return launch(args, argv)

@@ -84,14 +84,15 @@ def _sharded_worker(rank, world, port, n_views, q):
         dist.destroy_process_group()
 
 
-@pytest.mark.parametrize('world,n_views', [(2, 4), (2, 3), (4, 3), (8, 9)])
+@pytest.mark.parametrize('world,n_views', [(2, 4), (2, 3), (4, 3), (4, 5)])
 def test_sharded_path_multi_rank_on_one_gpu(cuda, world, n_views):
     """The COMPLETE view-sharded pipeline on the HIP kernels with several ranks (all on this one GPU, gloo carrying the
     collectives -- RCCL refuses two ranks per device): sources dealt round-robin (world 2) and the two siamese
     directions of a source on different ranks with the depth_view exchange (world 4, 2 sources: the odd ranks own NO
     forward view -- nothing to refine, empty AANet input -- and still run the eager path and the ShardedGraphedInference
-    chain), and BASELINE configs[3]'s partition (world 8, 9 views: one source per rank).  Every rank must end with the
-    single-process depth map."""
+    chain), and the partition of BASELINE configs[3] (one source per rank, both directions on it) at world 4, 5 views:
+    every rank is a process of its own on the one device, so the world stays small here; world 8 / 9 views itself runs
+    on gloo without the GPU (tests/test_parallel_gloo.py).  Every rank must end with the single-process depth map."""
     import numpy as np
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
@@ -155,7 +156,7 @@ def test_sharded_path_two_devices_over_rccl(cuda, n_views):
     the test skips there and runs the day a multi-GPU box executes the suite (until then the RCCL transport has run with
     one rank only; the N > 1 logic is covered on gloo: tests/test_parallel_gloo.py and the tests above)."""
     if torch.cuda.device_count() < 2:
-        pytest.skip('needs two GPUs (RCCL refuses two ranks on one device)')
+        pytest.skip('needs 2 GPUs (RCCL refuses two ranks on one device), found %d' % torch.cuda.device_count())
     import numpy as np
     import torch.multiprocessing as mp
     ctx = mp.get_context('spawn')
