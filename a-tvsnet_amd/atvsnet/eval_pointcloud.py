@@ -22,8 +22,9 @@ from .. import variables
 from ..flags import FLAGS
 from ..tools.common import Notify
 from . import example
-from .preprocess import (center_image, crop_mvs_input, gen_pipeline_mvs_list, load_cam, scale_image, scale_mvs_camera,
-                         scale_mvs_input, write_cam, write_pfm)
+from . import scene
+from .preprocess import (center_image, crop_mvs_input, crop_window, gen_pipeline_mvs_list, load_cam, scale_camera, scale_image,
+                         scale_mvs_camera, scale_mvs_input, scaled_size, write_cam, write_pfm)
 
 ETH3D_LOW_RES_TEST = ['lakeside', 'sand_box', 'storage_room', 'storage_room_2', 'tunnel']
 
@@ -115,6 +116,109 @@ def load_data(sample_list, data_index):
             image_index)
 
 
+def load_cams(data, shapes):
+    """The host part of load_data for the scene driver (--scene_cache): the cameras of one pair.txt entry `data` whose views'
+    images are (h, w) = `shapes` (after the missing-source substitution) -> (cams (1,N,2,4,4) at sample_scale, the adaptive
+    scale).  The same steps on the same values as load_data: scale, crop offset, inverse-depth range, ground-truth range,
+    sample_scale."""
+    found = len(data) // 2
+    cams = []
+    for view in range(FLAGS.view_num):
+        src = view if view < found else 0
+        with open(data[2 * src + 1]) as f:
+            cam = load_cam(f, 1.0)
+        if view < found and cam[1][3][2] == 0:
+            cam[1][3][2] = FLAGS.max_d
+        cams.append(cam)
+    resize_scale = scene.adaptive_scale(shapes) if FLAGS.adaptive_scaling else 1
+    if resize_scale is None:
+        print("max_h, max_w should < W and H!")
+        print(shapes[-1], 'h_scale', max(float(FLAGS.max_h) / s[0] for s in shapes),
+              'w_scale', max(float(FLAGS.max_w) / s[1] for s in shapes))
+        sys.exit(-1)
+    for v in range(FLAGS.view_num):
+        cams[v] = scale_camera(cams[v], scale=resize_scale)
+        y0, x0, _, _ = crop_window(*scaled_size(shapes[v][0], shapes[v][1], resize_scale), base_image_size=32)
+        cams[v][1][0][2] -= x0
+        cams[v][1][1][2] -= y0
+    if FLAGS.inverse_depth:
+        for cam in cams:
+            _inverse_depth_range(cam)
+    _ground_truth_depth_range(data[0], cams)
+    cams = scale_mvs_camera(cams, scale=FLAGS.sample_scale)
+    return np.stack(cams, 0)[None], resize_scale
+
+
+class _Decoder(object):
+    """Host uint8 BGR images by path: decoded on demand or by ONE background thread ahead of use (prefetch)."""
+
+    def __init__(self):
+        from concurrent.futures import ThreadPoolExecutor
+        self.pool = ThreadPoolExecutor(1)
+        self.pending = {}
+
+    def prefetch(self, paths):
+        for p in paths:
+            if p not in self.pending:
+                self.pending[p] = self.pool.submit(example._imread_bgr, p)
+
+    def __call__(self, path):
+        f = self.pending.pop(path, None)
+        return f.result() if f is not None else example._imread_bgr(path)
+
+    @staticmethod
+    def shape(path):
+        from PIL import Image
+        with Image.open(path) as im:
+            w, h = im.size
+        return h, w
+
+    def close(self):
+        self.pool.shutdown(wait=True)
+        self.pending.clear()
+
+
+class _Writer(object):
+    """finish()'s file writing on one background thread behind a bounded queue (threaded=False: in the caller)."""
+
+    def __init__(self, threaded, depth=4):
+        import queue
+        import threading
+        self.threaded, self.error, self.busy = threaded, None, 0.0          # busy: seconds spent writing
+        if threaded:
+            self.queue = queue.Queue(maxsize=depth)
+            self.thread = threading.Thread(target=self._loop, name='atvs-writer', daemon=True)
+            self.thread.start()
+
+    def _loop(self):
+        while True:
+            job = self.queue.get()
+            if job is None:
+                return
+            if self.error is None:
+                t0 = time.time()
+                try:
+                    job()
+                except BaseException as e:       # re-raised in the driver's thread
+                    self.error = e
+                self.busy += time.time() - t0
+
+    def __call__(self, job):
+        if self.error is not None:
+            raise self.error
+        if self.threaded:
+            self.queue.put(job)
+        else:
+            job()
+
+    def close(self):
+        if self.threaded:
+            self.queue.put(None)
+            self.thread.join()
+        if self.error is not None:
+            raise self.error
+
+
 class _Pipelines(object):
     """One set of captured HIP graphs per input shape (scenes of one data set share it), SLOTS depth maps queued:
     submit() issues a depth map asynchronously, fetch() returns the oldest one's results as numpy arrays.
@@ -166,57 +270,131 @@ class _Pipelines(object):
         return self.fetch()
 
 
-def run_eval_pc(savepath, image_infos, use_graph=True):
-    """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]"""
+# host time of the last scene run_eval_pc processed, seconds summed over its maps: prepare (load_data / load_cams), submit, wait
+# (fetch / result), write (finish's files; with the writer thread: the hand-over); --scene_cache adds upload (the image uploads'
+# share of submit) and gpu_ms (each map's GPU time, SceneInference.gpu_ms) -- tools_dev/scene_rate.py reports them
+TIMES = {}
+
+
+def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
+    """finish()'s files of one depth map: PFMs, the 1/4 reference image, the camera text, the viridis PNG."""
+    from PIL import Image
+    depth, depth_up, prob, prob_up = outputs
+    disp_up = np.squeeze(depth_up.copy())
+    if FLAGS.inverse_depth:
+        for m in (depth, depth_up):
+            m[m <= 0] = float("inf")
+        depth, depth_up = 1.0 / depth, 1.0 / depth_up
+    stem = os.path.join(output_folder, '%08d' % out_index)
+    write_pfm(stem + '.pfm', np.squeeze(depth).astype(np.float32))
+    write_pfm(stem + '_prob.pfm', np.squeeze(prob).astype(np.float32))
+    if getattr(FLAGS, 'write_upsampled', False):      # commented out in the reference (:378-379)
+        write_pfm(stem + '_up.pfm', np.squeeze(depth_up).astype(np.float32))
+        write_pfm(stem + '_prob_up.pfm', np.squeeze(prob_up).astype(np.float32))
+    Image.fromarray(np.ascontiguousarray(image_raw[:, :, ::-1])).save(stem + '.jpg')
+    write_cam(stem + '.txt', cams)
+    plt.imsave(stem + '.png', disp_up, cmap='viridis')
+
+
+def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True):
+    """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
+    scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
+    background thread (write_thread=False: in this thread, same bytes)."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
-    from PIL import Image
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
+    if scene_cache and not use_graph:
+        raise ValueError('--scene_cache replays captured graphs: it cannot be combined with --eager')
     example._load_weights()
     torch.cuda.set_device(FLAGS.gpu_id)          # every kernel launches on the current device's stream
-    run = _Pipelines(torch.device('cuda:%d' % FLAGS.gpu_id), use_graph)
-    for image_info, _fmt in image_infos:
-        mvs_list = gen_data_list(image_info[0])
-        savepath_current = os.path.join(savepath, image_info[2])
-        output_folder = os.path.join(savepath_current, 'depths_atvsnet')
-        os.makedirs(output_folder, exist_ok=True)
-        scene_runtime = 0.0
-        start_time = time.time()
-        queued = []                  # host-side data of the depth maps in flight, in submission order
+    device = torch.device('cuda:%d' % FLAGS.gpu_id)
+    if scene_cache:
+        decoder = _Decoder()
+        run = scene.SceneInference(decoder, FLAGS.max_d, slots=_Pipelines.SLOTS, co_resident=_Pipelines.CO_RESIDENT or False,
+                                   device=device, shape=decoder.shape)
+        writer = _Writer(write_thread)
+    else:
+        run = _Pipelines(device, use_graph)
+    try:
+        for image_info, _fmt in image_infos:
+            mvs_list = gen_data_list(image_info[0])
+            savepath_current = os.path.join(savepath, image_info[2])
+            output_folder = os.path.join(savepath_current, 'depths_atvsnet')
+            os.makedirs(output_folder, exist_ok=True)
+            scene_runtime = 0.0
+            TIMES.clear()                # this scene's maps only
+            TIMES.update(prepare=0.0, submit=0.0, wait=0.0, write=0.0, maps=0)
+            if scene_cache:
+                run.times['upload'], run.gpu_ms = 0.0, []
+            start_time = time.time()
+            queued = []                  # host-side data of the depth maps in flight, in submission order
 
-        def finish():
-            image_data_raw, cams_data, out_index = queued.pop(0)
-            depth, depth_up, prob, prob_up = run.fetch()
-            disp_up = np.squeeze(depth_up.copy())
-            if FLAGS.inverse_depth:
-                for m in (depth, depth_up):
-                    m[m <= 0] = float("inf")
-                depth, depth_up = 1.0 / depth, 1.0 / depth_up
-            stem = os.path.join(output_folder, '%08d' % out_index)
-            write_pfm(stem + '.pfm', np.squeeze(depth).astype(np.float32))
-            write_pfm(stem + '_prob.pfm', np.squeeze(prob).astype(np.float32))
-            if getattr(FLAGS, 'write_upsampled', False):      # commented out in the reference (:378-379)
-                write_pfm(stem + '_up.pfm', np.squeeze(depth_up).astype(np.float32))
-                write_pfm(stem + '_prob_up.pfm', np.squeeze(prob_up).astype(np.float32))
-            Image.fromarray(np.ascontiguousarray(image_data_raw[0, 0][:, :, ::-1])).save(stem + '.jpg')
-            write_cam(stem + '.txt', cams_data[0, 0])
-            plt.imsave(stem + '.png', disp_up, cmap='viridis')
+            def finish():
+                t0 = time.time()
+                if scene_cache:
+                    ticket, cams_data, out_index = queued.pop(0)
+                    # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
+                    outputs = [example.check_finite(o.numpy(), 'a network output', flag=False) for o in run.result(ticket, host=True)]
+                    image_raw = run.reference_image(ticket)
+                else:
+                    image_data_raw, cams_data, out_index = queued.pop(0)
+                    outputs = run.fetch()
+                    image_raw = image_data_raw[0, 0]
+                t1 = time.time()
+                job = lambda: _write_map(output_folder, out_index, outputs, image_raw, cams_data[0, 0], plt)     # noqa: E731
+                if scene_cache:
+                    writer(job)
+                else:
+                    job()
+                TIMES['wait'] += t1 - t0
+                TIMES['write'] += time.time() - t1
+                TIMES['maps'] += 1
 
-        # the depth maps of a scene are independent: the next one is submitted before the previous one's results are
-        # fetched and written, so file I/O overlaps the GPU (which still runs one map at a time: _Pipelines.CO_RESIDENT)
-        for current_i in range(len(mvs_list)):
-            image_data_raw, images_data, cams_data, _depth, out_index = load_data(mvs_list, current_i)
-            if not run.room():
+            def views_of(i):
+                data = mvs_list[i]
+                found = len(data) // 2
+                return [data[2 * (v if v < found else 0)] for v in range(FLAGS.view_num)]
+
+            # the depth maps of a scene are independent: the next one is submitted before the previous one's results are
+            # fetched and written, so file I/O overlaps the GPU (which still runs one map at a time: _Pipelines.CO_RESIDENT)
+            for current_i in range(len(mvs_list)):
+                t0 = time.time()
+                if scene_cache:
+                    views = views_of(current_i)
+                    if current_i + 1 < len(mvs_list):
+                        decoder.prefetch([v for v in views_of(current_i + 1) if ('image', v) not in run.cache])
+                    cams_data, _ = load_cams(mvs_list[current_i], [run.shape(v) for v in views])
+                    out_index = int(os.path.splitext(os.path.basename(mvs_list[current_i][0]))[0])
+                else:
+                    image_data_raw, images_data, cams_data, _depth, out_index = load_data(mvs_list, current_i)
+                t1 = time.time()
+                if not run.room():
+                    finish()
+                t2 = time.time()
+                if scene_cache:
+                    queued.append((run.submit(views, cams_data), cams_data, out_index))
+                else:
+                    run.submit(images_data, cams_data)
+                    queued.append((image_data_raw, cams_data, out_index))
+                TIMES['prepare'] += t1 - t0
+                TIMES['submit'] += time.time() - t2
+            while queued:
                 finish()
-            run.submit(images_data, cams_data)
-            queued.append((image_data_raw, cams_data, out_index))
-        while queued:
-            finish()
-        scene_runtime = time.time() - start_time       # wall clock of the scene (the reference sums sess.run times)
-        with open(os.path.join(savepath_current, 'zz_runtime.txt'), "w") as text_file:
-            text_file.write('runtime ' + str(scene_runtime))
-        print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
+            if scene_cache:
+                writer.close()                       # this scene's files are on disk before its runtime is written
+                TIMES['writer_busy'] = writer.busy if write_thread else TIMES['write']
+                writer = _Writer(write_thread)
+                TIMES['upload'] = run.times['upload']            # part of `submit`
+                TIMES['gpu_ms'] = list(run.gpu_ms)
+            scene_runtime = time.time() - start_time       # wall clock of the scene (the reference sums sess.run times)
+            with open(os.path.join(savepath_current, 'zz_runtime.txt'), "w") as text_file:
+                text_file.write('runtime ' + str(scene_runtime))
+            print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
+    finally:
+        if scene_cache:
+            writer.close()
+            decoder.close()
 
 
 def main(scene_list=None, base_path='eth3d/'):
@@ -229,7 +407,8 @@ def main(scene_list=None, base_path='eth3d/'):
     for scene in scene_list:
         folder = os.path.join(FLAGS.data_root, base_path + scene)
         image_infos.append([[folder, os.path.join(folder, 'images'), scene], 'preprocessed'])
-    run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False))
+    run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
+                scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False))
 
 
 def cli(argv=None):
@@ -250,7 +429,13 @@ def cli(argv=None):
                         help='serial: one depth map on the GPU at a time (default); cu_split: the two queued depth maps run concurrently, '
                              'each on its own half of every XCD (example.cu_split_streams: no SIMD shared between them; same bits, '
                              'more depth maps per second, twice the latency of one)')
+    parser.add_argument('--scene_cache', action='store_true',
+                        help='prepare each image on the GPU and run the 2-D towers on it once per scene; maps are assembled from '
+                             'the cached features (atvsnet/scene.py); files are written by a background thread')
+    parser.add_argument('--sync_write', action='store_true', help='--scene_cache: write the files in the driver thread')
     args = parser.parse_args(argv)
+    if args.eager and args.scene_cache:
+        parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False
     for k, v in vars(args).items():

@@ -138,10 +138,25 @@ class _ViewStreams(object):
 
 def _infer_multiview_batched(images, cams, max_d, stages, out_prob_map):
     """infer_multiview with every per-view network evaluated once over all views (model.*_batch)."""
-    n = images.shape[1]
+    # the towers are issued where the body first needs their output (feature tower first, shallow tower after AAM1)
+    return infer_multiview_from_features(lambda: feature_extraction_batch(images), lambda: shallow_feature_batch(images), cams,
+                                         max_d, stages, out_prob_map)
+
+
+def multiview_towers(images):
+    """Both 2-D towers of every view: (1,N,H,W,3) -> (features (N,H/4,W/4,32), shallow features (N,H/4,W/4,16)); per-image
+    statistics, so each row depends on its own image only (the scene cache, atvsnet/scene.py, computes them once per image)."""
+    return feature_extraction_batch(images), shallow_feature_batch(images)
+
+
+def infer_multiview_from_features(feats, shallow, cams, max_d, stages=None, out_prob_map=False):
+    """The batched multi-view pipeline after the towers: feats (N,h,w,32) and shallow (N,h,w,16) of the N views (tensors, or
+    callables computing them when first needed), cams (1,N,2,4,4)."""
+    max_d = FLAGS.max_d if max_d is None else max_d
+    n = cams.shape[1]
     src = list(range(1, n))
     depth_start, depth_interval = depth_range(cams)
-    feats = feature_extraction_batch(images)
+    feats = feats() if callable(feats) else feats
     hom = {}                       # the plane sweeps of the camera pairs: computed once per depth map
     filtered, _, _, depth_view = base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=src, rev=src, hom=hom)
     del feats
@@ -151,7 +166,7 @@ def _infer_multiview_batched(images, cams, max_d, stages, out_prob_map):
     depth_agg_init = prob2depth(prob_volume_agg, max_d, depth_start, depth_interval, out_prob_map=False)
     del filtered
     # refinement of every source against the aggregated estimate
-    shallow = shallow_feature_batch(images)
+    shallow = shallow() if callable(shallow) else shallow
     # refined_cost = filtered_cost + residual (model.py:438) of every source: formed by the pass that forms the residuals
     _, _, refined = refinement_batch(depth_agg_init, depth_view, prob_volume_agg, cams, max_d, depth_start, depth_interval, src,
                                      shallow, hom=hom, residual_base=cost_volume_agg)
@@ -226,23 +241,29 @@ class GraphedInference(object):
     Inputs live in static device buffers: pass new images / cams to __call__ to overwrite them.
     """
 
-    def __init__(self, images, cams, max_d=None, view_streams=True, out_prob_map=False, batched=None):
+    def __init__(self, images, cams, max_d=None, view_streams=True, out_prob_map=False, batched=None, features=False, fp32_fn=None):
+        """features=True: `images` is (features (N,h,w,32), shallow features (N,h,w,16)) of the N views and the graph is the
+        pipeline after the towers (infer_multiview_from_features; the scene driver, atvsnet/scene.py).  fp32_fn: what
+        fp32_rerun returns instead of replaying an fp32 capture of this graph (scene mode recomputes the towers too)."""
         from .. import ops
         self.max_d = FLAGS.max_d if max_d is None else max_d
         self.split16 = bool(ops.cfg.split16)    # the kernels this graph was captured with (a replay ignores later switches)
         self._fp32 = None                       # the same pipeline captured on the fp32 matrix cores, built on first need
+        self.fp32_fn = fp32_fn
         self.out_prob_map = out_prob_map
         self.batched = BATCHED if batched is None else batched
-        self.images = images.clone()
+        self.features = bool(features)
+        self.images = tuple(t.clone() for t in images) if self.features else images.clone()
         self.cams = cams.clone()
-        self.twoview = images.shape[1] == 2
+        self.twoview = not self.features and images.shape[1] == 2
         self.view_streams = view_streams
-        side = torch.cuda.Stream(images.device)
-        side.wait_stream(torch.cuda.current_stream(images.device))
+        dev = cams.device
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
         with torch.cuda.stream(side):          # warm-up: weight packing / uploads, function attributes
             self._run()
-        torch.cuda.current_stream(images.device).wait_stream(side)
-        torch.cuda.synchronize(images.device)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
         self.graph = torch.cuda.CUDAGraph()
         # thread_local: other threads (e.g. the RCCL watchdog of a multi-GPU run) may issue HIP calls meanwhile
         with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
@@ -252,6 +273,8 @@ class GraphedInference(object):
         self._weights = (ops.cache_snapshot(), variables.default_store().device_snapshot())
 
     def _run(self):
+        if self.features:
+            return infer_multiview_from_features(self.images[0], self.images[1], self.cams, self.max_d, out_prob_map=self.out_prob_map)
         if self.twoview:
             return infer_twoview(self.images, self.cams, self.max_d, batched=self.batched)
         return infer_multiview(self.images, self.cams, self.max_d, view_streams=self.view_streams,
@@ -259,7 +282,11 @@ class GraphedInference(object):
 
     def __call__(self, images=None, cams=None):
         if images is not None:
-            self.images.copy_(images)
+            if self.features:
+                for d, t in zip(self.images, images):
+                    d.copy_(t)
+            else:
+                self.images.copy_(images)
         if cams is not None:
             self.cams.copy_(cams)
         self.graph.replay()
@@ -271,7 +298,7 @@ class GraphedInference(object):
         returned -- the reference is fp32 end to end (cnn_wrapper/network.py:165-167, 570-601), a drop-in must not need a
         user action to have fp32's range.  FloatingPointError only if the fp32 kernels see non-finite values too."""
         out = self(images, cams)
-        dev = self.images.device
+        dev = self.cams.device
         from .. import ops
         if ops.nonfinite_seen(dev):
             out = self.fp32_rerun()
@@ -282,14 +309,16 @@ class GraphedInference(object):
         (built once, in this process -- never a re-exec of a process that has touched the GPU), replayed synchronously.
         Raises FloatingPointError if this graph already IS the fp32 form or the fp32 kernels see non-finite moments too."""
         from .. import ops
-        dev = self.images.device
+        dev = self.cams.device
         if not self.split16:
             raise FloatingPointError('a batch norm saw non-finite moments on the fp32 kernels: ' + _NONFINITE_HINT)
         _log_fp32_fallback()
+        if self.fp32_fn is not None:
+            return self.fp32_fn()
         if self._fp32 is None:
             with ops.configure(split16=False):
                 self._fp32 = GraphedInference(self.images, self.cams, self.max_d, view_streams=self.view_streams,
-                                              out_prob_map=self.out_prob_map, batched=self.batched)
+                                              out_prob_map=self.out_prob_map, batched=self.batched, features=self.features)
             ops.nonfinite_seen(dev)            # the capture's warm-up ran on the inputs too: start from a clear flag
         out = self._fp32(self.images, self.cams)
         if ops.nonfinite_seen(dev):
@@ -370,7 +399,7 @@ class PipelinedInference(object):
     def __init__(self, images, cams, max_d=None, slots=2, co_resident=False, **kw):
         if slots < 1:
             raise ValueError('PipelinedInference: slots >= 1')
-        self.device = images.device
+        self.device = cams.device
         if co_resident not in (False, True, 'cu_split'):
             raise ValueError("PipelinedInference: co_resident is False, True or 'cu_split'")
         self.cu_split = co_resident == 'cu_split'
@@ -400,8 +429,10 @@ class PipelinedInference(object):
             self.streams = cu_split_streams(self.device, self.slots) if split else [torch.cuda.Stream(self.device) for _ in range(self.slots)]
         self.cu_split, self.co_resident, self.last = split, bool(co_resident), None
 
-    def submit(self, images=None, cams=None):
-        """Issue one depth map on the next slot (its previous result must have been fetched); returns the ticket."""
+    def submit(self, images=None, cams=None, fill=None):
+        """Issue one depth map on the next slot (its previous result must have been fetched); returns the ticket.
+        images: a tensor, or the (features, shallow features) pair of a features-mode graph.  fill(slot): called on the slot's
+        stream before the replay, after the slot's ordering waits (the scene driver computes and copies the views' features there)."""
         s = self.next
         if self.busy[s]:
             raise RuntimeError('PipelinedInference: slot %d still holds an unfetched result' % s)
@@ -411,7 +442,8 @@ class PipelinedInference(object):
         # streams in the legacy sense -- any operation on the default stream (an event record, a copy) waits for every map in flight
         # and holds the next one back, which serialises the slots (34 instead of 62 maps/s at configs[2]); so HOST tensors (or None)
         # are copied by the slot's own stream with no default-stream operation at all, and only device inputs pay for the ordering
-        if not self.cu_split or any(t is not None and t.is_cuda for t in (images, cams)):
+        inputs = (list(images) if isinstance(images, (tuple, list)) else [images]) + [cams]
+        if not self.cu_split or any(t is not None and t.is_cuda for t in inputs):
             cur = torch.cuda.current_stream(self.device)
             if self.cu_split and cur == torch.cuda.default_stream(self.device) and not getattr(self, '_warned', False):
                 self._warned = True
@@ -421,12 +453,14 @@ class PipelinedInference(object):
             st.wait_stream(cur)
         if not self.co_resident and self.last is not None and self.last != s:
             st.wait_event(self.events[self.last])                   # one depth map on the GPU at a time
-        for t in (images, cams):
+        for t in inputs:
             # the copy into the slot's static buffers runs on the slot's stream, possibly long after this call returns:
             # tell the caching allocator, or the caller's next allocation could re-use the block while it is still read
             if t is not None and t.is_cuda:
                 t.record_stream(st)
         with torch.cuda.stream(st):
+            if fill is not None:
+                fill(s)
             self.graphs[s](images, cams)
             self.events[s].record(st)
         self.busy[s] = True
@@ -588,11 +622,11 @@ def check_device(device=None):
         raise FloatingPointError('a batch norm saw non-finite moments: ' + _RANGE_HINT)
 
 
-def check_finite(arr, what='depth map'):
+def check_finite(arr, what='depth map', flag=True):
     """The split-operand convolutions carry activations as two fp16 pieces: a value beyond +-65504 turns
     into inf/NaN there instead of a silently wrong depth.  The host drivers call this on every result they copy back so that
     the failure names its cause (ATVS_SPLIT16=0 selects the fp32 matrix-core kernels, which have fp32's range)."""
-    if torch.cuda.is_available() and torch.cuda.is_initialized():
+    if flag and torch.cuda.is_available() and torch.cuda.is_initialized():     # flag=False: the caller has read the flag itself
         check_device()
     if not np.isfinite(arr).all():
         raise FloatingPointError('%s holds %d non-finite values: an activation or weight left the fp16 range of the split-operand '

@@ -59,6 +59,19 @@ def _resize_taps(n_dst, n_src, step):
     return left, np.minimum(left + 1, n_src - 1), frac
 
 
+def resize_taps_u8(n_dst, n_src, step):
+    """The 8-bit INTER_LINEAR taps of one axis: (left index, right index, left weight, right weight), the weights in 11-bit
+    fixed point (sum 2048).  scale_image's uint8 path and the GPU view preparation (ops.prepare_view) both use these."""
+    left, right, frac = _resize_taps(n_dst, n_src, step)
+    q = lambda t: np.rint(t * _COEF_ONE).astype(np.int64)                         # noqa: E731
+    return left, right, q(1.0 - frac), q(frac)
+
+
+def scaled_size(h, w, scale):
+    """(rows, cols) of scale_image(an h x w image, scale)."""
+    return int(np.rint(h * scale)), int(np.rint(w * scale))
+
+
 def scale_image(image, scale=1, interpolation='linear'):
     """cv2.resize(image, None, fx=scale, fy=scale, INTER_LINEAR | INTER_NEAREST)."""
     if interpolation not in ('linear', 'nearest'):
@@ -73,18 +86,18 @@ def scale_image(image, scale=1, interpolation='linear'):
         rows = np.minimum((np.arange(H) * step).astype(np.int64), h - 1)
         cols = np.minimum((np.arange(W) * step).astype(np.int64), w - 1)
         return src[rows][:, cols]
-    y0, y1, wy = _resize_taps(H, h, step)
-    x0, x1, wx = _resize_taps(W, w, step)
     px = src.reshape(h, w, -1)
     if src.dtype == np.uint8:
-        q = lambda t: np.rint(t * _COEF_ONE).astype(np.int64)                     # noqa: E731
-        ax0, ax1, by0, by1 = q(1.0 - wx), q(wx), q(1.0 - wy), q(wy)
+        y0, y1, by0, by1 = resize_taps_u8(H, h, step)
+        x0, x1, ax0, ax1 = resize_taps_u8(W, w, step)
         p = px.astype(np.int64)
         horiz = p[:, x0] * ax0[None, :, None] + p[:, x1] * ax1[None, :, None]     # 8.11 fixed point
         top, bot = horiz[y0] >> 4, horiz[y1] >> 4
         acc = ((by0[:, None, None] * top) >> 16) + ((by1[:, None, None] * bot) >> 16)
         out = np.clip((acc + 2) >> 2, 0, 255).astype(np.uint8)
     else:
+        y0, y1, wy = _resize_taps(H, h, step)
+        x0, x1, wx = _resize_taps(W, w, step)
         p = px.astype(np.float32)
         cx, cy = wx[None, :, None], wy[:, None, None]
         horiz = p[:, x0] * (1.0 - cx) + p[:, x1] * cx
@@ -121,6 +134,12 @@ def crop_mvs_input(images, cams, depth_image=None, base_image_size=32):
     if depth_image is None:
         return images, cams
     return images, cams, depth_image[y0:y1, x0:x1]          # the last view's window, as in the reference
+
+
+def crop_window(h, w, base_image_size=32):
+    """crop_mvs_input's window of ONE h x w view: (y0, x0, rows, cols)."""
+    nh, nw = _fit(h, FLAGS.max_h, base_image_size), _fit(w, FLAGS.max_w, base_image_size)
+    return int(math.ceil((h - nh) / 2)), int(math.ceil((w - nw) / 2)), nh, nw
 
 
 def mask_depth_image(depth_image, min_depth, max_depth):

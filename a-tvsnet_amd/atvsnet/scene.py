@@ -1,0 +1,377 @@
+"""Scene mode: every image of a scene prepared on the GPU and run through both 2-D towers ONCE; each depth map is assembled from
+cached features (eval_pointcloud --scene_cache).
+
+In an ETH3D pair.txt scene every image is the reference of one depth map and a source of about seven others.  The per-map path
+(eval_pointcloud.load_data + GraphedInference) decodes, resizes and centres each image, and runs the towers on it, once per map it
+appears in.  Here:
+
+* the image is decoded once and uploaded as uint8; ops.prepare_view resizes it by the map's adaptive scale, crops and centres it,
+  and forms the 1/4-scale image (bit for bit scale_image; the centring may differ from center_image in the last bits);
+* one captured graph per (image shape, output shape, slot) runs preparation + both towers (example.multiview_towers at N = 1:
+  every tower has per-image statistics, so a row does not depend on the other images of a launch);
+* the cache maps (image id, adaptive scale, crop window) -> (features, shallow features, 1/4 image), and image id -> the device
+  uint8 image, bounded in bytes with LRU eviction;
+* each map replays a features-mode graph (example.GraphedInference(features=True)) from PipelinedInference's slots.
+
+Range rule: a map whose replay or whose newly computed tower features raised the non-finite flag is
+recomputed entirely on the fp32 kernels from the uint8 images (what ops.configure(split16=False) computes for it), and the cache
+entries its submission made are dropped.  Entries belong to the weights they were computed with: a change of the variable store
+clears the cache and the captured graphs.
+"""
+from __future__ import print_function
+
+import collections
+import gc
+import math
+import time
+import weakref
+
+import numpy as np
+import torch
+
+from .. import ops, variables
+from ..flags import FLAGS
+from . import example
+from .preprocess import crop_window, scaled_size
+
+
+def pad_views(views, view_num):
+    """A pair.txt entry's views (reference first) -> exactly view_num of them: missing sources are the reference (load_data)."""
+    views = list(views)[:view_num]
+    return views + [views[0]] * (view_num - len(views))
+
+
+def adaptive_scale(shapes, max_h=None, max_w=None):
+    """load_data's resize_scale of a map whose views have `shapes` [(h, w), ...] (FLAGS.adaptive_scaling); None if an image is
+    smaller than max_h x max_w (load_data exits then)."""
+    if not FLAGS.adaptive_scaling:
+        return 1
+    max_h = FLAGS.max_h if max_h is None else max_h
+    max_w = FLAGS.max_w if max_w is None else max_w
+    h_scale = max(float(max_h) / s[0] for s in shapes)
+    w_scale = max(float(max_w) / s[1] for s in shapes)
+    if h_scale > 1 or w_scale > 1:
+        return None
+    return max(h_scale, w_scale)
+
+
+def view_key(image_id, scale, crop):
+    """Cache key of one prepared view."""
+    return (image_id, float(scale), tuple(int(v) for v in crop))
+
+
+def tensor_bytes(*ts):
+    return sum(int(t.numel()) * t.element_size() for t in ts)
+
+
+class ViewCache(object):
+    """key -> value with a byte bound and least-recently-used eviction; cleared when the weights change (`generation`).
+    The most recent entry is always kept, even alone above the bound."""
+
+    def __init__(self, max_bytes):
+        self.max_bytes = int(max_bytes)
+        self.items = collections.OrderedDict()          # key -> (value, bytes)
+        self.bytes = 0
+        self.generation = None
+        self.evictions = 0
+
+    def check_generation(self, generation):
+        """Clear if the weights changed since the entries were made; True if it cleared."""
+        if generation == self.generation:
+            return False
+        self.clear()
+        self.generation = generation
+        return True
+
+    def get(self, key):
+        item = self.items.get(key)
+        if item is None:
+            return None
+        self.items.move_to_end(key)
+        return item[0]
+
+    def put(self, key, value, nbytes):
+        self.drop(key)
+        self.items[key] = (value, int(nbytes))
+        self.bytes += int(nbytes)
+        while self.bytes > self.max_bytes and len(self.items) > 1:
+            _, (_, b) = self.items.popitem(last=False)
+            self.bytes -= b
+            self.evictions += 1
+
+    def drop(self, key):
+        item = self.items.pop(key, None)
+        if item is not None:
+            self.bytes -= item[1]
+
+    def clear(self):
+        self.items.clear()
+        self.bytes = 0
+
+    def __contains__(self, key):
+        return key in self.items
+
+    def __len__(self):
+        return len(self.items)
+
+
+class _Entry(object):
+    """Device tensors made on `stream`, complete at `event`."""
+    __slots__ = ('tensors', 'stream', 'event')
+
+    def __init__(self, tensors, stream):
+        self.tensors, self.stream = tensors, stream
+        self.event = torch.cuda.Event()
+        self.event.record(stream)
+
+    def use(self, stream):
+        """Make the tensors usable on `stream` (an event wait between two side streams: no default-stream operation)."""
+        if stream != self.stream:
+            stream.wait_event(self.event)
+            for t in self.tensors:
+                t.record_stream(stream)
+        return self.tensors
+
+
+class _TowerGraph(object):
+    """ops.prepare_view + example.multiview_towers of one image, captured for one (source shape, output shape); the taps are
+    static inputs, so one graph serves every scale / crop with those shapes."""
+
+    def __init__(self, plan, scale, crop, sample_scale, device):
+        self.image = torch.zeros(plan.src_shape, dtype=torch.uint8, device=device)
+        self.ws = (torch.empty(plan.shape, dtype=torch.float32, device=device),
+                   torch.empty(plan.quarter_shape, dtype=torch.uint8, device=device)) + ops.prepare_workspace(plan, device)
+        self.args = (scale, crop, sample_scale)
+        torch.cuda.current_stream(device).wait_event(plan.ready)
+        self.taps = [t.clone() for t in plan.taps]
+        side = torch.cuda.Stream(device)
+        side.wait_stream(torch.cuda.current_stream(device))
+        with torch.cuda.stream(side):           # warm-up: weight packing / uploads
+            self._run()
+        torch.cuda.current_stream(device).wait_stream(side)
+        torch.cuda.synchronize(device)
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
+            self.out = self._run()
+        self._weights = (ops.cache_snapshot(), variables.default_store().device_snapshot())
+
+    def _run(self):
+        scale, crop, sample_scale = self.args
+        centred, quarter = ops.prepare_view(self.image, scale, crop, sample_scale, out=self.ws, taps=self.taps)
+        feats, shallow = example.multiview_towers(centred.view((1, 1) + tuple(centred.shape)))
+        return feats, shallow, quarter
+
+    def __call__(self, image, plan):
+        self.image.copy_(image)
+        for d, t in zip(self.taps, plan.taps):
+            d.copy_(t)
+        self.graph.replay()
+        return self.out
+
+
+class SceneInference(object):
+    """Depth maps of one or more scenes from cached per-image features.
+
+        scene = SceneInference(loader, max_d, slots=2, co_resident=False)
+        scale, crops = scene.layout(views)               # views: image ids, reference first, padded to view_num
+        t = scene.submit(views, cams)                    # cams (1,N,2,4,4) at FLAGS.sample_scale, host or device
+        depth, depth_up, prob, prob_up = scene.result(t, host=True)
+        quarter = scene.reference_image(t)               # the reference's 1/4-scale uint8 BGR image (host)
+
+    loader(image_id) -> (h,w,3) uint8 BGR numpy; shape(image_id) -> (h, w) (defaults to the loader's image).  Slot semantics
+    are PipelinedInference's (slots, co_resident False | 'cu_split', result(host=True)).  In cu_split mode nothing runs on the
+    default stream between submissions once every (views, crop size) has been captured: image and tap uploads (from pinned
+    memory), tower replays and feature copies run on the slot's stream.
+    Instrumentation: times['upload'] (host seconds spent issuing image uploads), gpu_ms (per fetched map: its GPU time on the
+    slot's stream, from after the slot's ordering waits to the end of its replay)."""
+
+    def __init__(self, loader, max_d=None, slots=2, co_resident=False, max_bytes=4 << 30, device=None, shape=None,
+                 sample_scale=None, view_num=None):
+        if co_resident not in (False, 'cu_split'):
+            raise ValueError("SceneInference: co_resident is False or 'cu_split'")
+        self.loader, self._shape_fn = loader, shape
+        self.max_d = FLAGS.max_d if max_d is None else max_d
+        self.view_num = FLAGS.view_num if view_num is None else view_num
+        self.sample_scale = FLAGS.sample_scale if sample_scale is None else sample_scale
+        self.slots, self.co_resident = slots, co_resident
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        self.cache = ViewCache(max_bytes)
+        self.shapes = {}
+        self.tower_runs = 0
+        self.times, self.gpu_ms = {'upload': 0.0}, []
+        self.streams = example.cu_split_streams(self.device, slots) if co_resident == 'cu_split' else None
+        self._reset()
+
+    def _reset(self):
+        self.towers, self.pipelines = {}, {}
+        self.slot_map, self.slot_new, self.slot_quarter, self.slot_events = {}, {}, {}, {}
+        self.last = None                                   # (pipeline, slot) of the latest submission
+
+    def _check_weights(self):
+        if self.cache.check_generation(variables.default_store().generation) and self.cache.generation is not None:
+            self._reset()                                  # graphs hold the weights they were captured with
+
+    def shape(self, image_id):
+        s = self.shapes.get(image_id)
+        if s is None:
+            s = tuple(self._shape_fn(image_id)) if self._shape_fn is not None else tuple(self.loader(image_id).shape[:2])
+            self.shapes[image_id] = s
+        return s
+
+    def layout(self, views):
+        """(adaptive scale, [crop window per view]) of a map; ValueError if an image is smaller than max_h x max_w."""
+        shapes = [self.shape(v) for v in views]
+        scale = adaptive_scale(shapes)
+        if scale is None:
+            raise ValueError('max_h, max_w should < W and H! (views %s)' % (shapes,))
+        return scale, [crop_window(*scaled_size(h, w, scale)) for h, w in shapes]
+
+    def room(self):
+        return sum(p.busy.count(True) for p in self.pipelines.values()) < self.slots
+
+    # -- device images and cache entries ------------------------------------------------------------------------------------
+    def _device_image(self, image_id, stream):
+        key = ('image', image_id)
+        e = self.cache.get(key)
+        if e is None:
+            host = torch.from_numpy(np.ascontiguousarray(self.loader(image_id), dtype=np.uint8))
+            t0 = time.time()
+            with torch.cuda.stream(stream):
+                # from pinned memory: the copy is queued on the slot's stream and the host does not wait for the map in flight
+                img = host.pin_memory().to(self.device, non_blocking=True)
+                e = _Entry((img,), stream)
+            self.times['upload'] += time.time() - t0
+            self.shapes[image_id] = tuple(img.shape[:2])
+            self.cache.put(key, e, tensor_bytes(img))
+        return e.use(stream)[0]
+
+    def _tower_graph(self, plan, scale, crop, slot):
+        key = (plan.src_shape, plan.shape, plan.quarter_shape, slot)
+        g = self.towers.get(key)
+        if g is None:
+            gc.collect()
+            g = self.towers[key] = _TowerGraph(plan, scale, crop, self.sample_scale, self.device)
+        return g
+
+    def _pipeline(self, n, H, W, cams):
+        key = (n, H, W)
+        p = self.pipelines.get(key)
+        if p is None:
+            gc.collect()                                    # no unreachable graph of an earlier run may be freed during the capture
+            h, w = int(math.ceil(H / 4.0)), int(math.ceil(W / 4.0))
+            feats = (torch.zeros((n, h, w, 32), device=self.device), torch.zeros((n, h, w, 16), device=self.device))
+            p = example.PipelinedInference(feats, cams.to(self.device, torch.float32), self.max_d, slots=self.slots,
+                                           co_resident=self.co_resident, out_prob_map=True, features=True)
+            if self.streams is not None:
+                p.streams = self.streams                    # every shape's slot k on the same CU share
+            # weak references only: a cycle scene -> pipeline -> graph -> scene would leave the captured graphs to the cyclic garbage
+            # collector, which may then destroy one in the middle of a later capture (not permitted while a stream is capturing)
+            me, pw = weakref.ref(self), weakref.ref(p)
+            for s, g in enumerate(p.graphs):
+                g.fp32_fn = (lambda s=s: me()._fp32_map(pw(), s))
+            self.pipelines[key] = p
+        return p
+
+    # -- submission ---------------------------------------------------------------------------------------------------------
+    def submit(self, views, cams):
+        """Issue the depth map of `views` (image ids, reference first; fewer than view_num: padded with the reference) with
+        cameras `cams` (1,N,2,4,4); returns the ticket."""
+        self._check_weights()
+        views = pad_views(views, self.view_num)
+        scale, crops = self.layout(views)
+        sizes = set((c[2], c[3]) for c in crops)
+        if len(sizes) != 1:
+            raise ValueError('SceneInference: the views of a map crop to different sizes %s' % sorted(sizes))
+        cams = cams if isinstance(cams, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cams, dtype=np.float32))
+        p = self._pipeline(len(views), crops[0][2], crops[0][3], cams)
+        slot = p.next
+        with torch.cuda.stream(p.streams[slot]):            # a new (size, scale, crop) uploads its taps on the slot's stream
+            plans = [ops.view_plan(self.shape(v)[0], self.shape(v)[1], scale, c, self.sample_scale, self.device)
+                     for v, c in zip(views, crops)]
+        for v, c, plan in zip(views, crops, plans):         # first use of a shape: capture now, not inside the slot's stream
+            if view_key(v, scale, c) not in self.cache:
+                self._tower_graph(plan, scale, c, slot)
+        last = self.last
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+
+        def fill(s):
+            st = torch.cuda.current_stream(self.device)
+            if not self.co_resident and last is not None and last[0] is not p and last[0].busy[last[1]]:
+                st.wait_event(last[0].events[last[1]])      # one depth map on the GPU at a time, across shapes too
+            start.record(st)
+            if host_cams is not None:                       # pinned: queued on the slot's stream, the host does not wait
+                p.graphs[s].cams.copy_(host_cams, non_blocking=True)
+            feats, shallow = p.graphs[s].images
+            new, quarter = [], None
+            for i, (v, c, plan) in enumerate(zip(views, crops, plans)):
+                key = view_key(v, scale, c)
+                e = self.cache.get(key)
+                if e is None:
+                    img = self._device_image(v, st)
+                    st.wait_event(plan.ready)
+                    f, sh, q = self._tower_graph(plan, scale, c, s)(img, plan)
+                    e = _Entry((f.clone(), sh.clone(), q.clone()), st)
+                    self.cache.put(key, e, tensor_bytes(*e.tensors))
+                    new.append(key)
+                    self.tower_runs += 1
+                f, sh, q = e.use(st)
+                feats[i].copy_(f[0])
+                shallow[i].copy_(sh[0])
+                if i == 0:
+                    quarter = q
+            self.slot_map[(id(p), s)] = (views, scale, crops)
+            self.slot_new[(id(p), s)] = new
+            self.slot_quarter[(id(p), s)] = quarter
+
+        host_cams = None if cams.is_cuda else cams.to(torch.float32).contiguous().pin_memory()
+        s = p.submit(None, cams if cams.is_cuda else None, fill=fill)
+        end.record(p.streams[s])
+        self.slot_events[(id(p), s)] = (start, end)
+        self.last = (p, s)
+        return (p, s)
+
+    def result(self, ticket, host=False):
+        """The (depth, depth_up, prob, prob_up) of `ticket` (PipelinedInference.result: an overflowed map comes back computed on
+        the fp32 kernels); the cache entries of every map found suspect are dropped.  The non-finite flag is device-wide: when it
+        is found up, every map in flight in ANY of the scene's pipelines (one per crop size) becomes suspect."""
+        p, s = ticket
+        if not p.busy[s]:
+            raise RuntimeError('SceneInference: nothing in flight on slot %d' % s)
+        p.events[s].synchronize()
+        with torch.cuda.stream(p.streams[s]):                # the flag read: on the slot's (idle) stream
+            if ops.nonfinite_seen(self.device):
+                torch.cuda.synchronize(self.device)
+                ops.nonfinite_seen(self.device)
+                for q in self.pipelines.values():
+                    q.suspect.update(t for t, b in enumerate(q.busy) if b)
+                if p not in self.pipelines.values():
+                    p.suspect.update(t for t, b in enumerate(p.busy) if b)
+        for q in list(self.pipelines.values()) + [p]:
+            for t in q.suspect:
+                for key in self.slot_new.pop((id(q), t), []):
+                    self.cache.drop(key)                   # made while the flag was up: never reused
+        out = p.result(s, host=host)
+        start, end = self.slot_events.pop((id(p), s))
+        end.synchronize()
+        self.gpu_ms.append(start.elapsed_time(end))
+        return out
+
+    def reference_image(self, ticket):
+        """The reference view's sample_scale uint8 BGR image of `ticket`'s map (host numpy; after result())."""
+        p, s = ticket
+        with torch.cuda.stream(p.streams[s]):
+            return self.slot_quarter[(id(p), s)].cpu().numpy()
+
+    def _fp32_map(self, p, s):
+        """The map now in slot s, computed entirely on the fp32 kernels from the uint8 images (towers included)."""
+        views, scale, crops = self.slot_map[(id(p), s)]
+        for key in self.slot_new.pop((id(p), s), []):
+            self.cache.drop(key)                             # made while the flag was up
+        st = torch.cuda.current_stream(self.device)
+        with ops.configure(split16=False):
+            imgs = torch.stack([ops.prepare_view(self._device_image(v, st), scale, c, self.sample_scale)[0]
+                                for v, c in zip(views, crops)], 0)[None]
+            out = example.infer_multiview(imgs, p.graphs[s].cams, self.max_d, out_prob_map=True)
+        if ops.nonfinite_seen(self.device):
+            raise FloatingPointError('a batch norm saw non-finite moments on the fp32 kernels too: ' + example._NONFINITE_HINT)
+        return out

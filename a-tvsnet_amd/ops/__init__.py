@@ -1,4 +1,4 @@
-"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in seven modules --
+"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in eight modules --
 
     base      ctypes plumbing, the dispatch switches (`cfg`, `configure`), launch timing
     packing   weights in operand order + their cache, tap lists, the chunk-planar layout
@@ -7,6 +7,7 @@
     launch    dispatch policy (`*_ok`) and single-kernel launch wrappers
     convolution  `conv()` and the composite forms (SplitVolume, siblings, stems, transposed convolution)
     aanet     AANet aggregation, depth-map fusion
+    prepare   the scene driver's view preparation (uint8 image -> network input, 1/4 image)
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -30,5 +31,6 @@ from .launch import (Fin, XPAIR_TAPS, _fin_counter, _fin_pool, _from5, _pick_til
 from .convolution import (SplitVolume, _DECONV_OFFSETS, _deconv_virtual_kernel, _fold_split_weights, conv, conv3d_8to1,
     conv3d_transpose_s2, conv_siblings, conv_split, conv_split_into_plane, conv_split_siblings, deconv_sum_ok,
     photo_pieces_ok, planar_concat_ok, refine_stems, siblings_ok)      # noqa: F401
+from .prepare import (ViewPlan, prepare_taps, prepare_view, prepare_workspace, resize_u8_host, view_plan)      # noqa: F401
 from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, divide, fusibile)      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

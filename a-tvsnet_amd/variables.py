@@ -115,10 +115,12 @@ class VariableStore(object):
         self.host = {}
         self._dev = {}
         self.strict = False      # True: unknown names raise instead of being synthesised
+        self.generation = 0      # bumped on every change of a value (owners of cached activations compare it)
 
     def _invalidate(self):
         """Arranged copies of the weights (ops' pack caches) are keyed by name: drop them when a value changes."""
         from . import ops
+        self.generation += 1
         ops.invalidate_weights()
 
     def clear(self):

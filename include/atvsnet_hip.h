@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 43
+#define ATVS_ABI_VERSION 44
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -675,6 +675,17 @@ int atvs_conv_c16b_sum_supported(int Cin);
 int atvs_conv_c16b_sum_f32(const float* x0, const float* params0, const float* x1, const float* params1, int relu_mask,
                            const unsigned char* packed_w, const float* bias, float* y, double* stats_partial, int groups, int D,
                            int H, int W, int Cin, int ldy, int y_coff, int relu, atvs_stream_t stream);
+
+/* View preparation of the scene driver (eval_pointcloud --scene_cache), csrc/prepare.hip.  Images are uint8 BGR (h,w,3).
+ * atvs_prepare_resize_u8: cv2.resize(INTER_LINEAR) of 8-bit images exactly as preprocess.scale_image computes it, for the
+ * output rows / columns the host lists: ytap (4,H) and xtap (4,W) int32 = (left index, right index, left weight, right weight),
+ * the 11-bit weights preprocess.py forms (a centre crop is a slice of the full lists).  src (h,w,3) -> dst (H,W,3).  sums: NULL,
+ * or 6 unsigned 64-bit words set to (sum x, sum x^2) of each channel of dst (zeroed on the stream, then integer atomics).
+ * atvs_prepare_center: y (pixels,3) float32 = (x - mu) / (sd + 1e-8f) per channel (center_image), mu and sd from those sums in
+ * double, each rounded once to float32.  pixels <= 11e6. */
+int atvs_prepare_resize_u8(const unsigned char* src, int h, int w, unsigned char* dst, int H, int W, const int* ytap,
+                           const int* xtap, unsigned long long* sums, atvs_stream_t stream);
+int atvs_prepare_center(const unsigned char* x, long pixels, const unsigned long long* sums, float* y, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
