@@ -61,10 +61,11 @@ def infer_twoview(images, cams, max_d=None, batched=None):
         # model.TVSNet (reference model.py:346-377) with both towers, both siamese directions in one pass each
         feats = feature_extraction_batch(images)
         hom = {}
-        _, prob_b2, depth_b2, dview = base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=[1], rev=[1], hom=hom)
+        _, prob_b2, depth_b2, dview = base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=[1], rev=[1], hom=hom,
+                                                       filtered=False)
         shallow = shallow_feature_batch(images)
         _, prob_residual = refinement_batch(depth_b2, dview, prob_b2, cams, max_d, depth_start, depth_interval, [1], shallow,
-                                            hom=hom)
+                                            hom=hom, cost=False)
         refined_prob_volume = ops.add_n([prob_b2, prob_residual])
         _, depth_refined = prob2depth_upsample(refined_prob_volume, max_d, depth_start, depth_interval, out_prob_map=False)
         return depth_refined
@@ -158,7 +159,9 @@ def infer_multiview_from_features(feats, shallow, cams, max_d, stages=None, out_
     depth_start, depth_interval = depth_range(cams)
     feats = feats() if callable(feats) else feats
     hom = {}                       # the plane sweeps of the camera pairs: computed once per depth map
-    filtered, _, _, depth_view = base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=src, rev=src, hom=hom)
+    # only the forward filtered volumes and the reverse depths are read: the head runs over the reverse samples alone
+    filtered, _, _, depth_view = base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=src, rev=src, hom=hom,
+                                                  fwd_prob=False)
     del feats
     # AAM1
     cost_volume_agg = cost_volume_aggregation(filtered, reuse=False, keepchannel=True)
@@ -167,9 +170,10 @@ def infer_multiview_from_features(feats, shallow, cams, max_d, stages=None, out_
     del filtered
     # refinement of every source against the aggregated estimate
     shallow = shallow() if callable(shallow) else shallow
-    # refined_cost = filtered_cost + residual (model.py:438) of every source: formed by the pass that forms the residuals
+    # refined_cost = filtered_cost + residual (model.py:438) of every source: formed by the pass that forms the residuals, which
+    # are read by nothing else (no probability head, the residual itself not written)
     _, _, refined = refinement_batch(depth_agg_init, depth_view, prob_volume_agg, cams, max_d, depth_start, depth_interval, src,
-                                     shallow, hom=hom, residual_base=cost_volume_agg)
+                                     shallow, hom=hom, residual_base=cost_volume_agg, cost=False, prob=False)
     # AAM2
     refined_cost_volume_agg = cost_volume_aggregation_refine(refined, reuse=False, keepchannel=True)
     refined_prob_volume_agg = output_conv_refine(refined_cost_volume_agg, reuse=False)

@@ -197,7 +197,13 @@ def _hull_view(ref_id):
     return ids[1]
 
 
-def _refine_net(bufs, prob_vol, chan, independent, residual_base=None):
+def _samples(t, lo, hi):
+    """Samples [lo, hi) of a batch-first layer; a pending one stays pending (only those samples are ever formed)."""
+    return t.samples(lo, hi) if isinstance(t, (ops.PendingBN, ops.PendingSum)) else t[lo:hi]
+
+
+def _refine_net(bufs, prob_vol, chan, independent, residual_base=None, cost=True, prob=True):
+    """-> (cost residual or None, prob residual or None[, residual_base + cost residual]); cost / prob: does the caller read it."""
     photo_var, photo_const, geo_var, geo_const, hull = bufs
     cmap = [('v', i) for i in range(chan)] + [('c', i) for i in range(2 * chan)]
     if photo_var.dim() == 3:
@@ -208,8 +214,11 @@ def _refine_net(bufs, prob_vol, chan, independent, residual_base=None):
     inputs = {'photo_group': photo, 'geo_group': geo, 'prob_vol': prob_vol, 'vis_hull': hull}
     if residual_base is not None:
         inputs['residual_base'] = residual_base
-    tower = CostVolRefineNet(inputs, is_training=True, reuse=AUTO_REUSE, independent_samples=independent)
-    out = (tower.get_output_by_name('global_refine_3dconv6_1'), tower.get_output().squeeze(-1))
+    tower = CostVolRefineNet(inputs, is_training=True, reuse=AUTO_REUSE, independent_samples=independent, head=prob,
+                             keep_residual=cost)
+    # the head (if any) ran first, forming the pending skip sum on load; the residual itself is formed only if it is read
+    out = (tower.get_output_by_name('global_refine_3dconv6_1') if cost else None,
+           tower.get_output_by_name('global_refined_cost_vol').squeeze(-1) if prob else None)
     if residual_base is not None:
         out += (tower.get_output_by_name('global_refine_3dconv6_1_plus'),)
     return out
@@ -254,7 +263,7 @@ def refinement(init_depth_images, cams, depth_num, depth_start, depth_interval, 
 
 
 def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_start, depth_interval, sources,
-                     shallow, ref_id=0, shallow_index=None, hom=None, residual_base=None):
+                     shallow, ref_id=0, shallow_index=None, hom=None, residual_base=None, cost=True, prob=True):
     """`refinement` of several source views against one reference estimate in ONE pass of the network
     (the reference calls it once per source, example.py:163-172): depth_ref (1,h,w,1), depth_views {source: (1,h,w,1)},
     prob_vol (1,D,h,w) shared, shallow (N,h,w,16) features of every view (shallow_index: {view id: row of shallow} when
@@ -262,7 +271,8 @@ def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_st
     its own batch statistics.  cams are indexed by the view ids themselves.  hom: the depth map's homography cache
     (_cached_homographies), e.g. the one base_stage_batch filled.  residual_base (1,D,h,w,8): the cost volume the residuals are
     added to (TVSNet_refine, reference :439) -- a third result, residual_base + cost residual (S,D,h,w,8), then comes out of the
-    pass that forms the residuals."""
+    pass that forms the residuals.  cost=False / prob=False: the caller reads no cost / prob residual (None in its place): the
+    probability head does not run, the cost residual is not written."""
     si = (lambda v: v) if shallow_index is None else (lambda v: shallow_index[v])
     D = int(depth_num)
     S = len(sources)
@@ -287,7 +297,7 @@ def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_st
                             shallow[si(ref_id):si(ref_id) + 1], shallow[si(v):si(v) + 1], D, ds, di, depth_start,
                             depth_interval, hom, ((ref_id, v), (ref_id, _hull_view(ref_id))), tr)
     pv = ops.stack([prob_vol[0].unsqueeze(-1)] * S, 0) if S > 1 else prob_vol.unsqueeze(-1)      # the shared volume, once per sample
-    return _refine_net(bufs, pv, chan, True, residual_base)
+    return _refine_net(bufs, pv, chan, True, residual_base, cost, prob)
 
 
 def feature_extraction_batch(images):
@@ -327,23 +337,39 @@ def build_cost_volumes(features, cams, pairs, depth_num, depth_start, depth_inte
                            planar=(D, h, w) if planar else False, pieces=pieces)
 
 
-def base_stage_batch(features, cams, depth_num, depth_start, depth_interval, fwd, rev, ref_i=0, feature_index=None, hom=None):
+def base_stage_batch(features, cams, depth_num, depth_start, depth_interval, fwd, rev, ref_i=0, feature_index=None, hom=None,
+                     filtered=True, fwd_prob=True):
     """TVSNet_base_siamese for several source views in ONE pass of the regulariser (the reference runs it per source,
     example.py:144-149): `fwd` = sources whose reference->source direction is wanted (filtered cost volume, probability
     volume, depth), `rev` = sources whose source->reference direction is wanted (depth_view).
-    -> (filtered (F,D,h,w,8), prob (F,D,h,w), depth_b2 (F,h,w,1), depth_view {source: (1,h,w,1)})."""
+    -> (filtered (F,D,h,w,8), prob (F,D,h,w), depth_b2 (F,h,w,1), depth_view {source: (1,h,w,1)}).
+    filtered=False / fwd_prob=False: the caller reads no filtered cost volume / no forward probability or depth (None in their
+    place): the probability head and the soft-argmin then run over the reverse samples only."""
     D = int(depth_num)
     pairs = [(ref_i, v) for v in fwd] + [(v, ref_i) for v in rev]
     cv = build_cost_volumes(features, cams, pairs, D, depth_start, depth_interval, feature_index, hom)
-    tower = StackedUNet_prob({'data': cv}, is_training=True, reuse=AUTO_REUSE, independent_samples=True)
+    tower = StackedUNet({'data': cv}, is_training=True, reuse=AUTO_REUSE, independent_samples=True)
     del cv
-    prob = tower.get_output().squeeze(-1)                        # (B,D,h,w)
-    filt = tower.get_output_by_name('conv_b2_6_1')               # (B,D,h,w,8)
-    depth = ops.softargmin(prob, _scalar(depth_start), _scalar(depth_interval), groups=prob.shape[0])   # (B,h,w)
-    nf = len(fwd)
-    h, w = depth.shape[1:]
-    depth_view = {v: depth[nf + i].reshape(1, h, w, 1) for i, v in enumerate(rev)}
-    return filt[:nf], prob[:nf], depth[:nf].unsqueeze(-1), depth_view
+    nf, B = len(fwd), len(pairs)
+    s = tower.layers['conv_b2_6_1']                              # (B,D,h,w,8), still pending: the head forms it on load
+    lo = 0 if fwd_prob else nf
+    prob, depth = None, None
+    if B > lo:
+        # StackedUNet_prob's head conv_b2_6_2, over the samples whose probability is read
+        prob = tower.feed(s if lo == 0 else _samples(s, lo, B)).conv(3, 1, 1, relu=False, name='conv_b2_6_2').get_output()
+        prob = prob.squeeze(-1)                                  # (B - lo,D,h,w)
+        depth = ops.softargmin(prob, _scalar(depth_start), _scalar(depth_interval), groups=prob.shape[0])   # (B - lo,h,w)
+    filt = None
+    if filtered and nf:
+        filt = _samples(s, 0, nf)
+        filt = filt.materialize() if isinstance(filt, ops.LAZY) else filt
+    depth_view = {}
+    if rev:
+        h, w = depth.shape[1:]
+        depth_view = {v: depth[nf - lo + i].reshape(1, h, w, 1) for i, v in enumerate(rev)}
+    if not fwd_prob:
+        return filt, None, None, depth_view
+    return filt, prob[:nf], depth[:nf].unsqueeze(-1), depth_view
 
 
 def TVSNet_feature_extraction(images, view_i):

@@ -46,7 +46,8 @@ def _stacked_unet(net, with_prob_head):
         net.feed(*skip2).add(name=n('4_1')).deconv_bn(3, f * 2, 2, name=n('5_0'), defer_bn=True)
         skip1 = [n('5_0'), n('1_1')] + ([] if b == 0 else ['conv_b0_1_1'])
         net.feed(*skip1).add(name=n('5_1'), defer=True).deconv_bn(3, f, 2, name=n('6_0'), defer_bn=True)     # summed on load
-    net.feed('conv_b2_6_0', 'conv_b2_0_1').add(name='conv_b2_6_1')
+    # left pending: the 8 -> 1 head forms it on load (conv3d_8to1), any other reader materialises it (get_output_by_name)
+    net.feed('conv_b2_6_0', 'conv_b2_0_1').add(name='conv_b2_6_1', defer=True)
     if with_prob_head:
         net.conv(3, 1, 1, relu=False, name='conv_b2_6_2')
 
@@ -158,7 +159,13 @@ class ResNetDS2SPP(Network):
 
 class CostVolRefineNet(Network):
     """Refinement network over the photo / geo / probability / visual-hull volumes
-    (reference atvsnet.py:295-336)."""
+    (reference atvsnet.py:295-336).  Extension for callers that read less: head=False leaves out the probability head
+    global_refined_cost_vol; keep_residual=False (with 'residual_base' and head=False) does not write global_refine_3dconv6_1
+    itself, only global_refine_3dconv6_1_plus."""
+
+    def __init__(self, inputs, *args, head=True, keep_residual=True, **kwargs):
+        self.head, self.keep_residual = bool(head), bool(keep_residual)
+        super(CostVolRefineNet, self).__init__(inputs, *args, **kwargs)
 
     def setup(self):
         f = 8
@@ -183,7 +190,11 @@ class CostVolRefineNet(Network):
              .add(name=g + '3dconv5_1', defer=True)          # summed on load by the transposed convolution
              .deconv_bn(3, f, 2, name=g + '3dconv6_0', defer_bn=True))
         # extension: with an input 'residual_base' (the aggregated cost volume every source's residual is added to, model.py:438)
-        # the layer global_refine_3dconv6_1_plus = residual_base + global_refine_3dconv6_1 comes out of the same pass
-        (self.feed(g + '3dconv6_0', g + '3dconv0_1')
-             .add(name=g + '3dconv6_1', plus=('residual_base' if 'residual_base' in self.layers else None))
-             .conv(3, 1, 1, relu=False, name='global_refined_cost_vol'))
+        # the layer global_refine_3dconv6_1_plus = residual_base + global_refine_3dconv6_1 comes out of the same pass; without it
+        # the sum is left pending: the head forms it on load (conv3d_8to1), any other reader materialises it
+        plus = 'residual_base' if 'residual_base' in self.layers else None
+        # (the head reads the sum: keep_residual=False drops it only where no head runs)
+        self.feed(g + '3dconv6_0', g + '3dconv0_1').add(name=g + '3dconv6_1', plus=plus, defer=True,
+                                                       keep_sum=self.keep_residual or self.head or plus is None)
+        if self.head:
+            self.conv(3, 1, 1, relu=False, name='global_refined_cost_vol')

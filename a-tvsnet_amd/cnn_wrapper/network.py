@@ -206,13 +206,16 @@ class Network(object):
             bias = self._vec('%s/bias' % name, filters, raw) if biased else None
             return ops.conv(raw, name + '/kernel', w, stride=1, dilation=rate, padding='SAME', bias=bias, relu=relu,
                             groups=raw.shape[0], in_params=params, in_relu=in_relu)
+        if rank == 5 and kernel_size == 3 and filters == 1 and input.shape[-1] == 8 and strides == 1 and rate == 1 \
+                and padding == 'SAME' and not biased and not relu:
+            # the 8 -> 1 probability heads: HBM-bound, dedicated FMA kernel; a pending skip sum (conv_b2_6_1,
+            # global_refine_3dconv6_1) is formed while the kernel stages it
+            lazy = isinstance(input, ops.PendingSum) and (input.shape[0] == 1 or self.independent_samples)
+            x = input if lazy else self._bt(input, name)
+            wd = self.store.get('%s/kernel' % name, (3, 3, 3, 8, 1), x.device)
+            return ops.conv3d_8to1(x, wd, groups=x.shape[0])
         x = self._bt(input, name)
         G, cin = x.shape[0], x.shape[-1]
-        if rank == 5 and kernel_size == 3 and filters == 1 and cin == 8 and strides == 1 and rate == 1 \
-                and padding == 'SAME' and not biased and not relu:
-            # the 8 -> 1 probability heads: HBM-bound, dedicated FMA kernel
-            wd = self.store.get('%s/kernel' % name, (3, 3, 3, 8, 1), x.device)
-            return ops.conv3d_8to1(x, wd, groups=G)
         w = self._kernel('%s/kernel' % name, (kernel_size,) * (rank - 2) + (cin, filters))
         bias = self._vec('%s/bias' % name, filters, x) if biased else None
         return ops.conv(x, name + '/kernel', w, stride=strides, dilation=rate, padding=padding, bias=bias, relu=relu,
@@ -587,12 +590,13 @@ class Network(object):
         return ops.concat_channels([self._bt(t, name) for t in inputs])
 
     @layer
-    def add(self, inputs, name, defer=False, plus=None):
+    def add(self, inputs, name, defer=False, plus=None, keep_sum=True):
         '''tf.add_n (reference network.py:695-697).  Inputs whose batch norm is still pending (conv_bn /
         deconv_bn with defer_bn=True) are normalised inside the add kernel.  defer=True (extension): a sum of two or three
         whose consumer can add on load (conv_bn_siblings, deconv_bn) is handed over unformed.  plus (extension): the name of an
         input layer holding ONE sample; the layer `name + '_plus'` = that sample + this sum (per sample of the sum) is formed in
-        the same pass where the add kernel runs, else by add_n per sample.'''
+        the same pass where the add kernel runs, else by add_n per sample; keep_sum=False (with plus): the sum itself is wanted by
+        no one -- the layer may be None.'''
         inputs = [t.materialize() if isinstance(t, (ops.PendingSum, ops.LazySlice)) else t for t in inputs]
         if defer and plus is None and self.training and len(inputs) in (2, 3) and all(t.dim() == 5 for t in inputs):
             return ops.PendingSum([t if isinstance(t, ops.PendingBN) else self._bt(t, name) for t in inputs])
@@ -605,7 +609,7 @@ class Network(object):
             items = [t if isinstance(t, ops.PendingBN) else self._bt(t, name) for t in inputs]
             if base is None:
                 return ops.bn_add(items)
-            y, self.layers[name + '_plus'] = ops.bn_add(items, plus=base)
+            y, self.layers[name + '_plus'] = ops.bn_add(items, plus=base, keep_sum=keep_sum)
             return y
         y = ops.add_n([self._bt(t, name) for t in inputs])
         if base is not None:

@@ -37,6 +37,8 @@ class Config(object):
                    instead of a bn_add pass (needs prologue)
     norm3d         pending batch norms / two-term skip sums formed while conv_c16b, conv3d_b, conv3d_s2b stage their halo instead of
                    a bn_apply / bn_add pass (needs sum_on_load)
+    head_sum       the 8 -> 1 heads form a pending two-term skip sum while they stage it (conv3d_8to1), and bn_add_plus leaves out
+                   a sum nobody reads, instead of a bn_add pass / the written sum (needs sum_on_load; ATVS_HEAD_SUM=0: off)
     force_impl     None (automatic) | 'tiled' | 'gather': the generic convolution kernel to use
     fused_finalize batch-norm moments finished inside the convolution launch (measured slower: off)
     side_streams   independent small launches of one layer on side streams (parallel branches of a captured graph)
@@ -52,7 +54,8 @@ class Config(object):
         aanet_fused=os.environ.get('ATVS_AANET_FUSED', '1') != '0',
         bottleneck=os.environ.get('ATVS_BOTTLENECK', '1') != '0',
         prologue=True, sum_on_load=os.environ.get('ATVS_SUM_ON_LOAD', '1') != '0',
-        norm3d=os.environ.get('ATVS_NORM3D', '1') != '0', force_impl=None, fused_finalize=False,
+        norm3d=os.environ.get('ATVS_NORM3D', '1') != '0', head_sum=os.environ.get('ATVS_HEAD_SUM', '1') != '0',
+        force_impl=None, fused_finalize=False,
         side_streams=os.environ.get('ATVS_SIDE_STREAMS', '1') != '0')
 
     def __init__(self):

@@ -12,7 +12,7 @@ from .packing import (_Packed, _fold_cache, _pack_cache, _virt_cache, _xkind, co
     deconv_up_ok, pack_conv3d_b, pack_conv_c16, pack_conv_c16b, pack_conv_weights, pack_conv_weights_tiled, pack_conv_xp,
     pack_conv_xp_sibling, pack_deconv_up, planar_pieces_decode, planar_stride, planar_view, same_pad, split_on)
 from .geometry import tile_planes
-from .norm import LAZY, PendingBN, PendingSum, bn_apply, channel_stats, copy_channels, siblings_prologue_ok
+from .norm import LAZY, PendingBN, PendingSum, _param_groups, bn_apply, channel_stats, copy_channels, siblings_prologue_ok
 from .launch import (Fin, XPAIR_TAPS, _fin_counter, _from5, _stats_buffer, _to5, _xpair_virtual_kernel, conv1x1,
     conv1x1_ok, conv2d_lds, conv2d_lds_ok, conv_blocks, conv_launch, conv_tiled_launch, conv_xp_launch, pack_conv2d_lds,
     tiled_blocks, tiled_tile_y, xp_blocks)
@@ -272,7 +272,25 @@ def conv(x, key, w_host, stride=1, dilation=1, padding='SAME', explicit_pad=None
 
 def conv3d_8to1(x, w_dev, groups=None):
     """3x3x3 SAME convolution (D,H,W,8) -> (D,H,W,1) (groups=G: (G,D,H,W,8) -> (G,D,H,W,1)); w_dev: device tensor
-    of the TF kernel [3,3,3,8,1]."""
+    of the TF kernel [3,3,3,8,1].  x may be a PendingSum of two pending batch norms (a U-Net's last skip add): with
+    cfg.sum_on_load and cfg.head_sum the kernel forms the sum while it stages (atvs_conv3d_8to1_bn2, the bits of bn_add + this
+    head), otherwise it is materialised first."""
+    if isinstance(x, PendingSum):
+        pair = x.two_pending() if cfg.sum_on_load and cfg.head_sum and groups is not None else None
+        if pair is None:
+            x = x.materialize()
+        else:
+            a, b = pair
+            G = int(groups)
+            if a.raw.dim() != 5 or a.raw.shape[0] != G or a.raw.shape[-1] != 8 or w_dev.numel() != 216 \
+                    or _param_groups(a.params) != G:
+                raise ValueError('conv3d_8to1: a volume with 8 input channels and a [3,3,3,8,1] kernel')
+            _, D, H, W, _ = a.raw.shape
+            y = _new(a.raw, (G, D, H, W, 1))
+            if _dev_ok(a.raw, b.raw, a.params, b.params, w_dev):
+                _call('atvs_conv3d_8to1_bn2', _p(a.raw), _p(a.params), _p(b.raw), _p(b.params), int(a.relu) | (int(b.relu) << 1),
+                      _p(w_dev), _p(y), G, D, H, W, _stream())
+            return y
     x5, nsp = _to5(x, groups, 'conv3d_8to1 input')
     G, D, H, W, C = x5.shape
     if nsp != 3 or C != 8 or w_dev.numel() != 216:

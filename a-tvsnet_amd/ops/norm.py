@@ -131,6 +131,15 @@ class PendingBN(object):
             self._final = bn_apply(raw, self.params, self.relu)
         return self._final
 
+    def samples(self, lo, hi):
+        """Samples [lo, hi) of a batch-first layer, still pending (per-sample parameters (B,3,C) sliced alike)."""
+        if self._final is not None:
+            return self._final[lo:hi]
+        if self.planar:
+            raise ValueError('PendingBN.samples: a chunk-planar buffer is materialised first')
+        params = self.params[lo:hi] if self.params.dim() == 3 else self.params
+        return PendingBN(self.raw[lo:hi], params, self.relu)
+
     def prologue(self):
         """(tensor, (None, params, None, relu, False)): this layer as the normalise-on-load input of a convolution."""
         if self._final is not None:
@@ -169,6 +178,24 @@ class PendingSum(object):
             else:
                 self._final = add_n([t.materialize() if isinstance(t, PendingBN) else t for t in self.items])
         return self._final
+
+    def samples(self, lo, hi):
+        """Samples [lo, hi) of the sum, still unformed: a consumer of some samples only forms (or reads) only those."""
+        if self._final is not None:
+            return self._final[lo:hi]
+        return PendingSum([t.samples(lo, hi) if isinstance(t, PendingBN) else t[lo:hi] for t in self.items])
+
+    def two_pending(self):
+        """The (PendingBN, PendingBN) of a sum of two raw, channel-last, contiguous batch norms with one sample count -- the form
+        ops.conv3d_8to1 forms while it stages -- else None."""
+        if self._final is not None or len(self.items) != 2:
+            return None
+        a, b = self.items
+        if not all(isinstance(t, PendingBN) and t._final is None and not t.planar and t.raw.is_contiguous() for t in (a, b)):
+            return None
+        if _param_groups(a.params) != _param_groups(b.params):
+            return None
+        return a, b
 
     def prologue(self):
         if self._final is not None:
@@ -228,9 +255,10 @@ def siblings_prologue_ok(src):
     return False
 
 
-def bn_add(items, plus=None):
+def bn_add(items, plus=None, keep_sum=True):
     """Sum of 2 or 3 items, each a dense tensor or a PendingBN (normalised on the fly); dims without batch.
-    plus: ONE sample (the items' shape without the leading axis) -> (sum, plus + sum) from the same pass."""
+    plus: ONE sample (the items' shape without the leading axis) -> (sum, plus + sum) from the same pass; keep_sum=False: the
+    sum itself is not written (None in its place) when cfg.sum_on_load and cfg.head_sum allow it."""
     xs, ps, mask = [], [], 0
     for i, it in enumerate(items):
         if isinstance(it, PendingBN) and it._final is None and not it.planar:
@@ -251,10 +279,11 @@ def bn_add(items, plus=None):
     if plus is not None:
         if tuple(plus.shape) != tuple(out.shape[1:]) or out.shape[0] != G or not plus.is_contiguous():
             raise ValueError('bn_add: plus must be one contiguous sample of the items')
-        out2 = _new(out, out.shape)
+        out2 = out if not keep_sum and cfg.sum_on_load and cfg.head_sum else _new(out, out.shape)
+        out = None if out2 is out else out
         if _dev_ok(*(xs + [p for p in ps if p is not None] + [plus])):
             _call('atvs_bn_add_plus', _p(xs[0]), _p(ps[0]), _p(xs[1]), _p(ps[1]), _p(x2), _p(p2), _p(out), _p(plus), _p(out2), G,
-                  ctypes.c_long(out.numel() // C // G), C, int(mask), _stream())
+                  ctypes.c_long(out2.numel() // C // G), C, int(mask), _stream())
         return out, out2
     if _dev_ok(*(xs + [p for p in ps if p is not None])):
         _call('atvs_bn_add', _p(xs[0]), _p(ps[0]), _p(xs[1]), _p(ps[1]), _p(x2), _p(p2), _p(out), G,

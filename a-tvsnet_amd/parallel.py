@@ -253,7 +253,7 @@ class HipLocalStages(object):
         index = {v: i for i, v in enumerate(local)}
         feats = model.feature_extraction_batch(torch.cat([images[:, i] for i in local], 0).unsqueeze(0))
         filtered, _, _, dview = model.base_stage_batch(feats, cams, max_d, depth_start, depth_interval, fwd=fwd, rev=rev,
-                                                       ref_i=0, feature_index=index)
+                                                       ref_i=0, feature_index=index, fwd_prob=False)
         h, w = images.shape[2] // 4, images.shape[3] // 4
         return (filtered if fwd else None), {v: dview[v].reshape(h, w) for v in rev}
 
@@ -270,7 +270,7 @@ class HipLocalStages(object):
         index = {v: i for i, v in enumerate(local)}
         shallow = model.shallow_feature_batch(torch.cat([images[:, i] for i in local], 0).unsqueeze(0))
         cres, _ = model.refinement_batch(depth_init, dviews, prob_agg, cams, max_d, depth_start, depth_interval, list(fwd),
-                                         shallow, ref_id=0, shallow_index=index)
+                                         shallow, ref_id=0, shallow_index=index, prob=False)
         refined = torch.empty_like(cres)
         for b in range(len(fwd)):
             ops.add_n([cost_agg, cres[b]], out=refined[b])

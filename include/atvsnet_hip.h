@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 44
+#define ATVS_ABI_VERSION 45
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -506,6 +506,12 @@ int atvs_refine_stems_f32(const float* photo_raw, const float* geo, const float*
  * 242,336).  x (D,H,W,8); w = the TF kernel [3,3,3,8,1] (216 floats, device); y (D,H,W).
  * One output channel: packed-FMA kernel with four outputs per thread, not MFMA (conv8to1.hip). */
 int atvs_conv3d_8to1(const float* x, const float* w, float* y, int groups, int D, int H, int W, atvs_stream_t stream);
+/* The same head over the two-term sum atvs_bn_add would form, x = relu?(bn(x0; params0)) + relu?(bn(x1; params1)) (relu_mask bit i:
+ * ReLU after term i), formed while the kernel stages its halo: y is bit for bit atvs_bn_add(x0, params0, x1, params1) followed by
+ * atvs_conv3d_8to1, and the sum is never written (conv_b2_6_1 -> conv_b2_6_2, global_refine_3dconv6_1 -> global_refined_cost_vol).
+ * x0, x1 (groups,D,H,W,8) raw; params_i (groups,3,8).  Voxels outside the volume pad the SUM with 0.  relu_mask > 3: ATVS_ERR_ARG. */
+int atvs_conv3d_8to1_bn2(const float* x0, const float* params0, const float* x1, const float* params1, int relu_mask,
+                         const float* w, float* y, int groups, int D, int H, int W, atvs_stream_t stream);
 
 /* ------------------------------------------------------------------------- *
  * Batch norm with batch statistics, element-wise glue  (cnn_wrapper/network.py)
@@ -545,7 +551,7 @@ int atvs_bn_add(const float* x0, const float* params0, const float* x1, const fl
                 const float* params2, float* y, int groups, long rows, int C, int relu_mask, atvs_stream_t stream);
 /* atvs_bn_add that also writes y2 = base + y, base (rows,C) ONE sample shared by the `groups` samples (global_refine_3dconv6_1 and
  * refined_cost = filtered_cost + cost_residual of every source view, model.py:438, in one pass): y / y2 bit for bit atvs_bn_add /
- * atvs_add_n(base, y). */
+ * atvs_add_n(base, y).  y may be NULL: only y2 is written (a caller that reads no cost residual). */
 int atvs_bn_add_plus(const float* x0, const float* params0, const float* x1, const float* params1, const float* x2,
                      const float* params2, float* y, const float* base, float* y2, int groups, long rows, int C, int relu_mask,
                      atvs_stream_t stream);
