@@ -4,11 +4,9 @@ fusion entry point (after the hot path).
 
 import ctypes
 
-import torch
-
 from .. import _lib
 from .base import _Timed, _call, _dev_ok, _new, _p, _ptr_array, _stream, cfg
-from .packing import _Packed, _pack_cache, split_on
+from .packing import _abi_pack, split_on
 
 
 def aanet_combine(srs, xs, out=None):
@@ -31,25 +29,7 @@ def aanet_fused_ok(xs):
 def aanet_fused(xs, key, w_shared, w_unique):
     """AANet over the views xs (list of (D,H,W,8)): score convolutions + cross-view softmax + weighted sum in one launch ->
     (D,H,W,8).  w_shared / w_unique: host TF kernels [3,3,3,8,8]; key: pack-cache key."""
-    import numpy as np
-    dev = xs[0].device
-    ck = ('aanet_b', key, str(dev))
-    pk = _pack_cache.get(ck)
-    if pk is None:
-        L = _lib.lib()
-        pf = ctypes.c_long()
-        L.atvs_aanet_b_pack_size(ctypes.byref(pf))
-        packed = np.empty(pf.value, np.uint8)
-        ws = np.ascontiguousarray(w_shared, dtype=np.float32)
-        wu = np.ascontiguousarray(w_unique, dtype=np.float32)
-        rc = L.atvs_aanet_b_pack(ws.ctypes.data_as(ctypes.c_void_p), wu.ctypes.data_as(ctypes.c_void_p),
-                                 packed.ctypes.data_as(ctypes.c_void_p))
-        if rc:
-            raise RuntimeError('atvs_aanet_b_pack failed (%d)' % rc)
-        pk = _Packed()
-        pk.key, pk.tab = key, None
-        pk.wp = None if dev.type == 'meta' else torch.from_numpy(packed).to(dev)
-        _pack_cache[ck] = pk
+    pk = _abi_pack('aanet_b', key, (w_shared, w_unique), xs[0].device, 'aanet_b_pack', (), True)
     D, H, W, _ = xs[0].shape
     out = _new(xs[0], xs[0].shape)
     if _dev_ok(out, *xs):

@@ -177,6 +177,19 @@ class Stats(object):
         self.groups = 1         # independent samples: partial is (groups, blocks, 2, cpad), count per sample
 
 
+def _stats_buffer(ref, blocks, cpad, zero=False, groups=1):
+    f = torch.zeros if zero else torch.empty
+    return f((groups, blocks, 2, cpad), dtype=torch.float64, device=ref.device)
+
+
+def _stats(ref, rows, cpad, count, groups, fold=1):
+    """(Stats, its partial-sum buffer (groups, rows, 2, cpad)) of a launch with `rows` workgroups per sample."""
+    st = Stats()
+    st.partial = _stats_buffer(ref, int(rows), cpad, groups=groups)
+    st.blocks, st.cpad, st.count, st.groups, st.fold = int(rows), cpad, count, groups, fold
+    return st, st.partial
+
+
 _watch = {'tag': None, 'events': []}
 
 

@@ -7,15 +7,14 @@ import ctypes
 import torch
 
 from .. import _lib
-from .base import Stats, _Timed, _call, _dev_ok, _new, _p, _side_stream, _stream, cfg
-from .packing import (_Packed, _fold_cache, _pack_cache, _virt_cache, _xkind, conv_taps, deconv_s2_class_taps,
-    deconv_up_ok, pack_conv3d_b, pack_conv_c16, pack_conv_c16b, pack_conv_weights, pack_conv_weights_tiled, pack_conv_xp,
-    pack_conv_xp_sibling, pack_deconv_up, planar_pieces_decode, planar_stride, planar_view, same_pad, split_on)
+from .base import _Timed, _call, _dev_ok, _new, _p, _side_stream, _stats, _stats_buffer, _stream, cfg
+from .packing import (_abi_pack, _fold_cache, _virt_cache, _xkind, conv_taps, deconv_s2_class_taps, deconv_up_ok,
+    pack_conv3d_b, pack_conv_c16, pack_conv_c16b, pack_conv_weights, pack_conv_weights_tiled, pack_conv_xp,
+    pack_conv_xp_sibling, pack_deconv_up, planar_pieces_decode, planar_stride, planar_view, split_on)
 from .geometry import tile_planes
 from .norm import LAZY, PendingBN, PendingSum, _param_groups, bn_apply, channel_stats, copy_channels, siblings_prologue_ok
-from .launch import (Fin, XPAIR_TAPS, _fin_counter, _from5, _stats_buffer, _to5, _xpair_virtual_kernel, conv1x1,
-    conv1x1_ok, conv2d_lds, conv2d_lds_ok, conv_blocks, conv_launch, conv_tiled_launch, conv_xp_launch, pack_conv2d_lds,
-    tiled_blocks, tiled_tile_y, xp_blocks)
+from .launch import (Fin, XPAIR_TAPS, _fin_counter, _from5, _to5, _xpair_virtual_kernel, conv1x1, conv2d_lds, conv_blocks,
+    conv_launch, conv_plan, conv_tiled_launch, conv_xp_launch, pack_conv2d_lds, tiled_blocks, tiled_tile_y, xp_blocks)
 
 
 def conv(x, key, w_host, stride=1, dilation=1, padding='SAME', explicit_pad=None, bias=None, residual=None,
@@ -27,106 +26,34 @@ def conv(x, key, w_host, stride=1, dilation=1, padding='SAME', explicit_pad=None
     w_host: TF-layout numpy kernel [k.., Cin, Cout]; `key` names it for the pack cache.
     padding: 'SAME' | 'VALID'; explicit_pad = (before, after) per spatial axis overrides it
     (bottleneck conv2, network.py:589-595).  in_params (G,3,Cin) [+ in_relu]: x is a raw convolution output whose
-    batch norm is applied on load (only where the kernel of this shape supports it: norm_on_load_2d_ok / norm_on_load_3d_ok;
-    a 3-D shape without such a form gets the normalised tensor from a bn_apply pass here).  in_sum = (x1, params1 | None,
+    batch norm is applied on load (only where the kernel of this shape supports it: conv_plan decides the kernel family and
+    this; a 3-D shape without such a form gets the normalised tensor from a bn_apply pass here, a 2-D one is refused).  in_sum = (x1, params1 | None,
     relu1) (3-D 16 -> 16 only): the input is x [normalised by in_params] + x1 [normalised by params1], formed on load.
     Returns y or (y, Stats).
     """
     x5, nsp = _to5(x, groups, 'conv input')
-    G = x5.shape[0]
-    ks = (1,) * (3 - nsp) + tuple(int(k) for k in w_host.shape[:nsp])
-    ins = tuple(x5.shape[1:4])
-    pads, outs = [], []
-    for i in range(3):
-        if ks[i] == 1 and i < 3 - nsp:
-            pads.append(0)
-            outs.append(1)
-            continue
-        ax = i - (3 - nsp)
-        if explicit_pad is not None:
-            pb, pe = explicit_pad[ax]
-            pads.append(pb)
-            outs.append((ins[i] + pb + pe - ((ks[i] - 1) * dilation + 1)) // stride + 1)
-        elif padding == 'SAME':
-            pb, o = same_pad(ins[i], ks[i], stride, dilation)
-            pads.append(pb)
-            outs.append(o)
-        else:
-            pads.append(0)
-            outs.append((ins[i] - ((ks[i] - 1) * dilation + 1)) // stride + 1)
-    taps = conv_taps(ks, dilation, pads)
+    G, ins = x5.shape[0], tuple(x5.shape[1:4])
     cin, cout = int(w_host.shape[-2]), int(w_host.shape[-1])
     if cin != x5.shape[4]:
         raise ValueError('conv %s: input has %d channels, kernel wants %d' % (key, x5.shape[4], cin))
-    y5 = None
-    if out is not None:
-        y5, _ = _to5(out, groups, 'conv output buffer')
-        if tuple(y5.shape[:4]) != (G,) + tuple(outs):
-            raise ValueError('conv %s: output buffer %s does not match %s' % (key, tuple(y5.shape), (G,) + tuple(outs)))
+    y5 = _to5(out, groups, 'conv output buffer')[0] if out is not None else None
+    ks = tuple(int(k) for k in w_host.shape[:nsp])
+    lazy = 'sum' if in_sum is not None else 'bn' if in_params is not None else None
+    plan = conv_plan(ins[3 - nsp:], ks, cin, cout, stride, dilation,
+                     padding if explicit_pad is None else explicit_pad, bias is not None, residual is not None,
+                     plane_bias is not None, None if y5 is None else (int(y5.shape[-1]), int(y_coff)), lazy)
+    fam, outs = plan.family, plan.outs
+    M = outs[0] * outs[1] * outs[2]
+    if y5 is not None and tuple(y5.shape[:4]) != (G,) + outs:
+        raise ValueError('conv %s: output buffer %s does not match %s' % (key, tuple(y5.shape), (G,) + outs))
     res5 = _to5(residual, groups, 'residual')[0] if residual is not None else None
     if plane_bias is not None:
         pb_shape = ((G,) if groups is not None else ()) + (outs[1], outs[2], 3 * cout)
         if tuple(plane_bias.shape) != pb_shape:
             raise ValueError('conv %s: plane_bias %s, expected %s' % (key, tuple(plane_bias.shape), pb_shape))
-    M = outs[0] * outs[1] * outs[2]
-
-    # ---- 2-D, 3x3, stride 1, SAME on wide channels: the LDS-tiled tower kernel
-    if nsp == 2 and stride == 1 and ks == (1, 3, 3) and tuple(pads[1:]) == (dilation, dilation) \
-            and tuple(outs) == ins and plane_bias is None \
-            and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0)) \
-            and conv2d_lds_ok(cin, cout, dilation, ins[1], ins[2]):
-        r = conv2d_lds(x5[:, 0], key, w_host, dilation, bias, None if res5 is None else res5[:, 0], relu, want_stats,
-                       None if y5 is None else y5[:, 0], y_coff, in_params, in_relu)
-        y4, st = r if want_stats else (r, None)
-        y = out if out is not None else _from5(y4.unsqueeze(1), nsp, groups)
-        return (y, st) if want_stats else y
-    # ---- 2-D, 3x3, stride 2 behind explicit symmetric padding 1 (the strided conv2 of a residual unit's first block)
-    if nsp == 2 and stride == 2 and dilation == 1 and ks == (1, 3, 3) and explicit_pad is not None \
-            and tuple(tuple(int(v) for v in pr) for pr in explicit_pad) == ((1, 1), (1, 1)) and ins[1] % 2 == 0 and ins[2] % 2 == 0 \
-            and residual is None and plane_bias is None and in_params is None and y5 is None and cfg.force_impl is None \
-            and cfg.conv2d_lds and split_on('c2b') and ins[1] >= 16 and ins[2] >= 32 \
-            and bool(_lib.lib().atvs_conv2d_b_s2_supported(int(cin), int(cout))):
-        pk = pack_conv2d_lds(key, w_host, x.device)
-        if pk.kind == 'b':
-            Ho, Wo = ins[1] // 2, ins[2] // 2
-            y4 = _new(x, (G, Ho, Wo, cout))
-            st, sbuf = None, None
-            if want_stats:
-                rows = int(_lib.lib().atvs_conv2d_lds_rows(Ho, Wo, cout))
-                sbuf = torch.empty((G, rows, 2, cout), dtype=torch.float64, device=x.device)
-                st = Stats()
-                st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, cout, Ho * Wo, G
-            if _dev_ok(x5, y4, bias):
-                with _Timed(key, (1, ins[1], ins[2], cin), cout, G):
-                    _call('atvs_conv2d_b_s2_f32', _p(x5), _p(pk.wp), _p(bias), _p(y4),
-                          ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G, ins[1], ins[2], cin, cout,
-                          int(bool(relu)), _stream())
-            y = _from5(y4.unsqueeze(1), nsp, groups)
-            return (y, st) if want_stats else y
-    # ---- 2-D 1x1, stride 1: the LDS-staged GEMM kernel
-    if nsp == 2 and stride == 1 and ks == (1, 1, 1) and plane_bias is None and conv1x1_ok(cin, cout) \
-            and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0)):
-        r = conv1x1(x5[:, 0], key, w_host, bias, None if res5 is None else res5[:, 0], relu, want_stats,
-                    None if y5 is None else y5[:, 0], y_coff, in_params, in_relu)
-        y4, st = r if want_stats else (r, None)
-        y = out if out is not None else _from5(y4.unsqueeze(1), nsp, groups)
-        return (y, st) if want_stats else y
-    if (in_params is not None or in_sum is not None) and nsp == 2:
-        raise ValueError('conv %s: no normalise-on-load form for this shape' % (key,))
-    # 3-D: which split-operand kernel (if any) takes this shape, and does it form a lazy input on load?
-    c16_shape = nsp == 3 and stride == 1 and dilation == 1 and ks == (3, 3, 3) and tuple(pads) == (1, 1, 1) \
-        and residual is None and plane_bias is None and cfg.conv_c16 and cfg.force_impl is None \
-        and tuple(outs) == ins and ins[2] >= 12 and 4.0 * M * (cout if y5 is None else y5.shape[-1]) < 2.0 ** 32 \
-        and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0))
-    b3 = split_on('c3b') and cin % 16 == 0 and cout in (32, 64) and bool(_lib.lib().atvs_conv3d_b_supported(int(cin), int(cout)))
-    b16 = split_on('c16b') and cin in (8, 16) and cout == 16
-    s2b = nsp == 3 and stride == 2 and dilation == 1 and ks == (3, 3, 3) and padding == 'SAME' and explicit_pad is None \
-        and split_on('s2b') and cfg.conv_c16 and cfg.force_impl is None and residual is None and plane_bias is None \
-        and bool(_lib.lib().atvs_conv3d_s2b_supported(int(cin), int(cout))) and outs[2] >= 8 \
-        and 4.0 * M * (cout if y5 is None else y5.shape[-1]) < 2.0 ** 32 \
-        and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0))
-    lazy_ok = cfg.sum_on_load and cfg.norm3d and ((c16_shape and ((b3 and in_sum is None) or (b16 and cin == 16))) or (s2b and in_sum is None))
-    if (in_params is not None or in_sum is not None) and not lazy_ok:
+    if lazy and not plan.on_load:
+        if nsp == 2:
+            raise ValueError('conv %s: no normalise-on-load form for this shape' % (key,))
         # no form of this shape forms its input on load: the passes the lazy input stands for, then the plain convolution
         if in_sum is not None:
             a = PendingBN(x, in_params, in_relu) if in_params is not None else x
@@ -136,136 +63,96 @@ def conv(x, key, w_host, stride=1, dilation=1, padding='SAME', explicit_pad=None
             x = bn_apply(x, in_params, in_relu, out=_new(x, x.shape))
         x5, _ = _to5(x, groups, 'conv input')
         in_params, in_sum = None, None
+    lib = _lib.lib()
+    st = sbuf = None
 
-    # ---- 3-D, 3x3x3, 1-2 input channels -> 8: the refinement stems, HBM-bound FMA kernel
-    if nsp == 3 and stride == 1 and dilation == 1 and ks == (3, 3, 3) and tuple(pads) == (1, 1, 1) and cout == 8 \
-            and cin <= 2 and bias is None and residual is None and cfg.stem and cfg.force_impl is None \
-            and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0)):
-        import numpy as np
-        ck = ('stem', key, str(x.device))
-        wd = _pack_cache.get(ck)
-        if wd is None:
-            wd = _Packed()
-            wd.key, wd.tab, wd.cin, wd.cout = key, None, cin, cout
-            wd.wp = None if x.is_meta else torch.from_numpy(np.ascontiguousarray(w_host, dtype=np.float32)).to(x.device)
-            _pack_cache[ck] = wd
-        if y5 is None:
-            y5 = _new(x, (G,) + tuple(outs) + (8,))
-        st, sbuf = None, None
+    if fam in ('conv2d_lds', 'conv1x1'):
+        args = (bias, None if res5 is None else res5[:, 0], relu, want_stats, None if y5 is None else y5[:, 0], y_coff, in_params,
+                in_relu)
+        r = conv2d_lds(x5[:, 0], key, w_host, dilation, *args) if fam == 'conv2d_lds' else conv1x1(x5[:, 0], key, w_host, *args)
+        y4, st = r if want_stats else (r, None)
+        y5 = y4.unsqueeze(1)
+    elif fam == 'conv2d_b_s2':
+        pk = pack_conv2d_lds(key, w_host, x.device)
+        Ho, Wo = outs[1:]
+        y5 = _new(x, (G, 1, Ho, Wo, cout))
         if want_stats:
-            rows = int(_lib.lib().atvs_conv_stem_rows(*outs))
-            sbuf = _stats_buffer(x, rows, 16, groups=G)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, 16, M, G
+            st, sbuf = _stats(x, lib.atvs_conv2d_lds_rows(Ho, Wo, cout), cout, Ho * Wo, G)
+        if _dev_ok(x5, y5, bias):
+            with _Timed(key, (1, ins[1], ins[2], cin), cout, G):
+                _call('atvs_conv2d_b_s2_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), G, ins[1], ins[2], cin, cout,
+                      int(bool(relu)), _stream())
+    elif fam == 'stem':
+        wd = _abi_pack('stem', key, w_host, x.device, None, None, cin=cin, cout=cout)
+        if y5 is None:
+            y5 = _new(x, (G,) + outs + (8,))
+        if want_stats:
+            st, sbuf = _stats(x, lib.atvs_conv_stem_rows(*outs), 16, M, G)
         if _dev_ok(x5, y5, plane_bias):
             with _Timed(key, x5.shape[1:], 8, G):
-                _call('atvs_conv_stem_f32', _p(x5), _p(wd.wp), _p(plane_bias), _p(y5),
-                      ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G, outs[0], outs[1],
-                      outs[2], cin, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-        y = out if out is not None else _from5(y5, nsp, groups)
-        return (y, st) if want_stats else y
-
-    # ---- 3-D, 3x3x3, 8 / 16 / 32 -> 16 and 16..64 -> 32 channels: one workgroup per CU, fully unrolled (the half- and
-    # quarter-resolution U-Net layers, the AANet modules' shared | unique convolution)
-    if c16_shape and ((cout == 16 and cin in (8, 16, 32)) or (cout == 32 and cin in (16, 32, 48, 64)) or b3):
-        pk = pack_conv3d_b(key, w_host, x.device) if b3 else \
-            pack_conv_c16b(key, w_host, x.device) if b16 else pack_conv_c16(key, w_host, x.device)
+                _call('atvs_conv_stem_f32', _p(x5), _p(wd.wp), _p(plane_bias), _p(y5), _p(sbuf), G, outs[0], outs[1], outs[2],
+                      cin, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
+    elif fam in ('c16', 'c16b', 'c16b_sum', 'c3b', 'c3b_norm', 's2b', 's2b_norm'):
+        # one workgroup per CU: the half- and quarter-resolution U-Net layers, the AANet modules' shared | unique convolution,
+        # the stride-2 encoders below half resolution (s2b: the launch takes the input grid)
+        s2 = fam.startswith('s2b')
+        pk = pack_conv3d_b(key, w_host, x.device, 's2b' if s2 else 'b') if fam[:2] in ('s2', 'c3') else \
+            pack_conv_c16b(key, w_host, x.device) if fam.startswith('c16b') else pack_conv_c16(key, w_host, x.device)
         if y5 is None:
-            y5 = _new(x, (G,) + tuple(outs) + (cout,))
-        st, sbuf = None, None
+            y5 = _new(x, (G,) + outs + (cout,))
         if want_stats:
-            rows = int(_lib.lib().atvs_conv_c16_grid(outs[0], outs[1], outs[2], G))
-            sbuf = _stats_buffer(x, rows, cout, groups=G)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, cout, M, G
+            st, sbuf = _stats(x, (lib.atvs_conv3d_s2b_grid if s2 else lib.atvs_conv_c16_grid)(*(outs + (G,))), cout, M, G)
         if _dev_ok(x5, y5, bias):
+            grid = (G,) + (ins if s2 else outs) + (cin,)
+            tail = (int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
             with _Timed(key, x5.shape[1:], cout, G):
-                if b3 and in_params is not None:
-                    _call('atvs_conv3d_b_norm_f32', _p(x5), _p(in_params), int(bool(in_relu)), _p(pk.wp), _p(bias), _p(y5), _p(sbuf),
-                          G, outs[0], outs[1], outs[2], cin, cout, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-                elif b3:
-                    _call('atvs_conv3d_b_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), G, outs[0], outs[1], outs[2], cin,
-                          cout, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-                elif b16 and (in_params is not None or in_sum is not None):
+                if fam in ('c3b_norm', 's2b_norm'):
+                    _call('atvs_conv3d_s2b_norm_f32' if s2 else 'atvs_conv3d_b_norm_f32', _p(x5), _p(in_params), int(bool(in_relu)),
+                          _p(pk.wp), _p(bias), _p(y5), _p(sbuf), *(grid + (cout,) + tail))
+                elif fam == 'c16b_sum':
                     x1, p1, r1 = in_sum if in_sum is not None else (None, None, False)
-                    mask = (1 if in_relu else 0) | (2 if r1 else 0)
-                    _call('atvs_conv_c16b_sum_f32', _p(x5), _p(in_params), _p(x1), _p(p1), int(mask), _p(pk.wp), _p(bias), _p(y5),
-                          _p(sbuf), G, outs[0], outs[1], outs[2], cin, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-                elif b16:
-                    _call('atvs_conv_c16b_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), G, outs[0], outs[1], outs[2], cin,
-                          int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
+                    _call('atvs_conv_c16b_sum_f32', _p(x5), _p(in_params), _p(x1), _p(p1), (1 if in_relu else 0) | (2 if r1 else 0),
+                          _p(pk.wp), _p(bias), _p(y5), _p(sbuf), *(grid + tail))
+                elif fam == 'c16b':
+                    _call('atvs_conv_c16b_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), *(grid + tail))
                 else:
-                    _call('atvs_conv_c16_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), G, outs[0], outs[1], outs[2], cin,
-                          cout, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-        y = out if out is not None else _from5(y5, nsp, groups)
-        return (y, st) if want_stats else y
-
-    # ---- 3-D, 3x3x3, stride 2, SAME, 16 k -> 32 / 64 channels: the U-Net encoders below half resolution on split-fp16 operands
-    if s2b:
-        pk = pack_conv3d_b(key, w_host, x.device, kind='s2b')
+                    _call({'c16': 'atvs_conv_c16_f32', 'c3b': 'atvs_conv3d_b_f32', 's2b': 'atvs_conv3d_s2b_f32'}[fam], _p(x5),
+                          _p(pk.wp), _p(bias), _p(y5), _p(sbuf), *(grid + (cout,) + tail))
+    else:
+        # the generic kernels: x-pair (one workgroup per CU | LDS-tiled over a virtual kernel), LDS-tiled, gather
+        taps = conv_taps((1,) * (3 - nsp) + ks, dilation, plan.pads)
+        tile_y = tiled_tile_y(ins[1], ins[2], cout) if fam != 'gather' else 0
+        if fam == 'xp':
+            pk = pack_conv_xp(key, w_host, x.device)
+            blocks = xp_blocks(outs[0], outs[1], outs[2], G)
+        elif fam == 'gather':
+            pk = pack_conv_weights(key, w_host, taps, False, x.device)
+            blocks, tm = conv_blocks(M, pk.ntiles, groups=G)
+        else:
+            if fam == 'xpair_tiled':
+                tile_y = 4 if cin > 8 else tile_y
+                pk = pack_conv_weights_tiled(key, _xpair_virtual_kernel(key, w_host), XPAIR_TAPS, False, x.device, tile_y, True)
+                pk.cout = 8
+            else:
+                pk = pack_conv_weights_tiled(key, w_host, taps, False, x.device, tile_y)
+            blocks = tiled_blocks(outs[0], outs[1], outs[2], tile_y, pk.cin, pk.cout, fam == 'xpair_tiled', G)
         if y5 is None:
-            y5 = _new(x, (G,) + tuple(outs) + (cout,))
-        st, sbuf = None, None
+            y5 = _new(x, (G,) + outs + (pk.cout,))
         if want_stats:
-            rows = int(_lib.lib().atvs_conv3d_s2b_grid(outs[0], outs[1], outs[2], G))
-            sbuf = _stats_buffer(x, rows, cout, groups=G)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, cout, M, G
-        if _dev_ok(x5, y5, bias):
-            with _Timed(key, x5.shape[1:], cout, G):
-                if in_params is not None:
-                    _call('atvs_conv3d_s2b_norm_f32', _p(x5), _p(in_params), int(bool(in_relu)), _p(pk.wp), _p(bias), _p(y5),
-                          _p(sbuf), G, ins[0], ins[1], ins[2], cin, cout, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-                else:
-                    _call('atvs_conv3d_s2b_f32', _p(x5), _p(pk.wp), _p(bias), _p(y5), _p(sbuf), G, ins[0], ins[1], ins[2], cin,
-                          cout, int(y5.shape[-1]), int(y_coff), int(bool(relu)), _stream())
-        y = out if out is not None else _from5(y5, nsp, groups)
-        return (y, st) if want_stats else y
-
-    tile_y = 0
-    if nsp == 3 and stride == 1 and dilation == 1 and ks == (3, 3, 3) and tuple(pads) == (1, 1, 1) \
-            and tuple(outs) == ins:
-        tile_y = tiled_tile_y(ins[1], ins[2], cout)
-    xpair = bool(tile_y) and cfg.xpair and cout == 8 and (ins[2] >= 24 or cfg.force_impl == 'tiled') \
-        and (y5 is None or (y5.shape[-1] % 4 == 0 and y_coff % 4 == 0))
-    xp1w = xpair and cfg.xp1w and cin % 8 == 0 and residual is None
-    if xp1w:
-        pk = pack_conv_xp(key, w_host, x.device)
-    elif xpair:
-        tile_y = 4 if cin > 8 else tile_y
-        pk = pack_conv_weights_tiled(key, _xpair_virtual_kernel(key, w_host), XPAIR_TAPS, False, x.device, tile_y, True)
-        pk.cout = 8
-    elif tile_y:
-        pk = pack_conv_weights_tiled(key, w_host, taps, False, x.device, tile_y)
-    else:
-        pk = pack_conv_weights(key, w_host, taps, False, x.device)
-    if y5 is None:
-        y5 = _new(x, (G,) + tuple(outs) + (pk.cout,))
-    if xp1w:
-        blocks, tm = xp_blocks(outs[0], outs[1], outs[2], G), 0
-    elif tile_y:
-        blocks, tm = tiled_blocks(outs[0], outs[1], outs[2], tile_y, pk.cin, pk.cout, xpair, G), 0
-    else:
-        blocks, tm = conv_blocks(M, pk.ntiles, groups=G)
-    st = None
-    sbuf = None
-    if want_stats:
-        sbuf = _stats_buffer(x, blocks, pk.ntiles * 16, groups=G)
-        st = Stats()
-        st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, blocks, pk.ntiles * 16, M, G
-    if xp1w:
-        conv_xp_launch(x5, pk, y5, y_coff, bias, relu, sbuf, plane_bias)
-    elif tile_y:
-        fin = None
-        if want_stats and cfg.fused_finalize and pk.cout <= 64 and not x.is_meta and G == 1:
-            fin = Fin()
-            fin.counter, fin.params, fin.stats = _fin_counter(x.device), _new(x, (3, pk.cout)), sbuf
-            fin.rows, fin.arrivals, fin.channels, fin.fold, fin.count = blocks, blocks, pk.cout, 1, M
-            st.params = fin.params
-        conv_tiled_launch(x5, pk, y5, 1, (0, 0, 0), y_coff, tile_y, bias, res5, relu, sbuf, plane_bias, xpair=xpair,
-                          fin=fin)
-    else:
-        conv_launch(x5, pk, y5, outs, stride, 1, (0, 0, 0), y_coff, bias, res5, relu, sbuf, tm, plane_bias, pads[0])
+            st, sbuf = _stats(x, blocks, pk.ntiles * 16, M, G)
+        if fam == 'xp':
+            conv_xp_launch(x5, pk, y5, y_coff, bias, relu, sbuf, plane_bias)
+        elif fam == 'gather':
+            conv_launch(x5, pk, y5, outs, stride, 1, (0, 0, 0), y_coff, bias, res5, relu, sbuf, tm, plane_bias, plan.pads[0])
+        else:
+            fin = None
+            if want_stats and cfg.fused_finalize and pk.cout <= 64 and not x.is_meta and G == 1:
+                fin = Fin()
+                fin.counter, fin.params, fin.stats = _fin_counter(x.device), _new(x, (3, pk.cout)), sbuf
+                fin.rows, fin.arrivals, fin.channels, fin.fold, fin.count = blocks, blocks, pk.cout, 1, M
+                st.params = fin.params
+            conv_tiled_launch(x5, pk, y5, 1, (0, 0, 0), y_coff, tile_y, bias, res5, relu, sbuf, plane_bias,
+                              xpair=fam == 'xpair_tiled', fin=fin)
     y = out if out is not None else _from5(y5, nsp, groups)
     return (y, st) if want_stats else y
 
@@ -436,9 +323,7 @@ def conv_split_into_plane(sv, key, w_host, buf, plane, planar):
     if pk.kind != 'xb':
         raise ValueError('conv_split_into_plane: the split-fp16 x-pair kernel only')
     blocks = xp_blocks(D, H, W, B)
-    sbuf = _stats_buffer(buf, blocks, 16, groups=B)
-    st = Stats()
-    st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, blocks, 16, D * H * W, B
+    st, sbuf = _stats(buf, blocks, 16, D * H * W, B)
     if sv.pieces:
         conv_xp_launch(sv._var, pk, buf, 0, None, False, sbuf, pb, ldy=8, y_gstride=K * pstride, y_off=int(plane) * pstride,
                        planar=sv.planar, pieces=True)
@@ -459,30 +344,16 @@ def refine_stems(photo_raw, geo_var, geo_plane_bias, prob, hull, key, w_geo, w_p
     if planar_out is not None and (tuple(planar_out.shape) != (B, 4, planar_stride(D, H, W)) or not planar_out.is_contiguous()):
         raise ValueError('refine_stems: planar_out must be a contiguous (B, 4, planar_stride(D,h,w)) buffer')
     photo_raw = geo_var if planar_out is not None else photo_raw      # (device / meta reference below)
-    ck = ('stems', key, str(photo_raw.device))
-    pk = _pack_cache.get(ck)
-    if pk is None:
-        packed = np.empty(27 * 4 * 8, np.float32)
-        args = [np.ascontiguousarray(a, dtype=np.float32) for a in (w_geo, w_prob, w_hull)]
-        if args[0].shape != (3, 3, 3, 2, 8) or args[1].shape != (3, 3, 3, 1, 8) or args[2].shape != (3, 3, 3, 1, 8):
-            raise ValueError('refine_stems: kernels [3,3,3,2,8], [3,3,3,1,8], [3,3,3,1,8]')
-        rc = _lib.lib().atvs_refine_stems_pack(*[a.ctypes.data_as(ctypes.c_void_p) for a in args],
-                                               packed.ctypes.data_as(ctypes.c_void_p))
-        if rc:
-            raise RuntimeError('atvs_refine_stems_pack failed (%d)' % rc)
-        pk = _Packed()
-        pk.key, pk.tab, pk.cin, pk.cout = key, None, 4, 24
-        pk.wp = None if photo_raw.is_meta else torch.from_numpy(packed).to(photo_raw.device)
-        _pack_cache[ck] = pk
+    if tuple(np.shape(w_geo)) != (3, 3, 3, 2, 8) or tuple(np.shape(w_prob)) != (3, 3, 3, 1, 8) \
+            or tuple(np.shape(w_hull)) != (3, 3, 3, 1, 8):
+        raise ValueError('refine_stems: kernels [3,3,3,2,8], [3,3,3,1,8], [3,3,3,1,8]')
+    pk = _abi_pack('stems', key, (w_geo, w_prob, w_hull), photo_raw.device, 'refine_stems_pack', 27 * 4 * 8, cin=4, cout=24)
     buf = _new(photo_raw, (B, D, H, W, 32)) if planar_out is None else planar_out
-    rows = int(_lib.lib().atvs_conv_stem_rows(D, H, W))
-    st = Stats()
-    st.partial = torch.empty((B, rows, 2, 24), dtype=torch.float64, device=photo_raw.device)
-    st.blocks, st.cpad, st.count, st.groups = rows, 24, D * H * W, B
+    st, sbuf = _stats(photo_raw, _lib.lib().atvs_conv_stem_rows(D, H, W), 24, D * H * W, B)
     if _dev_ok(photo_raw, geo_var, geo_plane_bias, prob, hull, buf):
         with _Timed(key, (D, H, W, 4), 24, B):
             _call('atvs_refine_stems_f32', _p(photo_raw if planar_out is None else None), _p(geo_var), _p(geo_plane_bias),
-                  _p(prob), _p(hull), _p(pk.wp), _p(buf), ctypes.c_void_p(st.partial.data_ptr()), B, D, H, W,
+                  _p(prob), _p(hull), _p(pk.wp), _p(buf), _p(sbuf), B, D, H, W,
                   ctypes.c_long(planar_stride(D, H, W) if planar_out is not None else 0), _stream())
     return buf, st
 
@@ -527,10 +398,8 @@ def conv_siblings(x, key, w_host, key2, w2_host, plane_bias=None, plane_bias2=No
     lead = () if groups is None else (G,)
     y, y2 = _new(x, lead + (D, H, W, 8)), _new(x, lead + (D2, H2, W2, 16))
     blocks = xp_blocks(D, H, W, G)
-    sbuf, sbuf2 = _stats_buffer(x, blocks, 16, groups=G), _stats_buffer(x, blocks, 16, groups=G)
-    st, st2 = Stats(), Stats()
-    st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, blocks, 16, D * H * W, G
-    st2.partial, st2.blocks, st2.cpad, st2.count, st2.groups = sbuf2, blocks, 16, D2 * H2 * W2, G
+    st, sbuf = _stats(x, blocks, 16, D * H * W, G)
+    st2, sbuf2 = _stats(x, blocks, 16, D2 * H2 * W2, G)
     if plane_bias is not None and tuple(plane_bias.shape) != lead + (H, W, 24):
         raise ValueError('conv_siblings %s: plane_bias %s' % (key, tuple(plane_bias.shape)))
     if plane_bias2 is not None and tuple(plane_bias2.shape) != lead + (H2, W2, 48):
@@ -632,11 +501,7 @@ def conv3d_transpose_s2(x, key, w_host, relu=False, want_stats=False, groups=Non
         pk = pack_deconv_up(key, w_host, x.device, '_b' if split else '')
         grid_fn = _lib.lib().atvs_deconv_up_b_grid if split else _lib.lib().atvs_deconv_up_grid
         blocks = int(grid_fn(int(D), int(H), int(W), int(cout), int(G)))
-        st, sbuf = None, None
-        if want_stats:
-            sbuf = _stats_buffer(x, blocks, 16, groups=G)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, blocks, 16, 8 * M, G
+        st, sbuf = _stats(x, blocks, 16, 8 * M, G) if want_stats else (None, None)
         if terms is not None and not split:
             raise RuntimeError('deconv_sum_ok admitted a sum the split-operand kernel does not take')
         if _dev_ok(x5, y5, *[t for tr in (terms or []) for t in tr[:2]]):
@@ -659,11 +524,7 @@ def conv3d_transpose_s2(x, key, w_host, relu=False, want_stats=False, groups=Non
         # the 64 -> 32 layer (conv_b*_4_0) as two 16-channel launches of the split-fp16 kernel into the halves of y
         import numpy as np
         blocks = int(_lib.lib().atvs_deconv_up_b_grid(int(D), int(H), int(W), 16, int(G)))
-        st, sbuf = None, None
-        if want_stats:
-            sbuf = _stats_buffer(x, blocks, 32, groups=G)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, blocks, 32, 8 * M, G
+        st, sbuf = _stats(x, blocks, 32, 8 * M, G) if want_stats else (None, None)
         w = np.asarray(w_host)
         for h in range(2):
             pk = pack_deconv_up((key, 'half', h), np.ascontiguousarray(w[:, :, :, 16 * h:16 * h + 16, :]), x.device, '_b')
@@ -689,9 +550,7 @@ def conv3d_transpose_s2(x, key, w_host, relu=False, want_stats=False, groups=Non
         if want_stats and in_kernel:
             # one statistics buffer per launch (class group), each (G, blocks, 2, cpad); bn_finalize folds the
             # launches' columns through `fold` on a buffer laid out (G, nl * blocks, 2, cpad)
-            sall = torch.empty((G, nl * blocks, 2, nt * 16), dtype=torch.float64, device=x.device)
-            st = Stats()
-            st.partial, st.blocks, st.cpad, st.count, st.fold, st.groups = sall, blocks * nl, nt * 16, 8 * M, per, G
+            st, _ = _stats(x, nl * blocks, nt * 16, 8 * M, G, fold=per)
             sbufs = [_stats_buffer(x, blocks, nt * 16, groups=G) for _ in range(nl)] if (nl > 1 and G > 1) else None
         fin = None
         if st is not None and cfg.fused_finalize and cout <= 64 and not x.is_meta and G == 1:
@@ -734,9 +593,7 @@ def conv3d_transpose_s2(x, key, w_host, relu=False, want_stats=False, groups=Non
     st = None
     sbufs = None
     if want_stats:
-        st = Stats()
-        st.partial = torch.empty((G, blocks * 8, 2, cpad), dtype=torch.float64, device=x.device)
-        st.blocks, st.cpad, st.count, st.groups = blocks * 8, cpad, 8 * M, G
+        st, _ = _stats(x, blocks * 8, cpad, 8 * M, G)
         sbufs = [_stats_buffer(x, blocks, cpad, groups=G) for _ in range(8)] if G > 1 else None
     for i, (par, pk) in enumerate(zip(classes, pks)):
         sb = None

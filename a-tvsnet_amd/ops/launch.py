@@ -2,47 +2,135 @@
 tower layers and the generic / tiled / x-pair 3-D kernels.
 """
 
+import collections
 import ctypes
 
 import torch
 
 from .. import _lib
-from .base import Stats, _Timed, _call, _dev_ok, _new, _p, _stream, cfg
-from .packing import _Packed, _pack_cache, _xp_cache, planar_stride, split_on
+from .base import _Timed, _call, _dev_ok, _new, _p, _stats, _stream, cfg
+from .packing import _abi_pack, _xp_cache, planar_stride, same_pad, split_on
 from .norm import PendingBN, PendingSum, _param_groups
 
 
+def conv_geometry(ins, ks, stride, dilation, padding, nsp=3):
+    """(pads before, output size) per axis of (D,H,W) inputs `ins` (D = 1 for a 2-D convolution, nsp = 2).  padding: 'SAME' |
+    'VALID' | explicit (before, after) per spatial axis."""
+    pads, outs = [], []
+    for i in range(3):
+        if ks[i] == 1 and i < 3 - nsp:
+            pads.append(0)
+            outs.append(1)
+            continue
+        if not isinstance(padding, str):
+            pb, pe = padding[i - (3 - nsp)]
+            pads.append(pb)
+            outs.append((ins[i] + pb + pe - ((ks[i] - 1) * dilation + 1)) // stride + 1)
+        elif padding == 'SAME':
+            pb, o = same_pad(ins[i], ks[i], stride, dilation)
+            pads.append(pb)
+            outs.append(o)
+        else:
+            pads.append(0)
+            outs.append((ins[i] - ((ks[i] - 1) * dilation + 1)) // stride + 1)
+    return tuple(pads), tuple(outs)
+
+
+ConvPlan = collections.namedtuple('ConvPlan', 'family on_load pads outs')
+
+
+def _lazy_form(cin, cout, stride, lazy):
+    """The split-operand family that forms a lazy input of a 3x3x3 SAME convolution with these channels on load (conv_c16b: a
+    pending batch norm or a two-term sum, 16 -> 16; conv3d_b: a pending batch norm, Cin % 16 == 0 -> 32 / 64; conv3d_s2b: the
+    same at stride 2), or None.  conv_plan adds the shape limits of the kernels."""
+    if not (lazy and cfg.sum_on_load and cfg.norm3d and cfg.conv_c16 and cfg.force_impl is None):
+        return None
+    if stride == 1 and cin == 16 and cout == 16 and split_on('c16b'):
+        return 'c16b_sum'
+    if lazy == 'bn' and cin % 16 == 0 and cout in (32, 64) and split_on('s2b' if stride == 2 else 'c3b') and stride in (1, 2):
+        return 's2b_norm' if stride == 2 else 'c3b_norm'
+    return None
+
+
+def conv_plan(shape, ksize, cin, cout, stride=1, dilation=1, padding='SAME', bias=False, residual=False, plane_bias=False,
+              out=None, lazy=None):
+    """The kernel family ops.conv launches for a convolution of one sample of `shape` ((H,W) or (D,H,W)), and whether it
+    forms a lazy input on load -> ConvPlan(family, on_load, pads, outs).  Pure host logic: no tensor is touched.
+
+    ksize: int or per-axis tuple; padding as ops.conv (explicit (before, after) pairs for explicit_pad); bias / residual /
+    plane_bias: whether those operands are given; out: (row length, channel offset) of a given output buffer; lazy: None,
+    'bn' (a pending batch norm: in_params) or 'sum' (a two-term skip sum: in_sum).  on_load is False when the family has no
+    form for the lazy input: ops.conv materialises a 3-D one first and refuses a 2-D one."""
+    nsp = len(shape)
+    ks = (1,) * (3 - nsp) + (tuple(int(k) for k in ksize) if isinstance(ksize, tuple) else (int(ksize),) * nsp)
+    ins = (1,) * (3 - nsp) + tuple(int(s) for s in shape)
+    if not isinstance(padding, str):
+        padding = tuple(tuple(int(v) for v in pr) for pr in padding)
+    pads, outs = conv_geometry(ins, ks, stride, dilation, padding, nsp)
+    M = outs[0] * outs[1] * outs[2]
+    aligned = out is None or (out[0] % 4 == 0 and out[1] % 4 == 0)
+    small = 4.0 * M * (cout if out is None else out[0]) < 2.0 ** 32
+    plain = cfg.force_impl is None and not residual and not plane_bias
+
+    def plan(family, on_load=False):
+        return ConvPlan(family, bool(lazy) and on_load, pads, outs)
+    if nsp == 2:
+        if stride == 1 and ks == (1, 3, 3) and pads[1:] == (dilation, dilation) and outs == ins and not plane_bias \
+                and aligned and conv2d_lds_ok(cin, cout, dilation, ins[1], ins[2]):
+            return plan('conv2d_lds', lazy == 'bn' and split_on('c2b') and cin % 32 == 0)
+        # stride 2 behind explicit symmetric padding 1 (the strided conv2 of a residual unit's first block)
+        if stride == 2 and dilation == 1 and ks == (1, 3, 3) and padding == ((1, 1), (1, 1)) and ins[1] % 2 == 0 \
+                and ins[2] % 2 == 0 and plain and not lazy and out is None and cfg.conv2d_lds and split_on('c2b') \
+                and cin % 32 == 0 and ins[1] >= 16 and ins[2] >= 32 and bool(_lib.lib().atvs_conv2d_b_s2_supported(int(cin), int(cout))):
+            return plan('conv2d_b_s2')
+        if stride == 1 and ks == (1, 1, 1) and not plane_bias and conv1x1_ok(cin, cout) and aligned:
+            return plan('conv1x1', lazy == 'bn')
+    form = _lazy_form(cin, cout, stride, lazy) if nsp == 3 else None
+    if nsp == 3 and ks == (3, 3, 3) and dilation == 1:
+        if stride == 1 and pads == (1, 1, 1) and cout == 8 and cin <= 2 and not bias and not residual and cfg.stem \
+                and cfg.force_impl is None and aligned:
+            return plan('stem')      # the refinement stems, HBM-bound FMA kernel
+        # 8 / 16 / 32 -> 16 and 16..64 -> 32 channels: one workgroup per CU, fully unrolled
+        if stride == 1 and pads == (1, 1, 1) and plain and cfg.conv_c16 and outs == ins and ins[2] >= 12 and small and aligned:
+            if split_on('c3b') and cin % 16 == 0 and cout in (32, 64) and bool(_lib.lib().atvs_conv3d_b_supported(int(cin), int(cout))):
+                return plan('c3b_norm', True) if form == 'c3b_norm' else plan('c3b')
+            if split_on('c16b') and cin in (8, 16) and cout == 16:
+                return plan('c16b_sum', True) if form == 'c16b_sum' else plan('c16b')
+            if (cout == 16 and cin in (8, 16, 32)) or (cout == 32 and cin in (16, 32, 48, 64)):
+                return plan('c16')
+        # stride 2, SAME, 16 k -> 32 / 64 channels: the U-Net encoders below half resolution
+        if stride == 2 and padding == 'SAME' and split_on('s2b') and cfg.conv_c16 and plain and outs[2] >= 8 and small \
+                and aligned and bool(_lib.lib().atvs_conv3d_s2b_supported(int(cin), int(cout))):
+            return plan('s2b_norm', True) if form == 's2b_norm' else plan('s2b')
+    tile_y = 0
+    if nsp == 3 and stride == 1 and dilation == 1 and ks == (3, 3, 3) and pads == (1, 1, 1) and outs == ins:
+        tile_y = tiled_tile_y(ins[1], ins[2], cout)
+    if tile_y and cfg.xpair and cout == 8 and (ins[2] >= 24 or cfg.force_impl == 'tiled') and aligned:
+        return plan('xp' if cfg.xp1w and cin % 8 == 0 and not residual else 'xpair_tiled')
+    return plan('tiled' if tile_y else 'gather')
+
+
 def norm_on_load_2d_ok(src, ksize, filters, stride=1, rate=1):
-    """Can a 2-D convolution of this shape take a pending batch norm (PendingBN, channel-last) as it is -- the kernel
-    normalises (+ ReLU) while staging (conv2d_b.hip / conv1x1_b.hip `in_params`)?"""
+    """Can a 2-D convolution (SAME) take a pending batch norm (PendingBN, channel-last) as it is -- the kernel normalises
+    (+ ReLU) while staging (conv2d_b.hip / conv1x1_b.hip `in_params`)?  conv_plan decides for the shape."""
     if not (cfg.prologue and isinstance(src, PendingBN) and src._final is None and not src.planar and src.dim() == 4
-            and src.raw.is_contiguous() and stride == 1):
+            and src.raw.is_contiguous()):
         return False
-    G, H, W, cin = src.shape
-    if ksize == 3:
-        return conv2d_lds_ok(cin, filters, rate, H, W) and split_on('c2b') and cin % 32 == 0
-    if ksize == 1:
-        return rate == 1 and conv1x1_ok(cin, filters)
-    return False
+    return conv_plan(tuple(src.shape[1:3]), ksize, int(src.shape[-1]), filters, stride, rate, lazy='bn').on_load
 
 
 def norm_on_load_3d_ok(src, ksize, filters, stride=1, rate=1):
-    """Can a 3-D convolution take this lazy input as it is (its batch norm / its skip sum formed while the kernel stages
-    the halo)?  Built forms: a pending batch norm in front of conv_c16b (16 -> 16), conv3d_b (Cin % 16 == 0 -> 32 / 64) and
-    the stride-2 conv3d_s2b; a sum of two (dense or pending) in front of conv_c16b.  ops.conv falls back to the passes
-    themselves for a shape its dispatch sends elsewhere."""
-    if not (cfg.sum_on_load and cfg.norm3d) or cfg.force_impl is not None or not cfg.conv_c16 or ksize != 3 or rate != 1 \
-            or src.dim() != 5:
+    """Can a 3-D convolution (SAME) take this lazy input as it is (its batch norm / its skip sum formed while the kernel
+    stages the halo)?  True where a family forms it (_lazy_form); for a shape outside that kernel's limits (conv_plan)
+    ops.conv forms the input itself with the passes it stands for."""
+    if src.dim() != 5 or ksize != 3 or rate != 1 or getattr(src, '_final', None) is not None:
         return False
-    cin = int(src.shape[-1])
     if isinstance(src, PendingBN):
-        if src._final is not None or src.planar or not src.raw.is_contiguous() or cin % 16:
+        if src.planar or not src.raw.is_contiguous():
             return False
-        if stride == 2:
-            return split_on('s2b') and filters in (32, 64)
-        return stride == 1 and ((cin == 16 and filters == 16 and split_on('c16b')) or (filters in (32, 64) and split_on('c3b')))
-    if isinstance(src, PendingSum):
-        if src._final is not None or len(src.items) != 2 or stride != 1 or cin != 16 or filters != 16 or not split_on('c16b'):
+        lazy = 'bn'
+    elif isinstance(src, PendingSum):
+        if len(src.items) != 2:
             return False
         gs = set()
         for t in src.items:
@@ -51,8 +139,12 @@ def norm_on_load_3d_ok(src, ksize, filters, stride=1, rate=1):
                 gs.add(_param_groups(t.params))
             if not raw.is_contiguous() or (isinstance(t, PendingBN) and t.planar):
                 return False
-        return len(gs) <= 1
-    return False
+        if len(gs) > 1:
+            return False
+        lazy = 'sum'
+    else:
+        return False
+    return _lazy_form(int(src.shape[-1]), filters, stride, lazy) is not None
 
 
 def conv2d_lds_ok(cin, cout, dilation, H, W):
@@ -66,31 +158,11 @@ def conv2d_lds_ok(cin, cout, dilation, H, W):
 
 def pack_conv2d_lds(key, w_host, device):
     """Packed weights of the LDS-tiled 2-D kernel for a TF kernel [3,3,Cin,Cout]; cached."""
-    import numpy as np
-    w = np.ascontiguousarray(w_host, dtype=np.float32)
-    cin, cout = int(w.shape[-2]), int(w.shape[-1])
+    cin, cout = int(w_host.shape[-2]), int(w_host.shape[-1])
     split = split_on('c2b') and cin % 32 == 0      # conv2d_b.hip: split-fp16 operands (its chunk loop runs in pairs)
     kind = 'b' if split else 'lds'
-    ck = ('c2' + kind, key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    L = _lib.lib()
-    pf = ctypes.c_long()
-    rc = getattr(L, 'atvs_conv2d_%s_pack_size' % kind)(cin, cout, ctypes.byref(pf))
-    if rc:
-        raise RuntimeError('atvs_conv2d_%s_pack_size failed (%d) for Cin=%d Cout=%d' % (kind, rc, cin, cout))
-    packed = np.empty(pf.value, np.uint8 if split else np.float32)
-    rc = getattr(L, 'atvs_conv2d_%s_pack' % kind)(w.ctypes.data_as(ctypes.c_void_p), cin, cout, packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_conv2d_%s_pack failed (%d)' % (kind, rc))
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 9, 4, 0, cout // 16, cin, cout
-    pk.key, pk.kind = key, kind
-    pk.tab = None
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    return _abi_pack('c2' + kind, key, w_host, device, 'conv2d_%s_pack' % kind, (cin, cout), split, ntaps=9,
+                     ntiles=cout // 16, cin=cin, cout=cout, kind=kind)
 
 
 def conv2d_lds(x, key, w_host, dilation=1, bias=None, residual=None, relu=False, want_stats=False, out=None, y_coff=0,
@@ -105,16 +177,11 @@ def conv2d_lds(x, key, w_host, dilation=1, bias=None, residual=None, relu=False,
     y = _new(x, (G, H, W, pk.cout)) if out is None else out
     if tuple(y.shape[:3]) != (G, H, W):
         raise ValueError('conv %s: output buffer %s does not match %s' % (key, tuple(y.shape), (G, H, W)))
-    st, sbuf = None, None
-    if want_stats:
-        rows = int(_lib.lib().atvs_conv2d_lds_rows(H, W, pk.cout))
-        sbuf = torch.empty((G, rows, 2, pk.cout), dtype=torch.float64, device=x.device)
-        st = Stats()
-        st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, pk.cout, H * W, G
+    st, sbuf = _stats(x, _lib.lib().atvs_conv2d_lds_rows(H, W, pk.cout), pk.cout, H * W, G) if want_stats else (None, None)
     if _dev_ok(x, y, bias, residual, in_params):
         with _Timed(pk.key, (1, H, W, cin), pk.cout, G):
             _call('atvs_conv2d_%s_f32' % pk.kind, _p(x), _p(pk.wp), _p(bias), _p(residual), _p(in_params), int(bool(in_relu)),
-                  _p(y), ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G, H, W, cin,
+                  _p(y), _p(sbuf), G, H, W, cin,
                   pk.cout, int(dilation), int(y.shape[-1]), int(y_coff), int(bool(relu)), _stream())
     return (y, st) if want_stats else y
 
@@ -130,27 +197,11 @@ def pack_conv1x1(key, w_host, cin, device):
     """Packed weights of the 1x1 GEMM kernels for a TF kernel [1,1,Cin,Cout] (or [Cin,Cout]); cached.  pk.kind: '_b' = fp16
     pieces for conv1x1_b.hip (and the 1x1 stages of bottleneck_b.hip), '' = fp32 for conv1x1.hip."""
     import numpy as np
-    lib = _lib.lib()
-    kind = '_b' if (split_on('c1b') and lib.atvs_conv1x1_b_supported(int(cin), int(np.asarray(w_host).size // cin))) else ''
-    ck = ('c1' + kind, key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is None:
-        w = np.ascontiguousarray(w_host, dtype=np.float32).reshape(cin, -1)
-        cout = int(w.shape[1])
-        pf = ctypes.c_long()
-        rc = getattr(lib, 'atvs_conv1x1%s_pack_size' % kind)(cin, cout, ctypes.byref(pf))
-        if rc:
-            raise RuntimeError('atvs_conv1x1%s_pack_size failed (%d) for Cin=%d Cout=%d' % (kind, rc, cin, cout))
-        packed = np.empty(pf.value, np.uint8 if kind else np.float32)       # split kernel: bytes of fp16 pieces
-        rc = getattr(lib, 'atvs_conv1x1%s_pack' % kind)(w.ctypes.data_as(ctypes.c_void_p), cin, cout,
-                                                        packed.ctypes.data_as(ctypes.c_void_p))
-        if rc:
-            raise RuntimeError('atvs_conv1x1%s_pack failed (%d)' % (kind, rc))
-        pk = _Packed()
-        pk.key, pk.tab, pk.cin, pk.cout, pk.ntiles, pk.kind = key, None, cin, cout, cout // 16, kind
-        pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-        _pack_cache[ck] = pk
-    return pk
+    w = np.asarray(w_host).reshape(cin, -1)
+    cout = int(w.shape[1])
+    kind = '_b' if (split_on('c1b') and _lib.lib().atvs_conv1x1_b_supported(int(cin), cout)) else ''
+    return _abi_pack('c1' + kind, key, w, device, 'conv1x1%s_pack' % kind, (cin, cout), bool(kind), ntiles=cout // 16,
+                     cin=cin, cout=cout, kind=kind)
 
 
 def conv1x1(x, key, w_host, bias=None, residual=None, relu=False, want_stats=False, out=None, y_coff=0, in_params=None,
@@ -165,14 +216,11 @@ def conv1x1(x, key, w_host, bias=None, residual=None, relu=False, want_stats=Fal
     y = _new(x, tuple(x.shape[:-1]) + (pk.cout,)) if out is None else out
     st, sbuf = None, None
     if want_stats:
-        rows = int(getattr(lib, 'atvs_conv1x1%s_rows' % kind)(ctypes.c_long(pixels)))
-        sbuf = torch.empty((G, rows, 2, pk.cout), dtype=torch.float64, device=x.device)
-        st = Stats()
-        st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, pk.cout, pixels, G
+        st, sbuf = _stats(x, getattr(lib, 'atvs_conv1x1%s_rows' % kind)(ctypes.c_long(pixels)), pk.cout, pixels, G)
     if _dev_ok(x, y, bias, residual, in_params):
         with _Timed(pk.key, (1, 1, pixels, cin), pk.cout, G):
             _call('atvs_conv1x1%s_f32' % kind, _p(x), _p(pk.wp), _p(bias), _p(residual), _p(in_params), int(bool(in_relu)),
-                  _p(y), ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G,
+                  _p(y), _p(sbuf), G,
                   ctypes.c_long(pixels), cin, pk.cout, int(y.shape[-1]), int(y_coff), int(bool(relu)), _stream())
     return (y, st) if want_stats else y
 
@@ -195,18 +243,13 @@ def bottleneck(x, in_params, keys, w1, b1, w2, b2, w3, b3, dilation=1, want_stat
     if p1.kind != '_b' or p3.kind != '_b' or p2.kind != 'b' or (p1.cout, p2.cout, p3.cout) != (C, C, C):
         raise ValueError('bottleneck: the fused unit takes the split-operand packs of three C -> C kernels')
     y = _new(x, x.shape)
-    st, sbuf = None, None
-    if want_stats:
-        rows = int(_lib.lib().atvs_bottleneck_b_rows(int(C), int(H), int(W)))
-        sbuf = torch.empty((G, rows, 2, C), dtype=torch.float64, device=x.device)
-        st = Stats()
-        st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, C, H * W, G
+    st, sbuf = _stats(x, _lib.lib().atvs_bottleneck_b_rows(int(C), int(H), int(W)), C, H * W, G) if want_stats else (None, None)
     if _dev_ok(x, y, in_params, b1, b2, b3):
         if in_params.numel() != G * 3 * C:
             raise ValueError('bottleneck: in_params must be (groups, 3, C)')
         with _Timed(k2, (1, H, W, C), C, G):
             _call('atvs_bottleneck_b_f32', _p(x), _p(in_params), _p(p1.wp), _p(b1), _p(p2.wp), _p(b2), _p(p3.wp), _p(b3), _p(y),
-                  ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G, H, W, C, int(dilation),
+                  _p(sbuf), G, H, W, C, int(dilation),
                   _stream())
     return (y, st) if want_stats else y
 
@@ -226,16 +269,11 @@ def conv2d_tail(x, keys, w2, b2, w3, b3, residual=None, dilation=1, want_stats=T
     if p2.kind != 'b' or p3.kind != '_b' or (p2.cout, p3.cout) != (C, C):
         raise ValueError('conv2d_tail: the split-operand packs of two C -> C kernels')
     y = _new(x, x.shape)
-    st, sbuf = None, None
-    if want_stats:
-        rows = int(_lib.lib().atvs_conv2d_lds_rows(H, W, C))
-        sbuf = torch.empty((G, rows, 2, C), dtype=torch.float64, device=x.device)
-        st = Stats()
-        st.partial, st.blocks, st.cpad, st.count, st.groups = sbuf, rows, C, H * W, G
+    st, sbuf = _stats(x, _lib.lib().atvs_conv2d_lds_rows(H, W, C), C, H * W, G) if want_stats else (None, None)
     if _dev_ok(x, y, b2, b3, residual):
         with _Timed(keys[0], (1, H, W, C), C, G):
             _call('atvs_conv2d_b_tail_f32', _p(x), _p(p2.wp), _p(b2), _p(p3.wp), _p(b3), _p(residual), _p(y),
-                  ctypes.c_void_p(sbuf.data_ptr()) if sbuf is not None else ctypes.c_void_p(0), G, H, W, C, int(dilation), _stream())
+                  _p(sbuf), G, H, W, C, int(dilation), _stream())
     return (y, st) if want_stats else y
 
 
@@ -251,8 +289,6 @@ def conv_xp_launch(x5, pk, y, y_coff, bias=None, relu=False, stats_buf=None, pla
     else:
         G, D, H, W, Cin = x5.shape
     ldy = y.shape[-1] if ldy is None else int(ldy)      # ldy / y_gstride given: y is a plane of a chunk-planar buffer (xb only)
-    null = ctypes.c_void_p(0)
-    sp = lambda t: ctypes.c_void_p(t.data_ptr()) if t is not None else null     # noqa: E731
     pk2, y2, y_coff2, sbuf2, pb2 = sibling if sibling is not None else (None, None, 0, None, None)
     x2, ipa, ipb, relu_a, relu_b = prologue if prologue is not None else (None, None, None, False, False)
     if x2 is not None and (tuple(x2.shape) != tuple(x5.shape) or not x2.is_contiguous()):
@@ -268,9 +304,9 @@ def conv_xp_launch(x5, pk, y, y_coff, bias=None, relu=False, stats_buf=None, pla
     if _dev_ok(x5, y, bias, plane_bias, y2, pb2, x2, ipa, ipb):
         with _Timed(pk.key, (D, H, W, Cin), pk.cout + (16 if pk2 is not None else 0), G):
             yp = ctypes.c_void_p(y.data_ptr() + 4 * int(y_off))     # y_off: floats into a chunk-planar buffer (with ldy / y_gstride)
-            args = [_p(x5), _p(pk.wp), _p(bias), _p(plane_bias), yp, sp(stats_buf), G, D, H, W, Cin,
-                    ldy, int(y_coff), int(bool(relu)), _p(pk2.wp) if pk2 is not None else null, _p(pb2), _p(y2),
-                    sp(sbuf2), int(y2.shape[-1]) if y2 is not None else 0, int(y_coff2), _p(x2), _p(ipa), _p(ipb),
+            args = [_p(x5), _p(pk.wp), _p(bias), _p(plane_bias), yp, _p(stats_buf), G, D, H, W, Cin,
+                    ldy, int(y_coff), int(bool(relu)), _p(pk2.wp if pk2 is not None else None), _p(pb2), _p(y2),
+                    _p(sbuf2), int(y2.shape[-1]) if y2 is not None else 0, int(y_coff2), _p(x2), _p(ipa), _p(ipb),
                     int(bool(relu_a)), int(bool(relu_b))]
             if kind == 'xb':
                 _call('atvs_conv_xb_f32', *(args + [ctypes.c_long(planar_stride(D, H, W) if planar else 0),
@@ -326,9 +362,9 @@ def conv_tiled_launch(x5, pk, y, out_stride, out_off, y_coff, tile_y, bias=None,
     Dy, Hy, Wy, ldy = y.shape[-4:]
     if _dev_ok(x5, y, bias, residual, plane_bias):
         with _Timed(pk.key, x5.shape[1:], pk.cout, G):
-            _call('atvs_conv_tiled_f32', _p(x5), _p(pk.wp), ctypes.c_void_p(pk.tab.data_ptr()), _p(bias), _p(residual),
+            _call('atvs_conv_tiled_f32', _p(x5), _p(pk.wp), _p(pk.tab), _p(bias), _p(residual),
                   _p(plane_bias), _p(y),
-                  ctypes.c_void_p(stats_buf.data_ptr()) if stats_buf is not None else ctypes.c_void_p(0), G, D, H, W,
+                  _p(stats_buf), G, D, H, W,
                   Cin, Dy, Hy, Wy, int(out_stride), int(out_off[0]), int(out_off[1]), int(out_off[2]), ldy, int(y_coff),
                   8 if xpair else pk.cout, pk.ntaps, int(tile_y), int(bool(relu)), int(class_cout), int(class_base),
                   int(bool(xpair)),
@@ -394,9 +430,9 @@ def conv_launch(x5, pk, y, out_grid, in_stride, out_stride, out_off, y_coff, bia
     M = Do * Ho * Wo
     tm = tile_m or _pick_tile_m(M * G, pk.ntiles)
     if _dev_ok(x5, y, bias, residual, plane_bias):
-        args = [_p(x5), _p(pk.wp), ctypes.c_void_p(pk.tab.data_ptr()), _p(bias), _p(residual), _p(plane_bias),
+        args = [_p(x5), _p(pk.wp), _p(pk.tab), _p(bias), _p(residual), _p(plane_bias),
                 int(pad_z), _p(y),
-                ctypes.c_void_p(stats_buf.data_ptr()) if stats_buf is not None else ctypes.c_void_p(0),
+                _p(stats_buf),
                 G, Di, Hi, Wi, Cin, Do, Ho, Wo, int(in_stride), Dy, Hy, Wy, int(out_stride), int(out_off[0]),
                 int(out_off[1]), int(out_off[2]), ldy, int(y_coff), pk.cout, pk.ntaps, tm, int(bool(relu)), _stream()]
         with _Timed(pk.key, x5.shape[1:], pk.cout, G):
@@ -408,11 +444,6 @@ def conv_blocks(M, ntiles, tile_m=None, groups=1):
     """(workgroups per sample, tile_m) of a gather launch."""
     tm = tile_m or _pick_tile_m(M * groups, ntiles)
     return -(-M // (64 * tm)), tm
-
-
-def _stats_buffer(ref, blocks, cpad, zero=False, groups=1):
-    f = torch.zeros if zero else torch.empty
-    return f((groups, blocks, 2, cpad), dtype=torch.float64, device=ref.device)
 
 
 def _to5(x, groups, what='tensor'):

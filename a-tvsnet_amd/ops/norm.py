@@ -7,7 +7,7 @@ import ctypes
 import torch
 
 from .. import _lib
-from .base import Stats, _call, _dev_ok, _new, _p, _stream, cfg
+from .base import _call, _dev_ok, _new, _p, _stats, _stream, cfg
 from .packing import _xkind, planar_view
 
 
@@ -17,11 +17,9 @@ def channel_stats(x, groups=None):
     G = 1 if groups is None else int(groups)
     rows = x.numel() // C // G
     blocks = int(_lib.lib().atvs_channel_stats_num_blocks(ctypes.c_long(rows)))
-    st = Stats()
-    st.partial = torch.empty((G, blocks, 2, C), dtype=torch.float64, device=x.device)
-    st.blocks, st.cpad, st.count, st.groups = blocks, C, rows, G
+    st, sbuf = _stats(x, blocks, C, rows, G)
     if _dev_ok(x):
-        _call('atvs_channel_stats', _p(x), G, ctypes.c_long(rows), C, ctypes.c_void_p(st.partial.data_ptr()), _stream())
+        _call('atvs_channel_stats', _p(x), G, ctypes.c_long(rows), C, _p(sbuf), _stream())
     return st
 
 

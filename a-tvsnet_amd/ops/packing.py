@@ -46,7 +46,50 @@ _pack_cache = {}
 
 
 class _Packed(object):
-    __slots__ = ('wp', 'tab', 'ntaps', 'vec', 'ksteps', 'ntiles', 'cin', 'cout', 'key', 'xw', 'kind')
+    """Weights arranged for one kernel family on one device.  wp: the packed weights (None on meta); tab: the tap table of the
+    generic kernels; the class values are the defaults a packer leaves alone."""
+    wp = tab = key = None
+    ntaps, vec, ksteps, ntiles, cin, cout, xw, kind = 0, 4, 0, 1, 0, 0, False, ''
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def _abi_pack(tag, key, w_host, device, entry, size_args, pieces=False, **fields):
+    """Weights packed by the host function atvs_<entry> of the C-ABI and uploaded to `device`; cached as (tag, key, device).
+    w_host: the TF kernel, or a tuple of kernels for an entry that packs several.  size_args: the arguments of
+    atvs_<entry>_size (they also follow the kernels in atvs_<entry>), or the packed length for an entry without one.
+    pieces: the packed form is bytes (fp16 pieces), else float32.  entry None: the kernel is uploaded as it is.
+    fields: the _Packed fields the family's launcher reads."""
+    import numpy as np
+    ck = (tag, key, str(device))
+    pk = _pack_cache.get(ck)
+    if pk is not None:
+        return pk
+    ws = [np.ascontiguousarray(w, dtype=np.float32) for w in (w_host if isinstance(w_host, tuple) else (w_host,))]
+    if entry is None:
+        packed = ws[0]
+    else:
+        L = _lib.lib()
+        n = size_args
+        if isinstance(size_args, tuple):
+            pf = ctypes.c_long()
+            rc = getattr(L, 'atvs_%s_size' % entry)(*(size_args + (ctypes.byref(pf),)))
+            if rc:
+                raise RuntimeError('atvs_%s_size failed (%d) for %s' % (entry, rc, size_args))
+            n = pf.value
+        else:
+            size_args = ()
+        packed = np.empty(n, np.uint8 if pieces else np.float32)
+        rc = getattr(L, 'atvs_' + entry)(*([w.ctypes.data_as(ctypes.c_void_p) for w in ws] + list(size_args)
+                                           + [packed.ctypes.data_as(ctypes.c_void_p)]))
+        if rc:
+            raise RuntimeError('atvs_%s failed (%d)' % (entry, rc))
+    pk = _Packed(key=key, **fields)
+    if torch.device(device).type != 'meta':
+        pk.wp = torch.from_numpy(packed).to(device)
+    _pack_cache[ck] = pk
+    return pk
 
 
 def pack_conv_weights(key, w_host, taps, transposed, device):
@@ -74,16 +117,8 @@ def pack_conv_weights(key, w_host, taps, transposed, device):
                           table.ctypes.data_as(ctypes.c_void_p))
     if rc:
         raise RuntimeError('atvs_conv_pack failed (%d)' % rc)
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = ntaps, vec.value, ks.value, nt.value, cin, cout
-    pk.key = key
-    if torch.device(device).type == 'meta':
-        pk.wp = pk.tab = None
-    else:
-        pk.wp = torch.from_numpy(packed).to(device)
-        pk.tab = torch.from_numpy(table).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    pk = _Packed(key=key, ntaps=ntaps, vec=vec.value, ksteps=ks.value, ntiles=nt.value, cin=cin, cout=cout)
+    return _upload_tabled(ck, pk, packed, table, device)
 
 
 def pack_conv_weights_tiled(key, w_host, taps, transposed, device, tile_y, xpair=False):
@@ -111,14 +146,13 @@ def pack_conv_weights_tiled(key, w_host, taps, transposed, device, tile_y, xpair
                                 packed.ctypes.data_as(ctypes.c_void_p), table.ctypes.data_as(ctypes.c_void_p))
     if rc:
         raise RuntimeError('atvs_conv_tiled_pack failed (%d)' % rc)
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = ntaps, 4, jc.value * nch.value, nt.value, cin, cout
-    pk.key = key
-    if torch.device(device).type == 'meta':
-        pk.wp = pk.tab = None
-    else:
-        pk.wp = torch.from_numpy(packed).to(device)
-        pk.tab = torch.from_numpy(table).to(device)
+    pk = _Packed(key=key, ntaps=ntaps, ksteps=jc.value * nch.value, ntiles=nt.value, cin=cin, cout=cout)
+    return _upload_tabled(ck, pk, packed, table, device)
+
+
+def _upload_tabled(ck, pk, packed, table, device):
+    if torch.device(device).type != 'meta':
+        pk.wp, pk.tab = torch.from_numpy(packed).to(device), torch.from_numpy(table).to(device)
     _pack_cache[ck] = pk
     return pk
 
@@ -163,89 +197,25 @@ def planar_cost_volume_ok(shape, F):
 
 def pack_conv_xp(key, w_host, device):
     """Packed weights of the one-workgroup-per-CU x-pair kernels (atvs_conv_xb_f32 / atvs_conv_xw_f32); cached."""
-    import numpy as np
     kind = _xkind()
-    xw = kind == 'xw'
-    ck = (kind, key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)           # [3,3,3,Cin,8]
-    cin = w.shape[-2]
-    L = _lib.lib()
-    pf = ctypes.c_long()
-    size_fn, pack_fn = getattr(L, 'atvs_conv_%s_pack_size' % kind), getattr(L, 'atvs_conv_%s_pack' % kind)
-    rc = size_fn(cin, ctypes.byref(pf))
-    if rc:
-        raise RuntimeError('atvs_conv_%s_pack_size failed (%d) for Cin=%d' % (kind, rc, cin))
-    packed = np.empty(pf.value, np.uint8 if kind == 'xb' else np.float32)      # xb: bytes (fp16 pieces)
-    rc = pack_fn(w.ctypes.data_as(ctypes.c_void_p), cin, packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_conv_%s_pack failed (%d)' % (kind, rc))
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 36, 4, 0, 1, cin, 8
-    pk.xw, pk.kind = xw, kind
-    pk.key = key
-    pk.tab = None
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cin = int(w_host.shape[-2])                                   # [3,3,3,Cin,8]
+    return _abi_pack(kind, key, w_host, device, 'conv_%s_pack' % kind, (cin,), kind == 'xb', ntaps=36, cin=cin, cout=8,
+                     xw=kind == 'xw', kind=kind)
 
 
 def pack_deconv_up(key, w_host, device, kind=''):
     """Packed weights of the 8- / 16-channel transposed-convolution kernels (atvs_deconv_up_f32; kind '_b': the split-fp16
     atvs_deconv_up_b_f32, bytes of fp16 pieces); cached."""
-    import numpy as np
-    ck = ('up' + kind, key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)           # [3,3,3,Cout,Cin]
-    cout, cin = int(w.shape[-2]), int(w.shape[-1])
-    L = _lib.lib()
-    pf = ctypes.c_long()
-    rc = getattr(L, 'atvs_deconv_up%s_pack_size' % kind)(cin, cout, ctypes.byref(pf))
-    if rc:
-        raise RuntimeError('atvs_deconv_up%s_pack_size failed (%d) for %d -> %d' % (kind, rc, cin, cout))
-    packed = np.empty(pf.value, np.uint8 if kind else np.float32)
-    rc = getattr(L, 'atvs_deconv_up%s_pack' % kind)(w.ctypes.data_as(ctypes.c_void_p), cin, cout,
-                                                    packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_deconv_up%s_pack failed (%d)' % (kind, rc))
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 27, 4, 0, 1, cin, cout
-    pk.key = key
-    pk.tab = None
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cout, cin = int(w_host.shape[-2]), int(w_host.shape[-1])      # [3,3,3,Cout,Cin]
+    return _abi_pack('up' + kind, key, w_host, device, 'deconv_up%s_pack' % kind, (cin, cout), bool(kind), ntaps=27,
+                     cin=cin, cout=cout)
 
 
 def pack_conv_c16(key, w_host, device):
     """Packed weights of the 16-output-channel 3x3x3 kernel (atvs_conv_c16_f32); cached."""
-    import numpy as np
-    ck = ('c16', key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)           # [3,3,3,Cin,Cout]
-    cin, cout = int(w.shape[-2]), int(w.shape[-1])
-    L = _lib.lib()
-    pf = ctypes.c_long()
-    rc = L.atvs_conv_c16_pack_size(cin, cout, ctypes.byref(pf))
-    if rc:
-        raise RuntimeError('atvs_conv_c16_pack_size failed (%d) for %d -> %d' % (rc, cin, cout))
-    packed = np.empty(pf.value, np.float32)
-    rc = L.atvs_conv_c16_pack(w.ctypes.data_as(ctypes.c_void_p), cin, cout, packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_conv_c16_pack failed (%d)' % rc)
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 27, 4, 0, cout // 16, cin, cout
-    pk.key = key
-    pk.tab = None
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cin, cout = int(w_host.shape[-2]), int(w_host.shape[-1])      # [3,3,3,Cin,Cout]
+    return _abi_pack('c16', key, w_host, device, 'conv_c16_pack', (cin, cout), ntaps=27, ntiles=cout // 16, cin=cin,
+                     cout=cout)
 
 
 def split_on(name):
@@ -256,55 +226,15 @@ def split_on(name):
 
 def pack_conv_c16b(key, w_host, device):
     """Packed fp16 pieces of a [3,3,3,Cin,16] kernel (Cin 8 or 16) for atvs_conv_c16b_f32; cached."""
-    import numpy as np
-    ck = ('c16b', key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)
-    cin = int(w.shape[-2])
-    L = _lib.lib()
-    pb = ctypes.c_long()
-    rc = L.atvs_conv_c16b_pack_size(cin, ctypes.byref(pb))
-    if rc:
-        raise RuntimeError('atvs_conv_c16b_pack_size failed (%d)' % rc)
-    packed = np.empty(pb.value, np.uint8)
-    rc = L.atvs_conv_c16b_pack(w.ctypes.data_as(ctypes.c_void_p), cin, packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_conv_c16b_pack failed (%d)' % rc)
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 27, 4, 0, 1, cin, 16
-    pk.key, pk.tab, pk.xw = key, None, False
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cin = int(w_host.shape[-2])
+    return _abi_pack('c16b', key, w_host, device, 'conv_c16b_pack', (cin,), True, ntaps=27, cin=cin, cout=16)
 
 
 def pack_conv3d_b(key, w_host, device, kind='b'):
     """Packed fp16 pieces of a [3,3,3,Cin,Cout] kernel (Cin % 16 == 0, Cout 32 / 64) for atvs_conv3d_b_f32 (kind 'b') or the
     stride-2 atvs_conv3d_s2b_f32 (kind 's2b'); cached."""
-    import numpy as np
-    ck = ('c3' + kind, key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)
-    cin, cout = int(w.shape[-2]), int(w.shape[-1])
-    L = _lib.lib()
-    pb = ctypes.c_long()
-    rc = getattr(L, 'atvs_conv3d_%s_pack_size' % kind)(cin, cout, ctypes.byref(pb))
-    if rc:
-        raise RuntimeError('atvs_conv3d_%s_pack_size failed (%d) for %d -> %d' % (kind, rc, cin, cout))
-    packed = np.empty(pb.value, np.uint8)
-    rc = getattr(L, 'atvs_conv3d_%s_pack' % kind)(w.ctypes.data_as(ctypes.c_void_p), cin, cout,
-                                                    packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('atvs_conv3d_%s_pack failed (%d)' % (kind, rc))
-    pk = _Packed()
-    pk.key, pk.tab, pk.cin, pk.cout = key, None, cin, cout
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cin, cout = int(w_host.shape[-2]), int(w_host.shape[-1])
+    return _abi_pack('c3' + kind, key, w_host, device, 'conv3d_%s_pack' % kind, (cin, cout), True, cin=cin, cout=cout)
 
 
 def deconv_up_ok(cin, cout):
@@ -313,35 +243,12 @@ def deconv_up_ok(cin, cout):
 
 def pack_conv_xp_sibling(key, w_host, device):
     """Packed weights of the stride-2 sibling [3,3,3,Cin,16] of an x-pair launch; cached."""
-    import numpy as np
     kind = _xkind()
-    xw = kind == 'xw'
-    ck = (kind + '2', key, str(device))
-    pk = _pack_cache.get(ck)
-    if pk is not None:
-        return pk
-    w = np.ascontiguousarray(w_host, dtype=np.float32)
-    cin = w.shape[-2]
-    if w.shape[-1] != 16:
-        raise ValueError('x-pair sibling: 16 output channels, got %d' % w.shape[-1])
-    L = _lib.lib()
-    pf = ctypes.c_long()
-    size_fn, pack_fn = getattr(L, 'atvs_conv_%s_pack_sibling_size' % kind), getattr(L, 'atvs_conv_%s_pack_sibling' % kind)
-    rc = size_fn(cin, ctypes.byref(pf))
-    if rc:
-        raise RuntimeError('x-pair sibling pack size failed (%d) for Cin=%d' % (rc, cin))
-    packed = np.empty(pf.value, np.uint8 if kind == 'xb' else np.float32)
-    rc = pack_fn(w.ctypes.data_as(ctypes.c_void_p), cin, packed.ctypes.data_as(ctypes.c_void_p))
-    if rc:
-        raise RuntimeError('x-pair sibling pack failed (%d)' % rc)
-    pk = _Packed()
-    pk.ntaps, pk.vec, pk.ksteps, pk.ntiles, pk.cin, pk.cout = 27, 4, 0, 1, cin, 16
-    pk.xw, pk.kind = xw, kind
-    pk.key = key
-    pk.tab = None
-    pk.wp = None if torch.device(device).type == 'meta' else torch.from_numpy(packed).to(device)
-    _pack_cache[ck] = pk
-    return pk
+    cin = int(w_host.shape[-2])
+    if w_host.shape[-1] != 16:
+        raise ValueError('x-pair sibling: 16 output channels, got %d' % w_host.shape[-1])
+    return _abi_pack(kind + '2', key, w_host, device, 'conv_%s_pack_sibling' % kind, (cin,), kind == 'xb', ntaps=27,
+                     cin=cin, cout=16, xw=kind == 'xw', kind=kind)
 
 
 _xp_cache = {}
