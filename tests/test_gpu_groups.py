@@ -7,6 +7,8 @@ import numpy as np
 import pytest
 import torch
 
+from numerics import term64 as _term64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -576,18 +578,6 @@ def _pending_seeded(G, shape, cin, seed, relu, cuda):
     par = torch.stack([_rand((G, cin), seed + 10) * 0.1, _rand((G, cin), seed + 30).abs() + 0.5,
                        _rand((G, cin), seed + 20) * 0.1], 1).to(cuda).contiguous()
     return ops.PendingBN(raw, par, relu=relu)
-
-
-def _term64(t):
-    """A term of a skip sum in float64 on the CPU: a finished tensor, or relu?((raw - mean) * rstd + beta) of a PendingBN."""
-    from atvsnet_amd import ops
-    if not isinstance(t, ops.PendingBN):
-        return t.cpu().double()
-    raw, par = t.raw.cpu().double(), t.params.cpu().double()
-    G, C = raw.shape[0], raw.shape[-1]
-    bc = (G,) + (1,) * (raw.dim() - 2) + (C,)
-    v = (raw - par[:, 0].reshape(bc)) * par[:, 1].reshape(bc) + par[:, 2].reshape(bc)
-    return torch.clamp(v, min=0) if t.relu else v
 
 
 @pytest.mark.parametrize('G,shape,cin,cout,stride,relu', [

@@ -1,0 +1,498 @@
+"""-m gpu: every launch form of the convolution kernels held element by element to a float64 evaluation (tests/numerics.py):
+|got - ref64| <= rel * cond + floor, at the SPLIT bar for the split-operand kernels and at the FP32_MFMA bar for
+their fp32 forms -- the kernels the overflow recompute falls back to.
+
+One row per launch form; each row asserts the kernel family it reaches (ops.conv_plan, or the entry point's predicate) and
+runs six operand regimes: randn, post-ReLU, scale 1e-3, log-uniform 1e-4 ... 1e2 per channel, below 2^-14 (both fp16 pieces
+subnormal), and a few entries near 6e4 with finite outputs.  Every run is under poison_allocator with NaN-bordered inputs:
+a read past an input, an unwritten output or statistics row, or a write outside the output's channel slice turns up as a
+NaN or a changed bit.  The batch-norm moments of each output are checked against float64 moments of what was written, and
+must not raise the sticky non-finite flag.  Rows with G = 3 scale the samples 1e-3, 1, 1e3 (where the range allows)."""
+import collections
+
+import numpy as np
+import pytest
+import torch
+
+from oracle import nets
+from oracle import tf_ops as T
+
+import numerics as N
+from numerics import FP32_MFMA, SPLIT
+
+pytestmark = pytest.mark.gpu
+
+REGIMES = ('randn', 'relu', 'small', 'loguniform', 'subnormal', 'near_max')
+_SCALE = {'randn': 1.0, 'relu': 1.0, 'small': 1e-3, 'loguniform': 1.0, 'subnormal': 2.0 ** -16, 'near_max': 1.0}
+SAMPLE_SCALES = (1e-3, 1.0, 1e3)
+
+# family: what the row asserts it reaches; split: its split-operand family (the ops.split_on names, xb = conv_xb.hip,
+# aanet_b = aanet_b.hip) or None; cfg: the ops.configure switches it runs under
+Row = collections.namedtuple('Row', 'name family split bar run cfg')
+FP32 = {'split16': False}
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def _input(shape, seed, regime, grouped=False):
+    """A CPU float32 operand (channel-last, channels on the last axis) of the regime; grouped: samples scaled 1e-3, 1, 1e3."""
+    g = _gen(seed)
+    x = torch.randn(shape, generator=g)
+    if regime == 'relu':
+        x = x.clamp(min=0)
+    elif regime == 'small':
+        x = x * 1e-3
+    elif regime == 'loguniform':
+        x = x * 10.0 ** (torch.rand(shape[-1], generator=g) * 6 - 4)
+    elif regime == 'subnormal':
+        x = (x * 2.0 ** -16).clamp(-2.0 ** -14 * 0.99, 2.0 ** -14 * 0.99)
+    elif regime == 'near_max':
+        flat = x.view(-1)
+        idx = torch.randperm(flat.numel(), generator=g)[:6]
+        flat[idx] = torch.tensor([6.0e4, -6.0e4, 5.9e4, -5.95e4, 6.05e4, 6.1e4])[:idx.numel()]
+    if grouped and shape[0] == 3 and regime in ('randn', 'relu', 'small'):
+        x = x * torch.tensor(SAMPLE_SCALES).reshape((3,) + (1,) * (len(shape) - 1))
+    return x
+
+
+def _weights(shape, seed):
+    fan = int(np.prod(shape[:-1]))
+    return torch.randn(shape, generator=_gen(seed)) * (2.0 / fan) ** 0.5
+
+
+def _params(G, C, seed, regime):
+    """(G,3,C) batch-norm parameters (mean, rstd, beta) of a lazy input; rstd <= 1 keeps a near-6e4 raw value in range."""
+    g, s = _gen(seed), _SCALE[regime]
+    return torch.stack([torch.randn(G, C, generator=g) * 0.1 * s, torch.rand(G, C, generator=g) * 0.5 + 0.5,
+                        torch.randn(G, C, generator=g) * 0.1 * s], 1).contiguous()
+
+
+def _dev(t, dev):
+    return N.nan_bordered(t.to(dev))
+
+
+def _relu(t, on=True):
+    return t.clamp(min=0) if on else t
+
+
+def _winograd_cond(x, w):
+    """cond of conv_xw.hip's Winograd F(2,3) along y (its fp32 form): the products are U_p * t_p with U_p sums of the three y
+    taps and t_p sums of two of the four input rows of an output-row pair, so an accumulation error scales with
+    sum_(kd,kx,ci) (sum_ky |w|) * (sum of |x| over the rows y-2 .. y+2), not with sum |x||w|."""
+    k5 = w.double().abs().sum(1, keepdim=True).expand(-1, 5, -1, -1, -1)
+    return T.conv(x.double().abs(), k5, 1, 'SAME')
+
+
+class Case(object):
+    """One launch's result: got (CPU) against want64 / cond64, the absolute floor, and what to check beside the values."""
+
+    def __init__(self, got, want64, cond64, floor, stats=None, kept=None):
+        self.got, self.want64, self.cond64, self.floor = got, want64, cond64, floor
+        self.stats = stats            # (Stats, device output of the same values, channels) or None
+        self.kept = kept              # (NaN-filled device buffer, lo, hi) or None
+
+
+def _check_stats(st, y, C, what):
+    """The per-sample moments the launch wrote (all rows, the first C channels) against float64 moments of y; then
+    bn_params must not raise the sticky non-finite flag."""
+    from atvsnet_amd import ops
+    G = st.groups
+    part = st.partial.detach().cpu()
+    assert bool(torch.isfinite(part[..., :C]).all()), '%s: a statistics row holds a non-finite value' % what
+    # every launch form in this table writes its rows unfolded (fold > 1 is the tiled transposed-convolution fallback only)
+    assert st.fold == 1, '%s: statistics folded by %d' % (what, st.fold)
+    s = part.reshape(G, -1, 2, st.cpad).sum(1)[..., :C]
+    v = y.detach().cpu().double().reshape(G, -1, C)
+    for k, want in ((0, v.sum(1)), (1, (v * v).sum(1))):
+        tol = 1e-5 * (v.abs() if k == 0 else v * v).sum(1) + 1e-30
+        bad = (s[:, k] - want).abs() > tol
+        assert not bool(bad.any()), '%s: moment %d of sample/channel %s: %.9e vs %.9e' % (
+            what, k, tuple(bad.nonzero()[0].tolist()), float(s[:, k][bad][0]), float(want[bad][0]))
+    ops.bn_params(st, C, torch.empty(1, device=y.device))
+    assert not ops.nonfinite_seen(y.device), '%s: bn_params raised the non-finite flag' % what
+
+
+# ------------------------------------------------------------------------------------------------------- ops.conv rows
+
+def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation=1, explicit_pad=None, lazy=None, bias=True,
+             relu=True, cfg=None, slice_out=True, winograd=False):
+    nsp = len(sp)
+    ks = (k,) * nsp
+
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        x = _input((G,) + sp + (cin,), 1, regime, grouped=True)
+        w = _weights(ks + (cin, cout), 2)
+        b = torch.randn(cout, generator=_gen(3)) * 0.1 * _SCALE[regime] if bias else None
+        padding = 'SAME' if explicit_pad is None else 'VALID'
+        out_spec = (cout + 8, 4) if slice_out else None
+        plan = ops.conv_plan(sp, k, cin, cout, stride, dilation, padding if explicit_pad is None else explicit_pad,
+                             bias, False, False, out_spec, lazy)
+        assert plan.family == family, '%s: conv_plan chose %s' % (name, plan.family)
+        assert plan.on_load == bool(lazy), '%s: the lazy input is not formed on load' % name
+        if family in ('conv2d_lds', 'conv1x1'):
+            pk = (ops.pack_conv2d_lds if family == 'conv2d_lds' else
+                  (lambda kk, ww, dd: ops.pack_conv1x1(kk, ww, cin, dd)))((name, 'probe'), w.numpy(), dev)
+            assert (pk.kind in ('b', '_b')) == (bar is SPLIT), '%s: packed for %r' % (name, pk.kind)
+        if family == 'xp':
+            assert ops.pack_conv_xp((name, 'probe'), w.numpy(), dev).kind == ('xb' if bar is SPLIT else 'xw')
+        kw = dict(stride=stride, dilation=dilation, explicit_pad=explicit_pad, relu=relu, want_stats=True, groups=G,
+                  bias=None if b is None else b.to(dev))
+        terms = []
+        if lazy is None:
+            xin = _dev(x, dev)
+            terms = [x]
+        else:
+            pa = ops.PendingBN(_dev(x, dev), _params(G, cin, 4, regime).to(dev), relu=True)
+            kw.update(in_params=pa.params, in_relu=True)
+            xin, terms = pa.raw, [pa]
+            if lazy == 'sum':
+                x1 = _input((G,) + sp + (cin,), 5, regime, grouped=True)
+                pb = ops.PendingBN(_dev(x1, dev), _params(G, cin, 6, regime).to(dev), relu=False)
+                kw.update(in_sum=(pb.raw, pb.params, False))
+                terms.append(pb)
+        buf = None
+        if slice_out:
+            buf = N.nan_output((G,) + plan.outs[3 - nsp:] + (cout + 8,), dev)
+            kw.update(out=buf, y_coff=4)
+        y, st = ops.conv(xin, name, w.numpy(), **kw)
+        ys = buf[..., 4:4 + cout] if slice_out else y
+
+        def op(*a):
+            xs, (wt, bt) = a[:-2], a[-2:]
+            s = xs[0] if len(xs) == 1 else xs[0] + xs[1]
+            return _relu(T.conv(s, wt, stride, padding, dilation, bias=bt, explicit_pad=explicit_pad), relu)
+        bb = b if b is not None else torch.zeros(cout)
+        cnd = _winograd_cond(x, w) + bb.double().abs() if winograd else N.cond(op, *terms, w, bb)
+        return [Case(ys.cpu(), N.ref64(op, *terms, w, bb), cnd, N.floor_of(w, bar),
+                     stats=(st, ys, cout), kept=(buf, 4, 4 + cout) if slice_out else None)]
+    return Row(name, family, split, bar, run, cfg or {})
+
+
+# ------------------------------------------------------------------------------------------------ the other entry points
+
+def _residual_floor(want, *ws):
+    """The floor of a fused residual unit: the weights' floors plus the fp32 rounding of the final residual add (2^-23 |y|).
+    The residual itself (exact fp32) stays out of cond, so a defect in the branch is measured against the branch alone."""
+    return sum(N.floor_of(w, SPLIT) for w in ws) + 2.0 ** -23 * want.abs()
+
+
+def tail_row(name, G, H, W, C, dil):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        assert ops.conv2d_tail_ok(C, dil, H, W)
+        x = _input((G, H, W, C), 11, regime, grouped=True)
+        res = _input((G, H, W, C), 12, regime, grouped=True)
+        w2, w3 = _weights((3, 3, C, C), 13), _weights((1, 1, C, C), 14)
+        b2, b3 = (torch.randn(C, generator=_gen(s)) * 0.1 * _SCALE[regime] for s in (15, 16))
+        y, st = ops.conv2d_tail(_dev(x, dev), ((name, 2), (name, 3)), w2.numpy(), b2.to(dev), w3.numpy(), b3.to(dev),
+                                residual=_dev(res, dev), dilation=dil)
+
+        def branch(x, w2, b2, w3, b3):
+            return T.conv(_relu(T.conv(x, w2, 1, 'SAME', dil, bias=b2)), w3, 1, 'SAME', bias=b3)
+        a = (x, w2, b2, w3, b3)
+        want = N.ref64(branch, *a) + res.double()
+        return [Case(y.cpu(), want, N.cond(branch, *a), _residual_floor(want, w2, w3), stats=(st, y, C))]
+    return Row(name, 'conv2d_tail', 'btl', SPLIT, run, {})
+
+
+def bottleneck_row(name, G, H, W, C):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        assert ops.bottleneck_ok(C, 1, H, W)
+        x = _input((G, H, W, C), 21, regime, grouped=True)
+        par = _params(G, C, 22, regime)
+        ws = [_weights(s, 23 + i) for i, s in enumerate(((1, 1, C, C), (3, 3, C, C), (1, 1, C, C)))]
+        bs = [torch.randn(C, generator=_gen(26 + i)) * 0.1 * _SCALE[regime] for i in range(3)]
+        pend = ops.PendingBN(_dev(x, dev), par.to(dev), relu=True)
+        y, st = ops.bottleneck(pend.raw, pend.params, tuple((name, i) for i in range(3)), ws[0].numpy(), bs[0].to(dev),
+                               ws[1].numpy(), bs[1].to(dev), ws[2].numpy(), bs[2].to(dev))
+
+        def branch(xn, w1, b1, w2, b2, w3, b3):
+            r = _relu(T.conv(xn, w1, 1, 'SAME', bias=b1))
+            r = _relu(T.conv(r, w2, 1, 'SAME', bias=b2))
+            return T.conv(r, w3, 1, 'SAME', bias=b3)
+        a = (pend, ws[0], bs[0], ws[1], bs[1], ws[2], bs[2])
+        want = N.ref64(branch, *a) + x.double()
+        return [Case(y.cpu(), want, N.cond(branch, *a), _residual_floor(want, *ws), stats=(st, y, C))]
+    return Row(name, 'bottleneck', 'btl', SPLIT, run, {})
+
+
+def siblings_row(name, G, D, H, W, cin, bar, cfg=None):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        assert ops.siblings_ok((D, H, W), cin, 8, 16)
+        x = _input((G, D, H, W, cin), 31, regime, grouped=True)
+        w1, w2 = _weights((3, 3, 3, cin, 8), 32), _weights((3, 3, 3, cin, 16), 33)
+        assert ops.pack_conv_xp((name, 'probe'), w1.numpy(), dev).kind == ('xb' if bar is SPLIT else 'xw')
+        (y, st), (y2, st2) = ops.conv_siblings(_dev(x, dev), (name, 1), w1.numpy(), (name, 2), w2.numpy(), groups=G)
+        out = []
+        for yy, s, w, stride, c in ((y, st, w1, 1, 8), (y2, st2, w2, 2, 16)):
+            def op(x, w, stride=stride):
+                return T.conv(x, w, stride, 'SAME')
+            cnd = _winograd_cond(x, w) if (stride == 1 and bar is FP32_MFMA) else N.cond(op, x, w)
+            out.append(Case(yy.cpu(), N.ref64(op, x, w), cnd, N.floor_of(w, bar), stats=(s, yy, c)))
+        return out
+    return Row(name, 'xp_siblings', 'xb' if bar is SPLIT else None, bar, run, cfg or {})
+
+
+def plane_row(name, G, D, H, W, cv, cc, bar):
+    """conv_split: the D-varying channels on the x-pair kernel, the D-constant ones as a depth-plane bias (2-D convolution)."""
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        var = _input((G, D, H, W, cv), 41, regime, grouped=True)
+        const = _input((G, H, W, cc), 42, regime, grouped=True)
+        cmap = [('c', i) for i in range(cc)] + [('v', i) for i in range(cv)]
+        w = _weights((3, 3, 3, cc + cv, 8), 43)
+        plan = ops.conv_plan((D, H, W), 3, cv, 8, plane_bias=True)
+        assert plan.family == 'xp'
+        sv = ops.SplitVolume(_dev(var, dev), _dev(const, dev), cmap)
+        y, st = ops.conv_split(sv, name, w.numpy(), want_stats=True)
+
+        def op(var, const, w):
+            dense = torch.cat([const[:, None].expand(-1, D, -1, -1, -1), var], -1)
+            return T.conv(dense, w, 1, 'SAME')
+        return [Case(y.cpu(), N.ref64(op, var, const, w), N.cond(op, var, const, w), N.floor_of(w, bar), stats=(st, y, 8))]
+    return Row(name, 'xp_plane_bias', 'xb', bar, run, {})
+
+
+def into_plane_row(name, G, D, H, W, cv, cc, pieces, plane=2):
+    """conv_split_into_plane: the photo stem written into one plane of the chunk-planar concat (B, 4, planar_stride).  With
+    pieces the D-varying input is the chunk-planar fp16 pieces warp_planes writes (built here from DESIGN.md 8's split)."""
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        var = _input((G, D, H, W, cv), 101, regime, grouped=True)
+        const = _input((G, H, W, cc), 102, regime, grouped=True)
+        cmap = [('c', i) for i in range(cc)] + [('v', i) for i in range(cv)]
+        w = _weights((3, 3, 3, cc + cv, 8), 103)
+        assert ops._xkind() == 'xb'
+        ps, n, K = ops.planar_stride(D, H, W), D * H * W * 8, cv // 8
+        if pieces:
+            h0, h1 = N.emulate_split(var.reshape(G, D, H, W, K, 8).permute(0, 4, 1, 2, 3, 5))     # (G, K, D, H, W, 8)
+            pc = torch.full((G, K, ps), float('nan'))
+            pc[..., :n] = torch.stack([h0.half(), h1.half()], 2).reshape(G, K, -1).view(torch.float32)
+            sv = ops.SplitVolume(_dev(pc, dev), _dev(const, dev), cmap, planar=(D, H, W), pieces=True)
+        else:
+            sv = ops.SplitVolume(_dev(var, dev), _dev(const, dev), cmap)
+        buf = N.nan_output((G, 4, ps), dev)
+        st = ops.conv_split_into_plane(sv, name, w.numpy(), buf, plane, (D, H, W))
+        got = ops.planar_view(buf, D, H, W)[:, plane]
+        # everything but the plane's n values (the other planes, the padding behind every plane) keeps its NaN bits
+        bits = buf.cpu().view(torch.int32).clone()
+        bits[:, plane, :n] = torch.full((), float('nan')).view(torch.int32)
+        assert bool((bits == torch.full((), float('nan')).view(torch.int32)).all()), '%s: wrote outside its plane' % name
+
+        def op(var, const, w):
+            dense = torch.cat([const[:, None].expand(-1, D, -1, -1, -1), var], -1)
+            return T.conv(dense, w, 1, 'SAME')
+        return [Case(got.cpu(), N.ref64(op, var, const, w), N.cond(op, var, const, w), N.floor_of(w, SPLIT),
+                     stats=(st, got, 8))]
+    return Row(name, 'xp_into_plane', 'xb', SPLIT, run, {})
+
+
+def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cfg=None):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        x = _input((G, D, H, W, cin), 51, regime, grouped=True)
+        w = _weights((3, 3, 3, cout, cin), 52)
+        lib = ops._lib.lib()
+        if family == 'deconv_halves':
+            assert not ops.deconv_up_ok(cin, cout) and cout == 32 and bool(lib.atvs_deconv_up_b_supported(cin, 16))
+        else:
+            assert ops.deconv_up_ok(cin, cout) and bool(lib.atvs_deconv_up_b_supported(cin, cout))
+        assert ops.split_on('upb') == (bar is SPLIT)
+        terms = [x]
+        src = _dev(x, dev)
+        if summed:
+            a = ops.PendingBN(src, _params(G, cin, 53, regime).to(dev), relu=True)
+            x1 = _input((G, D, H, W, cin), 54, regime, grouped=True)
+            b = ops.PendingBN(_dev(x1, dev), _params(G, cin, 55, regime).to(dev), relu=False)
+            src = ops.PendingSum([a, b])
+            assert ops.deconv_sum_ok(src, cout, G)
+            terms = [a, b]
+        y, st = ops.conv3d_transpose_s2(src, name, w.numpy(), relu=True, want_stats=True, groups=G)
+
+        def op(*a):
+            xs, w = a[:-1], a[-1]
+            s = xs[0] if len(xs) == 1 else xs[0] + xs[1]
+            return _relu(T.conv3d_transpose_same(s, w))
+        return [Case(y.cpu(), N.ref64(op, *terms, w), N.cond(op, *terms, w), N.floor_of(w.permute(0, 1, 2, 4, 3), bar),
+                     stats=(st, y, cout))]
+    return Row(name, family, split, bar, run, cfg or {})
+
+
+def aanet_row(name, nv, D, H, W):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        X = _input((nv, D, H, W, 8), 61, regime)
+        ws, wu = _weights((3, 3, 3, 8, 8), 62), _weights((3, 3, 3, 8, 8), 63)
+        xs = [_dev(X[n], dev) for n in range(nv)]
+        assert ops.aanet_fused_ok(xs)
+        y = ops.aanet_fused(xs, name, ws.numpy(), wu.numpy())
+        Wd = {'a/attention_activation/weight_unique': wu.double(), 'a/attention_activation/weight_shared': ws.double()}
+        want = nets.attention_aggregation(X.double().permute(1, 2, 3, 4, 0).unsqueeze(0), Wd, 'a')[0]
+        # the linearised bound of the score convolutions' errors through the softmax (numerics.aanet_cond); with one view the
+        # softmax is identically 1 and the row checks the pass-through of X alone
+        cnd, spread = N.aanet_cond(X, ws, wu)
+        return [Case(y.cpu(), want, cnd, 2.0 * N.floor_of(torch.cat([ws, wu], -1), SPLIT) * spread)]
+    return Row(name, 'aanet_b', 'aanet_b', SPLIT, run, {})
+
+
+def stem_row(name, G, D, H, W, cin):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        x = _input((G, D, H, W, cin), 71, regime, grouped=True)
+        w = _weights((3, 3, 3, cin, 8), 72)
+        assert ops.conv_plan((D, H, W), 3, cin, 8).family == 'stem'
+        y, st = ops.conv(_dev(x, dev), name, w.numpy(), want_stats=True, groups=G)
+
+        def op(x, w):
+            return T.conv(x, w, 1, 'SAME')
+        return [Case(y.cpu(), N.ref64(op, x, w), N.cond(op, x, w), N.floor_of(w, FP32_MFMA), stats=(st, y, 8))]
+    return Row(name, 'stem', None, FP32_MFMA, run, {})
+
+
+def refine_stems_row(name, G, D, H, W):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        photo = _input((G, D, H, W, 8), 81, regime, grouped=True)
+        geo, prob, hull = (_input((G, D, H, W, c), 82 + i, regime, grouped=True) for i, c in enumerate((2, 1, 1)))
+        wg, wp, wh = _weights((3, 3, 3, 2, 8), 85), _weights((3, 3, 3, 1, 8), 86), _weights((3, 3, 3, 1, 8), 87)
+        buf, st = ops.refine_stems(_dev(photo, dev), _dev(geo, dev), None, _dev(prob, dev), _dev(hull, dev), name,
+                                   wg.numpy(), wp.numpy(), wh.numpy())
+        assert torch.equal(buf[..., :8].cpu(), photo)
+
+        def op(geo, prob, hull, wg, wp, wh):
+            return torch.cat([T.conv(geo, wg, 1, 'SAME'), T.conv(prob, wp, 1, 'SAME'), T.conv(hull, wh, 1, 'SAME')], -1)
+        a = (geo, prob, hull, wg, wp, wh)
+        return [Case(buf[..., 8:].cpu(), N.ref64(op, *a), N.cond(op, *a), N.floor_of(wg, FP32_MFMA),
+                     stats=(st, buf[..., 8:], 24))]
+    return Row(name, 'refine_stems', None, FP32_MFMA, run, {})
+
+
+def head_row(name, G, D, H, W, summed=False):
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        x = _input((G, D, H, W, 8), 91, regime, grouped=True)
+        w = _weights((3, 3, 3, 8, 1), 92)
+        terms = [x]
+        src = _dev(x, dev)
+        if summed:
+            a = ops.PendingBN(src, _params(G, 8, 93, regime).to(dev), relu=True)
+            x1 = _input((G, D, H, W, 8), 94, regime, grouped=True)
+            b = ops.PendingBN(_dev(x1, dev), _params(G, 8, 95, regime).to(dev), relu=True)
+            src = ops.PendingSum([a, b])
+            assert src.two_pending() is not None and ops.cfg.head_sum and ops.cfg.sum_on_load
+            terms = [a, b]
+        y = ops.conv3d_8to1(src, w.reshape(-1).to(dev), groups=G)
+
+        def op(*a):
+            xs, w = a[:-1], a[-1]
+            return T.conv(xs[0] if len(xs) == 1 else xs[0] + xs[1], w, 1, 'SAME')
+        return [Case(y.cpu(), N.ref64(op, *terms, w), N.cond(op, *terms, w), N.floor_of(w, FP32_MFMA))]
+    return Row(name, '8to1', None, FP32_MFMA, run, {})
+
+
+ROWS = [
+    # ---- split-operand forms (the default configuration)
+    conv_row('c16b_cin16_G3_D2', 'c16b', 'c16b', SPLIT, 3, (2, 9, 13), 16, 16),
+    conv_row('c16b_cin8_D1_W12', 'c16b', 'c16b', SPLIT, 1, (1, 7, 12), 8, 16),
+    conv_row('c16b_sum', 'c16b_sum', 'c16b', SPLIT, 2, (3, 8, 14), 16, 16, lazy='sum'),
+    conv_row('c3b_cin48_G3', 'c3b', 'c3b', SPLIT, 3, (2, 9, 13), 48, 32),
+    conv_row('c3b_cin32_64', 'c3b', 'c3b', SPLIT, 1, (4, 6, 17), 32, 64),
+    conv_row('c3b_norm', 'c3b_norm', 'c3b', SPLIT, 2, (3, 7, 12), 32, 32, lazy='bn'),
+    conv_row('s2b_cin16_G3_Wo8', 's2b', 's2b', SPLIT, 3, (4, 9, 15), 16, 32, stride=2),
+    conv_row('s2b_cin48_64', 's2b', 's2b', SPLIT, 1, (3, 8, 17), 48, 64, stride=2),
+    conv_row('s2b_norm', 's2b_norm', 's2b', SPLIT, 2, (5, 6, 16), 32, 32, stride=2, lazy='bn'),
+    conv_row('c2b_G3', 'conv2d_lds', 'c2b', SPLIT, 3, (8, 16), 32, 32),
+    conv_row('c2b_ragged', 'conv2d_lds', 'c2b', SPLIT, 1, (9, 37), 64, 64),
+    conv_row('c2b_dil2', 'conv2d_lds', 'c2b', SPLIT, 1, (10, 18), 128, 128, dilation=2),
+    conv_row('c2b_tiny', 'conv2d_lds', 'c2b', SPLIT, 2, (3, 5), 32, 32),
+    conv_row('c2b_on_load', 'conv2d_lds', 'c2b', SPLIT, 2, (8, 20), 32, 64, lazy='bn'),
+    conv_row('c2b_stride2', 'conv2d_b_s2', 'c2b', SPLIT, 1, (16, 32), 32, 64, stride=2, explicit_pad=((1, 1), (1, 1)),
+             slice_out=False),
+    tail_row('c2b_tail_dil2', 1, 8, 16, 128, 2),
+    conv_row('c1b_G3', 'conv1x1', 'c1b', SPLIT, 3, (5, 13), 64, 32, k=1),
+    conv_row('c1b_on_load', 'conv1x1', 'c1b', SPLIT, 1, (7, 9), 32, 128, k=1, lazy='bn'),
+    bottleneck_row('btl_G2', 2, 8, 16, 32),
+    conv_row('xb_cin24_G2_W24', 'xp', 'xb', SPLIT, 2, (2, 5, 24), 24, 8),
+    conv_row('xb_cin8_D1', 'xp', 'xb', SPLIT, 1, (1, 4, 25), 8, 8),
+    siblings_row('xb_siblings', 2, 3, 6, 24, 16, SPLIT),
+    plane_row('xb_plane_bias', 2, 3, 5, 26, 8, 3, SPLIT),
+    into_plane_row('xb_into_plane', 2, 3, 5, 26, 16, 3, False),
+    into_plane_row('xb_into_plane_pieces', 2, 3, 5, 26, 16, 3, True),
+    deconv_row('upb_cin16', 'deconv_up_b', 'upb', SPLIT, 2, 3, 4, 6, 16, 8),
+    deconv_row('upb_cin32_16_G3', 'deconv_up_b', 'upb', SPLIT, 3, 2, 3, 5, 32, 16),
+    deconv_row('upb_halves_64_32', 'deconv_halves', 'upb', SPLIT, 1, 2, 3, 4, 64, 32),
+    deconv_row('upb_sum', 'deconv_up_b_sum', 'upb', SPLIT, 2, 3, 4, 6, 16, 8, summed=True),
+    aanet_row('aanet_b_nv1', 1, 2, 5, 12),
+    aanet_row('aanet_b_nv2', 2, 3, 4, 13),
+    aanet_row('aanet_b_nv5', 5, 2, 3, 12),
+    aanet_row('aanet_b_nv8', 8, 2, 3, 14),
+    # ---- just below a split family's threshold: another (fp32) family takes the shape
+    conv_row('below_c16_W11_gather', 'gather', None, FP32_MFMA, 1, (3, 9, 11), 16, 16),
+    conv_row('tiled_cin24_16', 'tiled', None, FP32_MFMA, 2, (3, 9, 14), 24, 16),
+    conv_row('below_s2b_Wo7_gather', 'gather', None, FP32_MFMA, 1, (3, 6, 13), 16, 32, stride=2),
+    conv_row('below_xp_cin19_xpair_tiled', 'xpair_tiled', None, FP32_MFMA, 1, (3, 8, 24), 19, 8),
+    conv_row('below_xp_W23_tiled', 'tiled', None, FP32_MFMA, 2, (2, 5, 23), 24, 8),
+    conv_row('below_c2b_s2_H14_gather', 'gather', None, FP32_MFMA, 1, (14, 32), 32, 64, stride=2,
+             explicit_pad=((1, 1), (1, 1)), slice_out=False),
+    conv_row('below_c2b_s2_W30_gather', 'gather', None, FP32_MFMA, 1, (16, 30), 32, 64, stride=2,
+             explicit_pad=((1, 1), (1, 1)), slice_out=False),
+    conv_row('gather_cin24_W10', 'gather', None, FP32_MFMA, 2, (3, 5, 10), 24, 8),
+    # ---- the fp32 forms (ops.configure(split16=False)): what the overflow recompute runs
+    conv_row('fp32_c16_G3', 'c16', None, FP32_MFMA, 3, (2, 9, 13), 16, 16, cfg=FP32),
+    conv_row('fp32_c16_cin48', 'c16', None, FP32_MFMA, 1, (2, 9, 13), 48, 32, cfg=FP32),
+    conv_row('fp32_tiled_64', 'tiled', None, FP32_MFMA, 1, (4, 6, 17), 32, 64, cfg=FP32),
+    conv_row('fp32_gather_s2', 'gather', None, FP32_MFMA, 3, (4, 9, 15), 16, 32, stride=2, cfg=FP32),
+    conv_row('fp32_conv2d_lds', 'conv2d_lds', None, FP32_MFMA, 3, (8, 16), 32, 32, cfg=FP32),
+    conv_row('fp32_conv1x1', 'conv1x1', None, FP32_MFMA, 3, (5, 13), 64, 32, k=1, cfg=FP32),
+    conv_row('fp32_xw', 'xp', None, FP32_MFMA, 2, (2, 5, 24), 24, 8, cfg=FP32, winograd=True),
+    siblings_row('fp32_xw_siblings', 2, 3, 6, 24, 16, FP32_MFMA, cfg=FP32),
+    deconv_row('fp32_deconv_up', 'deconv_up', None, FP32_MFMA, 2, 3, 4, 6, 16, 8, cfg=FP32),
+    stem_row('stem_cin2_G3', 3, 3, 5, 12, 2),
+    stem_row('stem_cin1', 1, 2, 9, 33, 1),
+    refine_stems_row('refine_stems_G2', 2, 3, 9, 35),
+    head_row('8to1_G3', 3, 3, 5, 9),
+    head_row('8to1_sum', 2, 4, 6, 10, summed=True),
+]
+_WORST = {}
+
+
+@pytest.mark.parametrize('row', ROWS, ids=[r.name for r in ROWS])
+def test_elementwise_against_float64(cuda, row):
+    from atvsnet_amd import ops
+    with ops.configure(clear_pack_cache=True, **row.cfg):
+        ops.nonfinite_seen(cuda)                           # reset the sticky flag
+        for regime in REGIMES:
+            N.poison_allocator(cuda)
+            cases = row.run(cuda, regime)
+            torch.cuda.synchronize()
+            for i, c in enumerate(cases):
+                what = '%s[%s]#%d' % (row.name, regime, i)
+                r = N.assert_elementwise(c.got, c.want64, c.cond64, row.bar.rel * (N.NEAR_MAX if regime == 'near_max' else 1.0),
+                                         c.floor, what)
+                key = (row.family, 'split' if row.bar is SPLIT else 'fp32', regime)
+                _WORST[key] = max(_WORST.get(key, 0.0), r)
+                print('%-28s %-10s err/cond %.2e' % (row.name, regime, r))
+                if c.kept is not None:
+                    N.assert_bits_kept(*c.kept)
+                if c.stats is not None:
+                    _check_stats(c.stats[0], c.stats[1], c.stats[2], what)
+    ops.clear_pack_cache()
+
+
+@pytest.fixture(scope='module', autouse=True)
+def _report():
+    """After the rows: the largest err / cond per family and regime (what tests/numerics.py's constants were set from)."""
+    yield
+    for cls in ('split', 'fp32'):
+        keys = sorted(k for k in _WORST if k[1] == cls)
+        if not keys:
+            continue
+        print('\n%s: largest err/cond %.2e' % (cls, max(_WORST[k] for k in keys)))
+        for fam in sorted({k[0] for k in keys}):
+            print('  %-16s ' % fam + ' '.join('%s %.1e' % (reg, _WORST[(fam, cls, reg)]) for reg in REGIMES
+                                              if (fam, cls, reg) in _WORST))
