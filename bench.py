@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """Headline benchmark: depth-maps/sec of the A-TVSNet multi-view inference path.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline figure needs: it sets up (inputs, weights, ONE captured graph), runs W warm-up and K timed
+steps, writes --dump-outputs and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, `config`).
+Everything else below -- the regions with maps in flight, the five-source and all-fp32-MFMA runs, the power probe, the eager passes
+behind `roofline` / `roofline_hbm`, the committed profiles (`kernels`), `parity`, `cpu_baseline` and, with --gpus N > 1, the
+view-sharded runs -- is measured only with --full.
 
 A step = one depth map through the whole example.py pipeline (towers -> 2x stacked 3-D U-Net per source ->
 AAM1 -> refinement per source -> AAM2 -> x4 upsample + soft-argmin), inputs resident in HBM, synthetic
@@ -123,7 +129,7 @@ def parse(argv=None):
                    help='skip the secondary measurement of the same step with every convolution on the fp32 matrix cores')
     p.add_argument('--eager', action='store_true', help='issue every launch from Python instead of replaying a HIP graph')
     p.add_argument('--inflight', type=int, default=2,
-                   help='depth maps in flight per GPU (streams with one captured graph each); 1 = strictly one after the other')
+                   help='--full: depth maps in flight per GPU (streams with one captured graph each); 1 = strictly one after the other')
     p.add_argument('--parallel', choices=['maps', 'views', 'both'], default=None,
                    help='N > 1: maps = one depth map per rank (no collective), views = source views sharded inside groups; '
                         'the launcher default measures maps, then views as a secondary result of the same line')
@@ -133,6 +139,9 @@ def parse(argv=None):
                    help='no GPU: the ranks rendezvous over gloo, agree on the plan and print the line (launcher test)')
     p.add_argument('--dump-outputs', metavar='DIR', default=None,
                    help="write the timed path's output of its last timed step as DIR/<name>.npy (rank 0)")
+    p.add_argument('--full', action='store_true',
+                   help='also measure and check everything beyond the headline figure (maps in flight, other precisions and '
+                        'configurations, rooflines, parity, power, CPU baseline; N > 1: the view-sharded runs)')
     a = p.parse_args(argv)
     v, w, h, d = WORKLOADS[a.workload]
     a.custom = any(x is not None for x in (a.width, a.height, a.depths, a.views))
@@ -230,7 +239,7 @@ def launch(args, argv):
         sys.stdout.write(text)
         sys.stderr.write('bench.py: rank(s) failed: %s\n' % bad)
         return 1
-    if not args.dry and args.parallel in (None, 'both'):
+    if args.full and not args.dry and args.parallel in (None, 'both'):
         # secondary results of the same line, measured after the primary one is safe (a failure / hang there is reported
         # inside the line and on stderr, it does not cost the primary number):
         #   view_sharded       the same workload with its source views sharded inside groups (RCCL exchange in both AANets)
@@ -648,7 +657,7 @@ def top_kernels(k=5):
             rows.append((r['Name'].replace('(anonymous namespace)::', '').replace('void ', '').split('(')[0],
                          int(r['Calls']), float(r['AverageNs']) / 1e3, float(r['Percentage'])))
     rows.sort(key=lambda t: -t[3])
-    return {'source': KERNEL_STATS_FILE, 'head': profile_head(KERNEL_STATS_FILE), 'measured_in_run': False, 'command': 'rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --inflight 1',
+    return {'source': KERNEL_STATS_FILE, 'head': profile_head(KERNEL_STATS_FILE), 'measured_in_run': False, 'command': 'rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --inflight 1',
             'top': [{'kernel': n, 'calls': c, 'avg_us': round(a, 1), 'pct': round(p, 2)} for n, c, a, p in rows[:k]]}
 
 
@@ -765,8 +774,10 @@ def rank_main(args):
             # per rank: a chain of HIP graphs (the local compute between two exchanges) with the RCCL calls between
             graphed = parallel.ShardedGraphedInference(imgs, cams, args.depths, group=group)
         else:
-            # one HIP graph per depth map; `inflight` of them (own static buffers and stream each) for the timed region
-            pipe = ex.PipelinedInference(imgs, cams, args.depths, slots=max(1, args.inflight), co_resident=True)
+            # one HIP graph per depth map; the timed region replays the first.  --full: `inflight` of them (own static buffers
+            # and stream each) for the regions with maps in flight
+            slots = max(1, args.inflight) if args.full else 1
+            pipe = ex.PipelinedInference(imgs, cams, args.depths, slots=slots, co_resident=True)
             graphed = pipe.graphs[0]
 
     def eager_step(view_streams=True):
@@ -859,7 +870,7 @@ def rank_main(args):
     # SOURCE views + the reference view (flags.view_num = 5 counts the images of example/0,1: 5 images = 4 sources -- the metric's
     # N = 5; a scene with five sources is N = 6): one more pass of every per-view network, AANet modules over five views in one launch
     five = None
-    if world == 1 and graphed is not None and not args.custom and args.workload == 'cfg3' and not args.no_fp32_path:
+    if args.full and world == 1 and graphed is not None and not args.custom and args.workload == 'cfg3' and not args.no_fp32_path:
         try:
             im6, cm6 = synthetic.make_inputs(6, args.height, args.width, args.depths, seed=0)
             im6, cm6 = torch.from_numpy(im6).to(dev), torch.from_numpy(cm6).to(dev)
@@ -895,7 +906,7 @@ def rank_main(args):
     # (per-layer error against float64 below the fp32 MFMA kernel's; BASELINE configs[1] names "bf16 conv3d MFMA") -- so the
     # all-fp32-MFMA figure is printed next to it.
     split = None
-    if world == 1 and graphed is not None and not args.no_fp32_path:
+    if args.full and world == 1 and graphed is not None and not args.no_fp32_path:
         try:
             default_on = ops.cfg.split16
             ops.cfg.split16 = not default_on
@@ -923,7 +934,7 @@ def rank_main(args):
             ops.cfg.split16 = default_on
 
     power = None
-    if world == 1 and not args.no_power:
+    if args.full and world == 1 and not args.no_power:
         try:
             power = power_probe(step)
         except Exception as e:                                # noqa: BLE001
@@ -932,13 +943,15 @@ def rank_main(args):
     # the dominant kernel and the warp, timed by HIP events on their launch stream in ten eager single-stream passes
     # of the same step right after the timed region (kernels inside a replayed graph cannot be bracketed by events;
     # single stream: no other kernel shares the GPU with the one being timed)
-    ops.watch([DOMINANT, WARP])
-    for _ in range(EAGER_TIMING_PASSES):
-        eager_out = eager_step(view_streams=False)
-    watched = ops.watch(None)
+    watched, eager_out = {}, None
+    if args.full:
+        ops.watch([DOMINANT, WARP])
+        for _ in range(EAGER_TIMING_PASSES):
+            eager_out = eager_step(view_streams=False)
+        watched = ops.watch(None)
     assert torch.isfinite(out).all()
     comm = None
-    if sharded and graphed is not None and hasattr(graphed, 'timed_call'):
+    if args.full and sharded and graphed is not None and hasattr(graphed, 'timed_call'):
         comm = graphed.timed_call()              # ms of local graphs vs ms of the exchanges, this rank
     if world > 1:
         dist.barrier()
@@ -1082,20 +1095,19 @@ def rank_main(args):
                        'inflight': 1},
             'source_views_per_sec': round(n_groups * args.steps * (args.views - 1) / dt, 3),
             'latency_ms': round(1e3 * dt / args.steps, 3),
-            'pipelined': pipelined,
-            'pipelined_cu_split': pipelined_cu_split,
-            'split_operands': split,
-            'five_sources': five,
-            'roofline': roof, 'roofline_hbm': roof_hbm, 'power': power, 'kernels': top_kernels(),
+            'full': args.full,
         }
+        if args.full:
+            line.update(pipelined=pipelined, pipelined_cu_split=pipelined_cu_split, split_operands=split, five_sources=five,
+                        roofline=roof, roofline_hbm=roof_hbm, power=power, kernels=top_kernels())
         if comm is not None:
             line['exchange'] = comm
-        if not args.no_parity:
+        if args.full and not args.no_parity:
             try:
                 line['parity'] = parity_check(args, out, eager_out if (graphed is not None and not sharded) else None)
             except Exception as e:
                 line['parity'] = {'error': repr(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             try:
                 line['cpu_baseline'] = cpu_baseline(args)
             except Exception as e:                        # the baseline must never hide the GPU number

@@ -4,6 +4,9 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -81,9 +84,9 @@ def test_secondary_entries_name_their_mode_and_failures():
     assert bench.view_sharded_entry(l2, None)['ok'] is True
 
 
-def _fake_launch(monkeypatch, capsys, secondary_ok):
+def _fake_launch(monkeypatch, capsys, secondary_ok, full=True):
     """bench.launch() with the ranks replaced by canned lines: the primary `maps` run succeeds; the view-sharded
-    secondaries succeed or fail."""
+    secondaries (--full) succeed or fail."""
     sys.path.insert(0, ROOT)
     import bench
     calls = []
@@ -103,7 +106,7 @@ def _fake_launch(monkeypatch, capsys, secondary_ok):
 
     monkeypatch.setattr(bench, '_run_ranks', fake_run_ranks)
     monkeypatch.setattr(bench, 'visible_gpus', lambda *a, **k: 8)
-    argv = ['--gpus', '8', '--steps', '3', '--warmup', '1']
+    argv = ['--gpus', '8', '--steps', '3', '--warmup', '1'] + (['--full'] if full else [])
     rc = bench.launch(bench.parse(argv), argv)
     out = capsys.readouterr()
     lines = [ln for ln in out.out.splitlines() if ln.startswith('{')]
@@ -138,3 +141,39 @@ def test_launcher_promotes_the_view_sharded_numbers(monkeypatch, capsys):
     assert abs(line['view_sharded_value'] - 1e3 / 14.0) < 1e-9
     # the three secondary runs: views at N, cfg4 on one rank, cfg4 view-sharded at N
     assert [c[0] for c in calls] == [8, 8, 1, 8]
+
+
+def test_plain_launch_measures_the_primary_run_only(monkeypatch, capsys):
+    """Without --full the launcher starts only the N ranks of the primary run and prints their line: no view-sharded or
+    cfg4 runs, no secondary keys, and a secondary that would fail cannot fail the run."""
+    rc, line, err, calls = _fake_launch(monkeypatch, capsys, secondary_ok=False, full=False)
+    assert rc == 0 and line['value'] == 280.0
+    assert len(calls) == 1 and calls[0][0] == 8 and '--full' not in calls[0][1]
+    assert not any(k.startswith('view_sharded') for k in line) and 'failed' not in line
+
+
+def test_full_is_off_by_default_and_reaches_the_ranks(monkeypatch, capsys):
+    """--full is opt-in; given to the launcher, every rank of every run it starts gets it too."""
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse([]).full is False and bench.parse(['--full']).full is True
+    rc, line, err, calls = _fake_launch(monkeypatch, capsys, secondary_ok=True, full=True)
+    assert rc == 0 and all('--full' in argv for _, argv in calls)
+
+
+@pytest.mark.gpu
+def test_plain_run_prints_the_headline_only(tmp_path, cuda):
+    """A plain single-GPU run times its steps, dumps what the timed path returned and prints the headline: nothing that
+    --full measures (maps in flight, other precisions, rooflines, parity, power, CPU baseline) is in its line."""
+    dump = tmp_path / 'out'
+    rc, line, err = _run('--gpus', '1', '--workload', 'cfg2', '--steps', '2', '--warmup', '1', '--dump-outputs', str(dump))
+    assert rc == 0, err
+    assert line['full'] is False and line['ok'] is True and (line['steps'], line['warmup']) == (2, 1)
+    assert line['unit'] == 'depth-maps/sec' and line['higher_is_better'] is True and line['dtype'].startswith('f32')
+    assert line['value'] > 0 and abs(line['value'] * line['ms_per_step'] / 1e3 - 1) < 1e-2
+    moved = {'pipelined', 'pipelined_cu_split', 'split_operands', 'five_sources', 'roofline', 'roofline_hbm', 'power', 'kernels',
+             'parity', 'cpu_baseline', 'exchange'}
+    assert not moved & set(line)
+    got = np.load(str(dump / 'depth.npy'))
+    want = np.load(os.path.join(ROOT, 'tests', 'golden', 'fullsize_cfg2.npz'))['depth']
+    assert got.shape == (1, 512, 640, 1) and float(np.mean(np.abs(got.reshape(want.shape) - want) / np.abs(want))) <= 1e-3

@@ -22,7 +22,7 @@ def stamp(name):
 stats = os.path.join(src, 'prof', 'bench_kernel_stats.csv')
 if os.path.exists(stats):
     with open(stats) as f, open(os.path.join(prof, 'round6_bench_kernel_stats.csv'), 'w') as g:
-        g.write('# head %s  (rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline '
+        g.write('# head %s  (rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline '
                 '--no-fp32-path --no-power; 36 depth maps incl. warm-up and the eager timing passes)\n' % head)
         g.write(f.read())
     stamp('round6_bench_kernel_stats.csv')

@@ -7,7 +7,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for v in 1 0; do
   export $var=$v
-  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof$v -o bench -- python3 $root/bench.py --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline --no-fp32-path --no-power > $out/bench$v.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof$v -o bench -- python3 $root/bench.py --full --steps 20 --warmup 5 --inflight 1 --no-cpu-baseline --no-fp32-path --no-power > $out/bench$v.log 2>&1
   cp $(find $out/prof$v -name "*kernel_stats.csv" | head -1) $out/stats$v.csv
   rm -rf $out/prof$v
 done

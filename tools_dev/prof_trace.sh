@@ -5,7 +5,7 @@ root=$PWD
 out=$root/gpurun_out/$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $out/prof -o bench -- python3 $root/bench.py --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-fp32-path --no-power > $out/bench.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $out/prof -o bench -- python3 $root/bench.py --full --steps 3 --warmup 1 --inflight 1 --no-cpu-baseline --no-fp32-path --no-power > $out/bench.log 2>&1
 f=$(find $out/prof -name "*kernel_trace.csv" | head -1)
 python3 - "$f" "$out/last_map.csv" <<'P'
 import csv, sys
