@@ -18,13 +18,14 @@ consume them; ``--fusibile_exe_path`` is accepted and ignored.
 from __future__ import print_function
 
 import argparse
+import io
 import os
 import shutil
 import time
 
 import numpy as np
 
-from .preprocess import load_cam, load_pfm, write_pfm
+from .preprocess import cam_text, load_cam, load_pfm, write_pfm
 from ..tools import ply
 
 
@@ -210,6 +211,132 @@ def fuse_views(Ps, depths, normals, images_bgr, disp_thresh, normal_thresh, num_
         # (char)(int) of channels 2, 1, 0 of the averaged texture (fusibile/displayUtils.h:109-111)
         cols.append(np.stack([t[:, 2], t[:, 1], t[:, 0]], -1).astype(np.int32).astype(np.uint8))
     return np.concatenate(pts, 0), np.concatenate(cols, 0)
+
+
+# depth_map_fusion's normal threshold: 360 degrees, in radians as it passes it to fuse_views
+NORMAL_THRESHOLD = 360 * np.pi / 180.0
+
+
+def camera_row(cam):
+    """The 28 floats fuse_views packs for a camera that eval_pointcloud writes with write_cam, derived the way the file pipeline
+    derives them -- write_cam's text, load_cam, projection_matrix, the .P file (str() of each float64 value, which float() reads
+    back exactly) and pack_cameras -- in memory."""
+    return pack_cameras([projection_matrix(load_cam(io.StringIO(cam_text(cam))))])[0]
+
+
+def _plane(t, what):
+    """A depth / probability map as (rows, cols): the network's (1, rows, cols, 1) or any squeezable form of it."""
+    while t.ndim > 2 and t.shape[0] == 1:
+        t = t[0]
+    while t.ndim > 2 and t.shape[-1] == 1:
+        t = t[..., 0]
+    if t.ndim != 2:
+        raise ValueError('SceneFusion.add: %s must be a (rows, cols) map, got shape %s' % (what, tuple(t.shape)))
+    return t
+
+
+class SceneFusion(object):
+    """The point-cloud stage of a scene on the device, without the files: every depth map is staged into a scene-resident slab as
+    it is finished (`add`, atvs_fusion_stage_f32: the inverse-depth step of eval_pointcloud._write_map, probability_filter and
+    fake_colmap_normal), and `run` fuses all reference cameras in one pass (atvs_fusibile_scene) into the points and colours
+    fuse_views computes on the same maps, in the same order.  The cameras are ordered by `out_index` ascending, as the sorted
+    2333__%08d folders of depth_map_fusion order them.
+
+        fusion = SceneFusion(len(maps), rows, cols, device)
+        fusion.add(out_index, depth, prob, image_bgr_u8, cam)          # per map, any order
+        fusion.write_ply(path)                                         # = run() + tools/ply.write_ply
+
+    depth, prob: the network's outputs (host numpy or device tensors, any squeezable form of (rows, cols)); image_bgr_u8: the
+    1/4-scale reference image (rows, cols, 3) uint8; cam: the (2,4,4) camera eval_pointcloud writes with write_cam.  `stream`:
+    the stream the staging is enqueued on (default: the current one); run() orders itself after every staging."""
+
+    def __init__(self, n_maps, rows, cols, device=None, prob_threshold=0.8, disp_threshold=0.01, num_consistent=2,
+                 inverse_depth=None):
+        import torch
+        from ..flags import FLAGS
+        for name, v in (('n_maps', n_maps), ('rows', rows), ('cols', cols)):
+            if int(v) != v or int(v) <= 0:
+                raise ValueError('SceneFusion: %s must be a positive integer, got %r' % (name, v))
+        self.n_maps, self.rows, self.cols = int(n_maps), int(rows), int(cols)
+        self.device = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+        if self.device.type not in ('cuda', 'meta'):         # meta: the host code alone (shape checks, camera order), no launch
+            raise RuntimeError('SceneFusion runs on the MI355X only (no CPU fallback), got device %s' % self.device)
+        self.prob_threshold, self.disp_threshold = float(prob_threshold), float(disp_threshold)
+        self.num_consistent = int(num_consistent)
+        self.inverse_depth = FLAGS.inverse_depth if inverse_depth is None else bool(inverse_depth)
+        shape = (self.n_maps, self.rows, self.cols, 4)
+        self.nd = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self.img = torch.empty(shape, dtype=torch.float32, device=self.device)
+        self.cams = np.zeros((self.n_maps, 28), np.float32)
+        self.index, self.events = [], []          # out_index and staging event of each slot, in add() order
+        self.result = None
+
+    def _check_size(self, what, shape, want):
+        if tuple(int(s) for s in shape) != want:
+            raise RuntimeError('depth maps %s and %s %s differ in size: one scene fuses maps of one size'
+                               % ((self.rows, self.cols), what, tuple(int(s) for s in shape)))
+
+    def add(self, out_index, depth, prob, image_bgr_u8, cam, stream=None):
+        import torch
+        from .. import ops
+        out_index = int(out_index)
+        if len(self.index) == self.n_maps:
+            raise ValueError('SceneFusion.add: all %d slots are taken' % self.n_maps)
+        if out_index in self.index:
+            raise ValueError('SceneFusion.add: map %d was added before' % out_index)
+        depth, prob = _plane(depth, 'depth'), _plane(prob, 'prob')
+        self._check_size('depth map', depth.shape, (self.rows, self.cols))
+        self._check_size('probability map', prob.shape, (self.rows, self.cols))
+        self._check_size('image', tuple(image_bgr_u8.shape)[:2], (self.rows, self.cols))
+        row = camera_row(cam)
+        slot = len(self.index)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device) if isinstance(a, np.ndarray) else a    # noqa: E731
+        stage = lambda: ops.fusion_stage(up(depth), up(prob), up(image_bgr_u8), self.inverse_depth, self.prob_threshold,  # noqa: E731
+                                         self.nd[slot], self.img[slot])
+        ev = None
+        if self.device.type == 'meta':
+            stage()
+        else:
+            st = torch.cuda.current_stream(self.device) if stream is None else stream
+            with torch.cuda.stream(st):
+                stage()
+                ev = torch.cuda.Event()
+                ev.record(st)
+        self.cams[slot] = row
+        self.index.append(out_index)
+        self.events.append(ev)
+        self.result = None
+
+    def order(self):
+        """The slots in fusion order: by out_index ascending."""
+        return np.argsort(np.asarray(self.index, np.int64), kind='stable')
+
+    def run(self):
+        """-> (points (M,3) float32, colors (M,3) uint8 r,g,b) as numpy arrays: fuse_views of the staged maps."""
+        import torch
+        from .. import ops
+        k = len(self.index)
+        if k == 0:
+            raise RuntimeError('SceneFusion.run: no depth map was added')
+        if self.result is None:
+            cur = torch.cuda.current_stream(self.device)
+            for ev in self.events:
+                cur.wait_event(ev)
+            order = self.order()
+            nd, img = self.nd[:k], self.img[:k]
+            if not np.array_equal(order, np.arange(k)):
+                idx = torch.from_numpy(order).to(self.device)
+                nd, img = nd.index_select(0, idx), img.index_select(0, idx)
+            cams = torch.from_numpy(np.ascontiguousarray(self.cams[:k][order])).to(self.device)
+            pts, cols = ops.fusibile_scene(cams, nd, img, self.disp_threshold, NORMAL_THRESHOLD, self.num_consistent)
+            self.result = (pts.cpu().numpy(), cols.cpu().numpy())
+        return self.result
+
+    def write_ply(self, path):
+        """run() into a binary PLY at `path` (the layout depth_fusion.main copies to <dense_folder>/final3d_model.ply)."""
+        pts, cols = self.run()
+        ply.write_ply(path, pts, cols)
+        return len(pts)
 
 
 def _imread_bgr(path):

@@ -21,6 +21,7 @@ import torch
 from .. import variables
 from ..flags import FLAGS
 from ..tools.common import Notify
+from . import depth_fusion
 from . import example
 from . import scene
 from .preprocess import (center_image, crop_mvs_input, crop_window, gen_pipeline_mvs_list, load_cam, scale_camera, scale_image,
@@ -296,16 +297,21 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
     plt.imsave(stem + '.png', disp_up, cmap='viridis')
 
 
-def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True):
+def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
-    background thread (write_thread=False: in this thread, same bytes)."""
+    background thread (write_thread=False: in this thread, same bytes).
+    fuse: None, or dict(prob_threshold=, disp_threshold=, num_consistent=): every map is also staged on the device as it is
+    finished (depth_fusion.SceneFusion) and each scene ends with <savepath>/<scene>/final3d_model.ply, the point cloud
+    depth_fusion.main makes from the written files.  map_files=False (with fuse only): no per-map files."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     if scene_cache and not use_graph:
         raise ValueError('--scene_cache replays captured graphs: it cannot be combined with --eager')
+    if not map_files and fuse is None:
+        raise ValueError('map_files=False (--no_map_files) needs fuse (--fuse): the run would write nothing')
     example._load_weights()
     torch.cuda.set_device(FLAGS.gpu_id)          # every kernel launches on the current device's stream
     device = torch.device('cuda:%d' % FLAGS.gpu_id)
@@ -329,21 +335,43 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
                 run.times['upload'], run.gpu_ms = 0.0, []
             start_time = time.time()
             queued = []                  # host-side data of the depth maps in flight, in submission order
+            fusion = []                  # --fuse: this scene's SceneFusion, made at its first map (the maps' size)
+
+            def stage(out_index, depth, prob, image, cams_data, stream=None):
+                if not fusion:
+                    rows, cols = image.shape[:2]
+                    fusion.append(depth_fusion.SceneFusion(len(mvs_list), rows, cols, device, **fuse))
+                fusion[0].add(out_index, depth, prob, image, cams_data[0, 0], stream=stream)
 
             def finish():
                 t0 = time.time()
                 if scene_cache:
                     ticket, cams_data, out_index = queued.pop(0)
-                    # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
-                    outputs = [example.check_finite(o.numpy(), 'a network output', flag=False) for o in run.result(ticket, host=True)]
-                    image_raw = run.reference_image(ticket)
+                    if fuse is None:
+                        # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
+                        outputs = [example.check_finite(o.numpy(), 'a network output', flag=False)
+                                   for o in run.result(ticket, host=True)]
+                        image_raw = run.reference_image(ticket)
+                    else:
+                        # the slot's output buffers are overwritten by its next submission: staged from what result() returned
+                        # (an overflowed map's fp32 rerun), on the slot's stream, before submit() can reuse the slot
+                        dev_out = run.result(ticket)
+                        st = run.slot_stream(ticket)
+                        stage(out_index, dev_out[0], dev_out[2], run.reference_image(ticket, host=False), cams_data, stream=st)
+                        with torch.cuda.stream(st):
+                            outputs = [example.check_finite(o.cpu().numpy(), 'a network output', flag=False) for o in dev_out]
+                            image_raw = run.reference_image(ticket)
                 else:
                     image_data_raw, cams_data, out_index = queued.pop(0)
                     outputs = run.fetch()
                     image_raw = image_data_raw[0, 0]
+                    if fuse is not None:          # before _write_map's inverse-depth step rewrites the host maps in place
+                        stage(out_index, outputs[0], outputs[2], image_raw, cams_data)
                 t1 = time.time()
                 job = lambda: _write_map(output_folder, out_index, outputs, image_raw, cams_data[0, 0], plt)     # noqa: E731
-                if scene_cache:
+                if not map_files:
+                    pass
+                elif scene_cache:
                     writer(job)
                 else:
                     job()
@@ -390,6 +418,12 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
             scene_runtime = time.time() - start_time       # wall clock of the scene (the reference sums sess.run times)
             with open(os.path.join(savepath_current, 'zz_runtime.txt'), "w") as text_file:
                 text_file.write('runtime ' + str(scene_runtime))
+            if fusion:
+                # after every map's result: the slots are idle; the fusion runs on this thread's (ordinary) stream
+                t0 = time.time()
+                n_points = fusion.pop().write_ply(os.path.join(savepath_current, 'final3d_model.ply'))
+                TIMES['fuse'] = time.time() - t0
+                print(Notify.INFO, '%s: %d fused points' % (image_info[2], n_points), Notify.ENDC)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
         if scene_cache:
@@ -407,8 +441,12 @@ def main(scene_list=None, base_path='eth3d/'):
     for scene in scene_list:
         folder = os.path.join(FLAGS.data_root, base_path + scene)
         image_infos.append([[folder, os.path.join(folder, 'images'), scene], 'preprocessed'])
+    fuse = None
+    if getattr(FLAGS, 'fuse', False):
+        fuse = dict(prob_threshold=FLAGS.prob_threshold, disp_threshold=FLAGS.disp_threshold, num_consistent=FLAGS.num_consistent)
     run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
-                scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False))
+                scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
+                map_files=not getattr(FLAGS, 'no_map_files', False))
 
 
 def cli(argv=None):
@@ -433,9 +471,19 @@ def cli(argv=None):
                         help='prepare each image on the GPU and run the 2-D towers on it once per scene; maps are assembled from '
                              'the cached features (atvsnet/scene.py); files are written by a background thread')
     parser.add_argument('--sync_write', action='store_true', help='--scene_cache: write the files in the driver thread')
+    parser.add_argument('--fuse', action='store_true',
+                        help='stage every depth map on the GPU as it is finished and end each scene with <savepath>/<scene>/'
+                             'final3d_model.ply, the point cloud depth_fusion makes from the written files (depth_fusion.SceneFusion)')
+    parser.add_argument('--prob_threshold', type=float, default=0.8, help='--fuse: depth_fusion --prob_threshold')
+    parser.add_argument('--disp_threshold', type=float, default=0.01, help='--fuse: depth_fusion --disp_threshold')
+    parser.add_argument('--num_consistent', type=float, default=2, help='--fuse: depth_fusion --num_consistent')
+    parser.add_argument('--no_map_files', action='store_true',
+                        help='--fuse: do not write the per-map files of depths_atvsnet/ (zz_runtime.txt is still written)')
     args = parser.parse_args(argv)
     if args.eager and args.scene_cache:
         parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
+    if args.no_map_files and not args.fuse:
+        parser.error('--no_map_files needs --fuse: the run would write nothing')
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False
     for k, v in vars(args).items():

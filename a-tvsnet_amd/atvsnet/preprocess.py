@@ -165,14 +165,19 @@ def load_cam(file, interval_scale=1):
     return cam
 
 
-def write_cam(file, cam):
-    """The text form load_cam reads (31 words)."""
+def cam_text(cam):
+    """The text form load_cam reads (31 words): every value through str(), as the reference writes it."""
     row = lambda values: ''.join(str(v) + ' ' for v in values) + '\n'           # noqa: E731
     text = 'extrinsic\n' + ''.join(row(cam[0][i][:4]) for i in range(4)) + '\n'
     text += 'intrinsic\n' + ''.join(row(cam[1][i][:3]) for i in range(3))
     text += '\n' + ' '.join(str(cam[1][3][k]) for k in range(4)) + '\n'
+    return text
+
+
+def write_cam(file, cam):
+    """cam_text(cam) into `file`."""
     with open(file, 'w') as f:
-        f.write(text)
+        f.write(cam_text(cam))
 
 
 def load_pfm(file):

@@ -356,11 +356,19 @@ class SceneInference(object):
         self.gpu_ms.append(start.elapsed_time(end))
         return out
 
-    def reference_image(self, ticket):
-        """The reference view's sample_scale uint8 BGR image of `ticket`'s map (host numpy; after result())."""
+    def reference_image(self, ticket, host=True):
+        """The reference view's sample_scale uint8 BGR image of `ticket`'s map (host numpy; after result()).  host=False: the
+        device tensor, valid until the slot's next submission -- use it on slot_stream(ticket)."""
         p, s = ticket
+        if not host:
+            return self.slot_quarter[(id(p), s)]
         with torch.cuda.stream(p.streams[s]):
             return self.slot_quarter[(id(p), s)].cpu().numpy()
+
+    def slot_stream(self, ticket):
+        """The stream `ticket`'s map runs on: work enqueued there after result() precedes the slot's next submission."""
+        p, s = ticket
+        return p.streams[s]
 
     def _fp32_map(self, p, s):
         """The map now in slot s, computed entirely on the fp32 kernels from the uint8 images (towers included)."""

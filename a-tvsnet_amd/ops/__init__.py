@@ -32,5 +32,6 @@ from .convolution import (SplitVolume, _DECONV_OFFSETS, _deconv_virtual_kernel, 
     conv3d_transpose_s2, conv_siblings, conv_split, conv_split_into_plane, conv_split_siblings, deconv_sum_ok,
     photo_pieces_ok, planar_concat_ok, refine_stems, siblings_ok)      # noqa: F401
 from .prepare import (ViewPlan, prepare_taps, prepare_view, prepare_workspace, resize_u8_host, view_plan)      # noqa: F401
-from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, divide, fusibile)      # noqa: F401
+from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, divide, fusibile, fusibile_scene,
+    fusion_stage)      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

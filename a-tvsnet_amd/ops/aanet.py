@@ -1,11 +1,13 @@
 """AANet aggregation (one launch per module, or score convolution + combine, or the view-sharded partial forms) and the depth-map
-fusion entry point (after the hot path).
+fusion entry points (after the hot path: per reference camera, and the whole scene with its staging).
 """
 
 import ctypes
 
+import torch
+
 from .. import _lib
-from .base import _Timed, _call, _dev_ok, _new, _p, _ptr_array, _stream, cfg
+from .base import _ERR, _Timed, _call, _dev_ok, _new, _p, _ptr_array, _stream, cfg
 from .packing import _abi_pack, split_on
 
 
@@ -64,3 +66,75 @@ def fusibile(cams, normals_depths, images, ref, disp_thresh, normal_thresh, num_
         _call('atvs_fusibile', _p(cams), _p(normals_depths), _p(images), N, int(ref), rows, cols, ctypes.c_float(disp_thresh),
               ctypes.c_float(normal_thresh), int(num_consistent), _p(coord), _p(normal), _p(tex), _p(created), _stream())
     return coord, normal, tex, created
+
+
+def _fusion_args(*specs):
+    """Validation of a fusion entry point's tensor arguments before any launch, specs = (tensor, name, dtype, shape): first every
+    dtype, shape and layout, then the devices -- the current device, or `meta` for all of them (shape checks only, no launch).
+    -> True when the kernel is to be launched."""
+    for t, name, dtype, shape in specs:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s: expected a tensor, got %s' % (name, type(t).__name__))
+        if t.dtype != dtype:
+            raise TypeError('%s: expected %s, got %s' % (name, dtype, t.dtype))
+        if t.dim() != len(shape) or any(int(d) != s for d, s in zip(t.shape, shape)):
+            raise ValueError('%s: expected shape %s, got %s' % (name, tuple(shape), tuple(t.shape)))
+        if not t.is_contiguous():
+            raise ValueError('%s: must be contiguous' % name)
+    kinds = set(t.device.type for t, _, _, _ in specs)
+    if kinds == {'meta'}:
+        return False
+    if 'meta' in kinds:
+        raise RuntimeError('mixing meta and device tensors')
+    for t, name, _, _ in specs:
+        if t.device.type != 'cuda':
+            raise RuntimeError('%s: the fusion kernels run on the MI355X only (no CPU fallback), got a tensor on %s' % (name, t.device))
+        if t.device.index != torch.cuda.current_device():
+            raise RuntimeError('%s: on %s, the launch goes to the current device cuda:%d' % (name, t.device,
+                                                                                              torch.cuda.current_device()))
+    return True
+
+
+def fusion_stage(depth, prob, bgr, inverse_depth, prob_thresh, nd_out, img_out):
+    """One finished depth map into its slot of a scene's fusion slab (atvs_fusion_stage_f32): depth, prob (rows, cols) float32,
+    bgr (rows, cols, 3) uint8 -> nd_out (rows, cols, 4) = (normal, filtered depth), img_out (rows, cols, 4) = (b, g, r, 0), both
+    float32 and written in place (typically rows of a (N, rows, cols, 4) slab).  On the current stream."""
+    if not isinstance(depth, torch.Tensor) or depth.dim() != 2:
+        raise ValueError('fusion_stage: depth must be a (rows, cols) tensor')
+    rows, cols = (int(s) for s in depth.shape)
+    if _fusion_args((depth, 'depth', torch.float32, (rows, cols)), (prob, 'prob', torch.float32, (rows, cols)),
+                    (bgr, 'bgr', torch.uint8, (rows, cols, 3)), (nd_out, 'nd_out', torch.float32, (rows, cols, 4)),
+                    (img_out, 'img_out', torch.float32, (rows, cols, 4))):
+        _call('atvs_fusion_stage_f32', _p(depth), _p(prob), _p(bgr), rows, cols, int(bool(inverse_depth)),
+              ctypes.c_float(prob_thresh), _p(nd_out), _p(img_out), _stream())
+    return nd_out, img_out
+
+
+def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num_consistent):
+    """Every reference camera of the slab fused in one pass, the host filter of fuse_views applied and the kept points compacted on
+    the device (atvs_fusibile_scene).  cams (N,28), normals_depths / images (N,rows,cols,4) float32 -> (points (M,3) float32,
+    colors (M,3) uint8 r,g,b) on the device, camera-major and row-major as fuse_views concatenates them.  Reads the count back
+    (one synchronisation of the current stream)."""
+    if not isinstance(normals_depths, torch.Tensor) or normals_depths.dim() != 4:
+        raise ValueError('fusibile_scene: normals_depths must be a (N, rows, cols, 4) tensor')
+    N, rows, cols, _ = (int(s) for s in normals_depths.shape)
+    if not _fusion_args((cams, 'cams', torch.float32, (N, 28)), (normals_depths, 'normals_depths', torch.float32, (N, rows, cols, 4)),
+                        (images, 'images', torch.float32, (N, rows, cols, 4))):
+        raise RuntimeError('fusibile_scene: the number of points is only known after a launch (got meta tensors)')
+    lib = _lib.lib()
+    nbytes = ctypes.c_long(0)
+    rc = lib.atvs_fusibile_scene_scratch_size(N, rows, cols, ctypes.byref(nbytes))
+    if rc != 0:
+        raise RuntimeError('atvs_fusibile_scene_scratch_size failed: %s (%d) for %d maps of %dx%d' % (_ERR.get(rc, 'unknown'), rc, N,
+                                                                                                      cols, rows))
+    dev = normals_depths.device
+    capacity = N * rows * cols
+    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    points = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    _call('atvs_fusibile_scene', _p(cams), _p(normals_depths), _p(images), N, rows, cols, ctypes.c_float(disp_thresh),
+          ctypes.c_float(normal_thresh), int(num_consistent), _p(scratch), ctypes.c_long(scratch.numel()), _p(points), _p(colors),
+          ctypes.c_long(capacity), _p(count), _stream())
+    m = int(count.item())
+    return points[:m], colors[:m]

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 45
+#define ATVS_ABI_VERSION 46
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -630,6 +630,30 @@ int atvs_divide(const float* num, const float* den, float* out, long n, atvs_str
 int atvs_fusibile(const float* cams, const float* normals_depths, const float* images, int nviews, int ref, int rows,
                   int cols, float disp_thresh, float normal_thresh, int num_consistent, float* coord, float* normal,
                   float* texture, float* created, atvs_stream_t stream);
+
+/* One finished depth map -> its slot of a scene's fusion slab (csrc/fusion_scene.hip): per pixel what the file pipeline computes
+ * on the host -- eval_pointcloud._write_map (inverse_depth = 1: a value <= 0 becomes +inf, then 1 / value, correctly rounded),
+ * depth_fusion.probability_filter (depth := 0 where prob < prob_thresh) and fake_colmap_normal (each normal component
+ * float32(1) / float32(1.732050808) where the depth is > 0, else +0).
+ * depth, prob (rows, cols) floats; bgr (rows, cols, 3) uint8, the 1/4-scale reference image.  Outputs: nd_out (rows, cols, 4)
+ * = (nx, ny, nz, depth) and img_out (rows, cols, 4) = (b, g, r, 0), the two textures atvs_fusibile / atvs_fusibile_scene read.
+ * inverse_depth not 0 / 1: ATVS_ERR_ARG. */
+int atvs_fusion_stage_f32(const float* depth, const float* prob, const unsigned char* bgr, int rows, int cols,
+                          int inverse_depth, float prob_thresh, float* nd_out, float* img_out, atvs_stream_t stream);
+
+/* Bytes of the scratch atvs_fusibile_scene needs for nviews maps of rows x cols (HOST call). */
+int atvs_fusibile_scene_scratch_size(int nviews, int rows, int cols, long* bytes);
+
+/* atvs_fusibile for EVERY reference camera 0 .. nviews-1 in one pass, followed by the host filter of fusibile.cu:309
+ * (depth_fusion.fuse_views: keep a pixel whose point is created and has three non-zero coordinates) and a deterministic
+ * compaction (three launches on `stream`: count, scan, scatter; no atomics).  Each pixel's arithmetic is atvs_fusibile's.
+ * cams, normals_depths, images: as for atvs_fusibile.  scratch: atvs_fusibile_scene_scratch_size bytes (device).
+ * Outputs: points (capacity, 3) floats and colors (capacity, 3) uint8 r, g, b = (uint8)(int) of texture channels 2, 1, 0, the
+ * first *n_points rows written, camera-major and row-major within a camera; n_points: ONE device int.
+ * capacity < nviews * rows * cols, a short scratch, or nviews * rows * cols beyond int: ATVS_ERR_SHAPE. */
+int atvs_fusibile_scene(const float* cams, const float* normals_depths, const float* images, int nviews, int rows, int cols,
+                        float disp_thresh, float normal_thresh, int num_consistent, void* scratch, long scratch_bytes,
+                        float* points, unsigned char* colors, long capacity, int* n_points, atvs_stream_t stream);
 
 
 /* ---- 3x3x3 stride-2 SAME transposed convolution to 8 or 16 channels, all 8 output parity classes per staged input tile
