@@ -1,4 +1,4 @@
-"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in eight modules --
+"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in nine modules --
 
     base      ctypes plumbing, the dispatch switches (`cfg`, `configure`), launch timing
     packing   weights in operand order + their cache, tap lists, the chunk-planar layout
@@ -8,6 +8,7 @@
     convolution  `conv()` and the composite forms (SplitVolume, siblings, stems, transposed convolution)
     aanet     AANet aggregation, depth-map fusion
     prepare   the scene driver's view preparation (uint8 image -> network input, 1/4 image)
+    colmap    COLMAP model import: per-image depth range, co-visibility matrix
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -34,4 +35,5 @@ from .convolution import (SplitVolume, _DECONV_OFFSETS, _deconv_virtual_kernel, 
 from .prepare import (ViewPlan, prepare_taps, prepare_view, prepare_workspace, resize_u8_host, view_plan)      # noqa: F401
 from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, divide, fusibile, fusibile_scene,
     fusion_stage)      # noqa: F401
+from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

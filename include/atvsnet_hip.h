@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 46
+#define ATVS_ABI_VERSION 47
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -716,6 +716,29 @@ int atvs_conv_c16b_sum_f32(const float* x0, const float* params0, const float* x
 int atvs_prepare_resize_u8(const unsigned char* src, int h, int w, unsigned char* dst, int H, int W, const int* ytap,
                            const int* xtap, unsigned long long* sums, atvs_stream_t stream);
 int atvs_prepare_center(const unsigned char* x, long pixels, const unsigned long long* sums, float* y, atvs_stream_t stream);
+
+/* COLMAP model import (atvsnet/colmap.py, csrc/colmap.hip).  Pointers are device pointers to the types named.
+ *
+ * atvs_colmap_depth_range: ColmapSparse.estimate_max_disparities (atvsnet/colmap_helpers.py:317-331) without its sort.  points
+ * (n_points, 3) doubles X, Y, Z; cams (n_images, 18) doubles per image = R (3x3, row-major, world to camera), t (3), fx, fy, cx,
+ * cy, width, height.  For every (image, point) pair, in float64: c_k = ((R_k0 X + R_k1 Y) + R_k2 Z) + t_k, x = (c_0 / c_2) fx + cx,
+ * y = (c_1 / c_2) fy + cy, d = 1 / c_2; the point is in view when x >= 0, x < width, y >= 0, y < height and d > 0 (:322-327).
+ * Outputs per image: n_in_view (int), d_lo = the in-view disparities' order statistic of rank int(n * (1 - percentile)) and d_hi
+ * that of rank int(n * percentile) (:328-331 before the stretch; ranks formed in double as Python forms them), both exact (a radix
+ * select on the bit patterns, integer atomics only: deterministic); 0.0 where n is 0.  scratch:
+ * atvs_colmap_depth_range_scratch_size bytes (device; O(n_images), no images x points buffer).  Sixteen launches on `stream`.
+ * percentile outside (0, 1): ATVS_ERR_ARG; n_images outside [1, 524280], n_points beyond int or a short scratch: ATVS_ERR_SHAPE. */
+int atvs_colmap_depth_range_scratch_size(int n_images, long* bytes);
+int atvs_colmap_depth_range(const double* points, long n_points, const double* cams, int n_images, double percentile, void* scratch,
+                            long scratch_bytes, int* n_in_view, double* d_lo, double* d_hi, atvs_stream_t stream);
+
+/* atvs_colmap_covisibility: the shared-point counts of ColmapSparse.generate_neighbor_list (colmap_helpers.py:333-347,
+ * len(set_i & set_j)).  Tracks in CSR form: offsets (n_tracks + 1) int32, observers (n_obs) int32 image indices; each track lists
+ * the DISTINCT images observing one 3-D point.  covis (n_images, n_images) int32 is zeroed, then every ordered pair (i, j), i != j,
+ * of every track adds one to covis[i][j] (integer atomics; a track's pairs spread over a wave's lanes).  Tracks with an index
+ * outside the arrays add nothing.  n_images above 16384 (a matrix beyond 1 GiB) or below 1: ATVS_ERR_SHAPE. */
+int atvs_colmap_covisibility(const int* offsets, const int* observers, int n_tracks, int n_obs, int n_images, int* covis,
+                             atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
