@@ -22,6 +22,7 @@ from .. import variables
 from ..flags import FLAGS
 from ..tools.common import Notify
 from . import depth_fusion
+from . import eval_cloud
 from . import example
 from . import scene
 from .preprocess import (center_image, crop_mvs_input, crop_window, gen_pipeline_mvs_list, load_cam, scale_camera, scale_image,
@@ -297,13 +298,16 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
     plt.imsave(stem + '.png', disp_up, cmap='viridis')
 
 
-def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True):
+def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
+                gt_ply=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
     fuse: None, or dict(prob_threshold=, disp_threshold=, num_consistent=): every map is also staged on the device as it is
     finished (depth_fusion.SceneFusion) and each scene ends with <savepath>/<scene>/final3d_model.ply, the point cloud
-    depth_fusion.main makes from the written files.  map_files=False (with fuse only): no per-map files."""
+    depth_fusion.main makes from the written files.  map_files=False (with fuse only): no per-map files.
+    gt_ply (with fuse only): ground-truth PLY paths; each scene's fused points, as the PLY stores them, are scored against them
+    (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
@@ -312,6 +316,12 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         raise ValueError('--scene_cache replays captured graphs: it cannot be combined with --eager')
     if not map_files and fuse is None:
         raise ValueError('map_files=False (--no_map_files) needs fuse (--fuse): the run would write nothing')
+    if gt_ply and fuse is None:
+        raise ValueError('gt_ply (--gt_ply) needs fuse (--fuse): there is no point cloud to score')
+    gt_points = None
+    if gt_ply:
+        from ..tools.ply import read_ply_points
+        gt_points = np.concatenate([read_ply_points(p) for p in gt_ply], 0)
     example._load_weights()
     torch.cuda.set_device(FLAGS.gpu_id)          # every kernel launches on the current device's stream
     device = torch.device('cuda:%d' % FLAGS.gpu_id)
@@ -421,8 +431,16 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
             if fusion:
                 # after every map's result: the slots are idle; the fusion runs on this thread's (ordinary) stream
                 t0 = time.time()
-                n_points = fusion.pop().write_ply(os.path.join(savepath_current, 'final3d_model.ply'))
+                scene_fusion = fusion.pop()
+                n_points = scene_fusion.write_ply(os.path.join(savepath_current, 'final3d_model.ply'))
                 TIMES['fuse'] = time.time() - t0
+                if gt_points is not None:
+                    t0 = time.time()
+                    points = scene_fusion.run()[0].copy()
+                    points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
+                    eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'),
+                                          eval_cloud.evaluate(points, gt_points, device=device))
+                    TIMES['cloud_eval'] = time.time() - t0
                 print(Notify.INFO, '%s: %d fused points' % (image_info[2], n_points), Notify.ENDC)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
@@ -446,7 +464,7 @@ def main(scene_list=None, base_path='eth3d/'):
         fuse = dict(prob_threshold=FLAGS.prob_threshold, disp_threshold=FLAGS.disp_threshold, num_consistent=FLAGS.num_consistent)
     run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
                 scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
-                map_files=not getattr(FLAGS, 'no_map_files', False))
+                map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None)
 
 
 def cli(argv=None):
@@ -479,11 +497,17 @@ def cli(argv=None):
     parser.add_argument('--num_consistent', type=float, default=2, help='--fuse: depth_fusion --num_consistent')
     parser.add_argument('--no_map_files', action='store_true',
                         help='--fuse: do not write the per-map files of depths_atvsnet/ (zz_runtime.txt is still written)')
+    parser.add_argument('--gt_ply', type=str, default=None, metavar='FILE[,FILE...]',
+                        help='--fuse: score each scene\'s fused cloud against these ground-truth PLY file(s) (eval_cloud: accuracy, '
+                             'completeness, F-score; not the official ETH3D evaluator) into <savepath>/<scene>/cloud_eval.json')
     args = parser.parse_args(argv)
     if args.eager and args.scene_cache:
         parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
     if args.no_map_files and not args.fuse:
         parser.error('--no_map_files needs --fuse: the run would write nothing')
+    if args.gt_ply and not args.fuse:
+        parser.error('--gt_ply needs --fuse: there is no point cloud to score')
+    args.gt_ply = [p for p in args.gt_ply.split(',') if p] if args.gt_ply else None
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False
     for k, v in vars(args).items():

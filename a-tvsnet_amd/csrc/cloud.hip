@@ -1,0 +1,415 @@
+// Point-cloud scoring (gfx950): exact nearest neighbours within a radius between two clouds, and tolerance counts
+// (ops/cloud.py, atvsnet/eval_cloud.py).
+//
+// THE DEFINITION (tests/cloud_restated.py restates it with numpy; the tests compare bit for bit).  Reference cloud P (n,3) float32,
+// query cloud Q (m,3) float32, radius R > 0 (float32).  For a finite query q and a finite reference point p
+//     dx = q.x - p.x,  dy = q.y - p.y,  dz = q.z - p.z          (float32)
+//     d2 = (dx*dx + dy*dy) + dz*dz                              (float32, every operation rounded, no contraction: the library is
+//                                                                built with -ffp-contract=off)
+// Per query: d2min = the minimum of d2 over all finite reference points, idx = the LOWEST reference index attaining it; when
+// (double)d2min > (double)R * (double)R, or the query is not finite, or no reference point is finite: d2min = +inf, idx = -1.
+// Non-finite reference points are never neighbours.  The result is a function of P, Q, R alone: the grid below (cell size, origin,
+// order of the points inside a cell, launch shape) cannot be seen in it.  A tolerance tau (double) counts a query when
+// (double)d2min <= tau * tau (formed in double); tau > R is an argument error (distances beyond R are not known).
+//
+// THE GRID.  A uniform grid of cubic cells of edge h over the bounding box of the finite reference points, built by counting sort:
+//   bbox     per-wave minimum / maximum, then integer atomic max on order-preserving bit patterns (no float atomics anywhere);
+//   params   one thread: origin = the box's minimum corner, h, cells per axis (all in double, kept in the grid's header);
+//   count    cell of every point -> keys[i], one integer atomic add per point into the cell's counter;
+//   scan     exclusive prefix sum of the counters (tiles of 2048, tile sums, add);
+//   scatter  one returning integer atomic add per point on its cell's start: the point's slot; it is stored there as a 16-byte
+//            record (x, y, z, original index), so a candidate is one global_load_dwordx4.  Afterwards counter c holds the END of
+//            cell c = the start of cell c + 1; S = the counters with a zero in front: cell c is records S[c] .. S[c + 1].
+// Non-finite points go to one extra bucket behind the last cell and are never read.  The grid is built once per reference cloud;
+// memory is O(n + cells) with cells <= max(4096, min(8 n, 2^28)) known from n alone, so the host allocates before the box is known
+// and the build never synchronises.
+//
+// THE QUERY.  The queries are sorted by the SAME cells with the same counting sort (queries further than one cell outside the grid,
+// and non-finite ones, go to the extra bucket: not found).  One lane per query, in cell order: the lanes of a wavefront walk the same
+// cells, their loads hit the same lines (identical addresses are one request).  x runs fastest in the cell index, so the 27 cells
+// around a query are 9 contiguous runs of records.  Every lane keeps the minimum of (bits(d2) << 32) | index as one unsigned 64-bit
+// integer: d2 >= +0, so its bit pattern orders as its value does (+inf above every finite one), and the low word is the tie rule.
+// The results are written back to the queries' original positions.
+//
+// WHY 27 CELLS SUFFICE (the margin).  Let D be the true distance of a pair whose float32 d2 passes the test (double)d2 <= R^2.
+// Each difference carries one rounding (relative 2^-24), squaring doubles it, the product and the two sums add one each: the
+// float32 d2 is within 5 * 2^-24 < 2^-21 relative of D^2 (plus at most 3 * 2^-150 absolute where a product underflows), so
+// D <= R (1 + 2^-21).  The cell edge is h >= max(R (1 + 2^-20), 2^-60): D / h <= (1 + 2^-21) / (1 + 2^-20) < 1 - 2^-22 (and where R is
+// so small that underflow matters, h^2 = 2^-120 exceeds R^2 + 3 * 2^-150 by far).  A coordinate's cell is floor(((double)x - origin) /
+// h) in double: at most 2^28 cells per axis and three roundings of 2^-53 put the computed quotient within 2^-23 of the exact one.
+// Two points at most D apart on an axis therefore have computed quotients less than (1 - 2^-22) + 2 * 2^-23 = 1 apart, so their
+// cells differ by at most one.  Clamping a query's cell into the grid never widens that difference (a clamp is monotone and
+// 1-Lipschitz), and a query whose quotient lies below -1 or above the cell count is further than h (1 - 2^-23) > D from every
+// reference point.  Where the box would need more cells than the cap (a sparse cloud with a small R), h is made larger, which the
+// argument allows: a larger h only searches more.  With exactly h = R the argument fails, and so does the search: R = 0.25, query
+// x = 0.25 - 2^-26 (cell 0), reference x = 0.5 (cell 2): dx rounds to 0.25, the float32 d2 is 0.0625 = R^2 exactly.
+#include <math.h>
+
+#include "common.h"
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr long kMaxPoints = 1L << 30;
+constexpr long kMinCells = 4096;
+constexpr long kMaxCells = 1L << 28;
+constexpr long kCellsPerPoint = 8;
+constexpr int kScanItems = 8;                          // counters per thread of a scan tile
+constexpr int kScanTile = kThreads * kScanItems;       // 2048
+constexpr int kMaxTolerances = 16;
+constexpr size_t kHeaderBytes = 256;
+
+struct GridHeader {                // the first kHeaderBytes of a grid
+  double origin[3];                // minimum corner of the finite reference points
+  double h;                        // cell edge
+  double r2;                       // (double)R * (double)R
+  int dims[3];                     // cells per axis, x fastest
+  int ncells;                      // dims[0] * dims[1] * dims[2] <= cap; bucket `ncells` holds the points that are in no cell
+  unsigned box[6];                 // bbox pass: ~enc(min x, y, z), enc(max x, y, z); 0 = no finite point seen
+};
+static_assert(sizeof(GridHeader) <= kHeaderBytes, "header");
+
+struct Tolerances {
+  double t2[kMaxTolerances];
+  int k;
+};
+
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+inline long cell_cap(long n) { return n * kCellsPerPoint < kMinCells ? kMinCells : (n * kCellsPerPoint > kMaxCells ? kMaxCells : n * kCellsPerPoint); }
+inline long scan_tiles(long cap) { return (cap + 1 + kScanTile - 1) / kScanTile; }
+
+// One counting sort's buffers behind `front` bytes: S (cap + 2 counters), records (16 B per point), keys (4 B per point), tile sums.
+struct Layout {
+  size_t S, rec, keys, tiles, total;
+};
+inline Layout layout_for(long cap, long npts, size_t front) {
+  Layout L;
+  L.S = front;
+  L.rec = L.S + align256((size_t)(cap + 2) * sizeof(unsigned));
+  L.keys = L.rec + align256((size_t)npts * sizeof(float4));
+  L.tiles = L.keys + align256((size_t)npts * sizeof(int));
+  L.total = L.tiles + align256((size_t)scan_tiles(cap) * sizeof(unsigned));
+  return L;
+}
+
+// float bits <-> unsigned integers of the same order (finite values and infinities)
+__device__ __forceinline__ unsigned enc(float f) {
+  const unsigned u = __float_as_uint(f);
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); }
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+  const float big = __uint_as_float(0x7f800000u);
+  return fabsf(x) < big && fabsf(y) < big && fabsf(z) < big;        // NaN fails every comparison
+}
+
+// The quotient the margin argument speaks of; ONE definition for the grid's size, the reference points and the queries.
+__device__ __forceinline__ double cell_coord(float x, double origin, double h) { return floor(((double)x - origin) / h); }
+
+// Cell index of a finite point, or `ncells` when it lies more than one cell outside the grid (queries only: a reference point is
+// inside the box by construction).
+__device__ __forceinline__ int cell_of(const GridHeader& g, float x, float y, float z, int* cx, int* cy, int* cz) {
+  const double tx = cell_coord(x, g.origin[0], g.h), ty = cell_coord(y, g.origin[1], g.h), tz = cell_coord(z, g.origin[2], g.h);
+  if (!(tx >= -1.0 && tx <= (double)g.dims[0] && ty >= -1.0 && ty <= (double)g.dims[1] && tz >= -1.0 && tz <= (double)g.dims[2]))
+    return g.ncells;
+  *cx = min(max((int)tx, 0), g.dims[0] - 1);
+  *cy = min(max((int)ty, 0), g.dims[1] - 1);
+  *cz = min(max((int)tz, 0), g.dims[2] - 1);
+  return (*cz * g.dims[1] + *cy) * g.dims[0] + *cx;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_bbox_kernel(const float* __restrict__ pts, long n, GridHeader* __restrict__ hdr) {
+  unsigned m[6] = {0u, 0u, 0u, 0u, 0u, 0u};
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long)gridDim.x * kThreads) {
+    const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+    if (!finite3(x, y, z)) continue;
+    m[0] = max(m[0], ~enc(x)); m[1] = max(m[1], ~enc(y)); m[2] = max(m[2], ~enc(z));
+    m[3] = max(m[3], enc(x));  m[4] = max(m[4], enc(y));  m[5] = max(m[5], enc(z));
+  }
+  for (int k = 0; k < 6; ++k) {
+    unsigned v = m[k];
+    for (int off = 32; off > 0; off >>= 1) v = max(v, (unsigned)__shfl_xor((int)v, off));
+    if ((threadIdx.x & 63) == 0 && v) atomicMax(&hdr->box[k], v);
+  }
+}
+
+__global__ void cloud_params_kernel(GridHeader* __restrict__ hdr, float radius, long cap) {
+  if (blockIdx.x != 0 || threadIdx.x != 0) return;
+  GridHeader g = *hdr;
+  g.r2 = (double)radius * (double)radius;
+  double h = fmax((double)radius * (1.0 + 0x1p-20), 0x1p-60);
+  if (g.box[3] == 0u) {                                    // no finite reference point: one empty cell
+    g.origin[0] = g.origin[1] = g.origin[2] = 0.0;
+    g.dims[0] = g.dims[1] = g.dims[2] = 1;
+  } else {
+    float hi[3];
+    for (int k = 0; k < 3; ++k) {
+      g.origin[k] = (double)dec(~g.box[k]);
+      hi[k] = dec(g.box[3 + k]);
+    }
+    double d[3];
+    for (int it = 0;; ++it) {
+      for (int k = 0; k < 3; ++k) d[k] = cell_coord(hi[k], g.origin[k], h) + 1.0;
+      const double cells = d[0] * d[1] * d[2];
+      if (cells <= (double)cap) break;
+      if (it == 256) {                                     // cannot happen for finite boxes; one cell is always right
+        h = 2.0 * fmax(fmax((double)hi[0] - g.origin[0], (double)hi[1] - g.origin[1]), (double)hi[2] - g.origin[2]);
+        continue;
+      }
+      h *= 1.01 * fmax(cbrt(cells / (double)cap), 1.0);    // a coarser cell: invisible in the output (see the header comment)
+    }
+    for (int k = 0; k < 3; ++k) g.dims[k] = (int)d[k];
+  }
+  g.h = h;
+  g.ncells = g.dims[0] * g.dims[1] * g.dims[2];
+  *hdr = g;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_count_kernel(const float* __restrict__ pts, long n, const GridHeader* __restrict__ hdr,
+                                                               int* __restrict__ keys, unsigned* __restrict__ C) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const GridHeader g = *hdr;
+  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  int cx, cy, cz;
+  const int key = finite3(x, y, z) ? cell_of(g, x, y, z, &cx, &cy, &cz) : g.ncells;
+  keys[i] = key;
+  atomicAdd(C + key, 1u);
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_scatter_kernel(const float* __restrict__ pts, long n, const int* __restrict__ keys,
+                                                                 unsigned* __restrict__ C, float4* __restrict__ rec) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const unsigned pos = atomicAdd(C + keys[i], 1u);
+  if (pos < (unsigned)n) rec[pos] = make_float4(pts[i * 3 + 0], pts[i * 3 + 1], pts[i * 3 + 2], __int_as_float((int)i));
+}
+
+// Exclusive scan of `count` counters in place: tiles of kScanTile, the tile sums by one workgroup, then added back.
+__device__ __forceinline__ unsigned wave_inclusive(unsigned v, int lane) {
+  for (int off = 1; off < 64; off <<= 1) {
+    const unsigned y = (unsigned)__shfl_up((int)v, off);
+    if (lane >= off) v += y;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_scan_tile_kernel(unsigned* __restrict__ a, long count, unsigned* __restrict__ tile_sum) {
+  __shared__ unsigned wsum[kThreads / 64];
+  const long base = (long)blockIdx.x * kScanTile + (long)threadIdx.x * kScanItems;
+  unsigned v[kScanItems], run = 0u;
+  for (int k = 0; k < kScanItems; ++k) {
+    const unsigned t = base + k < count ? a[base + k] : 0u;
+    v[k] = run;
+    run += t;
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const unsigned incl = wave_inclusive(run, lane);
+  if (lane == 63) wsum[w] = incl;
+  __syncthreads();
+  unsigned before = 0u, total = 0u;
+  for (int k = 0; k < kThreads / 64; ++k) {
+    if (k < w) before += wsum[k];
+    total += wsum[k];
+  }
+  const unsigned excl = before + incl - run;
+  for (int k = 0; k < kScanItems; ++k)
+    if (base + k < count) a[base + k] = v[k] + excl;
+  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+}
+
+__global__ __launch_bounds__(1024) void cloud_scan_sums_kernel(unsigned* __restrict__ tile_sum, long tiles) {
+  __shared__ unsigned wsum[16];
+  __shared__ unsigned carry;
+  if (threadIdx.x == 0) carry = 0u;
+  __syncthreads();
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (long b = 0; b < tiles; b += 1024) {
+    const long i = b + threadIdx.x;
+    const unsigned t = i < tiles ? tile_sum[i] : 0u;
+    const unsigned incl = wave_inclusive(t, lane);
+    if (lane == 63) wsum[w] = incl;
+    __syncthreads();
+    unsigned before = 0u, total = 0u;
+    for (int k = 0; k < 16; ++k) {
+      if (k < w) before += wsum[k];
+      total += wsum[k];
+    }
+    if (i < tiles) tile_sum[i] = carry + before + incl - t;
+    __syncthreads();
+    if (threadIdx.x == 0) carry += total;
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_scan_add_kernel(unsigned* __restrict__ a, long count, const unsigned* __restrict__ tile_sum) {
+  const unsigned add = tile_sum[blockIdx.x];
+  const long base = (long)blockIdx.x * kScanTile;
+  for (int k = 0; k < kScanItems; ++k) {
+    const long i = base + (long)k * kThreads + threadIdx.x;
+    if (i < count) a[i] += add;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_nearest_kernel(const GridHeader* __restrict__ hdr, const unsigned* __restrict__ S,
+                                                                 const float4* __restrict__ rec, const unsigned* __restrict__ qS,
+                                                                 const float4* __restrict__ qrec, long m, float* __restrict__ d2out,
+                                                                 int* __restrict__ idxout) {
+  const long j = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (j >= m) return;
+  const GridHeader g = *hdr;
+  const float4 q = qrec[j];
+  const int orig = __float_as_int(q.w);
+  const unsigned long long none = (0x7f800000ull << 32) | 0xffffffffull;
+  unsigned long long best = none;
+  if (j < (long)qS[g.ncells]) {                             // not in the bucket of far / non-finite queries
+    int cx, cy, cz;
+    cell_of(g, q.x, q.y, q.z, &cx, &cy, &cz);
+    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dims[0] - 1);
+    for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dims[2] - 1); ++z) {
+      for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dims[1] - 1); ++y) {
+        const int row = (z * g.dims[1] + y) * g.dims[0];
+        const unsigned b = S[row + x0], e = S[row + x1 + 1];
+#pragma unroll 4
+        for (unsigned p = b; p < e; ++p) {
+          const float4 r = rec[p];
+          const float dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z;
+          const float d2 = (dx * dx + dy * dy) + dz * dz;
+          const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(r.w);
+          best = key < best ? key : best;
+        }
+      }
+    }
+  }
+  float d2 = __uint_as_float((unsigned)(best >> 32));
+  int idx = (int)(unsigned)(best & 0xffffffffull);
+  if (best == none || !((double)d2 <= g.r2)) {
+    d2 = __uint_as_float(0x7f800000u);
+    idx = -1;
+  }
+  d2out[orig] = d2;
+  idxout[orig] = idx;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_counts_kernel(const float* __restrict__ d2, long m, Tolerances tol,
+                                                                unsigned long long* __restrict__ counts) {
+  __shared__ unsigned long long s[kMaxTolerances];
+  if (threadIdx.x < kMaxTolerances) s[threadIdx.x] = 0ull;
+  __syncthreads();
+  unsigned c[kMaxTolerances];
+  for (int t = 0; t < kMaxTolerances; ++t) c[t] = 0u;
+  for (long i = (long)blockIdx.x * kThreads + threadIdx.x; i < m; i += (long)gridDim.x * kThreads) {
+    const double v = (double)d2[i];
+    for (int t = 0; t < kMaxTolerances; ++t) c[t] += (t < tol.k && v <= tol.t2[t]) ? 1u : 0u;
+  }
+  for (int t = 0; t < kMaxTolerances; ++t) {
+    unsigned v = c[t];
+    for (int off = 32; off > 0; off >>= 1) v += (unsigned)__shfl_down((int)v, off);
+    if ((threadIdx.x & 63) == 0 && v) atomicAdd(&s[t], (unsigned long long)v);
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < tol.k && s[threadIdx.x]) atomicAdd(counts + threadIdx.x, s[threadIdx.x]);
+}
+
+// count -> scan -> scatter of `npts` points by the cells of `hdr`, into the buffers of L inside `base`
+int counting_sort(const float* pts, long npts, const GridHeader* hdr, char* base, const Layout& L, long cap, hipStream_t st) {
+  unsigned* S = reinterpret_cast<unsigned*>(base + L.S);
+  unsigned* C = S + 1;                                     // S[0] stays 0: cell c is records S[c] .. S[c + 1] after the scatter
+  int* keys = reinterpret_cast<int*>(base + L.keys);
+  unsigned* tiles = reinterpret_cast<unsigned*>(base + L.tiles);
+  float4* rec = reinterpret_cast<float4*>(base + L.rec);
+  if (hipMemsetAsync(S, 0, (size_t)(cap + 2) * sizeof(unsigned), st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (npts == 0) return ATVS_OK;
+  const dim3 per_point((unsigned)cdiv(npts, kThreads));
+  hipLaunchKernelGGL(cloud_count_kernel, per_point, dim3(kThreads), 0, st, pts, npts, hdr, keys, C);
+  ATVS_LAUNCH_CHECK();
+  const long count = cap + 1, nt = scan_tiles(cap);
+  hipLaunchKernelGGL(cloud_scan_tile_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, C, count, tiles);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(1024), 0, st, tiles, nt);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_add_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, C, count, (const unsigned*)tiles);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scatter_kernel, per_point, dim3(kThreads), 0, st, pts, npts, (const int*)keys, C, rec);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+}  // namespace
+
+extern "C" int atvs_cloud_grid_scratch_size(long n, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  *bytes = (long)layout_for(cell_cap(n), n, kHeaderBytes).total;
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_grid_build(const float* points, long n, float radius, void* grid, long grid_bytes, atvs_stream_t stream) {
+  if (!grid || (n > 0 && !points)) return ATVS_ERR_NULL;
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!(radius > 0.f) || !(radius <= 3.4028234663852886e38f)) return ATVS_ERR_ARG;
+  const long cap = cell_cap(n);
+  const Layout L = layout_for(cap, n, kHeaderBytes);
+  if (grid_bytes < (long)L.total) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  GridHeader* hdr = static_cast<GridHeader*>(grid);
+  if (hipMemsetAsync(grid, 0, kHeaderBytes, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (n > 0) {
+    const unsigned blocks = (unsigned)(cdiv(n, kThreads) < 2048 ? cdiv(n, kThreads) : 2048);
+    hipLaunchKernelGGL(cloud_bbox_kernel, dim3(blocks), dim3(kThreads), 0, st, points, n, hdr);
+    ATVS_LAUNCH_CHECK();
+  }
+  hipLaunchKernelGGL(cloud_params_kernel, dim3(1), dim3(64), 0, st, hdr, radius, cap);
+  ATVS_LAUNCH_CHECK();
+  return counting_sort(points, n, hdr, static_cast<char*>(grid), L, cap, st);
+}
+
+extern "C" int atvs_cloud_nearest_scratch_size(long n, long m, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
+  *bytes = (long)layout_for(cell_cap(n), m, 0).total;
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_nearest(const void* grid, long grid_bytes, long n, const float* queries, long m, void* scratch,
+                                  long scratch_bytes, float* d2, int* idx, atvs_stream_t stream) {
+  if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (m == 0) return ATVS_OK;
+  if (!grid || !queries || !scratch || !d2 || !idx) return ATVS_ERR_NULL;
+  const long cap = cell_cap(n);
+  const Layout G = layout_for(cap, n, kHeaderBytes), Q = layout_for(cap, m, 0);
+  if (grid_bytes < (long)G.total || scratch_bytes < (long)Q.total) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  const char* g = static_cast<const char*>(grid);
+  const GridHeader* hdr = reinterpret_cast<const GridHeader*>(g);
+  char* s = static_cast<char*>(scratch);
+  const int rc = counting_sort(queries, m, hdr, s, Q, cap, st);
+  if (rc != ATVS_OK) return rc;
+  hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)cdiv(m, kThreads)), dim3(kThreads), 0, st, hdr,
+                     reinterpret_cast<const unsigned*>(g + G.S), reinterpret_cast<const float4*>(g + G.rec),
+                     reinterpret_cast<const unsigned*>(s + Q.S), reinterpret_cast<const float4*>(s + Q.rec), m, d2, idx);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, float radius, long long* counts,
+                                 atvs_stream_t stream) {
+  if (!counts || !tolerances || (m > 0 && !d2)) return ATVS_ERR_NULL;
+  if (m < 0 || m > kMaxPoints || k < 1 || k > kMaxTolerances) return ATVS_ERR_SHAPE;
+  if (!(radius > 0.f) || !(radius <= 3.4028234663852886e38f)) return ATVS_ERR_ARG;
+  Tolerances tol;
+  tol.k = k;
+  for (int t = 0; t < kMaxTolerances; ++t) {
+    const double tau = t < k ? tolerances[t] : 0.0;
+    if (!(tau >= 0.0) || tau > (double)radius) return ATVS_ERR_ARG;
+    tol.t2[t] = tau * tau;
+  }
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(counts, 0, (size_t)kMaxTolerances * sizeof(long long), st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (m == 0) return ATVS_OK;
+  const unsigned blocks = (unsigned)(cdiv(m, kThreads * 8) < 2048 ? cdiv(m, kThreads * 8) : 2048);
+  hipLaunchKernelGGL(cloud_counts_kernel, dim3(blocks), dim3(kThreads), 0, st, d2, m, tol, reinterpret_cast<unsigned long long*>(counts));
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}

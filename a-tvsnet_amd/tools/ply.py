@@ -34,3 +34,76 @@ def read_ply(path):
                 break
         v = np.fromfile(f, _VERTEX, n)
     return np.stack([v['x'], v['y'], v['z']], -1), np.stack([v['red'], v['green'], v['blue']], -1)
+
+
+_PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',
+              'int': 'i4', 'int32': 'i4', 'uint': 'u4', 'uint32': 'u4', 'float': 'f4', 'float32': 'f4', 'double': 'f8', 'float64': 'f8'}
+
+
+def read_ply_points(path):
+    """-> points (M,3) float32 of any PLY's `vertex` element: `ascii`, `binary_little_endian` or `binary_big_endian`; x, y, z as
+    `float` or `double` (a double is rounded once to float32) at any position among other scalar properties; elements after
+    `vertex` (faces) are ignored.  A list property inside `vertex`, an element in front of it, a missing coordinate, a malformed
+    header or a truncated body raises ValueError naming the file."""
+    def bad(why):
+        return ValueError('%s: %s' % (path, why))
+
+    with open(path, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise bad('not a PLY file (no "ply" magic)')
+        fmt, count, props, element = None, None, [], None
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise bad('the header has no end_header')
+            words = raw.decode('ascii', 'replace').split()
+            if not words or words[0] in ('comment', 'obj_info'):
+                continue
+            if words[0] == 'end_header':
+                break
+            if words[0] == 'format' and len(words) >= 2:
+                fmt = words[1]
+            elif words[0] == 'element' and len(words) == 3:
+                element = words[1]
+                if element == 'vertex':
+                    try:
+                        count = int(words[2])
+                    except ValueError:
+                        raise bad('element vertex: bad count %r' % words[2])
+                elif count is None:
+                    raise bad('element %r in front of the vertex element is not supported' % element)
+            elif words[0] == 'property' and element == 'vertex':
+                if len(words) >= 2 and words[1] == 'list':
+                    raise bad('a list property inside the vertex element is not supported')
+                if len(words) != 3 or words[1] not in _PLY_TYPES:
+                    raise bad('bad property line %r' % ' '.join(words))
+                props.append((words[2], _PLY_TYPES[words[1]]))
+        if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+            raise bad('unsupported format %r' % fmt)
+        if count is None or count < 0:
+            raise bad('no vertex element')
+        names = [p[0] for p in props]
+        for c in 'xyz':
+            if names.count(c) != 1:
+                raise bad('the vertex element has no (single) property %r' % c)
+            if dict(props)[c] not in ('f4', 'f8'):
+                raise bad('property %r is neither float nor double' % c)
+        if fmt == 'ascii':
+            cols = [names.index(c) for c in 'xyz']
+            out = np.empty((count, 3), np.float64)
+            for i in range(count):
+                words = f.readline().split()
+                if len(words) < len(props):
+                    raise bad('truncated body: vertex %d of %d' % (i, count))
+                try:
+                    out[i] = [float(words[c]) for c in cols]
+                except ValueError:
+                    raise bad('vertex %d: not a number' % i)
+            return out.astype(np.float32)
+        order = '<' if fmt == 'binary_little_endian' else '>'
+        dtype = np.dtype([(n, order + t) for n, t in props])
+        body = f.read(count * dtype.itemsize)
+        if len(body) != count * dtype.itemsize:
+            raise bad('truncated body: %d bytes for %d vertices of %d bytes' % (len(body), count, dtype.itemsize))
+        v = np.frombuffer(body, dtype, count)
+        return np.stack([v['x'].astype(np.float32), v['y'].astype(np.float32), v['z'].astype(np.float32)], -1).reshape(count, 3)

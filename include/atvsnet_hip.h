@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 47
+#define ATVS_ABI_VERSION 48
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -739,6 +739,35 @@ int atvs_colmap_depth_range(const double* points, long n_points, const double* c
  * outside the arrays add nothing.  n_images above 16384 (a matrix beyond 1 GiB) or below 1: ATVS_ERR_SHAPE. */
 int atvs_colmap_covisibility(const int* offsets, const int* observers, int n_tracks, int n_obs, int n_images, int* covis,
                              atvs_stream_t stream);
+
+/* Point-cloud scoring (ops/cloud.py, atvsnet/eval_cloud.py, csrc/cloud.hip).  Pointers are device pointers unless named host.
+ *
+ * The definition.  Reference cloud P (n,3) float32, query cloud Q (m,3) float32, radius R > 0 (float32).  For a finite query q
+ * and a finite reference point p: dx = q.x - p.x, dy = q.y - p.y, dz = q.z - p.z and d2 = (dx*dx + dy*dy) + dz*dz, every
+ * operation rounded to float32, nothing contracted.  Per query: d2min = the minimum of d2 over all finite reference points and
+ * idx = the LOWEST reference index that attains it; if (double)d2min > (double)R * (double)R, or the query is not finite, or no
+ * reference point is finite: d2min = +inf, idx = -1.  Non-finite reference points are never neighbours.  The result depends on
+ * P, Q and R only (not on the grid's cell size or origin, the order of points inside a cell, or the launch shape): integer
+ * atomics and a 64-bit integer minimum of (bits(d2) << 32) | index, no float atomics.
+ *
+ * atvs_cloud_grid_build: a uniform grid over the finite points of `points` (n,3), built by counting sort (bounding box by a
+ * reduction kernel, per-cell counts, exclusive scan, scatter into 16-byte records x, y, z, index).  The cell edge is at least
+ * R (1 + 2^-20) -- csrc/cloud.hip says why a 27-cell search is then exact -- and larger where the box would need more than
+ * max(4096, min(8 n, 2^28)) cells.  `grid`: atvs_cloud_grid_scratch_size(n) bytes, O(n + cells), owned by the caller; it IS the
+ * grid afterwards, valid for any number of atvs_cloud_nearest calls with the same n.  No host synchronisation.
+ * atvs_cloud_nearest: queries (m,3) -> d2 (m) float32, idx (m) int32 as defined above; the queries are sorted by cell and
+ * answered in that order, the results written to their original positions.  scratch: atvs_cloud_nearest_scratch_size(n, m) bytes.
+ * atvs_cloud_counts: counts (16 int64, zeroed on the stream) [t] = the number of i with (double)d2[i] <= tolerances[t]^2 (the
+ * square formed in double), t < k <= 16; `tolerances` is a HOST array of k doubles; radius = the R d2 was computed with.
+ * R <= 0 or not finite, a tolerance negative, NaN or above R: ATVS_ERR_ARG; n or m negative or beyond 2^30, a short grid or
+ * scratch, k outside [1, 16]: ATVS_ERR_SHAPE.  n = 0 and m = 0 are valid (every query not found; nothing launched over no points). */
+int atvs_cloud_grid_scratch_size(long n, long* bytes);
+int atvs_cloud_grid_build(const float* points, long n, float radius, void* grid, long grid_bytes, atvs_stream_t stream);
+int atvs_cloud_nearest_scratch_size(long n, long m, long* bytes);
+int atvs_cloud_nearest(const void* grid, long grid_bytes, long n, const float* queries, long m, void* scratch, long scratch_bytes,
+                       float* d2, int* idx, atvs_stream_t stream);
+int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, float radius, long long* counts,
+                      atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
