@@ -3,6 +3,8 @@ distance tolerances.
 
     python -m atvsnet_amd.atvsnet.eval_cloud --recon final3d_model.ply --gt scan1.ply [scan2.ply ...]
            [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--radius R] [--gt_transform T.txt] [--out cloud_eval.json] [--distances PREFIX]
+           [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v]] [--init_transform T.txt |
+            --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
 
 This is the PLAIN precision / recall definition (the one Tanks and Temples uses): per tolerance tau, `accuracy` is the share of
 reconstruction points with a ground-truth point within tau, `completeness` the share of ground-truth points with a reconstruction
@@ -12,6 +14,13 @@ scans' visibility (free space): the numbers are comparable between runs of this 
 Both directions of the nearest-neighbour search run on the device (ops.cloud_grid / cloud_nearest / cloud_counts, csrc/cloud.hip),
 exactly: per point the smallest float32 squared distance (dx*dx + dy*dy) + dz*dz to the other cloud, unknown (+inf) beyond
 `radius`; a point counts at tau when double(d2) <= tau * tau.  There is no CPU fallback.  `metrics` is the pure-host part.
+
+A reconstruction in another frame than the ground truth's (a COLMAP model: rotation, translation and scale are free) scores 0 as
+it stands.  --register aligns it first (atvsnet/register_cloud.py: voxel down-sampling, trimmed point-to-point ICP in stages, on the
+device), starting from --init_transform (a 4x4 matrix applied to the RECONSTRUCTION) or --init_cameras (the similarity between
+the camera centres of two COLMAP models of the same images); --save_transform keeps the matrix found.  --voxel scores the
+voxel-down-sampled clouds (both sides), so that point density does not weight the shares.  Without these options the result is
+what it was before they existed.
 """
 from __future__ import print_function
 
@@ -83,10 +92,25 @@ def transform_points(points, matrix):
     return (p @ T[:3, :3].T + T[:3, 3]).astype(np.float32)
 
 
-def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None):
+def _matrix(T, name):
+    T = np.asarray(T, np.float64)
+    if T.size != 16 or not np.isfinite(T).all():
+        raise ValueError('%s: expected the 16 finite numbers of a 4x4 matrix' % name)
+    return T.reshape(4, 4)
+
+
+def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None,
+             register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
-    distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays."""
+    distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
+
+    The rest changes nothing when left at its default.  init_transform: a 4x4 matrix applied to `recon` (on the device,
+    ops.cloud_transform).  register: align `recon` to `gt` by register_cloud.register before scoring, starting from
+    init_transform; with_scale, register_distances (default 4x, 2x, 1x the largest tolerance), register_voxel are its arguments;
+    the result gains `registration` (its dict; `matrix` includes init_transform).  Without register, init_transform is recorded
+    as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
+    result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds."""
     import torch
     from .. import ops
     tol, radius = _check_tolerances(tolerances, radius)
@@ -99,20 +123,58 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
 
     if gt_transform is not None:
         gt = transform_points(gt.cpu().numpy() if isinstance(gt, torch.Tensor) else gt, gt_transform)
+    if not register and (with_scale or register_distances is not None or register_voxel is not None):
+        raise ValueError('with_scale, register_distances and register_voxel need register=True')
+    if voxel is not None and not (float(voxel) > 0.0 and np.isfinite(float(voxel))):
+        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
+    init = None if init_transform is None else _matrix(init_transform, 'init_transform')
+    extra = {}
     with torch.cuda.device(dev):
         r, g = upload(recon), upload(gt)
+        if register:
+            from . import register_cloud
+            dist = [4.0 * max(tol), 2.0 * max(tol), max(tol)] if register_distances is None else list(register_distances)
+            extra['registration'] = register_cloud.register(r, g, init=init, with_scale=with_scale, distances=dist,
+                                                            voxel=register_voxel, device=dev)
+            r = ops.cloud_transform(r, extra['registration']['matrix'])
+        elif init is not None:
+            extra['init_transform'] = init.tolist()
+            r = ops.cloud_transform(r, init)
+        if voxel is not None:
+            extra.update(voxel=float(voxel), n_recon_full=int(r.shape[0]), n_gt_full=int(g.shape[0]))
+            r, g = ops.cloud_voxel_downsample(r, voxel)[0], ops.cloud_voxel_downsample(g, voxel)[0]
         d2_r, idx_r = ops.cloud_nearest(ops.cloud_grid(g, radius), r)
         d2_g, idx_g = ops.cloud_nearest(ops.cloud_grid(r, radius), g)
         counts = [ops.cloud_counts(d2, tol, radius).cpu().tolist() for d2 in (d2_r, d2_g)]
         d2_r, d2_g = d2_r.cpu().numpy(), d2_g.cpu().numpy()
         if distances is not None:
             distances.update(d2_recon=d2_r, idx_recon=idx_r.cpu().numpy(), d2_gt=d2_g, idx_gt=idx_g.cpu().numpy())
-    return metrics(d2_r, d2_g, tol, radius, counts=counts)
+    result = metrics(d2_r, d2_g, tol, radius, counts=counts)
+    result.update(extra)
+    return result
 
 
-def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform_path=None, distances=None):
+def load_matrix(path):
+    """A text file of 16 numbers -> the 4x4 matrix, row-major."""
+    T = np.loadtxt(path, dtype=np.float64)
+    if T.size != 16:
+        raise ValueError('%s: expected the 16 numbers of a 4x4 matrix, got %d' % (path, T.size))
+    return T.reshape(4, 4)
+
+
+def save_matrix(path, T):
+    """The 4x4 matrix as text that load_matrix reads back exactly (17 significant digits)."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    np.savetxt(path, np.asarray(T, np.float64).reshape(4, 4), fmt='%.17g')
+
+
+def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform_path=None, distances=None,
+                   init_transform_path=None, init_cameras=None, save_transform_path=None, **options):
     """`evaluate` of PLY files (tools/ply.read_ply_points): several ground-truth files are concatenated; gt_transform_path: a text
-    file of 16 numbers, the 4x4 matrix row-major."""
+    file of 16 numbers, the 4x4 matrix row-major.  init_transform_path: the same for evaluate's init_transform; init_cameras:
+    (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
+    result's `registration` / top level gains `init_cameras`: matched images and their rms).  save_transform_path: the matrix that
+    was applied to the reconstruction is written there.  options: evaluate's other keyword arguments."""
     recon = ply.read_ply_points(recon_path)
     gt = [ply.read_ply_points(p) for p in gt_paths]
     gt = np.concatenate(gt, 0) if gt else np.zeros((0, 3), np.float32)
@@ -121,7 +183,26 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
         T = np.loadtxt(gt_transform_path, dtype=np.float64)
         if T.size != 16:
             raise ValueError('%s: expected the 16 numbers of a 4x4 matrix, got %d' % (gt_transform_path, T.size))
-    return evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances)
+    init, cams = None, None
+    if init_transform_path is not None and init_cameras is not None:
+        raise ValueError('init_transform_path and init_cameras both give the starting matrix: choose one')
+    if init_transform_path is not None:
+        init = load_matrix(init_transform_path)
+    elif init_cameras is not None:
+        from . import register_cloud
+        init, matched, rms = register_cloud.init_from_cameras(*init_cameras)
+        cams = {'recon_sparse': str(init_cameras[0]), 'gt_sparse': str(init_cameras[1]), 'matched_images': matched, 'rms': rms}
+    if init is None and not options and save_transform_path is None:
+        return evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances)
+    result = evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances, init_transform=init, **options)
+    if cams is not None:
+        result['init_cameras'] = cams
+    if save_transform_path is not None:
+        applied = result['registration']['matrix'] if 'registration' in result else init
+        if applied is None:
+            raise ValueError('save_transform_path: no matrix was applied to the reconstruction (give register or an initial matrix)')
+        save_matrix(save_transform_path, applied)
+    return result
 
 
 def write_json(path, result):
@@ -130,7 +211,45 @@ def write_json(path, result):
         f.write('\n')
 
 
-def cli(argv=None):
+def register_options(parser, args):
+    """The registration options of a parsed command line as evaluate_files' keyword arguments ({} when none is given);
+    contradictory ones are argument errors."""
+    if args.init_transform and args.init_cameras:
+        parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
+    for name in ('with_scale', 'register_distances', 'register_voxel'):
+        if getattr(args, name) not in (None, False) and not args.register:
+            parser.error('--%s needs --register' % name)
+    if args.save_transform and not (args.register or args.init_transform or args.init_cameras):
+        parser.error('--save_transform needs --register, --init_transform or --init_cameras: no matrix is applied otherwise')
+    if args.voxel is not None and not args.voxel > 0.0:
+        parser.error('--voxel must be positive')
+    options = {}
+    if args.register:
+        options.update(register=True, with_scale=bool(args.with_scale))
+        if args.register_distances is not None:
+            try:
+                options['register_distances'] = [float(t) for t in args.register_distances.split(',') if t.strip()]
+            except ValueError:
+                parser.error('--register_distances: expected comma-separated numbers, got %r' % args.register_distances)
+            d = options['register_distances']
+            if not d or any(not v > 0.0 for v in d) or any(b >= a for a, b in zip(d, d[1:])):
+                parser.error('--register_distances must be positive and decreasing')
+        if args.register_voxel is not None:
+            if not args.register_voxel >= 0.0:
+                parser.error('--register_voxel must be >= 0')
+            options['register_voxel'] = args.register_voxel
+    if args.init_transform:
+        options['init_transform_path'] = args.init_transform
+    if args.init_cameras:
+        options['init_cameras'] = tuple(args.init_cameras)
+    if args.save_transform:
+        options['save_transform_path'] = args.save_transform
+    if args.voxel is not None:
+        options['voxel'] = args.voxel
+    return options
+
+
+def make_parser():
     parser = argparse.ArgumentParser(description='accuracy / completeness / F-score of a point cloud against ground truth '
                                                  '(plain precision / recall; not the official ETH3D evaluator)')
     parser.add_argument('--recon', required=True, help='the reconstruction (PLY)')
@@ -142,16 +261,37 @@ def cli(argv=None):
     parser.add_argument('--distances', default=None, metavar='PREFIX',
                         help='write PREFIX_d2_recon.npy, PREFIX_idx_recon.npy, PREFIX_d2_gt.npy, PREFIX_idx_gt.npy')
     parser.add_argument('--gpu_id', type=int, default=0)
+    parser.add_argument('--register', action='store_true',
+                        help='align the reconstruction to the ground truth before scoring (voxel down-sampling + ICP in stages)')
+    parser.add_argument('--with_scale', action='store_true', help='--register: fit a similarity (scale too), not a rigid motion')
+    parser.add_argument('--register_distances', default=None, metavar='a,b,c',
+                        help='--register: the stages\' search distances, decreasing (default: 4, 2, 1 x the largest tolerance)')
+    parser.add_argument('--register_voxel', type=float, default=None, metavar='V',
+                        help='--register: voxel edge of the down-sampling before the fit (default: half the last distance; 0: none)')
+    parser.add_argument('--init_transform', default=None, metavar='FILE',
+                        help='text file with a 4x4 row-major matrix applied to the RECONSTRUCTION (the start of --register)')
+    parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
+                        help='two COLMAP sparse model folders of the same images, in the reconstruction\'s and the ground truth\'s '
+                             'frame: the similarity between their camera centres (matched by image name) is the initial matrix')
+    parser.add_argument('--save_transform', default=None, metavar='FILE', help='write the matrix applied to the reconstruction here')
+    parser.add_argument('--voxel', type=float, default=None, metavar='V',
+                        help='score the clouds after a voxel down-sampling of edge V (both sides)')
+    return parser
+
+
+def cli(argv=None):
+    parser = make_parser()
     args = parser.parse_args(argv)
     try:
         tol = [float(t) for t in args.tolerances.split(',') if t.strip()]
         tol, _ = _check_tolerances(tol, args.radius)
     except ValueError as e:
         parser.error(str(e))
+    options = register_options(parser, args)
     import torch
     torch.cuda.set_device(args.gpu_id)
     dist = {} if args.distances else None
-    result = evaluate_files(args.recon, args.gt, tol, args.radius, args.gt_transform, distances=dist)
+    result = evaluate_files(args.recon, args.gt, tol, args.radius, args.gt_transform, distances=dist, **options)
     if dist is not None:
         for k, v in dist.items():
             np.save('%s_%s.npy' % (args.distances, k), v)

@@ -299,7 +299,7 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None):
+                gt_ply=None, register=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
@@ -307,7 +307,9 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     finished (depth_fusion.SceneFusion) and each scene ends with <savepath>/<scene>/final3d_model.ply, the point cloud
     depth_fusion.main makes from the written files.  map_files=False (with fuse only): no per-map files.
     gt_ply (with fuse only): ground-truth PLY paths; each scene's fused points, as the PLY stores them, are scored against them
-    (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY."""
+    (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY.
+    register (with gt_ply only): None, or dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned
+    to the ground truth before it is scored (eval_cloud --register [--init_cameras]); cloud_eval.json carries `registration`."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
@@ -318,10 +320,20 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         raise ValueError('map_files=False (--no_map_files) needs fuse (--fuse): the run would write nothing')
     if gt_ply and fuse is None:
         raise ValueError('gt_ply (--gt_ply) needs fuse (--fuse): there is no point cloud to score')
-    gt_points = None
+    if register is not None and not gt_ply:
+        raise ValueError('register (--register) needs gt_ply (--gt_ply): there is nothing to align to')
+    gt_points, register_args, init_cameras = None, {}, None
     if gt_ply:
         from ..tools.ply import read_ply_points
         gt_points = np.concatenate([read_ply_points(p) for p in gt_ply], 0)
+    if register is not None:
+        register_args = dict(register=True, with_scale=bool(register.get('with_scale')))
+        if register.get('init_cameras'):
+            from . import register_cloud
+            init, matched, rms = register_cloud.init_from_cameras(*register['init_cameras'])
+            register_args['init_transform'] = init
+            init_cameras = {'recon_sparse': str(register['init_cameras'][0]), 'gt_sparse': str(register['init_cameras'][1]),
+                            'matched_images': matched, 'rms': rms}
     example._load_weights()
     torch.cuda.set_device(FLAGS.gpu_id)          # every kernel launches on the current device's stream
     device = torch.device('cuda:%d' % FLAGS.gpu_id)
@@ -438,8 +450,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
                     t0 = time.time()
                     points = scene_fusion.run()[0].copy()
                     points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
-                    eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'),
-                                          eval_cloud.evaluate(points, gt_points, device=device))
+                    score = eval_cloud.evaluate(points, gt_points, device=device, **register_args)
+                    if init_cameras is not None:
+                        score['init_cameras'] = init_cameras
+                    eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'), score)
                     TIMES['cloud_eval'] = time.time() - t0
                 print(Notify.INFO, '%s: %d fused points' % (image_info[2], n_points), Notify.ENDC)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
@@ -462,9 +476,13 @@ def main(scene_list=None, base_path='eth3d/'):
     fuse = None
     if getattr(FLAGS, 'fuse', False):
         fuse = dict(prob_threshold=FLAGS.prob_threshold, disp_threshold=FLAGS.disp_threshold, num_consistent=FLAGS.num_consistent)
+    register = None
+    if getattr(FLAGS, 'register', False):
+        register = dict(with_scale=getattr(FLAGS, 'with_scale', False), init_cameras=getattr(FLAGS, 'init_cameras', None) or None)
     run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
                 scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
-                map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None)
+                map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None,
+                register=register)
 
 
 def cli(argv=None):
@@ -500,6 +518,13 @@ def cli(argv=None):
     parser.add_argument('--gt_ply', type=str, default=None, metavar='FILE[,FILE...]',
                         help='--fuse: score each scene\'s fused cloud against these ground-truth PLY file(s) (eval_cloud: accuracy, '
                              'completeness, F-score; not the official ETH3D evaluator) into <savepath>/<scene>/cloud_eval.json')
+    parser.add_argument('--register', action='store_true',
+                        help='--gt_ply: align the fused cloud to the ground truth before scoring it (eval_cloud --register); '
+                             'cloud_eval.json then carries the `registration` object')
+    parser.add_argument('--with_scale', action='store_true', help='--register: fit the scale too')
+    parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
+                        help='--register: two COLMAP sparse model folders of the same images (the scene\'s own and one in the '
+                             'ground truth\'s frame); their camera centres give the initial similarity')
     args = parser.parse_args(argv)
     if args.eager and args.scene_cache:
         parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
@@ -507,6 +532,10 @@ def cli(argv=None):
         parser.error('--no_map_files needs --fuse: the run would write nothing')
     if args.gt_ply and not args.fuse:
         parser.error('--gt_ply needs --fuse: there is no point cloud to score')
+    if args.register and not args.gt_ply:
+        parser.error('--register needs --gt_ply: there is nothing to align to')
+    if (args.with_scale or args.init_cameras) and not args.register:
+        parser.error('--with_scale and --init_cameras need --register')
     args.gt_ply = [p for p in args.gt_ply.split(',') if p] if args.gt_ply else None
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False

@@ -1,0 +1,183 @@
+"""Register a reconstructed cloud to a ground-truth cloud before it is scored (eval_cloud --register).
+
+A COLMAP reconstruction lives in an arbitrary frame (rotation, translation and scale are gauge freedoms of structure from motion),
+a laser scan in the scanner's.  Three steps bring one into the other, as the Tanks and Temples protocol does:
+
+    init_from_cameras        a similarity from the camera centres of two COLMAP models of the same images, matched by image name
+    ops.cloud_voxel_downsample   both clouds thinned to one point per voxel, so that point density does not steer the fit
+    register                 trimmed point-to-point ICP in stages of decreasing distance
+
+The search (ops.cloud_grid / cloud_nearest), the move (ops.cloud_transform), the reduction of the matched pairs to 18 sums
+(ops.cloud_pair_moments) and the down-sampling run on the device; per iteration only 19 words cross to the host, where the
+closed form of Umeyama / Horn turns them into a 4x4 matrix in float64 (similarity_from_moments).  This module imports without a
+GPU; only `register` needs one.  Point-to-plane ICP, normals and a global (feature-based) registration are not here: without
+cameras or an initial matrix the clouds must already be within the first stage's distance of each other.
+"""
+import numpy as np
+
+from . import colmap
+
+DEFAULT_DISTANCES = (2.0, 1.0, 0.5)          # 4x, 2x, 1x eval_cloud's largest default tolerance: a default, not a measurement
+RANK_TOLERANCE = 1e-10                       # second / first singular value of the cross-covariance below this: collinear pairs
+
+
+def similarity_from_moments(count, moments, pivot_src=None, pivot_dst=None, with_scale=False):
+    """The least-squares similarity b ~ s R a + t of `count` pairs from their 18 sums (ops.cloud_pair_moments' layout: sum a (3),
+    sum b (3), sum a_r b_c (9), sum |a|^2, sum |b|^2, sum d2) with a = source - pivot_src, b = target - pivot_dst -> 4x4 float64.
+    Umeyama's closed form: cross-covariance sum(a b^T) / k - mean(a) mean(b)^T, its 3x3 SVD, the determinant fix (never a
+    reflection), s = tr(D E) / var(a) when with_scale else 1, t from the centroids.  ValueError for fewer than 3 pairs or a
+    cross-covariance of rank < 2 (collinear pairs): the fit is not determined."""
+    k = int(count)
+    m = np.asarray(moments, np.float64).reshape(-1)
+    if m.shape != (18,):
+        raise ValueError('moments: expected 18 sums, got %d' % m.size)
+    if k < 3:
+        raise ValueError('%d pairs: a similarity needs at least 3' % k)
+    ps = np.zeros(3) if pivot_src is None else np.asarray(pivot_src, np.float64).reshape(3)
+    pd = np.zeros(3) if pivot_dst is None else np.asarray(pivot_dst, np.float64).reshape(3)
+    ma, mb = m[0:3] / k, m[3:6] / k
+    cov = m[6:15].reshape(3, 3) / k - np.outer(ma, mb)          # cov[r][c] = cov(a_r, b_c)
+    var_a = m[15] / k - float(ma @ ma)
+    U, D, Vt = np.linalg.svd(cov.T)                              # cov^T = sum (b - mb)(a - ma)^T / k = U D V^T
+    if not (D[0] > 0.0 and D[1] > RANK_TOLERANCE * D[0]):
+        raise ValueError('the %d pairs are collinear (singular values %s): the fit is not determined' % (k, D.tolist()))
+    E = np.ones(3)
+    if np.linalg.det(U) * np.linalg.det(Vt) < 0.0:
+        E[2] = -1.0
+    R = (U * E) @ Vt
+    s = 1.0
+    if with_scale:
+        if not var_a > 0.0:
+            raise ValueError('the source pairs have no extent: the scale is not determined')
+        s = float((D * E).sum()) / var_a
+    T = np.eye(4)
+    T[:3, :3] = s * R
+    T[:3, 3] = (pd + mb) - s * (R @ (ps + ma))
+    return T
+
+
+def similarity_from_points(P, Q, with_scale=False):
+    """The same from explicit correspondences: P (k,3) -> Q (k,3), float64."""
+    P, Q = np.asarray(P, np.float64).reshape(-1, 3), np.asarray(Q, np.float64).reshape(-1, 3)
+    if P.shape != Q.shape:
+        raise ValueError('P %s and Q %s: one target per source point' % (P.shape, Q.shape))
+    if len(P) < 3:
+        raise ValueError('%d pairs: a similarity needs at least 3' % len(P))
+    ps, pd = P.mean(axis=0), Q.mean(axis=0)
+    a, b = P - ps, Q - pd
+    m = np.concatenate([a.sum(0), b.sum(0), (a[:, :, None] * b[:, None, :]).sum(0).reshape(-1),
+                        [(a * a).sum(), (b * b).sum(), ((Q - P) ** 2).sum()]])
+    return similarity_from_moments(len(P), m, ps, pd, with_scale)
+
+
+def apply(T, points):
+    """points (k,3) float64 through the 4x4 T, in float64 (host helper; the device form is ops.cloud_transform)."""
+    T = np.asarray(T, np.float64).reshape(4, 4)
+    return np.asarray(points, np.float64) @ T[:3, :3].T + T[:3, 3]
+
+
+def camera_centres(model):
+    """(N,3) float64: -R^T t of every image of a colmap.Model."""
+    return -np.einsum('nji,nj->ni', model.R, model.t)
+
+
+def init_from_cameras(recon_sparse_dir, gt_sparse_dir):
+    """Two COLMAP sparse model folders (colmap.read_model: text or binary) of the same images, the first in the reconstruction's
+    frame, the second in the ground truth's -> (4x4 similarity moving the first frame into the second, number of images matched
+    by NAME, rms distance of the matched camera centres after it).  ValueError when fewer than 3 names match or the matched
+    centres are collinear (a straight camera path leaves the rotation about it free)."""
+    a, b = colmap.read_model(recon_sparse_dir), colmap.read_model(gt_sparse_dir)
+    at = dict(zip(b.names, range(len(b.names))))
+    pairs = [(i, at[name]) for i, name in enumerate(a.names) if name in at]
+    if len(pairs) < 3:
+        raise ValueError('%s and %s have %d image names in common: at least 3 are needed' % (recon_sparse_dir, gt_sparse_dir, len(pairs)))
+    P = camera_centres(a)[[i for i, _ in pairs]]
+    Q = camera_centres(b)[[j for _, j in pairs]]
+    try:
+        T = similarity_from_points(P, Q, with_scale=True)
+    except ValueError as e:
+        raise ValueError('the %d matched camera centres do not determine a similarity: %s' % (len(pairs), e))
+    rms = float(np.sqrt(((apply(T, P) - Q) ** 2).sum(axis=1).mean()))
+    return T, len(pairs), rms
+
+
+def box_corners(lo, hi):
+    """The eight corners (8,3) of the box lo .. hi."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    return np.array([[(lo, hi)[(c >> k) & 1][k] for k in range(3)] for c in range(8)], np.float64)
+
+
+def corner_move(T0, T1, corners):
+    """The largest distance any corner moves between the matrices T0 and T1."""
+    d = apply(T1, corners) - apply(T0, corners)
+    return float(np.sqrt((d * d).sum(axis=1)).max())
+
+
+def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES, voxel=None, max_iterations=50, min_move=None,
+             device=None):
+    """Trimmed point-to-point ICP of `recon` (M,3) onto `gt` (N,3) (host arrays or device tensors, float32) on the device.
+
+    init: 4x4 starting matrix (None: identity).  with_scale: fit a similarity instead of a rigid motion.  distances: one search
+    radius per stage, decreasing.  voxel: both clouds are first reduced by ops.cloud_voxel_downsample with this edge (None: half
+    the last distance; 0: the clouds as they are).  Per stage of distance r: ops.cloud_grid(gt, r) once, then per iteration the
+    source is moved by the current matrix T, every moved point finds its nearest target within r, the pairs' moments are taken
+    between the ORIGINAL source and the target (errors do not compound), and T becomes their closed-form fit; the stage ends when
+    the eight corners of the source's bounding box move by at most min_move (None: 1e-3 r; 0: only an exact fixed point stops
+    it) or after max_iterations.
+    -> dict: matrix (4x4 nested lists: moves the RECONSTRUCTION into the ground truth's frame, `init` included), scale, init,
+    with_scale, voxel, n_recon / n_gt (points the fit used), stages [{distance, iterations, pairs, rmse, converged}] (pairs and
+    rmse: of the last search, i.e. under the matrix the last fit started from).  A stage with fewer than 3 pairs raises."""
+    import torch
+    from .. import ops
+    dist = [float(d) for d in distances]
+    if not dist or any(not (d > 0.0 and np.isfinite(d)) for d in dist) or any(b >= a for a, b in zip(dist, dist[1:])):
+        raise ValueError('distances must be a decreasing list of positive numbers, got %r' % (distances,))
+    if voxel is None:
+        voxel = dist[-1] / 2.0
+    voxel = float(voxel)
+    if not (voxel >= 0.0 and np.isfinite(voxel)):
+        raise ValueError('voxel must be >= 0, got %r' % voxel)
+    if int(max_iterations) < 1:
+        raise ValueError('max_iterations must be at least 1')
+    T0 = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+    def upload(x):
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1, 3))).to(dev)
+
+    with torch.cuda.device(dev):
+        src, dst = upload(recon), upload(gt)
+        if voxel > 0.0:
+            src, dst = ops.cloud_voxel_downsample(src, voxel)[0], ops.cloud_voxel_downsample(dst, voxel)[0]
+        s_lo, s_hi = ops.cloud_bounds(src)
+        d_lo, d_hi = ops.cloud_bounds(dst)
+        if s_lo is None or d_lo is None:
+            raise ValueError('register: a cloud has no finite point')
+        corners = box_corners(s_lo, s_hi)
+        pivot_src, pivot_dst = (s_lo + s_hi) / 2.0, (d_lo + d_hi) / 2.0
+        moved = torch.empty_like(src)
+        T, stages = T0.copy(), []
+        for k, r in enumerate(dist):
+            grid = ops.cloud_grid(dst, r)
+            move_tol = 1e-3 * r if min_move is None else float(min_move)
+            stage = {'distance': r, 'iterations': 0, 'pairs': 0, 'rmse': None, 'converged': False}
+            for _ in range(int(max_iterations)):
+                ops.cloud_transform(src, T, out=moved)
+                d2, idx = ops.cloud_nearest(grid, moved)
+                count, mom = ops.cloud_pair_moments(src, dst, idx, d2, pivot_src=pivot_src, pivot_dst=pivot_dst)
+                if count < 3:
+                    raise ValueError('register: %d pairs within %g in stage %d%s' % (
+                        count, r, k, ': the initial alignment is too far off for the first distance (give --init_cameras, '
+                        '--init_transform or larger --register_distances)' if k == 0 and stage['iterations'] == 0 else ''))
+                T_new = similarity_from_moments(count, mom, pivot_src, pivot_dst, with_scale)
+                move = corner_move(T, T_new, corners)
+                T = T_new
+                stage.update(iterations=stage['iterations'] + 1, pairs=count, rmse=float(np.sqrt(mom[17] / count)))
+                if move <= move_tol:
+                    stage['converged'] = True
+                    break
+            stages.append(stage)
+    return {'matrix': T.tolist(), 'scale': float(np.cbrt(np.linalg.det(T[:3, :3]))), 'init': T0.tolist(), 'with_scale': bool(with_scale),
+            'voxel': voxel, 'n_recon': int(src.shape[0]), 'n_gt': int(dst.shape[0]), 'stages': stages}

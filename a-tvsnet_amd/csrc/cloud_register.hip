@@ -1,0 +1,372 @@
+// Point-cloud registration (gfx950): moving a cloud through a matrix, the moments of matched pairs that a closed-form similarity fit
+// needs, and a sparse voxel down-sampler (ops/cloud.py, atvsnet/register_cloud.py).  The definitions are in include/atvsnet_hip.h;
+// tests/cloud_register_restated.py restates them with numpy and Python integers.  Built with -ffp-contract=off (every operation below
+// is rounded on its own); integer atomics only, so every output is a function of the inputs alone.
+//
+// PAIR MOMENTS, the shape of the sum.  Pair i belongs to workgroup i / (256 L), thread (i mod 256), L = kMomentRun: a thread adds
+// its at most L terms i, i + 256, ... in that order into an accumulator that starts at +0 (the first addition is exact), the 64
+// lanes of a wavefront fold in six steps (lane j takes lane j + 32, then + 16, ... + 1), the four wavefronts as (w0 + w1) + (w2 + w3).
+// That is one row of 19 words per workgroup.  Rows are folded 256 at a time by the same eight-step tree (row j takes row j + 128,
+// + 64, ... + 1; rows beyond the end are +0, and adding +0 is exact) until one is left: one pass up to 65 536 pairs x L, two up to
+// 2^24 x L, three beyond.  An accumulator therefore sees at most L serial additions and then at most
+// 8 + ceil(log2(rows)) + (passes - 1) tree levels that round, rows = ceil(m / (256 L)) -- no more than L + ceil(log2 m) in all for
+// every m <= 2^30 (m > 256 L (rows - 1) gives log2 m > 8 + log2 L + log2(rows - 1), and log2 L = 4 pays for the passes).
+//
+// VOXEL DOWN-SAMPLING.  insert: every finite point finds its voxel's slot in an open-addressing table (capacity = the power of two
+// >= max(2 n, 1024); linear probing from a multiplicative hash of the packed cell; one 64-bit compare-and-swap per probe) and adds
+// to the slot's count and three unsigned 64-bit sums, and takes the minimum of the slot's first index.  flag: a point that is its
+// voxel's first index is marked; an exclusive scan of the marks (cloud_scan.h) gives its output row.  emit: the marked points write
+// their voxel's mean and their own index there.  Which slot a voxel gets depends on arrival order; nothing that is written does.
+#include <math.h>
+
+#include "common.h"
+#include "cloud_scan.h"
+
+namespace {
+
+constexpr long kMaxPoints = 1L << 30;
+constexpr int kMomentRun = ATVS_CLOUD_MOMENT_RUN;      // L: serial additions per accumulator before the tree
+constexpr long kMomentTile = (long)kThreads * kMomentRun;
+constexpr int kWords = 19;                             // pair count (int64) + 18 doubles
+constexpr long kMinSlots = 1024;
+constexpr size_t kVoxelHeader = 256;
+constexpr unsigned long long kEmpty = ~0ull;
+constexpr double kCellLimit = 2097152.0;               // 2^21 cells per axis
+
+__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+struct Matrix12 {
+  double t[12];
+};
+
+struct MomentArgs {
+  double trim2;          // trim * trim
+  double ps[3], pd[3];   // pivots
+};
+
+struct VoxelArgs {
+  double origin[3];
+  double voxel;
+};
+
+__global__ __launch_bounds__(kThreads) void cloud_transform_kernel(const float* points, long n, Matrix12 M, float* out) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double x = (double)points[i * 3 + 0], y = (double)points[i * 3 + 1], z = (double)points[i * 3 + 2];
+  const double* T = M.t;
+  const float ox = (float)(((T[0] * x + T[1] * y) + T[2] * z) + T[3]);
+  const float oy = (float)(((T[4] * x + T[5] * y) + T[6] * z) + T[7]);
+  const float oz = (float)(((T[8] * x + T[9] * y) + T[10] * z) + T[11]);
+  out[i * 3 + 0] = ox;                                  // `out` may be `points`: all three coordinates were read above
+  out[i * 3 + 1] = oy;
+  out[i * 3 + 2] = oz;
+}
+
+// The fixed tree of one workgroup: v[0] is the pair count, v[1..18] the sums.  The result is valid in thread 0.
+__device__ __forceinline__ void block_tree(long long& cnt, double* v, long long* scnt, double (*ssum)[kWords - 1]) {
+  for (int off = 32; off > 0; off >>= 1) {
+    cnt += __shfl_down(cnt, off);
+#pragma unroll
+    for (int k = 0; k < kWords - 1; ++k) v[k] = v[k] + __shfl_down(v[k], off);
+  }
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  if (lane == 0) {
+    scnt[w] = cnt;
+#pragma unroll
+    for (int k = 0; k < kWords - 1; ++k) ssum[w][k] = v[k];
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    cnt = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
+#pragma unroll
+    for (int k = 0; k < kWords - 1; ++k) v[k] = (ssum[0][k] + ssum[1][k]) + (ssum[2][k] + ssum[3][k]);
+  }
+}
+
+__device__ __forceinline__ void store_row(unsigned long long* row, long long cnt, const double* v) {
+  row[0] = (unsigned long long)cnt;
+#pragma unroll
+  for (int k = 0; k < kWords - 1; ++k) row[1 + k] = (unsigned long long)__double_as_longlong(v[k]);
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_pair_moments_kernel(const float* __restrict__ src, const float* __restrict__ dst, long n,
+                                                                      const int* __restrict__ idx, const float* __restrict__ d2, long m,
+                                                                      MomentArgs A, unsigned long long* __restrict__ rows) {
+  __shared__ long long scnt[kThreads / 64];
+  __shared__ double ssum[kThreads / 64][kWords - 1];
+  long long cnt = 0;
+  double v[kWords - 1];
+#pragma unroll
+  for (int k = 0; k < kWords - 1; ++k) v[k] = 0.0;
+  const long base = (long)blockIdx.x * kMomentTile + threadIdx.x;
+  for (int r = 0; r < kMomentRun; ++r) {
+    const long i = base + (long)r * kThreads;
+    if (i >= m) break;
+    const int j = idx[i];
+    const float dd = d2[i];
+    if (j < 0 || (long)j >= n || !((double)dd <= A.trim2)) continue;
+    const double a0 = (double)src[i * 3 + 0] - A.ps[0], a1 = (double)src[i * 3 + 1] - A.ps[1], a2 = (double)src[i * 3 + 2] - A.ps[2];
+    const double b0 = (double)dst[(long)j * 3 + 0] - A.pd[0], b1 = (double)dst[(long)j * 3 + 1] - A.pd[1],
+                 b2 = (double)dst[(long)j * 3 + 2] - A.pd[2];
+    cnt += 1;
+    v[0] = v[0] + a0; v[1] = v[1] + a1; v[2] = v[2] + a2;
+    v[3] = v[3] + b0; v[4] = v[4] + b1; v[5] = v[5] + b2;
+    v[6] = v[6] + a0 * b0; v[7] = v[7] + a0 * b1; v[8] = v[8] + a0 * b2;
+    v[9] = v[9] + a1 * b0; v[10] = v[10] + a1 * b1; v[11] = v[11] + a1 * b2;
+    v[12] = v[12] + a2 * b0; v[13] = v[13] + a2 * b1; v[14] = v[14] + a2 * b2;
+    v[15] = v[15] + ((a0 * a0 + a1 * a1) + a2 * a2);
+    v[16] = v[16] + ((b0 * b0 + b1 * b1) + b2 * b2);
+    v[17] = v[17] + (double)dd;
+  }
+  block_tree(cnt, v, scnt, ssum);
+  if (threadIdx.x == 0) store_row(rows + (long)blockIdx.x * kWords, cnt, v);
+}
+
+// 256 rows -> one, by the same tree; rows beyond `count` are +0
+__global__ __launch_bounds__(kThreads) void cloud_moments_fold_kernel(const unsigned long long* __restrict__ in, long count,
+                                                                      unsigned long long* __restrict__ out) {
+  __shared__ long long scnt[kThreads / 64];
+  __shared__ double ssum[kThreads / 64][kWords - 1];
+  const long r = (long)blockIdx.x * kThreads + threadIdx.x;
+  long long cnt = 0;
+  double v[kWords - 1];
+#pragma unroll
+  for (int k = 0; k < kWords - 1; ++k) v[k] = 0.0;
+  if (r < count) {
+    cnt = (long long)in[r * kWords];
+#pragma unroll
+    for (int k = 0; k < kWords - 1; ++k) v[k] = __longlong_as_double((long long)in[r * kWords + 1 + k]);
+  }
+  block_tree(cnt, v, scnt, ssum);
+  if (threadIdx.x == 0) store_row(out + (long)blockIdx.x * kWords, cnt, v);
+}
+
+inline long moment_rows(long m) { return (m + kMomentTile - 1) / kMomentTile; }
+
+// ---- voxel down-sampling -------------------------------------------------------------------------------------------------------
+
+struct VoxelLayout {
+  size_t keys, first, zero, sums, cnt, slot, flags, tiles, total;   // [header | keys | first] are set to ~0 / 0, [sums .. flags] to 0
+  long slots;
+  int shift;                                                          // 64 - log2(slots)
+};
+inline long scan_tiles_for(long count) { return (count + kScanTile - 1) / kScanTile; }
+inline VoxelLayout voxel_layout(long n) {
+  VoxelLayout L;
+  long slots = kMinSlots;
+  int lg = 10;
+  while (slots < 2 * n) {
+    slots <<= 1;
+    ++lg;
+  }
+  L.slots = slots;
+  L.shift = 64 - lg;
+  L.keys = kVoxelHeader;
+  L.first = L.keys + align256((size_t)slots * 8);
+  L.zero = L.first + align256((size_t)slots * 4);
+  L.sums = L.zero;
+  L.cnt = L.sums + align256((size_t)slots * 24);
+  L.flags = L.cnt + align256((size_t)slots * 4);
+  L.slot = L.flags + align256((size_t)(n + 1) * 4);
+  L.tiles = L.slot + align256((size_t)n * 4);
+  L.total = L.tiles + align256((size_t)scan_tiles_for(n + 1) * 4);
+  return L;
+}
+
+__device__ __forceinline__ bool finite3(float x, float y, float z) {
+  const float big = __uint_as_float(0x7f800000u);
+  return fabsf(x) < big && fabsf(y) < big && fabsf(z) < big;
+}
+
+// cell c and fraction u of one coordinate; false when the cell leaves [0, 2^21)
+__device__ __forceinline__ bool voxel_coord(float x, double origin, double voxel, unsigned long long* c, unsigned long long* u) {
+  const double g = ((double)x - origin) / voxel;
+  const double cf = floor(g);
+  if (!(cf >= 0.0 && cf < kCellLimit)) return false;
+  const double f = floor((g - cf) * 4294967296.0);
+  *c = (unsigned long long)cf;
+  *u = f >= 4294967295.0 ? 4294967295ull : (unsigned long long)f;
+  return true;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_voxel_insert_kernel(const float* __restrict__ pts, long n, VoxelArgs A, long slots, int shift,
+                                                                      unsigned long long* __restrict__ keys, unsigned* __restrict__ first,
+                                                                      unsigned long long* __restrict__ sums, unsigned* __restrict__ cnt,
+                                                                      int* __restrict__ slot_of, int* __restrict__ err) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  int s = -1;
+  if (finite3(x, y, z)) {
+    unsigned long long c[3], u[3];
+    const bool ok = voxel_coord(x, A.origin[0], A.voxel, &c[0], &u[0]) & voxel_coord(y, A.origin[1], A.voxel, &c[1], &u[1]) &
+                    voxel_coord(z, A.origin[2], A.voxel, &c[2], &u[2]);
+    if (!ok) {
+      atomicOr(err, 1);
+    } else {
+      const unsigned long long key = c[0] | (c[1] << 21) | (c[2] << 42);
+      unsigned long long h = (key * 0x9E3779B97F4A7C15ull) >> shift;
+      for (long probe = 0; probe < slots; ++probe) {      // the table is at most half full: the loop ends long before `slots`
+        const unsigned long long seen = atomicCAS(keys + h, kEmpty, key);
+        if (seen == kEmpty || seen == key) {
+          s = (int)h;
+          break;
+        }
+        h = (h + 1) & (unsigned long long)(slots - 1);
+      }
+      if (s >= 0) {
+        atomicAdd(cnt + s, 1u);
+        atomicAdd(sums + (long)s * 3 + 0, u[0]);
+        atomicAdd(sums + (long)s * 3 + 1, u[1]);
+        atomicAdd(sums + (long)s * 3 + 2, u[2]);
+        atomicMin(first + s, (unsigned)i);
+      }
+    }
+  }
+  slot_of[i] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_voxel_flag_kernel(const int* __restrict__ slot_of, const unsigned* __restrict__ first, long n,
+                                                                    unsigned* __restrict__ flags) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot_of[i];
+  flags[i] = (s >= 0 && first[s] == (unsigned)i) ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_voxel_emit_kernel(const int* __restrict__ slot_of, long n, VoxelArgs A,
+                                                                    const unsigned long long* __restrict__ keys,
+                                                                    const unsigned* __restrict__ first,
+                                                                    const unsigned long long* __restrict__ sums,
+                                                                    const unsigned* __restrict__ cnt, const unsigned* __restrict__ pos,
+                                                                    const int* __restrict__ err, float* __restrict__ out_points,
+                                                                    long long* __restrict__ out_count, int* __restrict__ out_first) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  const bool bad = *err != 0;
+  if (i == 0) *out_count = bad ? -1ll : (long long)pos[n];
+  if (i >= n || bad) return;
+  const int s = slot_of[i];
+  if (s < 0 || first[s] != (unsigned)i) return;
+  const unsigned p = pos[i];
+  if ((long)p >= n) return;
+  const unsigned long long key = keys[s];
+  const double k = (double)cnt[s];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const double c = (double)((key >> (21 * a)) & 0x1fffffull);
+    const double mean = ((double)sums[(long)s * 3 + a] / k) / 4294967296.0;
+    out_points[(long)p * 3 + a] = (float)(A.origin[a] + A.voxel * (c + mean));
+  }
+  out_first[p] = (int)i;
+}
+
+}  // namespace
+
+extern "C" int atvs_cloud_transform(const float* points, long n, const double* matrix12, float* out, atvs_stream_t stream) {
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!matrix12 || (n > 0 && (!points || !out))) return ATVS_ERR_NULL;
+  if (n == 0) return ATVS_OK;
+  Matrix12 M;
+  for (int k = 0; k < 12; ++k) M.t[k] = matrix12[k];
+  hipLaunchKernelGGL(cloud_transform_kernel, dim3((unsigned)cdiv(n, kThreads)), dim3(kThreads), 0, as_stream(stream), points, n, M, out);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_pair_moments_scratch_size(long m, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
+  long rows = 0;
+  for (long r = moment_rows(m); r > 1; r = (r + kThreads - 1) / kThreads) rows += r;
+  *bytes = (long)align256((size_t)(rows + 1) * kWords * 8);
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_pair_moments(const float* src, const float* dst, long n, const int* idx, const float* d2, long m, double trim,
+                                       const double* pivot_src, const double* pivot_dst, void* scratch, long scratch_bytes, void* out,
+                                       atvs_stream_t stream) {
+  if (m < 0 || m > kMaxPoints || n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!out || !pivot_src || !pivot_dst || (m > 0 && (!src || !idx || !d2 || !scratch)) || (m > 0 && n > 0 && !dst)) return ATVS_ERR_NULL;
+  if (!(trim >= 0.0)) return ATVS_ERR_ARG;                  // NaN or negative; +inf is allowed
+  MomentArgs A;
+  A.trim2 = trim * trim;
+  for (int k = 0; k < 3; ++k) {
+    if (!(fabs(pivot_src[k]) <= 1.7976931348623157e308) || !(fabs(pivot_dst[k]) <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
+    A.ps[k] = pivot_src[k];
+    A.pd[k] = pivot_dst[k];
+  }
+  long need = 0;
+  atvs_cloud_pair_moments_scratch_size(m, &need);
+  if (m > 0 && scratch_bytes < need) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  unsigned long long* res = static_cast<unsigned long long*>(out);
+  if (m == 0) return hipMemsetAsync(out, 0, kWords * 8, st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
+  unsigned long long* level = static_cast<unsigned long long*>(scratch);
+  long rows = moment_rows(m);
+  hipLaunchKernelGGL(cloud_pair_moments_kernel, dim3((unsigned)rows), dim3(kThreads), 0, st, src, dst, n, idx, d2, m, A,
+                     rows == 1 ? res : level);
+  ATVS_LAUNCH_CHECK();
+  while (rows > 1) {
+    const long next = (rows + kThreads - 1) / kThreads;
+    unsigned long long* to = next == 1 ? res : level + rows * kWords;
+    hipLaunchKernelGGL(cloud_moments_fold_kernel, dim3((unsigned)next), dim3(kThreads), 0, st, (const unsigned long long*)level, rows, to);
+    ATVS_LAUNCH_CHECK();
+    level = to;
+    rows = next;
+  }
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  *bytes = (long)voxel_layout(n).total;
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_voxel_downsample(const float* points, long n, double voxel, const double* origin, void* scratch, long scratch_bytes,
+                                           float* out_points, long long* out_count, int* out_first, atvs_stream_t stream) {
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!origin || !out_count || (n > 0 && (!points || !scratch || !out_points || !out_first))) return ATVS_ERR_NULL;
+  if (!(voxel > 0.0) || !(voxel <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
+  VoxelArgs A;
+  A.voxel = voxel;
+  for (int k = 0; k < 3; ++k) {
+    if (!(fabs(origin[k]) <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
+    A.origin[k] = origin[k];
+  }
+  hipStream_t st = as_stream(stream);
+  if (n == 0) return hipMemsetAsync(out_count, 0, sizeof(long long), st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
+  const VoxelLayout L = voxel_layout(n);
+  if (scratch_bytes < (long)L.total) return ATVS_ERR_SHAPE;
+  char* s = static_cast<char*>(scratch);
+  int* err = reinterpret_cast<int*>(s);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s + L.keys);
+  unsigned* first = reinterpret_cast<unsigned*>(s + L.first);
+  unsigned long long* sums = reinterpret_cast<unsigned long long*>(s + L.sums);
+  unsigned* cnt = reinterpret_cast<unsigned*>(s + L.cnt);
+  unsigned* flags = reinterpret_cast<unsigned*>(s + L.flags);
+  int* slot_of = reinterpret_cast<int*>(s + L.slot);
+  unsigned* tiles = reinterpret_cast<unsigned*>(s + L.tiles);
+  if (hipMemsetAsync(s, 0, kVoxelHeader, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (hipMemsetAsync(s + L.keys, 0xff, L.zero - L.keys, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (hipMemsetAsync(s + L.zero, 0, L.slot - L.zero, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  const dim3 per_point((unsigned)cdiv(n, kThreads));
+  hipLaunchKernelGGL(cloud_voxel_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, keys, first, sums, cnt,
+                     slot_of, err);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_voxel_flag_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, (const unsigned*)first, n, flags);
+  ATVS_LAUNCH_CHECK();
+  const long count = n + 1, nt = scan_tiles_for(count);     // flags[n] = 0: after the scan it is the number of voxels
+  hipLaunchKernelGGL(cloud_scan_tile_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, flags, count, tiles);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(1024), 0, st, tiles, nt);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_add_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, flags, count, (const unsigned*)tiles);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_voxel_emit_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, n, A,
+                     (const unsigned long long*)keys, (const unsigned*)first, (const unsigned long long*)sums, (const unsigned*)cnt,
+                     (const unsigned*)flags, (const int*)err, out_points, out_count, out_first);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}

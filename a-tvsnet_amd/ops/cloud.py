@@ -1,6 +1,10 @@
 """Point-cloud scoring on the device (csrc/cloud.hip): a uniform grid over a reference cloud, the exact nearest reference point
 within a radius for every query, and tolerance counts.  The definition the kernels are held to is in include/atvsnet_hip.h; the
 evaluator built on them is atvsnet/eval_cloud.py.
+
+Registration (csrc/cloud_register.hip; atvsnet/register_cloud.py is built on it): cloud_transform moves a cloud through a matrix,
+cloud_pair_moments reduces matched pairs to the 18 sums of a closed-form similarity fit, cloud_voxel_downsample keeps one mean
+point per occupied voxel.
 """
 
 import ctypes
@@ -109,3 +113,106 @@ def cloud_counts(d2, tolerances, radius=None):
     arr = (ctypes.c_double * len(tol))(*tol)
     _call('atvs_cloud_counts', _p(d2), ctypes.c_long(int(d2.shape[0])), arr, len(tol), ctypes.c_float(r), _p(counts), _stream())
     return counts[:len(tol)]
+
+
+def _vec3(v, name):
+    a = np.zeros(3, np.float64) if v is None else np.asarray(v, np.float64).reshape(-1)
+    if a.shape != (3,) or not np.isfinite(a).all():
+        raise ValueError('%s: expected 3 finite numbers, got %r' % (name, v))
+    return (ctypes.c_double * 3)(*a.tolist())
+
+
+def cloud_transform(points, matrix, out=None):
+    """points (n,3) float32 through `matrix` (4x4, or its rows 0-2 as 3x4; host numbers) -> (n,3) float32: per coordinate k, in
+    double, ((T[k][0] x + T[k][1] y) + T[k][2] z) + T[k][3], rounded once to float32.  out: None (a new tensor) or a tensor to
+    write, which may be `points` itself."""
+    T = np.asarray(matrix, np.float64)
+    if T.shape not in ((4, 4), (3, 4)):
+        raise ValueError('matrix: expected a 4x4 (or 3x4) matrix, got shape %s' % (T.shape,))
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    if out is None:
+        out = torch.empty_like(points)
+    else:
+        _cloud_arg(out, 'out', torch.float32, (3,))
+        if out.shape != points.shape or out.device != points.device:
+            raise ValueError('out: expected %s on %s, got %s on %s' % (tuple(points.shape), points.device, tuple(out.shape), out.device))
+    arr = (ctypes.c_double * 12)(*T[:3].reshape(-1).tolist())
+    _call('atvs_cloud_transform', _p(points), ctypes.c_long(int(points.shape[0])), arr, _p(out), _stream())
+    return out
+
+
+def cloud_pair_moments(src, dst, idx, d2, trim=float('inf'), pivot_src=None, pivot_dst=None):
+    """src (m,3) float32: the queries as ops.cloud_nearest searched them; dst (n,3) float32: the grid's cloud in its original
+    order; idx (m,) int32, d2 (m,) float32: what cloud_nearest returned.  Pair i takes part when idx[i] >= 0 and
+    double(d2[i]) <= trim * trim.  With a = double(src[i]) - pivot_src, b = double(dst[idx[i]]) - pivot_dst (pivots: 3 host
+    numbers, default 0) -> (count, moments): the number of pairs as a Python int and a HOST numpy float64 (18,): sum a (3),
+    sum b (3), sum a_r b_c (9, row r of a), sum |a|^2, sum |b|^2, sum double(d2).  The 19 words are what crosses to the host
+    (one synchronising copy of 152 bytes); the same input gives the same words bit for bit."""
+    trim = float(trim)
+    if not trim >= 0.0:
+        raise ValueError('trim must be >= 0 (inf allowed), got %r' % (trim,))
+    ps, pd = _vec3(pivot_src, 'pivot_src'), _vec3(pivot_dst, 'pivot_dst')
+    _cloud_arg(src, 'src', torch.float32, (3,))
+    _cloud_arg(dst, 'dst', torch.float32, (3,))
+    _cloud_arg(idx, 'idx', torch.int32, ())
+    _cloud_arg(d2, 'd2', torch.float32, ())
+    m, n = int(src.shape[0]), int(dst.shape[0])
+    if int(idx.shape[0]) != m or int(d2.shape[0]) != m:
+        raise ValueError('idx %s and d2 %s must have one entry per row of src %s' % (tuple(idx.shape), tuple(d2.shape), tuple(src.shape)))
+    for t, name in ((dst, 'dst'), (idx, 'idx'), (d2, 'd2')):
+        if t.device != src.device:
+            raise RuntimeError('%s on %s, src on %s' % (name, t.device, src.device))
+    out = torch.empty(19, dtype=torch.int64, device=src.device)
+    scratch = torch.empty(_size('atvs_cloud_pair_moments_scratch_size', m), dtype=torch.uint8, device=src.device)
+    _call('atvs_cloud_pair_moments', _p(src), _p(dst), ctypes.c_long(n), _p(idx), _p(d2), ctypes.c_long(m), ctypes.c_double(trim),
+          ps, pd, _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    words = out.cpu().numpy()
+    return int(words[0]), words[1:].view(np.float64).copy()
+
+
+def cloud_voxel_downsample(points, voxel, origin=None):
+    """points (n,3) float32, voxel > 0 -> (means (k,3) float32, first (k,) int32): one point per occupied cubic voxel of edge
+    `voxel`, the exact mean of the voxel's finite points (integer sums of 32-bit fractions; include/atvsnet_hip.h), in ascending
+    order of the voxel's lowest original index, which is `first`.  Non-finite points are dropped.  origin: 3 host numbers, the
+    corner of voxel (0,0,0); None: the floor of the finite points' minimum (one small reduction and copy).  A point more than
+    2^21 voxels from the origin, or below it, raises with the voxel size that would fit.  Synchronises once, to read k."""
+    voxel = float(voxel)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
+    if origin is not None:
+        org = _vec3(origin, 'origin')
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    n = int(points.shape[0])
+    if origin is None:
+        lo = cloud_bounds(points)[0] if n else None
+        org = _vec3(None if lo is None else np.floor(lo), 'origin')
+    means = torch.empty((n, 3), dtype=torch.float32, device=points.device)
+    first = torch.empty(n, dtype=torch.int32, device=points.device)
+    count = torch.empty(1, dtype=torch.int64, device=points.device)
+    scratch = torch.empty(_size('atvs_cloud_voxel_downsample_scratch_size', n), dtype=torch.uint8, device=points.device)
+    _call('atvs_cloud_voxel_downsample', _p(points), ctypes.c_long(n), ctypes.c_double(voxel), org, _p(scratch),
+          ctypes.c_long(scratch.numel()), _p(means), _p(count), _p(first), _stream())
+    k = int(count.item())
+    if k < 0:
+        lo, hi = cloud_bounds(points)
+        o = np.array(list(org))
+        if (lo < o).any():
+            raise ValueError('cloud_voxel_downsample: a point lies below the origin %s (the finite minimum is %s)' % (o.tolist(), lo.tolist()))
+        fit = float((hi - o).max()) / float(1 << 21) * (1.0 + 1e-5)          # a little above the limit, so that the printed digits fit too
+        raise ValueError('cloud_voxel_downsample: voxel %r puts a point more than 2^21 voxels from the origin (bad shape); the '
+                         'smallest voxel that fits this cloud is %.8g' % (voxel, fit))
+    return means[:k], first[:k]
+
+
+def cloud_bounds(points):
+    """(min, max) host numpy float64 (3,) over the finite rows of a device cloud (n,3) float32, or (None, None) when there is
+    none.  Plumbing around the kernels (torch reductions, one small copy): the default origin of cloud_voxel_downsample, the
+    pivots and the box corners of register_cloud.register."""
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    ok = torch.isfinite(points).all(dim=1)
+    if not bool(ok.any()):
+        return None, None
+    big = torch.tensor(float('inf'), device=points.device)
+    lo = torch.where(ok[:, None], points, big).amin(dim=0)
+    hi = torch.where(ok[:, None], points, -big).amax(dim=0)
+    return lo.double().cpu().numpy(), hi.double().cpu().numpy()

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 48
+#define ATVS_ABI_VERSION 49
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -768,6 +768,47 @@ int atvs_cloud_nearest(const void* grid, long grid_bytes, long n, const float* q
                        float* d2, int* idx, atvs_stream_t stream);
 int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, float radius, long long* counts,
                       atvs_stream_t stream);
+
+/* Point-cloud registration (ops/cloud.py, atvsnet/register_cloud.py, csrc/cloud_register.hip).  Pointers are device pointers unless
+ * named host.  Integer atomics only: every output is a function of the inputs alone, bit for bit on every run.  No host
+ * synchronisation; scratch is the caller's.  tests/cloud_register_restated.py restates the three definitions.
+ *
+ * atvs_cloud_transform: out (n,3) float32 = points (n,3) through matrix12 (HOST, 12 doubles: rows 0-2 of a 4x4 matrix, row-major;
+ * copied into the launch).  Per point and output coordinate k, in double: ((T[k][0] x + T[k][1] y) + T[k][2] z) + T[k][3], every
+ * operation rounded to double, the result rounded once to float32.  Non-finite inputs propagate as IEEE gives them.  `out` may be
+ * `points`.
+ *
+ * atvs_cloud_pair_moments: src (m,3) float32 = the queries as they were searched, dst (n,3) float32 = the searched cloud in its
+ * original order, idx (m) int32 and d2 (m) float32 = what atvs_cloud_nearest returned.  Pair i takes part when 0 <= idx[i] < n and
+ * (double)d2[i] <= trim * trim (trim a double >= 0, +inf allowed; a NaN d2 takes no part).  With a = (double)src[i] - pivot_src and
+ * b = (double)dst[idx[i]] - pivot_dst (pivots: HOST, 3 finite doubles each, chosen by the caller so that the sums do not cancel far
+ * from the origin), `out` receives 19 8-byte words: [0] the pair count (int64), then 18 doubles: [1..3] sum a, [4..6] sum b,
+ * [7..15] sum a_r * b_c (row r of a: [7 + 3 r + c]), [16] sum (a0 a0 + a1 a1) + a2 a2, [17] sum (b0 b0 + b1 b1) + b2 b2,
+ * [18] sum (double)d2.  Every term is formed in double as written, each product and sum rounded.  The reduction has a FIXED shape
+ * (csrc/cloud_register.hip): an accumulator sees at most L = ATVS_CLOUD_MOMENT_RUN serial additions, then per-workgroup partial
+ * rows are folded by fixed trees in index order, at most L + ceil(log2 m) rounding additions deep in all.  m = 0: 19 zero words.
+ * scratch: atvs_cloud_pair_moments_scratch_size(m) bytes.  trim negative or NaN, a non-finite pivot: ATVS_ERR_ARG.
+ *
+ * atvs_cloud_voxel_downsample: one output point per occupied cubic voxel of edge `voxel` (double > 0): the mean of the voxel's
+ * finite points; non-finite points are dropped.  origin: HOST, 3 finite doubles.  Per axis, in double: g = ((double)x - origin) /
+ * voxel, c = floor(g), u = (uint64)floor((g - c) * 2^32) clamped to 2^32 - 1.  A voxel is the triple of c, packed 3 x 21 bits as
+ * the key of an open-addressing hash table (capacity = the power of two >= max(2 n, 1024); 64-bit compare-and-swap); its slot
+ * holds the count k, the three exact unsigned 64-bit sums S of u and the lowest original index.  The output coordinate is
+ * origin + voxel * ((double)c + ((double)S / (double)k) / 2^32), rounded once to float32.  Output order: ascending lowest original
+ * index of the voxel; out_first (k) int32 is that index, out_points (k,3) the means (both with room for n rows), out_count (one
+ * int64, device) the number of voxels.  A finite point whose cell coordinate leaves [0, 2^21) on an axis makes the call a
+ * shape error that only the device can see: out_count is -1 and out_points / out_first are not written (ops/cloud.py raises).
+ * scratch: atvs_cloud_voxel_downsample_scratch_size(n) bytes (40 B per slot, 8 B per point).  voxel <= 0 or not finite, a
+ * non-finite origin: ATVS_ERR_ARG.  n or m negative or beyond 2^30, a short scratch: ATVS_ERR_SHAPE. */
+#define ATVS_CLOUD_MOMENT_RUN 16
+int atvs_cloud_transform(const float* points, long n, const double* matrix12, float* out, atvs_stream_t stream);
+int atvs_cloud_pair_moments_scratch_size(long m, long* bytes);
+int atvs_cloud_pair_moments(const float* src, const float* dst, long n, const int* idx, const float* d2, long m, double trim,
+                            const double* pivot_src, const double* pivot_dst, void* scratch, long scratch_bytes, void* out,
+                            atvs_stream_t stream);
+int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes);
+int atvs_cloud_voxel_downsample(const float* points, long n, double voxel, const double* origin, void* scratch, long scratch_bytes,
+                                float* out_points, long long* out_count, int* out_first, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
