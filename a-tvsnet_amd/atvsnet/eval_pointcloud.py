@@ -21,6 +21,7 @@ import torch
 from .. import variables
 from ..flags import FLAGS
 from ..tools.common import Notify
+from . import clean_cloud
 from . import depth_fusion
 from . import eval_cloud
 from . import example
@@ -299,7 +300,7 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None, register=None):
+                gt_ply=None, register=None, clean=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
@@ -309,7 +310,12 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     gt_ply (with fuse only): ground-truth PLY paths; each scene's fused points, as the PLY stores them, are scored against them
     (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY.
     register (with gt_ply only): None, or dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned
-    to the ground truth before it is scored (eval_cloud --register [--init_cameras]); cloud_eval.json carries `registration`."""
+    to the ground truth before it is scored (eval_cloud --register [--init_cameras]); cloud_eval.json carries `registration`.
+    clean (with fuse only): None, or dict(voxel=, sor=(k, ratio, radius), radius_filter=(radius, min_neighbours)), the arguments of
+    clean_cloud.clean: each scene's fused points, as the PLY stores them, are cleaned into <savepath>/<scene>/
+    final3d_model_clean.ply with the report in cloud_clean.json; with gt_ply the cleaned cloud is scored too, into
+    cloud_eval_clean.json (with register: moved by the matrix found for the uncleaned cloud, not registered again).
+    final3d_model.ply and cloud_eval.json are what they are without it."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
@@ -322,6 +328,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         raise ValueError('gt_ply (--gt_ply) needs fuse (--fuse): there is no point cloud to score')
     if register is not None and not gt_ply:
         raise ValueError('register (--register) needs gt_ply (--gt_ply): there is nothing to align to')
+    if clean and fuse is None:
+        raise ValueError('clean (--clean_voxel, --clean_sor, --clean_radius_filter) needs fuse (--fuse): there is no point cloud to clean')
     gt_points, register_args, init_cameras = None, {}, None
     if gt_ply:
         from ..tools.ply import read_ply_points
@@ -446,15 +454,36 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
                 scene_fusion = fusion.pop()
                 n_points = scene_fusion.write_ply(os.path.join(savepath_current, 'final3d_model.ply'))
                 TIMES['fuse'] = time.time() - t0
+                points, colors = None, None
+                if gt_points is not None or clean:
+                    points, colors = scene_fusion.run()
+                    points = points.copy()
+                    points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
+                score = None
                 if gt_points is not None:
                     t0 = time.time()
-                    points = scene_fusion.run()[0].copy()
-                    points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
                     score = eval_cloud.evaluate(points, gt_points, device=device, **register_args)
                     if init_cameras is not None:
                         score['init_cameras'] = init_cameras
                     eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'), score)
                     TIMES['cloud_eval'] = time.time() - t0
+                if clean:
+                    from ..tools.ply import write_ply
+                    t0 = time.time()
+                    clean_points, clean_colors, clean_report = clean_cloud.clean(points, colors, device=device, **clean)
+                    write_ply(os.path.join(savepath_current, 'final3d_model_clean.ply'), clean_points, clean_colors)
+                    clean_cloud.write_json(os.path.join(savepath_current, 'cloud_clean.json'), clean_report)
+                    TIMES['cloud_clean'] = time.time() - t0
+                    if score is not None:
+                        # the same transform: the matrix found for the whole cloud (it includes the initial one), not a second fit
+                        moved = {}
+                        if 'registration' in score:
+                            moved['init_transform'] = score['registration']['matrix']
+                        elif 'init_transform' in score:
+                            moved['init_transform'] = score['init_transform']
+                        clean_score = eval_cloud.evaluate(clean_points, gt_points, device=device, **moved)
+                        eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval_clean.json'), clean_score)
+                    print(Notify.INFO, '%s: %d points after cleaning' % (image_info[2], len(clean_points)), Notify.ENDC)
                 print(Notify.INFO, '%s: %d fused points' % (image_info[2], n_points), Notify.ENDC)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
@@ -482,7 +511,7 @@ def main(scene_list=None, base_path='eth3d/'):
     run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
                 scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
                 map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None,
-                register=register)
+                register=register, clean=getattr(FLAGS, 'clean', None) or None)
 
 
 def cli(argv=None):
@@ -525,6 +554,7 @@ def cli(argv=None):
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
                         help='--register: two COLMAP sparse model folders of the same images (the scene\'s own and one in the '
                              'ground truth\'s frame); their camera centres give the initial similarity')
+    clean_cloud.add_options(parser, 'clean_')
     args = parser.parse_args(argv)
     if args.eager and args.scene_cache:
         parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
@@ -537,6 +567,9 @@ def cli(argv=None):
     if (args.with_scale or args.init_cameras) and not args.register:
         parser.error('--with_scale and --init_cameras need --register')
     args.gt_ply = [p for p in args.gt_ply.split(',') if p] if args.gt_ply else None
+    args.clean = clean_cloud.options(parser, args, 'clean_') or None
+    if args.clean and not args.fuse:
+        parser.error('--clean_voxel, --clean_sor and --clean_radius_filter need --fuse: there is no point cloud to clean')
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False
     for k, v in vars(args).items():

@@ -21,12 +21,11 @@
 
 #include "common.h"
 #include "cloud_scan.h"
+#include "cloud_tree.h"
 
 namespace {
 
 constexpr long kMaxPoints = 1L << 30;
-constexpr int kMomentRun = ATVS_CLOUD_MOMENT_RUN;      // L: serial additions per accumulator before the tree
-constexpr long kMomentTile = (long)kThreads * kMomentRun;
 constexpr int kWords = 19;                             // pair count (int64) + 18 doubles
 constexpr long kMinSlots = 1024;
 constexpr size_t kVoxelHeader = 256;
@@ -62,49 +61,14 @@ __global__ __launch_bounds__(kThreads) void cloud_transform_kernel(const float* 
   out[i * 3 + 2] = oz;
 }
 
-// The fixed tree of one workgroup: v[0] is the pair count, v[1..18] the sums.  The result is valid in thread 0.
-__device__ __forceinline__ void block_tree(long long& cnt, double* v, long long* scnt, double (*ssum)[kWords - 1]) {
-  for (int off = 32; off > 0; off >>= 1) {
-    cnt += __shfl_down(cnt, off);
-#pragma unroll
-    for (int k = 0; k < kWords - 1; ++k) v[k] = v[k] + __shfl_down(v[k], off);
-  }
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  if (lane == 0) {
-    scnt[w] = cnt;
-#pragma unroll
-    for (int k = 0; k < kWords - 1; ++k) ssum[w][k] = v[k];
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    cnt = (scnt[0] + scnt[1]) + (scnt[2] + scnt[3]);
-#pragma unroll
-    for (int k = 0; k < kWords - 1; ++k) v[k] = (ssum[0][k] + ssum[1][k]) + (ssum[2][k] + ssum[3][k]);
-  }
-}
-
-__device__ __forceinline__ void store_row(unsigned long long* row, long long cnt, const double* v) {
-  row[0] = (unsigned long long)cnt;
-#pragma unroll
-  for (int k = 0; k < kWords - 1; ++k) row[1 + k] = (unsigned long long)__double_as_longlong(v[k]);
-}
-
 __global__ __launch_bounds__(kThreads) void cloud_pair_moments_kernel(const float* __restrict__ src, const float* __restrict__ dst, long n,
                                                                       const int* __restrict__ idx, const float* __restrict__ d2, long m,
                                                                       MomentArgs A, unsigned long long* __restrict__ rows) {
-  __shared__ long long scnt[kThreads / 64];
-  __shared__ double ssum[kThreads / 64][kWords - 1];
-  long long cnt = 0;
-  double v[kWords - 1];
-#pragma unroll
-  for (int k = 0; k < kWords - 1; ++k) v[k] = 0.0;
-  const long base = (long)blockIdx.x * kMomentTile + threadIdx.x;
-  for (int r = 0; r < kMomentRun; ++r) {
-    const long i = base + (long)r * kThreads;
-    if (i >= m) break;
+  __shared__ MomentShared<kWords - 1> sh;
+  moment_row<kWords - 1>(m, [&](long i, long long& cnt, double* v) {
     const int j = idx[i];
     const float dd = d2[i];
-    if (j < 0 || (long)j >= n || !((double)dd <= A.trim2)) continue;
+    if (j < 0 || (long)j >= n || !((double)dd <= A.trim2)) return;
     const double a0 = (double)src[i * 3 + 0] - A.ps[0], a1 = (double)src[i * 3 + 1] - A.ps[1], a2 = (double)src[i * 3 + 2] - A.ps[2];
     const double b0 = (double)dst[(long)j * 3 + 0] - A.pd[0], b1 = (double)dst[(long)j * 3 + 1] - A.pd[1],
                  b2 = (double)dst[(long)j * 3 + 2] - A.pd[2];
@@ -117,31 +81,8 @@ __global__ __launch_bounds__(kThreads) void cloud_pair_moments_kernel(const floa
     v[15] = v[15] + ((a0 * a0 + a1 * a1) + a2 * a2);
     v[16] = v[16] + ((b0 * b0 + b1 * b1) + b2 * b2);
     v[17] = v[17] + (double)dd;
-  }
-  block_tree(cnt, v, scnt, ssum);
-  if (threadIdx.x == 0) store_row(rows + (long)blockIdx.x * kWords, cnt, v);
+  }, rows, sh);
 }
-
-// 256 rows -> one, by the same tree; rows beyond `count` are +0
-__global__ __launch_bounds__(kThreads) void cloud_moments_fold_kernel(const unsigned long long* __restrict__ in, long count,
-                                                                      unsigned long long* __restrict__ out) {
-  __shared__ long long scnt[kThreads / 64];
-  __shared__ double ssum[kThreads / 64][kWords - 1];
-  const long r = (long)blockIdx.x * kThreads + threadIdx.x;
-  long long cnt = 0;
-  double v[kWords - 1];
-#pragma unroll
-  for (int k = 0; k < kWords - 1; ++k) v[k] = 0.0;
-  if (r < count) {
-    cnt = (long long)in[r * kWords];
-#pragma unroll
-    for (int k = 0; k < kWords - 1; ++k) v[k] = __longlong_as_double((long long)in[r * kWords + 1 + k]);
-  }
-  block_tree(cnt, v, scnt, ssum);
-  if (threadIdx.x == 0) store_row(out + (long)blockIdx.x * kWords, cnt, v);
-}
-
-inline long moment_rows(long m) { return (m + kMomentTile - 1) / kMomentTile; }
 
 // ---- voxel down-sampling -------------------------------------------------------------------------------------------------------
 
@@ -276,9 +217,7 @@ extern "C" int atvs_cloud_transform(const float* points, long n, const double* m
 extern "C" int atvs_cloud_pair_moments_scratch_size(long m, long* bytes) {
   if (!bytes) return ATVS_ERR_NULL;
   if (m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
-  long rows = 0;
-  for (long r = moment_rows(m); r > 1; r = (r + kThreads - 1) / kThreads) rows += r;
-  *bytes = (long)align256((size_t)(rows + 1) * kWords * 8);
+  *bytes = (long)moment_scratch_bytes<kWords - 1>(m);
   return ATVS_OK;
 }
 
@@ -302,19 +241,10 @@ extern "C" int atvs_cloud_pair_moments(const float* src, const float* dst, long 
   unsigned long long* res = static_cast<unsigned long long*>(out);
   if (m == 0) return hipMemsetAsync(out, 0, kWords * 8, st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
   unsigned long long* level = static_cast<unsigned long long*>(scratch);
-  long rows = moment_rows(m);
-  hipLaunchKernelGGL(cloud_pair_moments_kernel, dim3((unsigned)rows), dim3(kThreads), 0, st, src, dst, n, idx, d2, m, A,
-                     rows == 1 ? res : level);
+  hipLaunchKernelGGL(cloud_pair_moments_kernel, dim3((unsigned)moment_rows(m)), dim3(kThreads), 0, st, src, dst, n, idx, d2, m, A,
+                     moment_first(m, level, res));
   ATVS_LAUNCH_CHECK();
-  while (rows > 1) {
-    const long next = (rows + kThreads - 1) / kThreads;
-    unsigned long long* to = next == 1 ? res : level + rows * kWords;
-    hipLaunchKernelGGL(cloud_moments_fold_kernel, dim3((unsigned)next), dim3(kThreads), 0, st, (const unsigned long long*)level, rows, to);
-    ATVS_LAUNCH_CHECK();
-    level = to;
-    rows = next;
-  }
-  return ATVS_OK;
+  return moment_fold<kWords - 1>(m, level, res, st);
 }
 
 extern "C" int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes) {

@@ -10,7 +10,8 @@
     prepare   the scene driver's view preparation (uint8 image -> network input, 1/4 image)
     colmap    COLMAP model import: per-image depth range, co-visibility matrix
     cloud     point-cloud scoring: uniform grid, exact nearest neighbour within a radius, tolerance counts;
-              registration: transform, pair moments, voxel down-sampling
+              registration: transform, pair moments, voxel down-sampling; neighbourhoods: k nearest neighbours, radius counts,
+              outlier statistics, bounding box
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -40,4 +41,5 @@ from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, d
 from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range      # noqa: F401
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401
 from .cloud import cloud_bounds, cloud_pair_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
+from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

@@ -5,6 +5,10 @@ evaluator built on them is atvsnet/eval_cloud.py.
 Registration (csrc/cloud_register.hip; atvsnet/register_cloud.py is built on it): cloud_transform moves a cloud through a matrix,
 cloud_pair_moments reduces matched pairs to the 18 sums of a closed-form similarity fit, cloud_voxel_downsample keeps one mean
 point per occupied voxel.
+
+Neighbourhoods (csrc/cloud_knn.hip; atvsnet/clean_cloud.py is built on it): cloud_knn finds the k nearest reference points within
+the grid's radius, cloud_radius_count counts the reference points inside it, cloud_knn_mean and cloud_sor_stats reduce the k-NN
+distances to the three numbers of statistical outlier removal, cloud_bounds is the bounding box of the finite rows.
 """
 
 import ctypes
@@ -18,6 +22,7 @@ from .base import _ERR, _call, _p, _stream
 
 CLOUD_MAX_POINTS = 1 << 30
 CLOUD_MAX_TOLERANCES = 16
+CLOUD_MAX_K = 32
 
 
 def _cloud_arg(t, name, dtype, trailing):
@@ -206,13 +211,96 @@ def cloud_voxel_downsample(points, voxel, origin=None):
 
 def cloud_bounds(points):
     """(min, max) host numpy float64 (3,) over the finite rows of a device cloud (n,3) float32, or (None, None) when there is
-    none.  Plumbing around the kernels (torch reductions, one small copy): the default origin of cloud_voxel_downsample, the
-    pivots and the box corners of register_cloud.register."""
+    none.  One reduction kernel (atvs_cloud_bounds, the bounding-box pass of the grid build) and one copy of 32 bytes: the default
+    origin of cloud_voxel_downsample, the pivots and the box corners of register_cloud.register."""
     _cloud_arg(points, 'points', torch.float32, (3,))
-    ok = torch.isfinite(points).all(dim=1)
-    if not bool(ok.any()):
+    out = torch.empty(8, dtype=torch.int32, device=points.device)
+    _call('atvs_cloud_bounds', _p(points), ctypes.c_long(int(points.shape[0])), _p(out), _stream())
+    words = out.cpu().numpy()
+    if not words[6]:
         return None, None
-    big = torch.tensor(float('inf'), device=points.device)
-    lo = torch.where(ok[:, None], points, big).amin(dim=0)
-    hi = torch.where(ok[:, None], points, -big).amax(dim=0)
-    return lo.double().cpu().numpy(), hi.double().cpu().numpy()
+    box = words[:6].view(np.float32).astype(np.float64)
+    return box[:3].copy(), box[3:].copy()
+
+
+def _search_args(grid, queries, exclude_same_index):
+    """The checks cloud_knn and cloud_radius_count share -> m."""
+    if not isinstance(grid, CloudGrid):
+        raise TypeError('grid: expected a CloudGrid (ops.cloud_grid), got %s' % type(grid).__name__)
+    if exclude_same_index and isinstance(queries, torch.Tensor) and queries.dim() == 2 and int(queries.shape[0]) != grid.n:
+        raise ValueError('exclude_same_index: the queries must be the grid\'s own cloud, row for row (%d queries, %d reference '
+                         'points)' % (int(queries.shape[0]), grid.n))
+    _cloud_arg(queries, 'queries', torch.float32, (3,))
+    if queries.device != grid.buf.device:
+        raise RuntimeError('queries on %s, the grid on %s' % (queries.device, grid.buf.device))
+    m = int(queries.shape[0])
+    return m
+
+
+def _check_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= CLOUD_MAX_K:
+        raise ValueError('k: expected an integer in 1..%d, got %r' % (CLOUD_MAX_K, k))
+    return int(k)
+
+
+def cloud_knn(grid, queries, k, exclude_same_index=False):
+    """queries (m,3) float32, 1 <= k <= 32 -> (d2 (m,k) float32, idx (m,k) int32): per query its k nearest finite points of the
+    grid's cloud within the grid's radius (double(d2) <= double(R)^2, d2 the float32 (dx*dx + dy*dy) + dz*dz), in ascending order
+    of (d2, index), padded with (+inf, -1); a non-finite query has none.  exclude_same_index: the queries are the grid's own cloud
+    and row j is no neighbour of itself (index j alone: a duplicate at another index is a neighbour at distance 0).  With k = 1
+    and the flag clear it is cloud_nearest bit for bit."""
+    k = _check_k(k)
+    m = _search_args(grid, queries, exclude_same_index)
+    d2 = torch.empty((m, k), dtype=torch.float32, device=queries.device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=queries.device)
+    if m == 0:
+        return d2, idx
+    scratch = torch.empty(_size('atvs_cloud_knn_scratch_size', grid.n, m), dtype=torch.uint8, device=queries.device)
+    _call('atvs_cloud_knn', _p(grid.buf), ctypes.c_long(grid.buf.numel()), ctypes.c_long(grid.n), _p(queries), ctypes.c_long(m),
+          ctypes.c_int(k), ctypes.c_int(1 if exclude_same_index else 0), _p(scratch), ctypes.c_long(scratch.numel()), _p(d2), _p(idx),
+          _stream())
+    return d2, idx
+
+
+def cloud_radius_count(grid, queries, exclude_same_index=False):
+    """queries (m,3) float32 -> count (m,) int32: the number of finite points of the grid's cloud with double(d2) <= double(R)^2
+    (cloud_knn's candidates and distance); 0 for a non-finite query.  exclude_same_index as for cloud_knn."""
+    m = _search_args(grid, queries, exclude_same_index)
+    count = torch.empty(m, dtype=torch.int32, device=queries.device)
+    if m == 0:
+        return count
+    scratch = torch.empty(_size('atvs_cloud_knn_scratch_size', grid.n, m), dtype=torch.uint8, device=queries.device)
+    _call('atvs_cloud_radius_count', _p(grid.buf), ctypes.c_long(grid.buf.numel()), ctypes.c_long(grid.n), _p(queries),
+          ctypes.c_long(m), ctypes.c_int(1 if exclude_same_index else 0), _p(scratch), ctypes.c_long(scratch.numel()), _p(count),
+          _stream())
+    return count
+
+
+def cloud_knn_mean(d2):
+    """d2 (m,k) float32 of cloud_knn -> s (m,) float64: the mean distance to the k neighbours, (sum_t sqrt(double(d2[j,t]))) / k
+    added in ascending t in double, or +inf where the row has fewer than k neighbours (a padded entry)."""
+    if not isinstance(d2, torch.Tensor):
+        raise TypeError('d2: expected a tensor, got %s' % type(d2).__name__)
+    k = int(d2.shape[1]) if d2.dim() == 2 else 0
+    if not 1 <= k <= CLOUD_MAX_K:
+        raise ValueError('d2: expected shape (m,k) with k in 1..%d, got %s' % (CLOUD_MAX_K, tuple(d2.shape)))
+    _cloud_arg(d2, 'd2', torch.float32, (k,))
+    m = int(d2.shape[0])
+    s = torch.empty(m, dtype=torch.float64, device=d2.device)
+    if m:
+        _call('atvs_cloud_knn_mean', _p(d2), ctypes.c_long(m), ctypes.c_int(k), _p(s), _stream())
+    return s
+
+
+def cloud_sor_stats(s):
+    """s (m,) float64 of cloud_knn_mean -> (count, mean, std) as Python numbers: the number of finite entries, their mean, and
+    the sample standard deviation sqrt(sum (s - mean)^2 / (count - 1)) (0 below two entries; the mean is 0 of none).  Two passes of
+    a fixed-shape sum on the device: the same s gives the same three words bit for bit; they are all that crosses to the host."""
+    _cloud_arg(s, 's', torch.float64, ())
+    m = int(s.shape[0])
+    out = torch.empty(3, dtype=torch.int64, device=s.device)
+    scratch = torch.empty(_size('atvs_cloud_sor_stats_scratch_size', m), dtype=torch.uint8, device=s.device)
+    _call('atvs_cloud_sor_stats', _p(s), ctypes.c_long(m), _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    words = out.cpu().numpy()
+    mean, std = words[1:].view(np.float64).tolist()
+    return int(words[0]), mean, std

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 49
+#define ATVS_ABI_VERSION 50
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -809,6 +809,46 @@ int atvs_cloud_pair_moments(const float* src, const float* dst, long n, const in
 int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes);
 int atvs_cloud_voxel_downsample(const float* points, long n, double voxel, const double* origin, void* scratch, long scratch_bytes,
                                 float* out_points, long long* out_count, int* out_first, atvs_stream_t stream);
+
+/* Point-cloud neighbourhoods (ops/cloud.py, atvsnet/clean_cloud.py, csrc/cloud_knn.hip): the k nearest reference points, the
+ * number of reference points inside the radius, and the statistics of statistical outlier removal.  Pointers are device pointers.
+ * No float atomics, no host synchronisation, no allocation; scratch is the caller's.  tests/cloud_knn_restated.py restates the
+ * definitions.  `grid` is a grid of atvs_cloud_grid_build over a reference cloud P (n,3) with radius R; Q (m,3) are the queries.
+ *
+ * Candidates.  A candidate of query j is every finite reference point i, except i == j when exclude_same_index is set (a cloud
+ * searched in itself: m must equal n; ONE index is excluded, not a position: a duplicate of the query at another index is a
+ * neighbour at distance 0).  d2 is the float32 expression above, (dx*dx + dy*dy) + dz*dz.  A candidate is kept when
+ * (double)d2 <= (double)R * (double)R.  Kept candidates are ordered by (bits(d2), i) ascending -- the 64-bit key
+ * (bits(d2) << 32) | i that atvs_cloud_nearest minimises.  A non-finite query, or one further than a cell outside the grid, has no
+ * candidate.
+ *
+ * atvs_cloud_knn: d2 (m,k) float32 and idx (m,k) int32, 1 <= k <= ATVS_CLOUD_MAX_K: per query the first k keys of that order,
+ * padded with (+inf, -1).  With k = 1 and the flag clear it is atvs_cloud_nearest bit for bit.  The output depends on P, Q, R, k
+ * and the flag only.  scratch: atvs_cloud_knn_scratch_size(n, m) bytes (the queries' counting sort, as for atvs_cloud_nearest).
+ * atvs_cloud_radius_count: count (m) int32 = the number of kept candidates; the same scratch.
+ * atvs_cloud_knn_mean: d2 (m,k) of atvs_cloud_knn -> s (m) float64: where all k entries are finite
+ * s = (sum_t sqrt((double)d2[j,t])) / k, added in ascending t from +0, every operation rounded to double; otherwise +inf (the k-th
+ * neighbour lies beyond the radius).
+ * atvs_cloud_sor_stats: s (m) float64 -> out, three 8-byte words: [0] c = the number of finite entries (int64), [1] their mean
+ * mu = (sum s) / c (double; 0 when c = 0), [2] sigma = sqrt((sum (s - mu)^2) / (c - 1)) (double; 0 when c < 2): the sample form
+ * PCL and Open3D use.  Two passes over s; the second reads mu from the first one's result on the device.  Both sums have the fixed
+ * shape of atvs_cloud_pair_moments (ATVS_CLOUD_MOMENT_RUN serial additions, then fixed trees in index order): no atomics, the
+ * same s gives the same three words bit for bit.  scratch: atvs_cloud_sor_stats_scratch_size(m) bytes.  m = 0: three zero words.
+ * atvs_cloud_bounds: out, eight 4-byte words: [0..2] the minimum, [3..5] the maximum x, y, z (float32) over the finite rows of
+ * points (n,3), [6] 1 when there is a finite row, else 0 (and [0..5] are 0), [7] 0.  The bounding-box pass of
+ * atvs_cloud_grid_build (integer atomic max on order-preserving bit patterns).
+ * k outside [1, ATVS_CLOUD_MAX_K], n or m negative or beyond 2^30, exclude_same_index with m != n, a short grid or scratch:
+ * ATVS_ERR_SHAPE.  m = 0 is valid (nothing is written). */
+#define ATVS_CLOUD_MAX_K 32
+int atvs_cloud_knn_scratch_size(long n, long m, long* bytes);
+int atvs_cloud_knn(const void* grid, long grid_bytes, long n, const float* queries, long m, int k, int exclude_same_index,
+                   void* scratch, long scratch_bytes, float* d2, int* idx, atvs_stream_t stream);
+int atvs_cloud_radius_count(const void* grid, long grid_bytes, long n, const float* queries, long m, int exclude_same_index,
+                            void* scratch, long scratch_bytes, int* count, atvs_stream_t stream);
+int atvs_cloud_knn_mean(const float* d2, long m, int k, double* s, atvs_stream_t stream);
+int atvs_cloud_sor_stats_scratch_size(long m, long* bytes);
+int atvs_cloud_sor_stats(const double* s, long m, void* scratch, long scratch_bytes, void* out, atvs_stream_t stream);
+int atvs_cloud_bounds(const float* points, long n, void* out, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
