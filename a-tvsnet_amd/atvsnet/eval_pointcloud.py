@@ -24,6 +24,7 @@ from ..tools.common import Notify
 from . import clean_cloud
 from . import depth_fusion
 from . import eval_cloud
+from . import eval_depth
 from . import example
 from . import scene
 from .preprocess import (center_image, crop_mvs_input, crop_window, gen_pipeline_mvs_list, load_cam, scale_camera, scale_image,
@@ -300,7 +301,7 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None, register=None, clean=None):
+                gt_ply=None, register=None, clean=None, score_maps=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
@@ -315,7 +316,12 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     clean_cloud.clean: each scene's fused points, as the PLY stores them, are cleaned into <savepath>/<scene>/
     final3d_model_clean.ply with the report in cloud_clean.json; with gt_ply the cleaned cloud is scored too, into
     cloud_eval_clean.json (with register: moved by the matrix found for the uncleaned cloud, not registered again).
-    final3d_model.ply and cloud_eval.json are what they are without it."""
+    final3d_model.ply and cloud_eval.json are what they are without it.
+    score_maps (with gt_ply only): None, or dict(splat=, occlusion_tol=, pixel_centre=), the arguments of eval_depth.render_scan:
+    after the scene's fusion the ground truth is rendered into the scene's cameras (in SceneFusion.order()) and the staged,
+    probability-filtered depth planes -- what enters the cloud -- are scored against it (eval_depth.score_maps) into
+    <savepath>/<scene>/depth_eval.json.  With register the ground truth is moved by the inverse of the matrix already found (no
+    second fit).  Every other output is what it is without it."""
     import matplotlib
     matplotlib.use('Agg')
     import matplotlib.pyplot as plt
@@ -330,6 +336,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         raise ValueError('register (--register) needs gt_ply (--gt_ply): there is nothing to align to')
     if clean and fuse is None:
         raise ValueError('clean (--clean_voxel, --clean_sor, --clean_radius_filter) needs fuse (--fuse): there is no point cloud to clean')
+    if score_maps is not None and not gt_ply:
+        raise ValueError('score_maps (--score_maps) needs gt_ply (--gt_ply): there is no scan to render')
     gt_points, register_args, init_cameras = None, {}, None
     if gt_ply:
         from ..tools.ply import read_ply_points
@@ -366,12 +374,15 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
             start_time = time.time()
             queued = []                  # host-side data of the depth maps in flight, in submission order
             fusion = []                  # --fuse: this scene's SceneFusion, made at its first map (the maps' size)
+            map_cams = {}                # --score_maps: out_index -> the (2,4,4) camera of its map
 
             def stage(out_index, depth, prob, image, cams_data, stream=None):
                 if not fusion:
                     rows, cols = image.shape[:2]
                     fusion.append(depth_fusion.SceneFusion(len(mvs_list), rows, cols, device, **fuse))
                 fusion[0].add(out_index, depth, prob, image, cams_data[0, 0], stream=stream)
+                if score_maps is not None:
+                    map_cams[out_index] = np.array(cams_data[0, 0], np.float64)
 
             def finish():
                 t0 = time.time()
@@ -467,6 +478,19 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
                         score['init_cameras'] = init_cameras
                     eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'), score)
                     TIMES['cloud_eval'] = time.time() - t0
+                if score_maps is not None:
+                    # run() has ordered this stream after every staging; nd[..., 3] is the depth plane the fusion read
+                    t0 = time.time()
+                    order = scene_fusion.order()
+                    indices = [scene_fusion.index[k] for k in order]
+                    moved = score['registration']['matrix'] if 'registration' in score else None
+                    gt_maps = eval_depth.render_scan(gt_points, np.stack([map_cams[i] for i in indices]), scene_fusion.rows,
+                                                     scene_fusion.cols, transform=moved, device=device, **score_maps)
+                    pred = scene_fusion.nd[:len(indices), :, :, 3][torch.from_numpy(order).to(device)]
+                    eval_depth.write_json(os.path.join(savepath_current, 'depth_eval.json'),
+                                          eval_depth.report(pred.cpu().numpy(), gt_maps.cpu().numpy(), indices=indices,
+                                                            transform=moved, **score_maps))
+                    TIMES['depth_eval'] = time.time() - t0
                 if clean:
                     from ..tools.ply import write_ply
                     t0 = time.time()
@@ -505,13 +529,18 @@ def main(scene_list=None, base_path='eth3d/'):
     fuse = None
     if getattr(FLAGS, 'fuse', False):
         fuse = dict(prob_threshold=FLAGS.prob_threshold, disp_threshold=FLAGS.disp_threshold, num_consistent=FLAGS.num_consistent)
+    score_maps = None
+    if getattr(FLAGS, 'score_maps', False):
+        score_maps = dict(splat=getattr(FLAGS, 'map_splat', eval_depth.DEFAULT_SPLAT),
+                          occlusion_tol=getattr(FLAGS, 'map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
+                          pixel_centre=getattr(FLAGS, 'map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE))
     register = None
     if getattr(FLAGS, 'register', False):
         register = dict(with_scale=getattr(FLAGS, 'with_scale', False), init_cameras=getattr(FLAGS, 'init_cameras', None) or None)
     run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
                 scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
                 map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None,
-                register=register, clean=getattr(FLAGS, 'clean', None) or None)
+                register=register, clean=getattr(FLAGS, 'clean', None) or None, score_maps=score_maps)
 
 
 def cli(argv=None):
@@ -554,6 +583,16 @@ def cli(argv=None):
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
                         help='--register: two COLMAP sparse model folders of the same images (the scene\'s own and one in the '
                              'ground truth\'s frame); their camera centres give the initial similarity')
+    parser.add_argument('--score_maps', action='store_true',
+                        help='--gt_ply: render the ground truth into the scene\'s cameras and score the depth maps that entered the '
+                             'cloud against it (eval_depth: mae, rmse, ..., inlier ratios per map; a point splat, not ETH3D\'s '
+                             'renderer) into <savepath>/<scene>/depth_eval.json; with --register the matrix found is used')
+    parser.add_argument('--map_splat', type=int, default=eval_depth.DEFAULT_SPLAT,
+                        help='--score_maps: half-width of the occlusion window in pixels, 0..4')
+    parser.add_argument('--map_occlusion_tol', type=float, default=eval_depth.DEFAULT_OCCLUSION_TOL,
+                        help='--score_maps: a pixel is kept when its depth is within (1 + this) of the nearest in its window')
+    parser.add_argument('--map_pixel_centre', type=float, default=eval_depth.DEFAULT_PIXEL_CENTRE,
+                        help='--score_maps: image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5 (the plane sweep\'s)')
     clean_cloud.add_options(parser, 'clean_')
     args = parser.parse_args(argv)
     if args.eager and args.scene_cache:
@@ -566,6 +605,15 @@ def cli(argv=None):
         parser.error('--register needs --gt_ply: there is nothing to align to')
     if (args.with_scale or args.init_cameras) and not args.register:
         parser.error('--with_scale and --init_cameras need --register')
+    if args.score_maps and not args.gt_ply:
+        parser.error('--score_maps needs --gt_ply: there is no scan to render')
+    if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
+                                or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
+        parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')
+    if not 0 <= args.map_splat <= 4:
+        parser.error('--map_splat must be in 0..4')
+    if not (args.map_occlusion_tol >= 0.0 and np.isfinite(args.map_occlusion_tol)) or not np.isfinite(args.map_pixel_centre):
+        parser.error('--map_occlusion_tol must be >= 0 and finite, --map_pixel_centre finite')
     args.gt_ply = [p for p in args.gt_ply.split(',') if p] if args.gt_ply else None
     args.clean = clean_cloud.options(parser, args, 'clean_') or None
     if args.clean and not args.fuse:

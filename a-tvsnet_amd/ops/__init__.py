@@ -11,7 +11,7 @@
     colmap    COLMAP model import: per-image depth range, co-visibility matrix
     cloud     point-cloud scoring: uniform grid, exact nearest neighbour within a radius, tolerance counts;
               registration: transform, pair moments, voxel down-sampling; neighbourhoods: k nearest neighbours, radius counts,
-              outlier statistics, bounding box
+              outlier statistics, bounding box; rendering: a scan splatted into cameras as nearest-depth maps
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -42,4 +42,5 @@ from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range   
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401
 from .cloud import cloud_bounds, cloud_pair_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
 from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401
+from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

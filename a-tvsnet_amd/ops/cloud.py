@@ -9,6 +9,9 @@ point per occupied voxel.
 Neighbourhoods (csrc/cloud_knn.hip; atvsnet/clean_cloud.py is built on it): cloud_knn finds the k nearest reference points within
 the grid's radius, cloud_radius_count counts the reference points inside it, cloud_knn_mean and cloud_sor_stats reduce the k-NN
 distances to the three numbers of statistical outlier removal, cloud_bounds is the bounding box of the finite rows.
+
+Rendering (csrc/scan_render.hip; atvsnet/eval_depth.py is built on it): scan_render splats a scan into a set of cameras and keeps
+the nearest depth per pixel, the ground-truth depth maps the network's maps are scored against.
 """
 
 import ctypes
@@ -23,6 +26,8 @@ from .base import _ERR, _call, _p, _stream
 CLOUD_MAX_POINTS = 1 << 30
 CLOUD_MAX_TOLERANCES = 16
 CLOUD_MAX_K = 32
+SCAN_RENDER_MAX_SPLAT = 4
+SCAN_RENDER_MAX_CAMS = 65535
 
 
 def _cloud_arg(t, name, dtype, trailing):
@@ -304,3 +309,38 @@ def cloud_sor_stats(s):
     words = out.cpu().numpy()
     mean, std = words[1:].view(np.float64).tolist()
     return int(words[0]), mean, std
+
+
+def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_tol=0.0):
+    """points (n,3) float32 in the cameras' frame, cams (n_cams,16) float64 = R (3x3 row-major, world to camera), t (3), fx, fy,
+    cx, cy -> depth (n_cams, rows, cols) float32: per pixel the nearest float32 depth c_2 of the points that project into it, in
+    float64, by u = floor((x - pixel_centre) + 0.5); 0 where none does, and 0 where that depth is further than (1 + occlusion_tol)
+    times the nearest depth landing within `splat` pixels (a background point seen through a hole).  splat 0..4; splat = 0 keeps
+    every pixel.  include/atvsnet_hip.h has the definition in full; the same inputs give the same bits (integer atomics)."""
+    for name, v in (('rows', rows), ('cols', cols)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
+            raise ValueError('%s: expected a positive integer, got %r' % (name, v))
+    if isinstance(splat, bool) or not isinstance(splat, (int, np.integer)) or not 0 <= int(splat) <= SCAN_RENDER_MAX_SPLAT:
+        raise ValueError('splat: expected an integer in 0..%d, got %r' % (SCAN_RENDER_MAX_SPLAT, splat))
+    tol, centre = float(occlusion_tol), float(pixel_centre)
+    if not (tol >= 0.0 and math.isfinite(tol)):
+        raise ValueError('occlusion_tol must be >= 0 and finite, got %r' % (occlusion_tol,))
+    if not math.isfinite(centre):
+        raise ValueError('pixel_centre must be finite, got %r' % (pixel_centre,))
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    _cloud_arg(cams, 'cams', torch.float64, (16,))
+    if cams.device != points.device:
+        raise RuntimeError('cams on %s, points on %s' % (cams.device, points.device))
+    n, n_cams, rows, cols = int(points.shape[0]), int(cams.shape[0]), int(rows), int(cols)
+    if not 1 <= n_cams <= SCAN_RENDER_MAX_CAMS:
+        raise ValueError('cams: 1 to %d cameras, got %d' % (SCAN_RENDER_MAX_CAMS, n_cams))
+    if n_cams * rows * cols >= 1 << 31:
+        raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n_cams, rows, cols))
+    depth = torch.empty((n_cams, rows, cols), dtype=torch.float32, device=points.device)
+    nbytes = ctypes.c_long(0)
+    _call('atvs_scan_render_scratch_size', ctypes.c_int(n_cams), ctypes.c_int(rows), ctypes.c_int(cols), ctypes.byref(nbytes))
+    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=points.device)
+    _call('atvs_scan_render', _p(points), ctypes.c_long(n), _p(cams), ctypes.c_int(n_cams), ctypes.c_int(rows), ctypes.c_int(cols),
+          ctypes.c_double(centre), ctypes.c_int(int(splat)), ctypes.c_double(tol), _p(scratch), ctypes.c_long(scratch.numel()),
+          _p(depth), _stream())
+    return depth

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 50
+#define ATVS_ABI_VERSION 51
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -849,6 +849,33 @@ int atvs_cloud_knn_mean(const float* d2, long m, int k, double* s, atvs_stream_t
 int atvs_cloud_sor_stats_scratch_size(long m, long* bytes);
 int atvs_cloud_sor_stats(const double* s, long m, void* scratch, long scratch_bytes, void* out, atvs_stream_t stream);
 int atvs_cloud_bounds(const float* points, long n, void* out, atvs_stream_t stream);
+
+/* A scan rendered into cameras (ops/cloud.py scan_render, atvsnet/eval_depth.py, csrc/scan_render.hip): the ground-truth depth
+ * maps a set of depth maps is scored against.  Pointers are device pointers.  Integer atomics only: the output is a function of the
+ * inputs alone, bit for bit on every run.  No host synchronisation, no allocation; scratch is the caller's.
+ * tests/scan_render_restated.py restates the definition.
+ *
+ * The definition.  points P (n,3) float32 in the cameras' frame; cams (n_cams,16) doubles per camera = R (3x3, row-major, world to
+ * camera), t (3), fx, fy, cx, cy; maps of rows x cols pixels.  Per (camera, point), in double, every operation rounded, nothing
+ * contracted: c_k = ((R_k0 X + R_k1 Y) + R_k2 Z) + t_k, x = (c_0 / c_2) fx + cx, y = (c_1 / c_2) fy + cy (atvs_colmap_depth_range's
+ * projection), xs = (x - pixel_centre) + 0.5, ys = (y - pixel_centre) + 0.5.  pixel_centre is the image coordinate of the centre
+ * of pixel (0,0): 0.0 is the convention of the fusion (fusion_pixel.h back-projects integer pixel coordinates), 0.5 the plane
+ * sweep's.  The pair takes part when c_2 > 0, z = (float)c_2 is finite and > 0, and xs >= -splat, xs < cols + splat,
+ * ys >= -splat, ys < rows + splat (compared in double before any integer conversion; NaN fails).  Then u = (int)floor(xs),
+ * v = (int)floor(ys).  Two planes of unsigned 32-bit words per camera, all-ones at first: near[v][u] = min(bits(z)) where (u, v)
+ * lies inside the image; front[v + dv][u + du] = min(bits(z)) for every |du|, |dv| <= splat inside the image (a positive float
+ * orders as its bits do).  Per pixel: depth = 0 where near is all-ones; otherwise, with z = float(near) and zf = float(front),
+ * depth = z when (double)z <= (double)zf * (1.0 + occlusion_tol), else 0 -- a background point seen through a hole of a nearer
+ * surface.  With splat = 0 every near pixel survives.  This is a point splat, not a visibility-aware renderer: the scan's own
+ * occlusions and holes are not modelled.
+ *
+ * atvs_scan_render: depth_out (n_cams, rows, cols) float32 as defined.  scratch: atvs_scan_render_scratch_size(n_cams, rows, cols)
+ * bytes (the two planes), filled by hipMemsetAsync on the stream.  Two launches (one when n = 0: all-zero maps).
+ * splat outside [0, 4], occlusion_tol negative or not finite, pixel_centre not finite: ATVS_ERR_ARG; n_cams * rows * cols >= 2^31,
+ * n_cams outside [1, 65535], rows or cols < 1, n negative or beyond 2^30, a short scratch: ATVS_ERR_SHAPE. */
+int atvs_scan_render_scratch_size(int n_cams, int rows, int cols, long* bytes);
+int atvs_scan_render(const float* points, long n, const double* cams, int n_cams, int rows, int cols, double pixel_centre, int splat,
+                     double occlusion_tol, void* scratch, long scratch_bytes, float* depth_out, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
