@@ -5,11 +5,23 @@ distance tolerances.
            [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--radius R] [--gt_transform T.txt] [--out cloud_eval.json] [--distances PREFIX]
            [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v]] [--init_transform T.txt |
             --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
+           [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
+            [--vis_window 1] [--free_space_margin 0]]
 
-This is the PLAIN precision / recall definition (the one Tanks and Temples uses): per tolerance tau, `accuracy` is the share of
-reconstruction points with a ground-truth point within tau, `completeness` the share of ground-truth points with a reconstruction
-point within tau, `f1` their harmonic mean.  It is NOT ETH3D's official evaluator, which also voxelises the clouds and uses the
-scans' visibility (free space): the numbers are comparable between runs of this tool, not with the ETH3D leaderboard.
+The top-level keys are the PLAIN precision / recall definition (the one Tanks and Temples uses): per tolerance tau, `accuracy` is
+the share of reconstruction points with a ground-truth point within tau, `completeness` the share of ground-truth points with a
+reconstruction point within tau, `f1` their harmonic mean.
+
+--eth3d adds the key `eth3d`: the same shares by ETH3D's published protocol, restated (atvsnet/eval_eth3d.py): formed per occupied
+voxel of --eth3d_voxel and averaged over voxels, with a reconstruction point that has no ground truth within tau counted
+inaccurate only where a laser scanner could have seen it (in front of what the scanner measured along that ray, or at most
+--free_space_margin behind it) and left out as unobserved otherwise.  It needs each scan on its own and its scanner's position:
+--gt_mlp (ETH3D's scan_alignment.mlp: the PLY files and their matrices, whose translation is the scanner's origin) replaces --gt,
+or --gt a.ply b.ply with --scanner_origins (a text file, one `x y z` per scan, in the ground truth's frame after --gt_transform).
+This is NOT ETH3D's official evaluation program and no run of that program pins it: it restates the published protocol.  What
+still differs by construction: the beams' radius and divergence (a pixel window of a cube map stands in for them), windows that
+stop at cube edges, and --cube_size, --vis_window, --free_space_margin, which are defaults chosen here, not measurements.  Compare
+its numbers between runs of this tool; against the leaderboard they are an approximation of unknown size.
 
 Both directions of the nearest-neighbour search run on the device (ops.cloud_grid / cloud_nearest / cloud_counts, csrc/cloud.hip),
 exactly: per point the smallest float32 squared distance (dx*dx + dy*dy) + dz*dz to the other cloud, unknown (+inf) beyond
@@ -100,7 +112,8 @@ def _matrix(T, name):
 
 
 def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None,
-             register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None):
+             register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None,
+             scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
     distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
@@ -110,10 +123,40 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     init_transform; with_scale, register_distances (default 4x, 2x, 1x the largest tolerance), register_voxel are its arguments;
     the result gains `registration` (its dict; `matrix` includes init_transform).  Without register, init_transform is recorded
     as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
-    result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds."""
+    result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds.
+
+    scans: the ground truth as a list of (n_i,3) arrays, one per laser scan, with scanner_origins (S,3), each scanner's position
+    in the scans' frame (after gt_transform); `gt` must then be None and is their concatenation.  The result gains `eth3d`
+    (atvsnet/eval_eth3d.py): the parameters and per tolerance accuracy, completeness, f1 averaged over voxels of eth3d_voxel,
+    n_accurate, n_inaccurate, n_unobserved (reconstruction points by class) and voxels_recon, voxels_gt (voxels counted).  Every
+    scanner's own points are rendered into a cube map of 6 x cube_size^2 pixels; a reconstruction point is looked up in a
+    (2 vis_window + 1)^2 window and is unobserved when it lies more than free_space_margin behind the nearest sample there.
+    eth3d_voxel = 0.01 and the default tolerances are ETH3D's published ones; cube_size, vis_window and free_space_margin are
+    defaults, not measurements of ETH3D's program.  With `voxel` it is an argument error: down-sampling loses which scanner saw a
+    point.  Every other key is what it is without scans."""
     import torch
     from .. import ops
     tol, radius = _check_tolerances(tolerances, radius)
+    origins = None
+    if scans is not None:
+        from . import eval_eth3d
+        if gt is not None:
+            raise ValueError('scans is the ground truth, one array per scan: gt must be None')
+        if voxel is not None:
+            raise ValueError('scans with voxel: the down-sampling loses which scanner saw a point (eth3d_voxel is the grid of the '
+                             'voxel-averaged shares)')
+        scans = [s.cpu().numpy() if isinstance(s, torch.Tensor) else s for s in scans]
+        scans = [np.ascontiguousarray(np.asarray(s, np.float32).reshape(-1, 3)) for s in scans]
+        origins = eval_eth3d.check_scans(scans, scanner_origins)
+        eth3d_args = eval_eth3d.check_options(eth3d_voxel, cube_size, vis_window, free_space_margin)
+        if gt_transform is not None:
+            scans = [transform_points(s, gt_transform) for s in scans]
+            gt_transform = None
+        gt = np.concatenate(scans, 0)
+    elif scanner_origins is not None:
+        raise ValueError('scanner_origins needs scans')
+    elif gt is None:
+        raise ValueError('gt: the ground truth is missing (or give scans)')
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
 
     def upload(x):
@@ -146,6 +189,8 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
         d2_r, idx_r = ops.cloud_nearest(ops.cloud_grid(g, radius), r)
         d2_g, idx_g = ops.cloud_nearest(ops.cloud_grid(r, radius), g)
         counts = [ops.cloud_counts(d2, tol, radius).cpu().tolist() for d2 in (d2_r, d2_g)]
+        if origins is not None:
+            extra['eth3d'] = eval_eth3d.score(r, g, [len(s) for s in scans], origins, d2_r, d2_g, tol, *eth3d_args)
         d2_r, d2_g = d2_r.cpu().numpy(), d2_g.cpu().numpy()
         if distances is not None:
             distances.update(d2_recon=d2_r, idx_recon=idx_r.cpu().numpy(), d2_gt=d2_g, idx_gt=idx_g.cpu().numpy())
@@ -169,20 +214,40 @@ def save_matrix(path, T):
 
 
 def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform_path=None, distances=None,
-                   init_transform_path=None, init_cameras=None, save_transform_path=None, **options):
+                   init_transform_path=None, init_cameras=None, save_transform_path=None, gt_mlp_path=None,
+                   scanner_origins_path=None, **options):
     """`evaluate` of PLY files (tools/ply.read_ply_points): several ground-truth files are concatenated; gt_transform_path: a text
     file of 16 numbers, the 4x4 matrix row-major.  init_transform_path: the same for evaluate's init_transform; init_cameras:
     (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
     result's `registration` / top level gains `init_cameras`: matched images and their rms).  save_transform_path: the matrix that
-    was applied to the reconstruction is written there.  options: evaluate's other keyword arguments."""
+    was applied to the reconstruction is written there.  options: evaluate's other keyword arguments.
+
+    The ETH3D-style score (evaluate's `scans`): gt_mlp_path, a MeshLab project (eval_eth3d.read_mlp) that replaces gt_paths -- each
+    scan is moved by gt_transform times its own matrix (float64, rounded once) and that product's translation is its scanner's
+    origin -- or gt_paths with scanner_origins_path, a text file of one `x y z` per scan in the frame after gt_transform."""
     recon = ply.read_ply_points(recon_path)
-    gt = [ply.read_ply_points(p) for p in gt_paths]
-    gt = np.concatenate(gt, 0) if gt else np.zeros((0, 3), np.float32)
     T = None
     if gt_transform_path is not None:
         T = np.loadtxt(gt_transform_path, dtype=np.float64)
         if T.size != 16:
             raise ValueError('%s: expected the 16 numbers of a 4x4 matrix, got %d' % (gt_transform_path, T.size))
+    if gt_mlp_path is not None or scanner_origins_path is not None:
+        from . import eval_eth3d
+        if gt_mlp_path is not None and (gt_paths or scanner_origins_path is not None):
+            raise ValueError('gt_mlp_path names the scans and their scanners: give neither gt_paths nor scanner_origins_path with it')
+        if gt_mlp_path is not None:
+            G = np.eye(4) if T is None else _matrix(T, gt_transform_path)
+            moves = [(p, G @ M) for p, M in eval_eth3d.read_mlp(gt_mlp_path)]
+            options['scans'] = [transform_points(ply.read_ply_points(p), M) for p, M in moves]
+            options['scanner_origins'] = np.array([M[:3, 3] for _, M in moves])
+            T = None
+        else:
+            options['scans'] = [ply.read_ply_points(p) for p in gt_paths]
+            options['scanner_origins'] = eval_eth3d.load_origins(scanner_origins_path)
+        gt = None
+    else:
+        gt = [ply.read_ply_points(p) for p in gt_paths]
+        gt = np.concatenate(gt, 0) if gt else np.zeros((0, 3), np.float32)
     init, cams = None, None
     if init_transform_path is not None and init_cameras is not None:
         raise ValueError('init_transform_path and init_cameras both give the starting matrix: choose one')
@@ -249,11 +314,45 @@ def register_options(parser, args):
     return options
 
 
+def eth3d_options(parser, args):
+    """The --eth3d options of a parsed command line as evaluate_files' keyword arguments ({} without --eth3d)."""
+    given = [n for n in ('eth3d_voxel', 'cube_size', 'vis_window', 'free_space_margin') if getattr(args, n) is not None]
+    if not args.eth3d:
+        for name in given + [n for n in ('gt_mlp', 'scanner_origins') if getattr(args, n)]:
+            parser.error('--%s needs --eth3d' % name)
+        if not args.gt:
+            parser.error('--gt is required (or --eth3d --gt_mlp)')
+        return {}
+    if not args.gt_mlp and not args.scanner_origins:
+        parser.error('--eth3d needs the scanners\' positions: --gt_mlp FILE (a MeshLab project, replaces --gt) or '
+                     '--gt a.ply b.ply with --scanner_origins FILE')
+    if args.gt_mlp and (args.gt or args.scanner_origins):
+        parser.error('--gt_mlp replaces --gt and --scanner_origins: give it alone')
+    if args.scanner_origins and not args.gt:
+        parser.error('--scanner_origins needs --gt: one PLY file per scan')
+    if args.voxel is not None:
+        parser.error('--eth3d with --voxel: the down-sampling loses which scanner saw a point (--eth3d_voxel is the grid of the '
+                     'voxel-averaged shares)')
+    options = {name: getattr(args, name) for name in given}
+    if args.gt_mlp:
+        options['gt_mlp_path'] = args.gt_mlp
+    else:
+        options['scanner_origins_path'] = args.scanner_origins
+    from . import eval_eth3d
+    try:
+        eval_eth3d.check_options(options.get('eth3d_voxel', 0.01), options.get('cube_size', 1024), options.get('vis_window', 1),
+                                 options.get('free_space_margin', 0.0))
+    except ValueError as e:
+        parser.error(str(e))
+    return options
+
+
 def make_parser():
     parser = argparse.ArgumentParser(description='accuracy / completeness / F-score of a point cloud against ground truth '
-                                                 '(plain precision / recall; not the official ETH3D evaluator)')
+                                                 '(plain precision / recall; --eth3d adds ETH3D\'s published protocol restated: '
+                                                 'voxel-averaged shares and scanner free space -- not the official ETH3D program)')
     parser.add_argument('--recon', required=True, help='the reconstruction (PLY)')
-    parser.add_argument('--gt', required=True, nargs='+', help='ground-truth PLY file(s), concatenated')
+    parser.add_argument('--gt', default=None, nargs='+', help='ground-truth PLY file(s), concatenated (required unless --gt_mlp)')
     parser.add_argument('--tolerances', default=','.join(str(t) for t in DEFAULT_TOLERANCES), help='comma-separated distances')
     parser.add_argument('--radius', type=float, default=None, help='search radius (default: the largest tolerance)')
     parser.add_argument('--gt_transform', default=None, help='text file with a 4x4 row-major matrix applied to the ground truth')
@@ -276,6 +375,24 @@ def make_parser():
     parser.add_argument('--save_transform', default=None, metavar='FILE', help='write the matrix applied to the reconstruction here')
     parser.add_argument('--voxel', type=float, default=None, metavar='V',
                         help='score the clouds after a voxel down-sampling of edge V (both sides)')
+    parser.add_argument('--eth3d', action='store_true',
+                        help='add the key `eth3d`: shares averaged over voxels, and points the laser scanners could not have seen '
+                             'left out (the published protocol restated, not the official program); needs --gt_mlp or '
+                             '--scanner_origins')
+    parser.add_argument('--gt_mlp', default=None, metavar='FILE',
+                        help='--eth3d: a MeshLab project (ETH3D\'s scan_alignment.mlp) naming the scans and their matrices; a '
+                             'matrix\'s translation is the scanner\'s origin; replaces --gt')
+    parser.add_argument('--scanner_origins', default=None, metavar='FILE',
+                        help='--eth3d: text file, one `x y z` per --gt file, in the ground truth\'s frame after --gt_transform')
+    parser.add_argument('--eth3d_voxel', type=float, default=None, metavar='V',
+                        help='--eth3d: voxel edge of the averaged shares (default 0.01, ETH3D\'s)')
+    parser.add_argument('--cube_size', type=int, default=None, metavar='N',
+                        help='--eth3d: pixels per edge of a scanner\'s cube-map face (default 1024: a default, not a measurement)')
+    parser.add_argument('--vis_window', type=int, default=None, metavar='W',
+                        help='--eth3d: the nearest scan sample within W pixels decides, 0..2 (default 1: a default, not a measurement)')
+    parser.add_argument('--free_space_margin', type=float, default=None, metavar='M',
+                        help='--eth3d: a point up to M behind the scan still counts as observed (default 0: a default, not a '
+                             'measurement)')
     return parser
 
 
@@ -288,10 +405,11 @@ def cli(argv=None):
     except ValueError as e:
         parser.error(str(e))
     options = register_options(parser, args)
+    options.update(eth3d_options(parser, args))
     import torch
     torch.cuda.set_device(args.gpu_id)
     dist = {} if args.distances else None
-    result = evaluate_files(args.recon, args.gt, tol, args.radius, args.gt_transform, distances=dist, **options)
+    result = evaluate_files(args.recon, args.gt or [], tol, args.radius, args.gt_transform, distances=dist, **options)
     if dist is not None:
         for k, v in dist.items():
             np.save('%s_%s.npy' % (args.distances, k), v)

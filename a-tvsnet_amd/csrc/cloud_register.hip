@@ -17,6 +17,9 @@
 // to the slot's count and three unsigned 64-bit sums, and takes the minimum of the slot's first index.  flag: a point that is its
 // voxel's first index is marked; an exclusive scan of the marks (cloud_scan.h) gives its output row.  emit: the marked points write
 // their voxel's mean and their own index there.  Which slot a voxel gets depends on arrival order; nothing that is written does.
+//
+// VOXEL-AVERAGED SHARES (atvs_cloud_voxel_shares): the same cells and table, per-voxel hit / observed counters
+// per tolerance instead of sums; described where its kernels are.
 #include <math.h>
 
 #include "common.h"
@@ -130,6 +133,20 @@ __device__ __forceinline__ bool voxel_coord(float x, double origin, double voxel
   return true;
 }
 
+// The slot of the voxel with cells c[] in the open-addressing table (ONE definition for the down-sampler and the shares): the key
+// packs the cells 3 x 21 bits, probing is linear from a multiplicative hash, one 64-bit compare-and-swap per probe.  The table is
+// at most half full, so the loop ends long before `slots`; -1 is never returned in practice.
+__device__ __forceinline__ int voxel_find_slot(const unsigned long long* c, unsigned long long* __restrict__ keys, long slots, int shift) {
+  const unsigned long long key = c[0] | (c[1] << 21) | (c[2] << 42);
+  unsigned long long h = (key * 0x9E3779B97F4A7C15ull) >> shift;
+  for (long probe = 0; probe < slots; ++probe) {
+    const unsigned long long seen = atomicCAS(keys + h, kEmpty, key);
+    if (seen == kEmpty || seen == key) return (int)h;
+    h = (h + 1) & (unsigned long long)(slots - 1);
+  }
+  return -1;
+}
+
 __global__ __launch_bounds__(kThreads) void cloud_voxel_insert_kernel(const float* __restrict__ pts, long n, VoxelArgs A, long slots, int shift,
                                                                       unsigned long long* __restrict__ keys, unsigned* __restrict__ first,
                                                                       unsigned long long* __restrict__ sums, unsigned* __restrict__ cnt,
@@ -145,16 +162,7 @@ __global__ __launch_bounds__(kThreads) void cloud_voxel_insert_kernel(const floa
     if (!ok) {
       atomicOr(err, 1);
     } else {
-      const unsigned long long key = c[0] | (c[1] << 21) | (c[2] << 42);
-      unsigned long long h = (key * 0x9E3779B97F4A7C15ull) >> shift;
-      for (long probe = 0; probe < slots; ++probe) {      // the table is at most half full: the loop ends long before `slots`
-        const unsigned long long seen = atomicCAS(keys + h, kEmpty, key);
-        if (seen == kEmpty || seen == key) {
-          s = (int)h;
-          break;
-        }
-        h = (h + 1) & (unsigned long long)(slots - 1);
-      }
+      s = voxel_find_slot(c, keys, slots, shift);
       if (s >= 0) {
         atomicAdd(cnt + s, 1u);
         atomicAdd(sums + (long)s * 3 + 0, u[0]);
@@ -199,6 +207,119 @@ __global__ __launch_bounds__(kThreads) void cloud_voxel_emit_kernel(const int* _
     out_points[(long)p * 3 + a] = (float)(A.origin[a] + A.voxel * (c + mean));
   }
   out_first[p] = (int)i;
+}
+
+// ---- voxel-averaged shares -----------------------------------------------------------------------------------------------------
+// The down-sampler's table once more (the same cells: voxel_coord), holding per voxel two counters per tolerance of a pass instead
+// of sums.  insert: every finite point finds its voxel's slot.  Then, kSharePass tolerances at a time: count (a point adds 1 to its
+// voxel's `hit` or `other` counter per tolerance, or to neither when it is unobserved), reduce (one lane per slot: the voxel's
+// fixed-point share q and the counts, summed over the workgroup and added to the four output words of the tolerance).  Unsigned
+// integer atomics only: which slot a voxel gets and who adds first depend on arrival order, no word that is written does.
+
+constexpr int kSharePass = 4;                          // tolerances per pass: 8 B of counters per slot each
+
+struct ShareLayout {
+  size_t keys, cnt, slot, total;                       // [header | keys] are set to 0 / ~0, cnt to 0 before every pass
+  long slots;
+  int shift;
+};
+inline ShareLayout share_layout(long n) {
+  const VoxelLayout V = voxel_layout(n);
+  ShareLayout L;
+  L.slots = V.slots;
+  L.shift = V.shift;
+  L.keys = kVoxelHeader;
+  L.cnt = L.keys + align256((size_t)L.slots * 8);
+  L.slot = L.cnt + align256((size_t)L.slots * 8 * kSharePass);
+  L.total = L.slot + align256((size_t)n * 4);
+  return L;
+}
+
+struct ShareArgs {
+  double tau2[kSharePass];                             // tau * tau
+  double margin;
+  int count;                                           // tolerances of this pass
+};
+
+__global__ __launch_bounds__(kThreads) void cloud_share_insert_kernel(const float* __restrict__ pts, long n, VoxelArgs A, long slots, int shift,
+                                                                      unsigned long long* __restrict__ keys, int* __restrict__ slot_of,
+                                                                      int* __restrict__ err) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  int s = -1;
+  if (finite3(x, y, z)) {
+    unsigned long long c[3], u[3];
+    const bool ok = voxel_coord(x, A.origin[0], A.voxel, &c[0], &u[0]) & voxel_coord(y, A.origin[1], A.voxel, &c[1], &u[1]) &
+                    voxel_coord(z, A.origin[2], A.voxel, &c[2], &u[2]);
+    if (!ok) {
+      atomicOr(err, 1);
+    } else {
+      s = voxel_find_slot(c, keys, slots, shift);
+    }
+  }
+  slot_of[i] = s;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_share_count_kernel(const int* __restrict__ slot_of, const float* __restrict__ d2,
+                                                                     const float* __restrict__ excess, long n, ShareArgs A,
+                                                                     unsigned* __restrict__ cnt) {
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const int s = slot_of[i];
+  if (s < 0) return;
+  const double d = (double)d2[i];
+  const bool observed = !excess || (double)excess[i] <= A.margin;      // NaN: unobserved
+  unsigned* __restrict__ c = cnt + (size_t)s * (2 * kSharePass);
+  for (int k = 0; k < A.count; ++k) {
+    if (d <= A.tau2[k]) atomicAdd(c + 2 * k, 1u);
+    else if (observed) atomicAdd(c + 2 * k + 1, 1u);
+  }
+}
+
+__device__ __forceinline__ unsigned long long wave_sum64(unsigned long long v) {      // lane 0 holds the sum of all 64 lanes
+  for (int off = 32; off > 0; off >>= 1) {
+    const unsigned lo = (unsigned)__shfl_down((int)(unsigned)(v & 0xffffffffull), off);
+    const unsigned hi = (unsigned)__shfl_down((int)(unsigned)(v >> 32), off);
+    v += ((unsigned long long)hi << 32) | (unsigned long long)lo;
+  }
+  return v;
+}
+
+__global__ __launch_bounds__(kThreads) void cloud_share_reduce_kernel(const unsigned long long* __restrict__ keys, long slots,
+                                                                      const unsigned* __restrict__ cnt, int count, int total,
+                                                                      const int* __restrict__ err, unsigned long long* __restrict__ out,
+                                                                      unsigned long long* __restrict__ out_all) {
+  __shared__ unsigned long long part[kThreads / 64][4 * kSharePass];
+  const long i = (long)blockIdx.x * kThreads + threadIdx.x;
+  if (*err != 0) {                                            // a point outside the 2^21 cells: every word of the result is -1
+    if (i < 4L * total) out_all[i] = ~0ull;
+    return;
+  }
+  const bool used = i < slots && keys[i] != kEmpty;
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  for (int k = 0; k < count; ++k) {                           // uniform: every lane takes part in the shuffles
+    unsigned long long hit = 0ull, den = 0ull;
+    if (used) {
+      hit = cnt[(size_t)i * (2 * kSharePass) + 2 * k];
+      den = hit + cnt[(size_t)i * (2 * kSharePass) + 2 * k + 1];
+    }
+    const unsigned long long q = wave_sum64(den ? (hit << 32) / den : 0ull);
+    const unsigned long long voxels = wave_sum64(den ? 1ull : 0ull);
+    const unsigned long long hits = wave_sum64(hit), dens = wave_sum64(den);
+    if (lane == 0) {
+      part[w][4 * k + 0] = q;
+      part[w][4 * k + 1] = voxels;
+      part[w][4 * k + 2] = hits;
+      part[w][4 * k + 3] = dens;
+    }
+  }
+  __syncthreads();
+  if ((int)threadIdx.x < 4 * count) {                         // one lane per output word adds the workgroup's four wavefronts
+    unsigned long long v = 0ull;
+    for (int j = 0; j < kThreads / 64; ++j) v += part[j][threadIdx.x];
+    if (v) atomicAdd(out + threadIdx.x, v);
+  }
 }
 
 }  // namespace
@@ -298,5 +419,57 @@ extern "C" int atvs_cloud_voxel_downsample(const float* points, long n, double v
                      (const unsigned long long*)keys, (const unsigned*)first, (const unsigned long long*)sums, (const unsigned*)cnt,
                      (const unsigned*)flags, (const int*)err, out_points, out_count, out_first);
   ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_voxel_shares_scratch_size(long n, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  *bytes = (long)share_layout(n).total;
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* excess, long n, double voxel, const double* origin,
+                                       const double* tolerances, int n_tolerances, double margin, void* scratch, long scratch_bytes,
+                                       long long* out, atvs_stream_t stream) {
+  if (n < 0 || n > kMaxPoints || n_tolerances < 1 || n_tolerances > 16) return ATVS_ERR_SHAPE;
+  if (!origin || !tolerances || !out || (n > 0 && (!points || !d2 || !scratch))) return ATVS_ERR_NULL;
+  if (!(voxel > 0.0) || !(voxel <= 1.7976931348623157e308) || margin != margin) return ATVS_ERR_ARG;
+  VoxelArgs A;
+  A.voxel = voxel;
+  for (int k = 0; k < 3; ++k) {
+    if (!(fabs(origin[k]) <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
+    A.origin[k] = origin[k];
+  }
+  for (int k = 0; k < n_tolerances; ++k)
+    if (!(tolerances[k] >= 0.0)) return ATVS_ERR_ARG;        // NaN or negative; +inf is allowed
+  const ShareLayout L = share_layout(n);
+  if (n > 0 && scratch_bytes < (long)L.total) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  if (hipMemsetAsync(out, 0, (size_t)n_tolerances * 4 * sizeof(long long), st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (n == 0) return ATVS_OK;
+  char* s = static_cast<char*>(scratch);
+  int* err = reinterpret_cast<int*>(s);
+  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s + L.keys);
+  unsigned* cnt = reinterpret_cast<unsigned*>(s + L.cnt);
+  int* slot_of = reinterpret_cast<int*>(s + L.slot);
+  if (hipMemsetAsync(s, 0, kVoxelHeader, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  if (hipMemsetAsync(s + L.keys, 0xff, L.cnt - L.keys, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+  const dim3 per_point((unsigned)cdiv(n, kThreads)), per_slot((unsigned)cdiv(L.slots, kThreads));
+  hipLaunchKernelGGL(cloud_share_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, keys, slot_of, err);
+  ATVS_LAUNCH_CHECK();
+  unsigned long long* res = reinterpret_cast<unsigned long long*>(out);
+  for (int k0 = 0; k0 < n_tolerances; k0 += kSharePass) {
+    ShareArgs S;
+    S.margin = margin;
+    S.count = n_tolerances - k0 < kSharePass ? n_tolerances - k0 : kSharePass;
+    for (int k = 0; k < kSharePass; ++k) S.tau2[k] = k < S.count ? tolerances[k0 + k] * tolerances[k0 + k] : 0.0;
+    if (hipMemsetAsync(s + L.cnt, 0, L.slot - L.cnt, st) != hipSuccess) return ATVS_ERR_LAUNCH;
+    hipLaunchKernelGGL(cloud_share_count_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, d2, excess, n, S, cnt);
+    ATVS_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cloud_share_reduce_kernel, per_slot, dim3(kThreads), 0, st, (const unsigned long long*)keys, L.slots,
+                       (const unsigned*)cnt, S.count, n_tolerances, (const int*)err, res + 4 * k0, res);
+    ATVS_LAUNCH_CHECK();
+  }
   return ATVS_OK;
 }

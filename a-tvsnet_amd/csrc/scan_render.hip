@@ -21,6 +21,7 @@
 // the L2 / Infinity Cache; the points are read once per camera group (12 bytes per kGroup pairs).  At splat = 0 the float64
 // arithmetic is the larger part; from splat = 2 (26 atomics per pair in view) the atomics are.  DESIGN.md section 12.3.
 #include "common.h"
+#include "scan_project.h"
 
 #include <math.h>
 
@@ -49,21 +50,10 @@ __global__ __launch_bounds__(kThreads) void splat_kernel(const float* __restrict
   const double hx = (double)cols + (double)splat, hy = (double)rows + (double)splat;
   const size_t plane = (size_t)rows * (size_t)cols;
   for (int g = g0; g < g1; ++g) {                             // wave-uniform: c[] are uniform addresses
-    const double* __restrict__ c = cams + (size_t)g * kCam;
-    const double c2 = ((c[6] * X + c[7] * Y) + c[8] * Z) + c[11];
-    if (!(c2 > 0.0)) continue;                                // behind the camera, on its plane, or NaN
-    const float z = (float)c2;
-    if (!(z > 0.f && z < INFINITY)) continue;                 // beyond float32's range either way
-    const double c0 = ((c[0] * X + c[1] * Y) + c[2] * Z) + c[9];
-    const double c1 = ((c[3] * X + c[4] * Y) + c[5] * Z) + c[10];
-    const double x = (c0 / c2) * c[12] + c[14];
-    const double y = (c1 / c2) * c[13] + c[15];
-    const double xs = (x - pixel_centre) + 0.5;
-    const double ys = (y - pixel_centre) + 0.5;
-    // in double, before any integer conversion: a point that projects 1e30 pixels away (or to NaN) never reaches the cast
-    if (!(xs >= lo && xs < hx && ys >= lo && ys < hy)) continue;
-    const int u = (int)floor(xs), v = (int)floor(ys);         // within [-splat, cols + splat) x [-splat, rows + splat)
-    const unsigned bits = __float_as_uint(z);
+    ScanProjection P;                                         // scan_project.h: shared with the visibility query
+    if (!scan_project(cams + (size_t)g * kCam, X, Y, Z, pixel_centre, lo, hx, hy, &P)) continue;
+    const int u = (int)floor(P.xs), v = (int)floor(P.ys);     // within [-splat, cols + splat) x [-splat, rows + splat)
+    const unsigned bits = __float_as_uint(P.z);
     if (u >= 0 && u < cols && v >= 0 && v < rows) atomicMin(near + (size_t)g * plane + (size_t)v * cols + u, bits);
     if (splat == 0) continue;
     unsigned* __restrict__ fg = front + (size_t)g * plane;

@@ -12,6 +12,10 @@ distances to the three numbers of statistical outlier removal, cloud_bounds is t
 
 Rendering (csrc/scan_render.hip; atvsnet/eval_depth.py is built on it): scan_render splats a scan into a set of cameras and keeps
 the nearest depth per pixel, the ground-truth depth maps the network's maps are scored against.
+
+ETH3D-style scoring (csrc/cloud_visibility.hip, csrc/cloud_register.hip; atvsnet/eval_cloud.py's `scans=` is built on it):
+cloud_scan_excess is a point's signed distance to what a scanner saw along its ray (cube maps rendered by scan_render),
+cloud_voxel_shares the per-voxel hit shares summed over voxels as integers.
 """
 
 import ctypes
@@ -28,6 +32,7 @@ CLOUD_MAX_TOLERANCES = 16
 CLOUD_MAX_K = 32
 SCAN_RENDER_MAX_SPLAT = 4
 SCAN_RENDER_MAX_CAMS = 65535
+CLOUD_SCAN_MAX_WINDOW = 2
 
 
 def _cloud_arg(t, name, dtype, trailing):
@@ -344,3 +349,91 @@ def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_t
           ctypes.c_double(centre), ctypes.c_int(int(splat)), ctypes.c_double(tol), _p(scratch), ctypes.c_long(scratch.numel()),
           _p(depth), _stream())
     return depth
+
+
+def cloud_scan_excess(points, cams, maps, pixel_centre=0.5, window=1):
+    """points (m,3) float32, cams (6 S,16) float64 and maps (6 S,N,N) float32: S scanners' cube maps, six faces each, as
+    ops.scan_render rendered them (0 = empty) -> (excess (m,) float32, scanner (m,) int32): the signed distance along the point's
+    ray to the nearest scan sample of the (2 window + 1)^2 pixels around where it projects, r (1 - z_scan / c_2) -- negative in
+    front of it (free space), positive behind -- minimised over the scanners that observe the point, and the lowest scanner
+    attaining it; (+inf, -1) where none does or the point is not finite.  The face is the first of the six in view; a window stays
+    inside its face.  window 0..2.  include/atvsnet_hip.h has the definition in full; the output is a function of the inputs."""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 0 <= int(window) <= CLOUD_SCAN_MAX_WINDOW:
+        raise ValueError('window: expected an integer in 0..%d, got %r' % (CLOUD_SCAN_MAX_WINDOW, window))
+    centre = float(pixel_centre)
+    if not math.isfinite(centre):
+        raise ValueError('pixel_centre must be finite, got %r' % (pixel_centre,))
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    _cloud_arg(cams, 'cams', torch.float64, (16,))
+    n_cams = int(cams.shape[0])
+    if n_cams < 6 or n_cams % 6 or n_cams > SCAN_RENDER_MAX_CAMS:
+        raise ValueError('cams: six faces per scanner, 6 to %d rows, got %d' % (SCAN_RENDER_MAX_CAMS // 6 * 6, n_cams))
+    if not isinstance(maps, torch.Tensor) or maps.dim() != 3 or int(maps.shape[1]) != int(maps.shape[2]) or int(maps.shape[1]) < 1:
+        raise ValueError('maps: expected a tensor of shape (%d,N,N), got %s' % (n_cams, tuple(getattr(maps, 'shape', ()))))
+    size = int(maps.shape[1])
+    _cloud_arg(maps, 'maps', torch.float32, (size, size))
+    if int(maps.shape[0]) != n_cams:
+        raise ValueError('maps: %d maps for %d cameras' % (int(maps.shape[0]), n_cams))
+    if n_cams * size * size >= 1 << 31:
+        raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n_cams, size, size))
+    for t, name in ((cams, 'cams'), (maps, 'maps')):
+        if t.device != points.device:
+            raise RuntimeError('%s on %s, points on %s' % (name, t.device, points.device))
+    m = int(points.shape[0])
+    excess = torch.empty(m, dtype=torch.float32, device=points.device)
+    scanner = torch.empty(m, dtype=torch.int32, device=points.device)
+    if m:
+        _call('atvs_cloud_scan_excess', _p(points), ctypes.c_long(m), _p(cams), _p(maps), ctypes.c_int(n_cams // 6), ctypes.c_int(size),
+              ctypes.c_double(centre), ctypes.c_int(int(window)), _p(excess), _p(scanner), _stream())
+    return excess, scanner
+
+
+def cloud_voxel_shares(points, d2, excess, voxel, origin, tolerances, margin=0.0):
+    """points (n,3) float32, d2 (n,) float32 of cloud_nearest, excess (n,) float32 of cloud_scan_excess or None, voxel > 0 and
+    origin (3 host numbers; None: the floor of the finite minimum) as for cloud_voxel_downsample, up to 16 tolerances -> (T,4) int64
+    on the device, per tolerance tau: sum over voxels of q = (hit * 2^32) // den, the number of voxels with den > 0, sum of hit, sum
+    of den.  hit: the voxel's points with double(d2) <= tau * tau; den: all its points when excess is None, else hit + the points
+    that are not hit and have double(excess) <= margin (the rest are unobserved).  The voxel-averaged share is
+    sum q / (voxels * 2^32).  Integer atomics only: the same inputs give the same words.  A point more than 2^21 voxels from the
+    origin, or below it, raises as cloud_voxel_downsample does.  Synchronises once, to read the error word."""
+    voxel, margin = float(voxel), float(margin)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
+    if math.isnan(margin):
+        raise ValueError('margin must be a number, got %r' % (margin,))
+    tol = [float(t) for t in tolerances]
+    if not 1 <= len(tol) <= CLOUD_MAX_TOLERANCES:
+        raise ValueError('1 to %d tolerances, got %d' % (CLOUD_MAX_TOLERANCES, len(tol)))
+    if any(not t >= 0.0 for t in tol):
+        raise ValueError('tolerances must be >= 0, got %r' % (tol,))
+    if origin is not None:
+        org = _vec3(origin, 'origin')
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    _cloud_arg(d2, 'd2', torch.float32, ())
+    n = int(points.shape[0])
+    for t, name in ((d2, 'd2'), (excess, 'excess')):
+        if t is None:
+            continue
+        if name == 'excess':
+            _cloud_arg(excess, 'excess', torch.float32, ())
+        if int(t.shape[0]) != n:
+            raise ValueError('%s %s must have one entry per row of points %s' % (name, tuple(t.shape), tuple(points.shape)))
+        if t.device != points.device:
+            raise RuntimeError('%s on %s, points on %s' % (name, t.device, points.device))
+    if origin is None:
+        lo = cloud_bounds(points)[0] if n else None
+        org = _vec3(None if lo is None else np.floor(lo), 'origin')
+    out = torch.empty((len(tol), 4), dtype=torch.int64, device=points.device)
+    scratch = torch.empty(_size('atvs_cloud_voxel_shares_scratch_size', n), dtype=torch.uint8, device=points.device)
+    arr = (ctypes.c_double * len(tol))(*tol)
+    _call('atvs_cloud_voxel_shares', _p(points), _p(d2), _p(excess), ctypes.c_long(n), ctypes.c_double(voxel), org, arr, len(tol),
+          ctypes.c_double(margin), _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    if int(out[0, 0].item()) < 0:
+        lo, hi = cloud_bounds(points)
+        o = np.array(list(org))
+        if (lo < o).any():
+            raise ValueError('cloud_voxel_shares: a point lies below the origin %s (the finite minimum is %s)' % (o.tolist(), lo.tolist()))
+        fit = float((hi - o).max()) / float(1 << 21) * (1.0 + 1e-5)
+        raise ValueError('cloud_voxel_shares: voxel %r puts a point more than 2^21 voxels from the origin (bad shape); the '
+                         'smallest voxel that fits this cloud is %.8g' % (voxel, fit))
+    return out
