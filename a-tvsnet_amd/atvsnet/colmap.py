@@ -5,11 +5,14 @@ ColmapSparse (colmap_helpers.py:255-371) reads the model, estimate_max_dispariti
 generate_neighbor_list its source views, load_cam (preprocess_colmap.py:168-236) its camera.  Here:
 
     read_model        cameras / images / points3D in COLMAP's text or binary format (binary when cameras.bin exists), parsed by
-                      content; PINHOLE and SIMPLE_PINHOLE cameras only (the output of `colmap image_undistorter`)
+                      content; PINHOLE and SIMPLE_PINHOLE cameras only (the output of `colmap image_undistorter`) unless
+                      allow_distorted: then every model but FOV, each as the pinhole camera its images are undistorted into
+                      (atvsnet/undistort.py)
     depth_ranges      ops.colmap_depth_range: every point projected into every image in float64, exact rank statistics
     covisibility      ops.colmap_covisibility: shared-point counts of every image pair from the tracks (CSR)
     select_sources    ranking by shared count (ties: higher scene index first), zero stops it, fallback around the reference
-    make_scene        all of it, written for eval_pointcloud
+    make_scene        all of it, written for eval_pointcloud; from a sparse model and its image folder, the
+                      images of distorted cameras are undistorted on the GPU on the way
 
 Images are ordered by ascending image_id; an image's position in that order is its scene index (%08d).  numpy only: no
 pyquaternion (R is the closed form of the normalised quaternion), and no Python loop per observation.
@@ -38,8 +41,13 @@ class Model(object):
     camera; intrinsics (N,4) fx, fy, cx, cy and size (N,2) width, height of each image's camera; xyz (P,3) of points3D in
     ascending POINT3D_ID order; tracks: offsets (T+1,) int32 and observers (offsets[-1],) int32, for every POINT3D_ID some
     image observes, the distinct scene indices observing it, ascending (PointList, colmap_helpers.py:18-27: -1 dropped, a
-    point seen twice by one image counted once)."""
-    __slots__ = ('image_ids', 'names', 'camera_ids', 'qvec', 'R', 't', 'intrinsics', 'size', 'xyz', 'offsets', 'observers')
+    point seen twice by one image counted once).
+
+    read_model(allow_distorted=True) adds models [N] (the camera model's name), params [N] (its raw parameter tuple) and
+    source_size (N,2) (the size of the image as taken); intrinsics and size are then those of the UNDISTORTED camera
+    (undistort.undistorted_camera).  None otherwise."""
+    __slots__ = ('image_ids', 'names', 'camera_ids', 'qvec', 'R', 't', 'intrinsics', 'size', 'xyz', 'offsets', 'observers',
+                 'models', 'params', 'source_size')
 
 
 def quaternion_to_rotation(q):
@@ -60,7 +68,17 @@ def quaternion_to_rotation(q):
     return R
 
 
-def _camera(camera_id, model, width, height, params):
+def _camera(camera_id, model, width, height, params, undistort=None):
+    """-> ((fx, fy, cx, cy), (width, height)[, model, params, (source width, source height)]); undistort: None, or the
+    (blank_pixels, min_scale, max_scale) of allow_distorted."""
+    if undistort is not None:
+        from . import undistort as U
+        if model not in U.PARAM_COUNT:
+            raise ValueError('camera %d has the %s model: it is not undistorted here (FOV is out of scope); run `colmap '
+                             'image_undistorter` on the reconstruction first and import its output folder' % (camera_id, model))
+        p = tuple(float(v) for v in params)
+        K, size = U.undistorted_camera(model, p, int(width), int(height), *undistort, camera='camera %d' % camera_id)
+        return K, size, model, p, (int(width), int(height))
     if model not in UNDISTORTED_MODELS:
         raise ValueError('camera %d has the %s model: only PINHOLE and SIMPLE_PINHOLE cameras are read; run `colmap '
                          'image_undistorter` on the reconstruction first and import its output folder' % (camera_id, model))
@@ -74,12 +92,12 @@ def _content_lines(path):
         return [ln.rstrip('\r\n') for ln in f if not ln.lstrip().startswith('#')]
 
 
-def _read_text(sparse):
+def _read_text(sparse, undistort=None):
     cameras = {}
     for ln in _content_lines(os.path.join(sparse, 'cameras.txt')):
         w = ln.split()
         if w:
-            cameras[int(w[0])] = _camera(int(w[0]), w[1], w[2], w[3], w[4:])
+            cameras[int(w[0])] = _camera(int(w[0]), w[1], w[2], w[3], w[4:], undistort)
     lines = _content_lines(os.path.join(sparse, 'images.txt'))
     images, i = [], 0
     while i < len(lines):
@@ -100,7 +118,7 @@ def _read_text(sparse):
     return cameras, images, np.array(ids, np.int64), np.array(xyz, np.float64).reshape(-1, 3)
 
 
-def _read_binary(sparse):
+def _read_binary(sparse, undistort=None):
     """COLMAP's binary model (src/colmap/scene/reconstruction_io.cc): little-endian, counts as uint64."""
     with open(os.path.join(sparse, 'cameras.bin'), 'rb') as f:
         buf = f.read()
@@ -109,9 +127,9 @@ def _read_binary(sparse):
         cid, mid, width, height = struct.unpack_from('<iiQQ', buf, pos)
         pos += 24
         name, npar = _MODELS.get(mid, ('model id %d' % mid, None))
-        if npar is None or name not in UNDISTORTED_MODELS:
-            _camera(cid, name, width, height, ())                # raises
-        cameras[cid] = _camera(cid, name, width, height, struct.unpack_from('<%dd' % npar, buf, pos))
+        if npar is None or (name not in UNDISTORTED_MODELS and (undistort is None or name == 'FOV')):
+            _camera(cid, name, width, height, (), undistort)     # raises
+        cameras[cid] = _camera(cid, name, width, height, struct.unpack_from('<%dd' % npar, buf, pos), undistort)
         pos += 8 * npar
     with open(os.path.join(sparse, 'images.bin'), 'rb') as f:
         buf = f.read()
@@ -140,14 +158,17 @@ def _read_binary(sparse):
     return cameras, images, ids, xyz
 
 
-def read_model(sparse):
-    """<sparse>/{cameras,images,points3D}.bin, else .txt -> Model."""
+def read_model(sparse, allow_distorted=False, blank_pixels=0.0, min_scale=0.2, max_scale=2.0):
+    """<sparse>/{cameras,images,points3D}.bin, else .txt -> Model.  allow_distorted: cameras of COLMAP's distorted models (all
+    but FOV) are read as the pinhole cameras undistort.undistorted_camera(blank_pixels, min_scale, max_scale) gives them -- what
+    their images are resampled into -- and the Model carries models, params and source_size."""
+    undistort = (blank_pixels, min_scale, max_scale) if allow_distorted else None
     binary = os.path.exists(os.path.join(sparse, 'cameras.bin'))
     for name in ('cameras', 'images', 'points3D'):
         path = os.path.join(sparse, name + ('.bin' if binary else '.txt'))
         if not os.path.exists(path):
             raise ValueError('%s does not exist: not a COLMAP sparse model folder' % path)
-    cameras, images, point_ids, xyz = (_read_binary if binary else _read_text)(sparse)
+    cameras, images, point_ids, xyz = (_read_binary if binary else _read_text)(sparse, undistort)
     images.sort(key=lambda r: r[0])
     m = Model()
     m.image_ids = np.array([r[0] for r in images], np.int64)
@@ -163,6 +184,11 @@ def read_model(sparse):
     m.t = np.array([r[2] for r in images], np.float64).reshape(-1, 3)
     m.intrinsics = np.array([cameras[c][0] for c in m.camera_ids.tolist()], np.float64).reshape(-1, 4)
     m.size = np.array([cameras[c][1] for c in m.camera_ids.tolist()], np.int64).reshape(-1, 2)
+    m.models = m.params = m.source_size = None
+    if allow_distorted:
+        m.models = [cameras[c][2] for c in m.camera_ids.tolist()]
+        m.params = [cameras[c][3] for c in m.camera_ids.tolist()]
+        m.source_size = np.array([cameras[c][4] for c in m.camera_ids.tolist()], np.int64).reshape(-1, 2)
     order = np.argsort(point_ids, kind='stable')
     m.xyz = np.ascontiguousarray(xyz[order])
     m.offsets, m.observers = _tracks([r[5] for r in images])
@@ -279,18 +305,85 @@ def _check_jpeg(path):
             raise ValueError('%s has a JPEG name but no JPEG signature' % path)
 
 
-def make_scene(dense_folder, out, max_d=128, num_neighbors=10, percentile=0.99, stretch=1.33333, link=False, device=None):
-    """<dense_folder> (sparse/ + images/, the output of `colmap image_undistorter`) -> <out>/{cams/%08d_cam.txt, images/%08d.jpg,
-    pair.txt, colmap_images.txt}.  Images with no point in view are left out (reported) but keep their scene index.
-    -> dict(model, n, d_lo, d_hi, shared, sources, skipped)."""
+def _undistort_images(m, todo, srcs, out, jpeg_quality, workers, device):
+    """Images `todo` (scene indices) of distorted cameras: decoded with PIL, warped on the GPU, written as images/%08d.jpg.  Decode
+    and encode run on a pool of `workers` threads, at most that many images ahead of / behind the GPU, which sees one upload, one
+    launch and one download per image (and one map launch per camera).  -> seconds spent in decode, gpu, encode (summed over
+    the threads)."""
+    import time
+    from concurrent.futures import ThreadPoolExecutor
+    import torch
+    from PIL import Image
+    from . import undistort as U
+    spent = dict(decode=0.0, gpu=0.0, encode=0.0)
+
+    def decode(k):
+        t0 = time.time()
+        with Image.open(srcs[k]) as im:
+            a = np.array(im.convert('RGB'))
+        return a, time.time() - t0
+
+    def encode(k, a):
+        t0 = time.time()
+        Image.fromarray(a).save(os.path.join(out, 'images', '%08d.jpg' % k), quality=jpeg_quality, subsampling=0)
+        return time.time() - t0
+
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    with ThreadPoolExecutor(workers) as pool, torch.cuda.device(dev):
+        decoding = {k: pool.submit(decode, k) for k in todo[:workers]}
+        encoding = []
+        for i, k in enumerate(todo):
+            a, dt = decoding.pop(k).result()
+            spent['decode'] += dt
+            if i + workers < len(todo):
+                decoding[todo[i + workers]] = pool.submit(decode, todo[i + workers])
+            t0 = time.time()
+            K, size = tuple(m.intrinsics[k].tolist()), tuple(m.size[k].tolist())
+            try:
+                warped = U.undistort_image(a, m.models[k], m.params[k], int(m.source_size[k, 0]), int(m.source_size[k, 1]), (K, size))
+            except ValueError as e:
+                raise ValueError('%s: %s' % (srcs[k], e))
+            spent['gpu'] += time.time() - t0
+            encoding.append(pool.submit(encode, k, warped))
+            if len(encoding) > workers:
+                spent['encode'] += encoding.pop(0).result()
+        for f in encoding:
+            spent['encode'] += f.result()
+    return spent
+
+
+def make_scene(dense_folder, out, max_d=128, num_neighbors=10, percentile=0.99, stretch=1.33333, link=False, device=None,
+               sparse=None, image_path=None, blank_pixels=0.0, min_scale=0.2, max_scale=2.0, jpeg_quality=100, workers=16):
+    """<dense_folder> (sparse/ + images/, the output of `colmap image_undistorter`), or, with dense_folder None, a sparse model
+    `sparse` of any camera models but FOV and its images under `image_path` -> <out>/{cams/%08d_cam.txt, images/%08d.jpg,
+    pair.txt, colmap_images.txt}.  Images of pinhole cameras are copied (or linked); images of distorted cameras are undistorted
+    on the GPU into the camera undistort.undistorted_camera(blank_pixels, min_scale, max_scale) gives, which cams/ then holds,
+    and written as JPEG of `jpeg_quality` without chroma subsampling.  Images with no point in view are left out (reported) but
+    keep their scene index.  -> dict(model, n, d_lo, d_hi, shared, sources, skipped, undistorted, seconds)."""
     if max_d < 2:
         raise ValueError('max_d must be at least 2, got %d' % max_d)
-    m = read_model(os.path.join(dense_folder, 'sparse'))
+    if (dense_folder is None) == (sparse is None and image_path is None) or (sparse is None) != (image_path is None):
+        raise ValueError('give either dense_folder, or sparse and image_path')
+    if not 1 <= jpeg_quality <= 100:
+        raise ValueError('jpeg_quality must lie in [1, 100], got %r' % jpeg_quality)
+    workers = min(max(int(workers), 1), 16)
+    if dense_folder is not None:
+        m = read_model(os.path.join(dense_folder, 'sparse'))
+        image_path = os.path.join(dense_folder, 'images')
+    else:
+        m = read_model(sparse, True, blank_pixels, min_scale, max_scale)
+        dense_folder = sparse
     if len(m.image_ids) == 0:
         raise ValueError('%s: the model has no images' % dense_folder)
-    srcs = [os.path.join(dense_folder, 'images', name) for name in m.names]
-    for p in srcs:
-        _check_jpeg(p)
+    srcs = [os.path.join(image_path, name) for name in m.names]
+    distorted = [m.models is not None and m.models[k] not in UNDISTORTED_MODELS for k in range(len(srcs))]
+    if link and any(distorted):
+        raise ValueError('%s has cameras of distorted models: their images are resampled, not linked (drop --link)' % dense_folder)
+    for p, d in zip(srcs, distorted):
+        if d and not os.path.isfile(p):
+            raise ValueError('%s does not exist' % p)
+        if not d:
+            _check_jpeg(p)
     n, d_lo, d_hi = depth_ranges(m, percentile, device)
     keep = n > 0
     skipped = np.flatnonzero(~keep).tolist()
@@ -307,14 +400,19 @@ def make_scene(dense_folder, out, max_d=128, num_neighbors=10, percentile=0.99, 
         dst = os.path.join(out, 'images', '%08d.jpg' % k)
         if os.path.lexists(dst):
             os.remove(dst)
+        if distorted[k]:
+            continue
         if link:
             os.symlink(os.path.abspath(srcs[k]), dst)
         else:
             shutil.copyfile(srcs[k], dst)
+    todo = [k for k in np.flatnonzero(keep).tolist() if distorted[k]]
+    seconds = _undistort_images(m, todo, srcs, out, jpeg_quality, workers, device) if todo else dict(decode=0.0, gpu=0.0, encode=0.0)
     with open(os.path.join(out, 'pair.txt'), 'w') as f:
         f.write(pair_text(sources))
     with open(os.path.join(out, 'colmap_images.txt'), 'w') as f:
         f.write('# scene index, COLMAP IMAGE_ID, NAME; images with no 3-D point in view are commented out\n')
         for k in range(len(m.image_ids)):
             f.write('%s%08d %d %s\n' % ('' if keep[k] else '# ', k, m.image_ids[k], m.names[k]))
-    return dict(model=m, n=n, d_lo=d_lo, d_hi=d_hi, shared=shared, sources=sources, skipped=skipped)
+    return dict(model=m, n=n, d_lo=d_lo, d_hi=d_hi, shared=shared, sources=sources, skipped=skipped, undistorted=todo,
+                seconds=seconds)

@@ -3,9 +3,14 @@
 
     python -m atvsnet_amd.atvsnet.colmap_scene --dense_folder <colmap dense dir> --out <data_root>/eth3d/<scene> \\
            [--max_d 128] [--num_neighbors 10] [--percentile 0.99] [--stretch 1.33333] [--link]
+    python -m atvsnet_amd.atvsnet.colmap_scene --sparse <colmap sparse model> --image_path <its images> --out ... \\
+           [--blank_pixels 0] [--min_scale 0.2] [--max_scale 2.0] [--jpeg_quality 100]
     python -m atvsnet_amd.atvsnet.eval_pointcloud --data_root <data_root> --scenes <scene> --scene_cache --fuse ...
 
-<dense_folder> is the output of `colmap image_undistorter` (sparse/ + images/).  Depth ranges and co-visibility run on the GPU.
+<dense_folder> is the output of `colmap image_undistorter` (sparse/ + images/).  --sparse / --image_path take a reconstruction as
+COLMAP's mapper leaves it (SIMPLE_RADIAL, OPENCV, ... cameras; every model but FOV): the images of distorted cameras are
+undistorted on the GPU (atvsnet/undistort.py), so no `colmap image_undistorter` run is needed.  Depth ranges and co-visibility run
+on the GPU.
 """
 from __future__ import print_function
 
@@ -15,24 +20,34 @@ import time
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
-    ap.add_argument('--dense_folder', required=True, help='sparse/ (text or binary model) and images/ of colmap image_undistorter')
+    ap.add_argument('--dense_folder', help='sparse/ (text or binary model) and images/ of colmap image_undistorter')
+    ap.add_argument('--sparse', help='instead of --dense_folder: a sparse model (text or binary) whose cameras may be distorted')
+    ap.add_argument('--image_path', help='with --sparse: the folder the model\'s image names are relative to')
     ap.add_argument('--out', required=True, help='scene folder to write (e.g. <data_root>/eth3d/<scene>)')
     ap.add_argument('--max_d', type=int, default=128, help='depth planes written into each camera (the driver sweeps its own --max_d)')
     ap.add_argument('--num_neighbors', type=int, default=10, help='source views listed per reference in pair.txt')
     ap.add_argument('--percentile', type=float, default=0.99, help='disparity quantiles p and 1 - p give the depth range')
     ap.add_argument('--stretch', type=float, default=1.33333, help='the range is widened by this factor on both ends')
     ap.add_argument('--link', action='store_true', help='symlink the undistorted JPEGs instead of copying them')
+    ap.add_argument('--blank_pixels', type=float, default=0.0, help='undistortion: 0 = no blank pixel in the output, 1 = every '
+                    'source pixel kept')
+    ap.add_argument('--min_scale', type=float, default=0.2, help='undistortion: lower bound of the output size / source size')
+    ap.add_argument('--max_scale', type=float, default=2.0, help='undistortion: upper bound of the output size / source size')
+    ap.add_argument('--jpeg_quality', type=int, default=100, help='quality of the undistorted JPEGs (written without chroma subsampling)')
     ap.add_argument('--gpu_id', type=int, default=0)
     a = ap.parse_args(argv)
+    if (a.dense_folder is None) == (a.sparse is None and a.image_path is None) or (a.sparse is None) != (a.image_path is None):
+        ap.error('give either --dense_folder, or --sparse together with --image_path')
     import torch
     from . import colmap
     torch.cuda.set_device(a.gpu_id)
     t0 = time.time()
     r = colmap.make_scene(a.dense_folder, a.out, max_d=a.max_d, num_neighbors=a.num_neighbors, percentile=a.percentile,
-                          stretch=a.stretch, link=a.link)
+                          stretch=a.stretch, link=a.link, sparse=a.sparse, image_path=a.image_path, blank_pixels=a.blank_pixels,
+                          min_scale=a.min_scale, max_scale=a.max_scale, jpeg_quality=a.jpeg_quality)
     m = r['model']
-    print('colmap import: %d images (%d left out), %d points, %d observations -> %s in %.2f s' %
-          (len(m.image_ids), len(r['skipped']), len(m.xyz), int(m.offsets[-1]), a.out, time.time() - t0))
+    print('colmap import: %d images (%d left out, %d undistorted), %d points, %d observations -> %s in %.2f s' %
+          (len(m.image_ids), len(r['skipped']), len(r['undistorted']), len(m.xyz), int(m.offsets[-1]), a.out, time.time() - t0))
     return r
 
 

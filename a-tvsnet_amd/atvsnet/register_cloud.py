@@ -81,24 +81,30 @@ def camera_centres(model):
     return -np.einsum('nji,nj->ni', model.R, model.t)
 
 
+def cameras_from_models(recon_sparse_dir, gt_sparse_dir):
+    """Two COLMAP sparse model folders of the same images -> (P, Q) (k,3) float64: the camera centres of the images both list, by
+    NAME, in the first and in the second model's frame.  Only poses are used, so cameras of any model but FOV are read
+    (colmap.read_model(allow_distorted=True)): ETH3D's own calibration folder (THIN_PRISM_FISHEYE) serves as the second."""
+    a, b = colmap.read_model(recon_sparse_dir, allow_distorted=True), colmap.read_model(gt_sparse_dir, allow_distorted=True)
+    at = dict(zip(b.names, range(len(b.names))))
+    pairs = [(i, at[name]) for i, name in enumerate(a.names) if name in at]
+    return camera_centres(a)[[i for i, _ in pairs]].reshape(-1, 3), camera_centres(b)[[j for _, j in pairs]].reshape(-1, 3)
+
+
 def init_from_cameras(recon_sparse_dir, gt_sparse_dir):
     """Two COLMAP sparse model folders (colmap.read_model: text or binary) of the same images, the first in the reconstruction's
     frame, the second in the ground truth's -> (4x4 similarity moving the first frame into the second, number of images matched
     by NAME, rms distance of the matched camera centres after it).  ValueError when fewer than 3 names match or the matched
     centres are collinear (a straight camera path leaves the rotation about it free)."""
-    a, b = colmap.read_model(recon_sparse_dir), colmap.read_model(gt_sparse_dir)
-    at = dict(zip(b.names, range(len(b.names))))
-    pairs = [(i, at[name]) for i, name in enumerate(a.names) if name in at]
-    if len(pairs) < 3:
-        raise ValueError('%s and %s have %d image names in common: at least 3 are needed' % (recon_sparse_dir, gt_sparse_dir, len(pairs)))
-    P = camera_centres(a)[[i for i, _ in pairs]]
-    Q = camera_centres(b)[[j for _, j in pairs]]
+    P, Q = cameras_from_models(recon_sparse_dir, gt_sparse_dir)
+    if len(P) < 3:
+        raise ValueError('%s and %s have %d image names in common: at least 3 are needed' % (recon_sparse_dir, gt_sparse_dir, len(P)))
     try:
         T = similarity_from_points(P, Q, with_scale=True)
     except ValueError as e:
-        raise ValueError('the %d matched camera centres do not determine a similarity: %s' % (len(pairs), e))
+        raise ValueError('the %d matched camera centres do not determine a similarity: %s' % (len(P), e))
     rms = float(np.sqrt(((apply(T, P) - Q) ** 2).sum(axis=1).mean()))
-    return T, len(pairs), rms
+    return T, len(P), rms
 
 
 def box_corners(lo, hi):

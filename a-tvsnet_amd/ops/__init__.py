@@ -8,7 +8,7 @@
     convolution  `conv()` and the composite forms (SplitVolume, siblings, stems, transposed convolution)
     aanet     AANet aggregation, depth-map fusion
     prepare   the scene driver's view preparation (uint8 image -> network input, 1/4 image)
-    colmap    COLMAP model import: per-image depth range, co-visibility matrix
+    colmap    COLMAP model import: per-image depth range, co-visibility matrix; undistortion: sampling map, image gather
     cloud     point-cloud scoring: uniform grid, exact nearest neighbour within a radius, tolerance counts;
               registration: transform, pair moments, voxel down-sampling; neighbourhoods: k nearest neighbours, radius counts,
               outlier statistics, bounding box; rendering: a scan splatted into cameras as nearest-depth maps; ETH3D-style
@@ -40,6 +40,7 @@ from .prepare import (ViewPlan, prepare_taps, prepare_view, prepare_workspace, r
 from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, divide, fusibile, fusibile_scene,
     fusion_stage)      # noqa: F401
 from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range      # noqa: F401
+from .colmap import UNDISTORT_MAX_SIDE, UNDISTORT_MODELS, undistort_map, undistort_remap      # noqa: F401
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401
 from .cloud import cloud_bounds, cloud_pair_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
 from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401

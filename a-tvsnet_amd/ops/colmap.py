@@ -1,5 +1,7 @@
 """COLMAP model import on the device (csrc/colmap.hip): the per-image depth range by exact rank selection and the co-visibility
-matrix of shared 3-D points.  The host side (model reader, CSR build, scene writer) is atvsnet/colmap.py.
+matrix of shared 3-D points; and the undistortion of distorted camera models (csrc/undistort.hip): the per-camera sampling map
+and the image gather.  The host side (model reader, CSR build, scene writer) is atvsnet/colmap.py, that of the undistortion
+(forward models, their inverse, the output camera) atvsnet/undistort.py.
 """
 
 import ctypes
@@ -10,6 +12,10 @@ from .. import _lib
 from .base import _ERR, _call, _p, _stream
 
 COVIS_MAX_IMAGES = 16384            # atvs_colmap_covisibility: an (images x images) int32 matrix of at most 1 GiB
+# atvs_undistort_map: COLMAP's camera model ids of the models it undistorts, and their parameter counts
+UNDISTORT_MODELS = {'SIMPLE_RADIAL': (2, 4), 'RADIAL': (3, 5), 'OPENCV': (4, 8), 'OPENCV_FISHEYE': (5, 8), 'FULL_OPENCV': (6, 12),
+                    'SIMPLE_RADIAL_FISHEYE': (8, 4), 'RADIAL_FISHEYE': (9, 5), 'THIN_PRISM_FISHEYE': (10, 12)}
+UNDISTORT_MAX_SIDE = 1 << 21        # (side - 1) * 1024 stays an int32
 
 
 def _colmap_args(*specs):
@@ -64,3 +70,56 @@ def colmap_covisibility(offsets, observers, n_images):
     _call('atvs_colmap_covisibility', _p(offsets), _p(observers), int(offsets.shape[0]) - 1, int(observers.shape[0]), int(n_images),
           _p(covis), _stream())
     return covis
+
+
+def _image_size(width, height, what):
+    width, height = int(width), int(height)
+    if not (1 <= width <= UNDISTORT_MAX_SIDE and 1 <= height <= UNDISTORT_MAX_SIDE and width * height <= 0x7fffffff):
+        raise ValueError('%s of %d x %d pixels: sides of 1 to %d and at most 2^31 - 1 pixels (the int32 pixel index)' %
+                         (what, width, height, UNDISTORT_MAX_SIDE))
+    return width, height
+
+
+def undistort_map(model, params, width, height, camera):
+    """The sampling map of one camera (atvs_undistort_map).  model: a name of UNDISTORT_MODELS, params: its parameters in COLMAP's
+    order, width x height: the distorted camera's size; camera = ((fx, fy, cx, cy), (W', H')) the undistorted pinhole camera
+    (atvsnet.undistort.undistorted_camera) -> (H', W', 2) int32 on the current device: per output pixel the source coordinate
+    in 22.10 fixed point, (INT32_MIN, 0) where it falls outside the source."""
+    if model not in UNDISTORT_MODELS:
+        raise ValueError('model %r: the undistortion knows %s' % (model, ', '.join(sorted(UNDISTORT_MODELS))))
+    model_id, npar = UNDISTORT_MODELS[model]
+    p = [float(v) for v in params]
+    if len(p) != npar:
+        raise ValueError('%s takes %d parameters, got %d' % (model, npar, len(p)))
+    (fx, fy, cx, cy), (wo, ho) = camera
+    k = [float(fx), float(fy), float(cx), float(cy)]
+    if not all(abs(v) < float('inf') for v in p + k):               # NaN fails the comparison too
+        raise ValueError('%s: parameters %r and camera %r must be finite' % (model, tuple(p), tuple(k)))
+    if k[0] == 0.0 or k[1] == 0.0:
+        raise ValueError('camera: a focal length of 0')
+    width, height = _image_size(width, height, 'a distorted camera')
+    wo, ho = _image_size(wo, ho, 'an undistorted camera')
+    if not torch.cuda.is_available():
+        raise RuntimeError('undistort_map: the COLMAP kernels run on the MI355X only (no CPU fallback)')
+    out = torch.empty((ho, wo, 2), dtype=torch.int32, device=torch.device('cuda', torch.cuda.current_device()))
+    _call('atvs_undistort_map', model_id, (ctypes.c_double * 12)(*(p + [0.0] * (12 - npar))), width, height,
+          (ctypes.c_double * 4)(*k), wo, ho, _p(out), _stream())
+    return out
+
+
+def undistort_remap(image_u8, map):
+    """image_u8 (H, W, 3) uint8, map (H', W', 2) int32 of undistort_map -> (H', W', 3) uint8 on the device: the integer bilinear
+    gather of atvs_undistort_remap, black where the map holds INT32_MIN."""
+    for t, name, dtype, last in ((image_u8, 'image_u8', torch.uint8, 3), (map, 'map', torch.int32, 2)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError('%s: expected a tensor, got %s' % (name, type(t).__name__))
+        if t.dim() != 3 or int(t.shape[2]) != last:
+            raise ValueError('%s: expected shape (rows, cols, %d), got %s' % (name, last, tuple(t.shape)))
+    height, width = (int(v) for v in image_u8.shape[:2])
+    ho, wo = (int(v) for v in map.shape[:2])
+    _colmap_args((image_u8, 'image_u8', torch.uint8, (width, 3)), (map, 'map', torch.int32, (wo, 2)))
+    _image_size(width, height, 'image_u8')
+    _image_size(wo, ho, 'map')
+    out = torch.empty((ho, wo, 3), dtype=torch.uint8, device=map.device)
+    _call('atvs_undistort_remap', _p(image_u8), width, height, _p(map), wo, ho, _p(out), _stream())
+    return out

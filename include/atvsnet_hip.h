@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 52
+#define ATVS_ABI_VERSION 53
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -739,6 +739,34 @@ int atvs_colmap_depth_range(const double* points, long n_points, const double* c
  * outside the arrays add nothing.  n_images above 16384 (a matrix beyond 1 GiB) or below 1: ATVS_ERR_SHAPE. */
 int atvs_colmap_covisibility(const int* offsets, const int* observers, int n_tracks, int n_obs, int n_images, int* covis,
                              atvs_stream_t stream);
+
+/* Undistortion of COLMAP's distorted camera models (atvsnet/undistort.py, csrc/undistort.hip): what
+ * `colmap image_undistorter` does to the images, restated.  model_id is COLMAP's camera model id: 2 SIMPLE_RADIAL (f, cx, cy, k),
+ * 3 RADIAL (f, cx, cy, k1, k2), 4 OPENCV (fx, fy, cx, cy, k1, k2, p1, p2), 5 OPENCV_FISHEYE (fx, fy, cx, cy, k1, k2, k3, k4),
+ * 6 FULL_OPENCV (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, k5, k6), 8 SIMPLE_RADIAL_FISHEYE (f, cx, cy, k), 9 RADIAL_FISHEYE
+ * (f, cx, cy, k1, k2), 10 THIN_PRISM_FISHEYE (fx, fy, cx, cy, k1, k2, p1, p2, k3, k4, sx1, sy1).  params: HOST, 12 doubles, the
+ * model's parameters in COLMAP's order, the rest ignored.  W x H: the distorted camera's size.
+ *
+ * atvs_undistort_map: one map per CAMERA.  camera: HOST, 4 doubles fx, fy, cx', cy' of the undistorted pinhole camera of
+ * Wo x Ho pixels.  map (Ho, Wo, 2) int32, device.  One thread per output pixel (X, Y), in float64, every operation rounded,
+ * nothing contracted: u = ((X + 0.5) - cx') / fx, v = ((Y + 0.5) - cy') / fy; (u_d, v_d) = the model's forward distortion in the
+ * operation order of DESIGN.md 11.1 (r4 = r2 r2, r6 = r4 r2, r8 = r6 r2; the fisheye models go through atan); the source
+ * coordinate s = ((fxs u_d + cxs) - 0.5, (fys v_d + cys) - 0.5) with the DISTORTED camera's fxs, fys, cxs, cys; stored in 22.10
+ * fixed point, q = floor(s 1024 + 0.5).  A pixel is valid iff both s are finite and 0 <= q_x <= (W - 1) 1024, 0 <= q_y <=
+ * (H - 1) 1024, decided in float64 before the conversion; an invalid pixel stores (INT32_MIN, 0).
+ *
+ * atvs_undistort_remap: a gather.  src (H, W, 3) uint8, map (Ho, Wo, 2) int32 (16-byte aligned), dst (Ho, Wo, 3) uint8 (4-byte
+ * aligned), device.  Per output pixel: q_x = INT32_MIN gives 0 0 0; else i = q >> 10, f = q & 1023 per axis, taps at i and
+ * min(i + 1, size - 1) (both clamped into the source, so no map makes the kernel read outside src), and per channel, in integers,
+ * top = p00 (1024 - f_x) + p01 f_x, bot likewise from the lower row, out = (top (1024 - f_y) + bot f_y + 2^19) >> 20.  Four
+ * consecutive pixels of the flat (Ho Wo) order per thread: three dword stores; the last thread finishes Ho Wo mod 4 pixels by bytes.
+ *
+ * Both: an unknown model_id, a non-finite parameter or camera value, fx or fy of 0, a size < 1, W or H above 2^21, W H or Wo Ho
+ * beyond the int32 pixel index, a misaligned map or dst: ATVS_ERR_ARG. */
+int atvs_undistort_map(int model_id, const double* params, int W, int H, const double* camera, int Wo, int Ho, int* map,
+                       atvs_stream_t stream);
+int atvs_undistort_remap(const unsigned char* src, int W, int H, const int* map, int Wo, int Ho, unsigned char* dst,
+                         atvs_stream_t stream);
 
 /* Point-cloud scoring (ops/cloud.py, atvsnet/eval_cloud.py, csrc/cloud.hip).  Pointers are device pointers unless named host.
  *
