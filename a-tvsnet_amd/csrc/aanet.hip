@@ -16,9 +16,9 @@
 
 #define AANET_MAX_VIEWS 16
 
-// e^(u - max) exactly as atvs_aanet_softmax_sum (common.h) forms it: 2^(u log2 e - ml), ml = max * log2 e
+// e^(u - max) exactly as atvs_aanet_softmax_sum (common.h) forms it: 2^((u - max) log2 e), exactly 1 at the maximum
 #define AA_L2E 1.44269504088896340736f
-__device__ __forceinline__ float aa_exp(float u, float ml) { return __builtin_amdgcn_exp2f(__builtin_fmaf(u, AA_L2E, -ml)); }
+__device__ __forceinline__ float aa_exp(float u, float m) { return __builtin_amdgcn_exp2f((u - m) * AA_L2E); }
 
 struct ViewPtrs {
   const float* sr[AANET_MAX_VIEWS];
@@ -76,12 +76,11 @@ __global__ __launch_bounds__(256) void aanet_combine_generic_kernel(ViewPtrs p, 
     m.w = fmaxf(m.w, (r.w - s.w) + ssum.w);
   }
   // atvs_aanet_softmax_sum's arithmetic (common.h) with the operands re-read per pass
-  const float4 ml = make_float4(m.x * AA_L2E, m.y * AA_L2E, m.z * AA_L2E, m.w * AA_L2E);
   float4 den = make_float4(0.f, 0.f, 0.f, 0.f), num = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int n = 0; n < nv; ++n) {
     float4 s = ld4(p.sr[n] + so), r = ld4(p.sr[n] + so + 8), x = ld4(p.x[n] + xo);
-    const float ex = aa_exp((r.x - s.x) + ssum.x, ml.x), ey = aa_exp((r.y - s.y) + ssum.y, ml.y);
-    const float ez = aa_exp((r.z - s.z) + ssum.z, ml.z), ew = aa_exp((r.w - s.w) + ssum.w, ml.w);
+    const float ex = aa_exp((r.x - s.x) + ssum.x, m.x), ey = aa_exp((r.y - s.y) + ssum.y, m.y);
+    const float ez = aa_exp((r.z - s.z) + ssum.z, m.z), ew = aa_exp((r.w - s.w) + ssum.w, m.w);
     den.x += ex; den.y += ey; den.z += ez; den.w += ew;
     num.x = __builtin_fmaf(ex, x.x, num.x); num.y = __builtin_fmaf(ey, x.y, num.y);
     num.z = __builtin_fmaf(ez, x.z, num.z); num.w = __builtin_fmaf(ew, x.w, num.w);
@@ -162,12 +161,11 @@ __global__ __launch_bounds__(256) void aanet_partial_kernel(ViewPtrs p, int nv, 
     return;
   }
   float4 m = ld4(umax + xo);
-  const float4 ml = make_float4(m.x * AA_L2E, m.y * AA_L2E, m.z * AA_L2E, m.w * AA_L2E);
   float4 den = make_float4(0.f, 0.f, 0.f, 0.f), num = make_float4(0.f, 0.f, 0.f, 0.f);
   for (int n = 0; n < nv; ++n) {
     float4 s = ld4(p.sr[n] + so), r = ld4(p.sr[n] + so + 8), x = ld4(p.x[n] + xo);
-    float ex = aa_exp((r.x - s.x) + ss.x, ml.x), ey = aa_exp((r.y - s.y) + ss.y, ml.y);
-    float ez = aa_exp((r.z - s.z) + ss.z, ml.z), ew = aa_exp((r.w - s.w) + ss.w, ml.w);
+    float ex = aa_exp((r.x - s.x) + ss.x, m.x), ey = aa_exp((r.y - s.y) + ss.y, m.y);
+    float ez = aa_exp((r.z - s.z) + ss.z, m.z), ew = aa_exp((r.w - s.w) + ss.w, m.w);
     den.x += ex; den.y += ey; den.z += ez; den.w += ew;
     num.x = __builtin_fmaf(ex, x.x, num.x); num.y = __builtin_fmaf(ey, x.y, num.y);
     num.z = __builtin_fmaf(ez, x.z, num.z); num.w = __builtin_fmaf(ew, x.w, num.w);

@@ -171,21 +171,22 @@ __device__ __forceinline__ void atvs_split4_f16(const float4& v, uint2* h0, uint
 // view axis, then sum_n score_n * X_n):  *out = sum_n softmax_n(u)[n] * x(n) = (sum_n e_n x_n) / (sum_n e_n), e_n = e^(u_n - max).
 // ONE definition for aanet_combine_kernel (aanet.hip) and the fused module (aanet_b.hip), which must agree bit for bit.  u[] is
 // overwritten.  Written for FEW vector instructions -- in aanet_b it runs on wavefronts that share their SIMD's issue slots with MFMA
-// wavefronts: e_n = 2^(u_n log2 e - max log2 e) as one fused multiply-add + v_exp_f32 (the rounding of max log2 e is a factor
-// common to every e_n: it cancels in the ratio), numerator and denominator accumulated side by side, ONE v_rcp_f32 (1 ulp) and one
-// multiplication at the end: 5 NV + 3 instructions instead of ~25 NV for expf and NV IEEE divisions; within a few ulp of the exact
-// softmax-weighted sum wherever a term matters (tests: 2e-5 of the output maximum against the oracle).
+// wavefronts: e_n = 2^((u_n - max) log2 e) as a subtraction, a multiplication and v_exp_f32, numerator and denominator accumulated
+// side by side, ONE v_rcp_f32 (1 ulp) and one multiplication at the end: 6 NV + 2 instructions instead of ~25 NV for expf and NV
+// IEEE divisions.  The winning view's exponent is EXACTLY 0 and its e exactly 1 (2^(u log2 e - round(max log2 e)) was 1 + a few
+// ulp there: a factor common to every e_n, but one that the roundings of num, of rcp and of their product do not cancel), so one
+// view gives x, a saturated softmax the winning x and an exact tie (x_a + x_b) / 2, all bit for bit
+// (tests/test_gpu_glue_kernels.py); elsewhere within REL * cond of the float64 formula per element (tests/glue_ref.py).
 template <int NV, class X>
 __device__ __forceinline__ void atvs_aanet_softmax_sum(float* u, X&& x, float* out) {
   constexpr float L2E = 1.44269504088896340736f;
   float m = -INFINITY;
 #pragma unroll
   for (int n = 0; n < NV; ++n) m = fmaxf(m, u[n]);
-  const float ml = m * L2E;
   float den = 0.f, num = 0.f;
 #pragma unroll
   for (int n = 0; n < NV; ++n) {
-    const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(u[n], L2E, -ml));
+    const float e = __builtin_amdgcn_exp2f((u[n] - m) * L2E);
     den += e;
     num = __builtin_fmaf(e, x(n), num);
   }
