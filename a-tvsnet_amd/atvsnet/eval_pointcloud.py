@@ -81,22 +81,38 @@ def _ground_truth_depth_range(ref_image, cams):
         cam[1][3][3] = disp_max
 
 
-def load_data(sample_list, data_index):
-    """One pair.txt entry -> (scaled BGR images (1,N,h/4,w/4,3), centred images (1,N,h,w,3), cameras at
-    sample_scale (1,N,2,4,4), a (1,h/4,w/4,1) placeholder, reference image index) (reference :97-203)."""
-    data = sample_list[data_index]
-    image_index = int(os.path.splitext(os.path.basename(data[0]))[0])
+def _view_paths(data):
+    """The image paths of the FLAGS.view_num views of one pair.txt entry: a missing source is replaced by the reference view."""
     found = len(data) // 2
-    images, cams = [], []
+    return [data[2 * (view if view < found else 0)] for view in range(FLAGS.view_num)]
+
+
+def _view_cams(data):
+    """The cameras of those views as the files give them; a source without a plane count gets max_d."""
+    found, cams = len(data) // 2, []
     for view in range(FLAGS.view_num):
-        src = view if view < found else 0            # missing sources are replaced by the reference view
-        images.append(example._imread_bgr(data[2 * src]))
-        with open(data[2 * src + 1]) as f:
+        with open(data[2 * (view if view < found else 0) + 1]) as f:
             cam = load_cam(f, 1.0)
         if view < found and cam[1][3][2] == 0:
             cam[1][3][2] = FLAGS.max_d
         cams.append(cam)
+    return cams
 
+
+def _sweep_cams(ref_image, cams):
+    """The closing steps on scaled and cropped cameras: inverse-depth range, ground-truth range, sample_scale."""
+    if FLAGS.inverse_depth:
+        for cam in cams:
+            _inverse_depth_range(cam)
+    _ground_truth_depth_range(ref_image, cams)
+    return scale_mvs_camera(cams, scale=FLAGS.sample_scale)
+
+
+def load_data(sample_list, data_index):
+    """One pair.txt entry -> (scaled BGR images (1,N,h/4,w/4,3), centred images (1,N,h,w,3), cameras at
+    sample_scale (1,N,2,4,4), a (1,h/4,w/4,1) placeholder, reference image index) (reference :97-203)."""
+    data = sample_list[data_index]
+    images, cams = [example._imread_bgr(v) for v in _view_paths(data)], _view_cams(data)
     resize_scale = 1
     if FLAGS.adaptive_scaling:
         h_scale = max(float(FLAGS.max_h) / im.shape[0] for im in images)
@@ -109,15 +125,11 @@ def load_data(sample_list, data_index):
     images, cams = scale_mvs_input(images, cams, scale=resize_scale)
     images, cams = crop_mvs_input(images, cams, base_image_size=32)
     centered = [center_image(im) for im in images]
-    if FLAGS.inverse_depth:
-        for cam in cams:
-            _inverse_depth_range(cam)
-    _ground_truth_depth_range(data[0], cams)
-    cams = scale_mvs_camera(cams, scale=FLAGS.sample_scale)
+    cams = _sweep_cams(data[0], cams)
     scaled = [scale_image(im, scale=FLAGS.sample_scale) for im in images]
     scaled_depth = scaled[-1][:, :, 0:1].copy()
     return (np.stack(scaled, 0)[None], np.stack(centered, 0)[None], np.stack(cams, 0)[None], scaled_depth[None],
-            image_index)
+            int(os.path.splitext(os.path.basename(data[0]))[0]))
 
 
 def load_cams(data, shapes):
@@ -125,15 +137,7 @@ def load_cams(data, shapes):
     images are (h, w) = `shapes` (after the missing-source substitution) -> (cams (1,N,2,4,4) at sample_scale, the adaptive
     scale).  The same steps on the same values as load_data: scale, crop offset, inverse-depth range, ground-truth range,
     sample_scale."""
-    found = len(data) // 2
-    cams = []
-    for view in range(FLAGS.view_num):
-        src = view if view < found else 0
-        with open(data[2 * src + 1]) as f:
-            cam = load_cam(f, 1.0)
-        if view < found and cam[1][3][2] == 0:
-            cam[1][3][2] = FLAGS.max_d
-        cams.append(cam)
+    cams = _view_cams(data)
     resize_scale = scene.adaptive_scale(shapes) if FLAGS.adaptive_scaling else 1
     if resize_scale is None:
         print("max_h, max_w should < W and H!")
@@ -145,12 +149,7 @@ def load_cams(data, shapes):
         y0, x0, _, _ = crop_window(*scaled_size(shapes[v][0], shapes[v][1], resize_scale), base_image_size=32)
         cams[v][1][0][2] -= x0
         cams[v][1][1][2] -= y0
-    if FLAGS.inverse_depth:
-        for cam in cams:
-            _inverse_depth_range(cam)
-    _ground_truth_depth_range(data[0], cams)
-    cams = scale_mvs_camera(cams, scale=FLAGS.sample_scale)
-    return np.stack(cams, 0)[None], resize_scale
+    return np.stack(_sweep_cams(data[0], cams), 0)[None], resize_scale
 
 
 class _Decoder(object):
@@ -183,12 +182,13 @@ class _Decoder(object):
 
 
 class _Writer(object):
-    """finish()'s file writing on one background thread behind a bounded queue (threaded=False: in the caller)."""
+    """A scene's file writing on one background thread behind a bounded queue (threaded=False: in the caller).  timed: times()
+    gives TIMES' writer_busy, the seconds spent in the jobs themselves (the scene-cache route reports it)."""
 
-    def __init__(self, threaded, depth=4):
+    def __init__(self, threaded, depth=4, timed=False):
         import queue
         import threading
-        self.threaded, self.error, self.busy = threaded, None, 0.0          # busy: seconds spent writing
+        self.thread, self.error, self.busy, self.timed = None, None, 0.0, timed
         if threaded:
             self.queue = queue.Queue(maxsize=depth)
             self.thread = threading.Thread(target=self._loop, name='atvs-writer', daemon=True)
@@ -200,25 +200,34 @@ class _Writer(object):
             if job is None:
                 return
             if self.error is None:
-                t0 = time.time()
                 try:
-                    job()
+                    self._run(job)
                 except BaseException as e:       # re-raised in the driver's thread
                     self.error = e
-                self.busy += time.time() - t0
+
+    def _run(self, job):
+        t0 = time.time()
+        try:
+            job()
+        finally:
+            self.busy += time.time() - t0
 
     def __call__(self, job):
         if self.error is not None:
             raise self.error
-        if self.threaded:
+        if self.thread is not None:
             self.queue.put(job)
         else:
-            job()
+            self._run(job)
+
+    def times(self):
+        return {'writer_busy': self.busy} if self.timed else {}
 
     def close(self):
-        if self.threaded:
+        if self.thread is not None:
             self.queue.put(None)
             self.thread.join()
+            self.thread = None
         if self.error is not None:
             raise self.error
 
@@ -269,16 +278,6 @@ class _Pipelines(object):
         out = t if p is None else p.result(t, host=True)
         return [example.check_finite(o.cpu().numpy(), 'a network output') for o in out]
 
-    def __call__(self, images_data, cams_data):
-        self.submit(images_data, cams_data)
-        return self.fetch()
-
-
-# host time of the last scene run_eval_pc processed, seconds summed over its maps: prepare (load_data / load_cams), submit, wait
-# (fetch / result), write (finish's files; with the writer thread: the hand-over); --scene_cache adds upload (the image uploads'
-# share of submit) and gpu_ms (each map's GPU time, SceneInference.gpu_ms) -- tools_dev/scene_rate.py reports them
-TIMES = {}
-
 
 def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
     """finish()'s files of one depth map: PFMs, the 1/4 reference image, the camera text, the viridis PNG."""
@@ -298,6 +297,245 @@ def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
     Image.fromarray(np.ascontiguousarray(image_raw[:, :, ::-1])).save(stem + '.jpg')
     write_cam(stem + '.txt', cams)
     plt.imsave(stem + '.png', disp_up, cmap='viridis')
+
+
+class _PipelineSource(object):
+    """The default route's maps: load_data's host arrays through _Pipelines; finish() hands out host arrays.  A map source is
+    driven by _run_scene: begin_scene(mvs_list), then per map load(i), room(), submit(what load gave) and finish(stage) ->
+    (out_index, the outputs on the host, the reference image, its (2,4,4) camera), end_scene() -> its own TIMES entries, close()."""
+
+    def __init__(self, device, use_graph):
+        self.run, self.queued = _Pipelines(device, use_graph), []          # queued: host data of the maps in flight, in order
+
+    def begin_scene(self, mvs_list):
+        self.mvs_list = mvs_list
+
+    def end_scene(self):
+        return {}
+
+    def room(self):
+        return self.run.room()
+
+    def close(self):
+        pass
+
+    def load(self, i):
+        return load_data(self.mvs_list, i)
+
+    def submit(self, loaded):
+        image_data_raw, images_data, cams_data, _depth, out_index = loaded
+        self.run.submit(images_data, cams_data)
+        self.queued.append((out_index, image_data_raw[0, 0], cams_data[0, 0]))
+
+    def finish(self, stage):
+        out_index, image_raw, cam = self.queued.pop(0)
+        outputs = self.run.fetch()                   # host arrays, under check_finite's range guard
+        if stage is not None:       # now: _write_map's inverse-depth step rewrites the host maps in place
+            stage(out_index, outputs[0], outputs[2], image_raw, cam)
+        return out_index, outputs, image_raw, cam
+
+
+class _SceneSource(object):
+    """--scene_cache's maps: every image prepared and run through the towers once per scene (scene.SceneInference), decoded one
+    map ahead by _Decoder, the cameras from load_cams; finish() stages device tensors on the slot's stream."""
+
+    def __init__(self, device):
+        self.decoder, self.queued = _Decoder(), []          # queued: (ticket, cameras, out_index) of the maps in flight, in order
+        self.run = scene.SceneInference(self.decoder, FLAGS.max_d, slots=_Pipelines.SLOTS, co_resident=_Pipelines.CO_RESIDENT or False,
+                                        device=device, shape=self.decoder.shape)
+
+    def begin_scene(self, mvs_list):
+        self.mvs_list = mvs_list
+        self.run.times['upload'], self.run.gpu_ms = 0.0, []
+
+    def end_scene(self):
+        return {'upload': self.run.times['upload'], 'gpu_ms': list(self.run.gpu_ms)}          # upload: part of `submit`
+
+    def room(self):
+        return self.run.room()
+
+    def close(self):
+        self.decoder.close()
+
+    def load(self, i):
+        views = _view_paths(self.mvs_list[i])
+        if i + 1 < len(self.mvs_list):          # before this map's cameras are read: the decoding overlaps them
+            self.decoder.prefetch([v for v in _view_paths(self.mvs_list[i + 1]) if ('image', v) not in self.run.cache])
+        cams_data, _ = load_cams(self.mvs_list[i], [self.run.shape(v) for v in views])
+        return views, cams_data, int(os.path.splitext(os.path.basename(self.mvs_list[i][0]))[0])
+
+    def submit(self, loaded):
+        views, cams_data, out_index = loaded
+        self.queued.append((self.run.submit(views, cams_data), cams_data[0, 0], out_index))
+
+    def finish(self, stage):
+        ticket, cam, out_index = self.queued.pop(0)
+        if stage is None:
+            # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
+            outputs = [example.check_finite(o.numpy(), 'a network output', flag=False) for o in self.run.result(ticket, host=True)]
+            return out_index, outputs, self.run.reference_image(ticket), cam
+        # the slot's output buffers are overwritten by its next submission: staged from what result() returned (an overflowed
+        # map's fp32 rerun), on the slot's stream, before submit() can reuse the slot; the host copies under that stream too
+        dev_out = self.run.result(ticket)
+        st = self.run.slot_stream(ticket)
+        stage(out_index, dev_out[0], dev_out[2], self.run.reference_image(ticket, host=False), cam, stream=st)
+        with torch.cuda.stream(st):
+            outputs = [example.check_finite(o.cpu().numpy(), 'a network output', flag=False) for o in dev_out]
+            return out_index, outputs, self.run.reference_image(ticket), cam
+
+
+# host time of the last scene run_eval_pc processed, seconds summed over its maps: prepare (load_data / load_cams), submit, wait
+# (fetch / result), write (finish's files; with the writer thread: the hand-over); --scene_cache adds upload (the image uploads'
+# share of submit) and gpu_ms (each map's GPU time, SceneInference.gpu_ms) -- tools_dev/scene_rate.py reports them
+TIMES = {}
+
+
+def _run_scene(source, mvs_list, savepath_current, writer, map_files=True, fuse=None, keep_cams=False, device=None):
+    """The depth maps of one scene from `source` (a _PipelineSource, a _SceneSource), their files through `writer`, which is closed
+    before zz_runtime.txt is written.  fuse: run_eval_pc's; every map is staged in the scene's SceneFusion, made at the first
+    map, and with keep_cams its (2,4,4) camera is kept.  -> (that SceneFusion or None, {out_index: camera}, the wall clock)."""
+    import matplotlib
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    output_folder = os.path.join(savepath_current, 'depths_atvsnet')
+    os.makedirs(output_folder, exist_ok=True)
+    TIMES.clear()                # this scene's maps only
+    TIMES.update(prepare=0.0, submit=0.0, wait=0.0, write=0.0, maps=0)
+    fusion, map_cams = [], {}
+
+    def stage(out_index, depth, prob, image, cam, stream=None):
+        if not fusion:               # made here: the maps' size
+            rows, cols = image.shape[:2]
+            fusion.append(depth_fusion.SceneFusion(len(mvs_list), rows, cols, device, **fuse))
+        fusion[0].add(out_index, depth, prob, image, cam, stream=stream)
+        if keep_cams:
+            map_cams[out_index] = np.array(cam, np.float64)
+
+    def finish():
+        t0 = time.time()
+        out_index, outputs, image_raw, cam = source.finish(stage if fuse is not None else None)
+        t1 = time.time()
+        if map_files:
+            writer(lambda: _write_map(output_folder, out_index, outputs, image_raw, cam, plt))
+        TIMES['wait'] += t1 - t0
+        TIMES['write'] += time.time() - t1
+        TIMES['maps'] += 1
+
+    source.begin_scene(mvs_list)
+    start_time = time.time()
+    # the depth maps of a scene are independent: the next one is submitted before the previous one's results are
+    # fetched and written, so file I/O overlaps the GPU (which still runs one map at a time: _Pipelines.CO_RESIDENT)
+    for current_i in range(len(mvs_list)):
+        t0 = time.time()
+        loaded = source.load(current_i)
+        t1 = time.time()
+        if not source.room():
+            finish()
+        t2 = time.time()
+        source.submit(loaded)
+        TIMES['prepare'] += t1 - t0
+        TIMES['submit'] += time.time() - t2
+    while TIMES['maps'] < len(mvs_list):
+        finish()
+    writer.close()                       # this scene's files are on disk before its runtime is written
+    TIMES.update(writer.times())
+    TIMES.update(source.end_scene())
+    scene_runtime = time.time() - start_time       # wall clock of the scene (the reference sums sess.run times)
+    with open(os.path.join(savepath_current, 'zz_runtime.txt'), "w") as text_file:
+        text_file.write('runtime ' + str(scene_runtime))
+    return (fusion[0] if fusion else None), map_cams, scene_runtime
+
+
+def _write_cloud(scene_fusion, folder):
+    """final3d_model.ply -> its point count.  After every map's result: the slots are idle; the fusion runs on this thread's
+    (ordinary) stream."""
+    t0 = time.time()
+    n_points = scene_fusion.write_ply(os.path.join(folder, 'final3d_model.ply'))
+    TIMES['fuse'] = time.time() - t0
+    return n_points
+
+
+def _score_cloud(points, folder, device, gt_points, register_args, init_cameras):
+    """cloud_eval.json -> the score."""
+    t0 = time.time()
+    score = eval_cloud.evaluate(points, gt_points, device=device, **register_args)
+    if init_cameras is not None:
+        score['init_cameras'] = init_cameras
+    eval_cloud.write_json(os.path.join(folder, 'cloud_eval.json'), score)
+    TIMES['cloud_eval'] = time.time() - t0
+    return score
+
+
+def _score_maps(scene_fusion, map_cams, score, folder, device, gt_points, score_maps):
+    """depth_eval.json.  run() has ordered this stream after every staging; nd[..., 3] is the depth plane the fusion read."""
+    t0 = time.time()
+    order = scene_fusion.order()
+    indices = [scene_fusion.index[k] for k in order]
+    moved = score['registration']['matrix'] if 'registration' in score else None
+    gt_maps = eval_depth.render_scan(gt_points, np.stack([map_cams[i] for i in indices]), scene_fusion.rows, scene_fusion.cols,
+                                     transform=moved, device=device, **score_maps)
+    pred = scene_fusion.nd[:len(indices), :, :, 3][torch.from_numpy(order).to(device)]
+    eval_depth.write_json(os.path.join(folder, 'depth_eval.json'),
+                          eval_depth.report(pred.cpu().numpy(), gt_maps.cpu().numpy(), indices=indices, transform=moved, **score_maps))
+    TIMES['depth_eval'] = time.time() - t0
+
+
+def _clean_cloud(points, colors, score, folder, device, gt_points, clean):
+    """final3d_model_clean.ply and cloud_clean.json, with a score cloud_eval_clean.json -> the cleaned point count."""
+    from ..tools.ply import write_ply
+    t0 = time.time()
+    clean_points, clean_colors, clean_report = clean_cloud.clean(points, colors, device=device, **clean)
+    write_ply(os.path.join(folder, 'final3d_model_clean.ply'), clean_points, clean_colors)
+    clean_cloud.write_json(os.path.join(folder, 'cloud_clean.json'), clean_report)
+    TIMES['cloud_clean'] = time.time() - t0
+    if score is not None:
+        # the same transform: the matrix found for the whole cloud (it includes the initial one), not a second fit
+        moved = {}
+        if 'registration' in score:
+            moved['init_transform'] = score['registration']['matrix']
+        elif 'init_transform' in score:
+            moved['init_transform'] = score['init_transform']
+        clean_score = eval_cloud.evaluate(clean_points, gt_points, device=device, **moved)
+        eval_cloud.write_json(os.path.join(folder, 'cloud_eval_clean.json'), clean_score)
+    return len(clean_points)
+
+
+def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register_args, init_cameras, score_maps, clean):
+    """A fused scene's files, each group by its own step: the PLY, the cloud's score, the maps' score, the cleaned cloud."""
+    n_points = _write_cloud(scene_fusion, folder)
+    points, colors, score = None, None, None
+    if gt_points is not None or clean:
+        points, colors = scene_fusion.run()
+        points = points.copy()
+        points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
+    if gt_points is not None:
+        score = _score_cloud(points, folder, device, gt_points, register_args, init_cameras)
+    if score_maps is not None:
+        _score_maps(scene_fusion, map_cams, score, folder, device, gt_points, score_maps)
+    if clean:
+        n_clean = _clean_cloud(points, colors, score, folder, device, gt_points, clean)
+        print(Notify.INFO, '%s: %d points after cleaning' % (name, n_clean), Notify.ENDC)
+    print(Notify.INFO, '%s: %d fused points' % (name, n_points), Notify.ENDC)
+
+
+def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True, gt_ply=None, register=None,
+                  clean=None, score_maps=None):
+    """What each of run_eval_pc's options needs -> every rule as (broken by these values, message)."""
+    return [
+        (scene_cache and not use_graph, '--scene_cache replays captured graphs: it cannot be combined with --eager (use_graph=False)'),
+        (not map_files and fuse is None, '--no_map_files needs --fuse (map_files=False needs fuse): the run would write nothing'),
+        (bool(gt_ply) and fuse is None, '--gt_ply needs --fuse (gt_ply needs fuse): there is no point cloud to score'),
+        (register is not None and not gt_ply, '--register needs --gt_ply (register needs gt_ply): there is nothing to align to'),
+        (bool(clean) and fuse is None, '--clean_voxel, --clean_sor and --clean_radius_filter need --fuse (clean needs fuse): there is no '
+                                       'point cloud to clean'),
+        (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')]
+
+
+def _check_options(**options):
+    """Raises ValueError with the message of the first of _option_rules that `options` break."""
+    for broken, message in _option_rules(**options):
+        if broken:
+            raise ValueError(message)
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
@@ -322,22 +560,9 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     probability-filtered depth planes -- what enters the cloud -- are scored against it (eval_depth.score_maps) into
     <savepath>/<scene>/depth_eval.json.  With register the ground truth is moved by the inverse of the matrix already found (no
     second fit).  Every other output is what it is without it."""
-    import matplotlib
-    matplotlib.use('Agg')
-    import matplotlib.pyplot as plt
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
-    if scene_cache and not use_graph:
-        raise ValueError('--scene_cache replays captured graphs: it cannot be combined with --eager')
-    if not map_files and fuse is None:
-        raise ValueError('map_files=False (--no_map_files) needs fuse (--fuse): the run would write nothing')
-    if gt_ply and fuse is None:
-        raise ValueError('gt_ply (--gt_ply) needs fuse (--fuse): there is no point cloud to score')
-    if register is not None and not gt_ply:
-        raise ValueError('register (--register) needs gt_ply (--gt_ply): there is nothing to align to')
-    if clean and fuse is None:
-        raise ValueError('clean (--clean_voxel, --clean_sor, --clean_radius_filter) needs fuse (--fuse): there is no point cloud to clean')
-    if score_maps is not None and not gt_ply:
-        raise ValueError('score_maps (--score_maps) needs gt_ply (--gt_ply): there is no scan to render')
+    _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
+                   clean=clean, score_maps=score_maps)
     gt_points, register_args, init_cameras = None, {}, None
     if gt_ply:
         from ..tools.ply import read_ply_points
@@ -353,167 +578,37 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     example._load_weights()
     torch.cuda.set_device(FLAGS.gpu_id)          # every kernel launches on the current device's stream
     device = torch.device('cuda:%d' % FLAGS.gpu_id)
-    if scene_cache:
-        decoder = _Decoder()
-        run = scene.SceneInference(decoder, FLAGS.max_d, slots=_Pipelines.SLOTS, co_resident=_Pipelines.CO_RESIDENT or False,
-                                   device=device, shape=decoder.shape)
-        writer = _Writer(write_thread)
-    else:
-        run = _Pipelines(device, use_graph)
+    source = _SceneSource(device) if scene_cache else _PipelineSource(device, use_graph)
     try:
         for image_info, _fmt in image_infos:
             mvs_list = gen_data_list(image_info[0])
             savepath_current = os.path.join(savepath, image_info[2])
-            output_folder = os.path.join(savepath_current, 'depths_atvsnet')
-            os.makedirs(output_folder, exist_ok=True)
-            scene_runtime = 0.0
-            TIMES.clear()                # this scene's maps only
-            TIMES.update(prepare=0.0, submit=0.0, wait=0.0, write=0.0, maps=0)
-            if scene_cache:
-                run.times['upload'], run.gpu_ms = 0.0, []
-            start_time = time.time()
-            queued = []                  # host-side data of the depth maps in flight, in submission order
-            fusion = []                  # --fuse: this scene's SceneFusion, made at its first map (the maps' size)
-            map_cams = {}                # --score_maps: out_index -> the (2,4,4) camera of its map
-
-            def stage(out_index, depth, prob, image, cams_data, stream=None):
-                if not fusion:
-                    rows, cols = image.shape[:2]
-                    fusion.append(depth_fusion.SceneFusion(len(mvs_list), rows, cols, device, **fuse))
-                fusion[0].add(out_index, depth, prob, image, cams_data[0, 0], stream=stream)
-                if score_maps is not None:
-                    map_cams[out_index] = np.array(cams_data[0, 0], np.float64)
-
-            def finish():
-                t0 = time.time()
-                if scene_cache:
-                    ticket, cams_data, out_index = queued.pop(0)
-                    if fuse is None:
-                        # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
-                        outputs = [example.check_finite(o.numpy(), 'a network output', flag=False)
-                                   for o in run.result(ticket, host=True)]
-                        image_raw = run.reference_image(ticket)
-                    else:
-                        # the slot's output buffers are overwritten by its next submission: staged from what result() returned
-                        # (an overflowed map's fp32 rerun), on the slot's stream, before submit() can reuse the slot
-                        dev_out = run.result(ticket)
-                        st = run.slot_stream(ticket)
-                        stage(out_index, dev_out[0], dev_out[2], run.reference_image(ticket, host=False), cams_data, stream=st)
-                        with torch.cuda.stream(st):
-                            outputs = [example.check_finite(o.cpu().numpy(), 'a network output', flag=False) for o in dev_out]
-                            image_raw = run.reference_image(ticket)
-                else:
-                    image_data_raw, cams_data, out_index = queued.pop(0)
-                    outputs = run.fetch()
-                    image_raw = image_data_raw[0, 0]
-                    if fuse is not None:          # before _write_map's inverse-depth step rewrites the host maps in place
-                        stage(out_index, outputs[0], outputs[2], image_raw, cams_data)
-                t1 = time.time()
-                job = lambda: _write_map(output_folder, out_index, outputs, image_raw, cams_data[0, 0], plt)     # noqa: E731
-                if not map_files:
-                    pass
-                elif scene_cache:
-                    writer(job)
-                else:
-                    job()
-                TIMES['wait'] += t1 - t0
-                TIMES['write'] += time.time() - t1
-                TIMES['maps'] += 1
-
-            def views_of(i):
-                data = mvs_list[i]
-                found = len(data) // 2
-                return [data[2 * (v if v < found else 0)] for v in range(FLAGS.view_num)]
-
-            # the depth maps of a scene are independent: the next one is submitted before the previous one's results are
-            # fetched and written, so file I/O overlaps the GPU (which still runs one map at a time: _Pipelines.CO_RESIDENT)
-            for current_i in range(len(mvs_list)):
-                t0 = time.time()
-                if scene_cache:
-                    views = views_of(current_i)
-                    if current_i + 1 < len(mvs_list):
-                        decoder.prefetch([v for v in views_of(current_i + 1) if ('image', v) not in run.cache])
-                    cams_data, _ = load_cams(mvs_list[current_i], [run.shape(v) for v in views])
-                    out_index = int(os.path.splitext(os.path.basename(mvs_list[current_i][0]))[0])
-                else:
-                    image_data_raw, images_data, cams_data, _depth, out_index = load_data(mvs_list, current_i)
-                t1 = time.time()
-                if not run.room():
-                    finish()
-                t2 = time.time()
-                if scene_cache:
-                    queued.append((run.submit(views, cams_data), cams_data, out_index))
-                else:
-                    run.submit(images_data, cams_data)
-                    queued.append((image_data_raw, cams_data, out_index))
-                TIMES['prepare'] += t1 - t0
-                TIMES['submit'] += time.time() - t2
-            while queued:
-                finish()
-            if scene_cache:
-                writer.close()                       # this scene's files are on disk before its runtime is written
-                TIMES['writer_busy'] = writer.busy if write_thread else TIMES['write']
-                writer = _Writer(write_thread)
-                TIMES['upload'] = run.times['upload']            # part of `submit`
-                TIMES['gpu_ms'] = list(run.gpu_ms)
-            scene_runtime = time.time() - start_time       # wall clock of the scene (the reference sums sess.run times)
-            with open(os.path.join(savepath_current, 'zz_runtime.txt'), "w") as text_file:
-                text_file.write('runtime ' + str(scene_runtime))
-            if fusion:
-                # after every map's result: the slots are idle; the fusion runs on this thread's (ordinary) stream
-                t0 = time.time()
-                scene_fusion = fusion.pop()
-                n_points = scene_fusion.write_ply(os.path.join(savepath_current, 'final3d_model.ply'))
-                TIMES['fuse'] = time.time() - t0
-                points, colors = None, None
-                if gt_points is not None or clean:
-                    points, colors = scene_fusion.run()
-                    points = points.copy()
-                    points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
-                score = None
-                if gt_points is not None:
-                    t0 = time.time()
-                    score = eval_cloud.evaluate(points, gt_points, device=device, **register_args)
-                    if init_cameras is not None:
-                        score['init_cameras'] = init_cameras
-                    eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval.json'), score)
-                    TIMES['cloud_eval'] = time.time() - t0
-                if score_maps is not None:
-                    # run() has ordered this stream after every staging; nd[..., 3] is the depth plane the fusion read
-                    t0 = time.time()
-                    order = scene_fusion.order()
-                    indices = [scene_fusion.index[k] for k in order]
-                    moved = score['registration']['matrix'] if 'registration' in score else None
-                    gt_maps = eval_depth.render_scan(gt_points, np.stack([map_cams[i] for i in indices]), scene_fusion.rows,
-                                                     scene_fusion.cols, transform=moved, device=device, **score_maps)
-                    pred = scene_fusion.nd[:len(indices), :, :, 3][torch.from_numpy(order).to(device)]
-                    eval_depth.write_json(os.path.join(savepath_current, 'depth_eval.json'),
-                                          eval_depth.report(pred.cpu().numpy(), gt_maps.cpu().numpy(), indices=indices,
-                                                            transform=moved, **score_maps))
-                    TIMES['depth_eval'] = time.time() - t0
-                if clean:
-                    from ..tools.ply import write_ply
-                    t0 = time.time()
-                    clean_points, clean_colors, clean_report = clean_cloud.clean(points, colors, device=device, **clean)
-                    write_ply(os.path.join(savepath_current, 'final3d_model_clean.ply'), clean_points, clean_colors)
-                    clean_cloud.write_json(os.path.join(savepath_current, 'cloud_clean.json'), clean_report)
-                    TIMES['cloud_clean'] = time.time() - t0
-                    if score is not None:
-                        # the same transform: the matrix found for the whole cloud (it includes the initial one), not a second fit
-                        moved = {}
-                        if 'registration' in score:
-                            moved['init_transform'] = score['registration']['matrix']
-                        elif 'init_transform' in score:
-                            moved['init_transform'] = score['init_transform']
-                        clean_score = eval_cloud.evaluate(clean_points, gt_points, device=device, **moved)
-                        eval_cloud.write_json(os.path.join(savepath_current, 'cloud_eval_clean.json'), clean_score)
-                    print(Notify.INFO, '%s: %d points after cleaning' % (image_info[2], len(clean_points)), Notify.ENDC)
-                print(Notify.INFO, '%s: %d fused points' % (image_info[2], n_points), Notify.ENDC)
+            writer = _Writer(scene_cache and write_thread, timed=scene_cache)
+            try:
+                scene_fusion, map_cams, scene_runtime = _run_scene(source, mvs_list, savepath_current, writer, map_files, fuse,
+                                                                   score_maps is not None, device)
+            finally:
+                writer.close()
+            if scene_fusion is not None:
+                _end_scene(image_info[2], scene_fusion, map_cams, savepath_current, device, gt_points, register_args, init_cameras,
+                           score_maps, clean)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
-        if scene_cache:
-            writer.close()
-            decoder.close()
+        source.close()
+
+
+def _run_options(flags):
+    """run_eval_pc's keyword arguments from a namespace of cli's options (FLAGS, cli's parsed arguments): one it lacks is off."""
+    opt = lambda name, default=None: getattr(flags, name, default)          # noqa: E731
+    return dict(
+        use_graph=not opt('eager'), scene_cache=opt('scene_cache', False), write_thread=not opt('sync_write'),
+        fuse=dict(prob_threshold=flags.prob_threshold, disp_threshold=flags.disp_threshold, num_consistent=flags.num_consistent)
+        if opt('fuse') else None,
+        map_files=not opt('no_map_files'), gt_ply=opt('gt_ply') or None, clean=opt('clean') or None,
+        register=dict(with_scale=opt('with_scale', False), init_cameras=opt('init_cameras') or None) if opt('register') else None,
+        score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
+                        occlusion_tol=opt('map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
+                        pixel_centre=opt('map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE)) if opt('score_maps') else None)
 
 
 def main(scene_list=None, base_path='eth3d/'):
@@ -526,21 +621,7 @@ def main(scene_list=None, base_path='eth3d/'):
     for scene in scene_list:
         folder = os.path.join(FLAGS.data_root, base_path + scene)
         image_infos.append([[folder, os.path.join(folder, 'images'), scene], 'preprocessed'])
-    fuse = None
-    if getattr(FLAGS, 'fuse', False):
-        fuse = dict(prob_threshold=FLAGS.prob_threshold, disp_threshold=FLAGS.disp_threshold, num_consistent=FLAGS.num_consistent)
-    score_maps = None
-    if getattr(FLAGS, 'score_maps', False):
-        score_maps = dict(splat=getattr(FLAGS, 'map_splat', eval_depth.DEFAULT_SPLAT),
-                          occlusion_tol=getattr(FLAGS, 'map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
-                          pixel_centre=getattr(FLAGS, 'map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE))
-    register = None
-    if getattr(FLAGS, 'register', False):
-        register = dict(with_scale=getattr(FLAGS, 'with_scale', False), init_cameras=getattr(FLAGS, 'init_cameras', None) or None)
-    run_eval_pc(FLAGS.savepath, image_infos, use_graph=not getattr(FLAGS, 'eager', False),
-                scene_cache=getattr(FLAGS, 'scene_cache', False), write_thread=not getattr(FLAGS, 'sync_write', False), fuse=fuse,
-                map_files=not getattr(FLAGS, 'no_map_files', False), gt_ply=getattr(FLAGS, 'gt_ply', None) or None,
-                register=register, clean=getattr(FLAGS, 'clean', None) or None, score_maps=score_maps)
+    run_eval_pc(FLAGS.savepath, image_infos, **_run_options(FLAGS))
 
 
 def cli(argv=None):
@@ -595,18 +676,9 @@ def cli(argv=None):
                         help='--score_maps: image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5 (the plane sweep\'s)')
     clean_cloud.add_options(parser, 'clean_')
     args = parser.parse_args(argv)
-    if args.eager and args.scene_cache:
-        parser.error('--scene_cache replays captured graphs: it cannot be combined with --eager')
-    if args.no_map_files and not args.fuse:
-        parser.error('--no_map_files needs --fuse: the run would write nothing')
-    if args.gt_ply and not args.fuse:
-        parser.error('--gt_ply needs --fuse: there is no point cloud to score')
-    if args.register and not args.gt_ply:
-        parser.error('--register needs --gt_ply: there is nothing to align to')
+    # what only the command line can break; the rest is _option_rules
     if (args.with_scale or args.init_cameras) and not args.register:
         parser.error('--with_scale and --init_cameras need --register')
-    if args.score_maps and not args.gt_ply:
-        parser.error('--score_maps needs --gt_ply: there is no scan to render')
     if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
                                 or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
         parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')
@@ -616,8 +688,10 @@ def cli(argv=None):
         parser.error('--map_occlusion_tol must be >= 0 and finite, --map_pixel_centre finite')
     args.gt_ply = [p for p in args.gt_ply.split(',') if p] if args.gt_ply else None
     args.clean = clean_cloud.options(parser, args, 'clean_') or None
-    if args.clean and not args.fuse:
-        parser.error('--clean_voxel, --clean_sor and --clean_radius_filter need --fuse: there is no point cloud to clean')
+    try:
+        _check_options(**_run_options(args))
+    except ValueError as e:
+        parser.error(str(e))
     scenes = args.scenes.split(',') if args.scenes else None
     _Pipelines.CO_RESIDENT = 'cu_split' if args.maps_in_flight == 'cu_split' else False
     for k, v in vars(args).items():
