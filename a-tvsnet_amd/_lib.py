@@ -104,11 +104,48 @@ def header_abi_version():
     return int(m.group(1))
 
 
+_ARG = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double}
+_RET = {'int': ctypes.c_int, 'long': ctypes.c_long, 'char *': ctypes.c_char_p}
+
+
+def _ctype(text, decl, ret=False):
+    """The ctypes type of one parameter (ret: of the return value) as the header spells it; anything else raises."""
+    words = [w for w in text.replace('*', ' * ').split() if w != 'const']
+    if not ret and len(words) > 1 and words[-1] != '*' and words[-1] not in _ARG:
+        words.pop()                                             # the parameter's name
+    key = ' '.join(words)
+    if ret:
+        t = _RET.get(key)
+    elif '*' in words or key == 'atvs_stream_t':
+        t = ctypes.c_void_p                 # device pointers arrive as integers: int, None, arrays and byref(...) all pass
+    else:
+        t = _ARG.get(key)
+    if t is None:
+        raise RuntimeError('include/atvsnet_hip.h: no ctypes rule for %r in `%s`' % (text.strip(), decl))
+    return t
+
+
+def prototypes(text=None):
+    """{name: (restype, [argtypes])} of every function include/atvsnet_hip.h (or `text`) declares: what `lib()` types the
+    library's symbols with.  A declaration outside the rules of `_ctype`, or an atvs_*( name this cannot read, raises."""
+    if text is None:
+        with open(HEADER) as f:
+            text = f.read()
+    text = re.sub(r'/\*.*?\*/|//[^\n]*|^[ \t]*#.*?$', '', text, flags=re.S | re.M)
+    out = {}
+    for m in re.finditer(r'([A-Za-z_][\w \t\n*]*?)\b(atvs_[a-z0-9_]+)\s*\(([^()]*)\)\s*;', text):
+        decl = ' '.join(m.group(0).split())
+        params = [] if m.group(3).strip() == 'void' else m.group(3).split(',')
+        out[m.group(2)] = (_ctype(m.group(1), decl, ret=True), [_ctype(a, decl) for a in params])
+    unread = set(re.findall(r'\b(atvs_[a-z0-9_]+)\s*\(', text)) - set(out)
+    if unread:
+        raise RuntimeError('include/atvsnet_hip.h: cannot read the declaration of %s' % ', '.join(sorted(unread)))
+    return out
+
+
 def declared_symbols():
     """Every function name declared in include/atvsnet_hip.h."""
-    with open(HEADER) as f:
-        text = re.sub(r'/\*.*?\*/', '', f.read(), flags=re.S)
-    return sorted(set(re.findall(r'\b(atvs_[a-z0-9_]+)\s*\(', text)))
+    return sorted(prototypes())
 
 
 def lib():
@@ -125,27 +162,12 @@ def lib():
         # torch stream would fail.
         import torch  # noqa: F401
         _lib = ctypes.CDLL(LIB_PATH)
-        for name in declared_symbols():
+        for name, (restype, argtypes) in prototypes().items():
             fn = getattr(_lib, name)          # AttributeError if the library lacks a declared symbol
-            fn.restype = ctypes.c_int
+            fn.restype, fn.argtypes = restype, argtypes
         have, want = _lib.atvs_abi_version(), header_abi_version()
         if have != want:          # a stale prebuilt library next to newer sources
             _lib = None
             raise RuntimeError('%s has ABI version %d, include/atvsnet_hip.h declares %d: rebuild it '
                                '(`python -c "import __graft_entry__ as g; g.build()"`)' % (LIB_PATH, have, want))
-        _lib.atvs_target_arch.restype = ctypes.c_char_p
-        _lib.atvs_conv_num_blocks.restype = ctypes.c_long
-        _lib.atvs_channel_stats_num_blocks.restype = ctypes.c_long
-        _lib.atvs_avg_pool_ws_floats.restype = ctypes.c_long
-        _lib.atvs_conv_tiled_num_blocks.restype = ctypes.c_long
-        _lib.atvs_conv_tiled_grid.restype = ctypes.c_long
-        _lib.atvs_conv_xpair_grid.restype = ctypes.c_long
-        _lib.atvs_conv2d_lds_rows.restype = ctypes.c_long
-        _lib.atvs_conv_stem_rows.restype = ctypes.c_long
-        _lib.atvs_conv1x1_rows.restype = ctypes.c_long
-        _lib.atvs_conv1x1_b_rows.restype = ctypes.c_long
-        _lib.atvs_bottleneck_b_rows.restype = ctypes.c_long
-        _lib.atvs_conv3d_s2b_grid.restype = ctypes.c_long
-        _lib.atvs_deconv_up_grid.restype = ctypes.c_long
-        _lib.atvs_conv_c16_grid.restype = ctypes.c_long
     return _lib

@@ -2,12 +2,10 @@
 fusion entry points (after the hot path: per reference camera, and the whole scene with its staging).
 """
 
-import ctypes
-
 import torch
 
 from .. import _lib
-from .base import _ERR, _Timed, _call, _dev_ok, _new, _p, _ptr_array, _stream, cfg
+from .base import _Timed, _call, _dev_ok, _new, _p, _ptr_array, _size, _stream, cfg
 from .packing import _abi_pack, split_on
 
 
@@ -16,8 +14,7 @@ def aanet_combine(srs, xs, out=None):
     (written into `out` when given)."""
     out = _new(xs[0], xs[0].shape) if out is None else out
     if _dev_ok(*(list(srs) + list(xs))):
-        _call('atvs_aanet_combine', _ptr_array(srs), _ptr_array(xs), len(xs), _p(out),
-              ctypes.c_long(out.numel() // 8), _stream())
+        _call('atvs_aanet_combine', _ptr_array(srs), _ptr_array(xs), len(xs), _p(out), out.numel() // 8, _stream())
     return out
 
 
@@ -45,14 +42,14 @@ def aanet_partial(srs, xs, stage, ssum=None, umax=None):
     out = _new(xs[0], ((2,) + V8) if stage == 2 else V8)
     if _dev_ok(*(list(srs) + list(xs))):
         _call('atvs_aanet_partial', _ptr_array(srs), _ptr_array(xs), len(srs), int(stage), _p(ssum), _p(umax), _p(out),
-              ctypes.c_long(xs[0].numel() // 8), _stream())
+              xs[0].numel() // 8, _stream())
     return out
 
 
 def divide(num, den):
     out = _new(num, num.shape)
     if _dev_ok(num, den):
-        _call('atvs_divide', _p(num), _p(den), _p(out), ctypes.c_long(num.numel()), _stream())
+        _call('atvs_divide', _p(num), _p(den), _p(out), num.numel(), _stream())
     return out
 
 
@@ -63,8 +60,8 @@ def fusibile(cams, normals_depths, images, ref, disp_thresh, normal_thresh, num_
     coord, normal, tex = (_new(images, (rows, cols, 4)) for _ in range(3))
     created = _new(images, (rows, cols))
     if _dev_ok(cams, normals_depths, images):
-        _call('atvs_fusibile', _p(cams), _p(normals_depths), _p(images), N, int(ref), rows, cols, ctypes.c_float(disp_thresh),
-              ctypes.c_float(normal_thresh), int(num_consistent), _p(coord), _p(normal), _p(tex), _p(created), _stream())
+        _call('atvs_fusibile', _p(cams), _p(normals_depths), _p(images), N, int(ref), rows, cols, disp_thresh, normal_thresh,
+              int(num_consistent), _p(coord), _p(normal), _p(tex), _p(created), _stream())
     return coord, normal, tex, created
 
 
@@ -105,8 +102,8 @@ def fusion_stage(depth, prob, bgr, inverse_depth, prob_thresh, nd_out, img_out):
     if _fusion_args((depth, 'depth', torch.float32, (rows, cols)), (prob, 'prob', torch.float32, (rows, cols)),
                     (bgr, 'bgr', torch.uint8, (rows, cols, 3)), (nd_out, 'nd_out', torch.float32, (rows, cols, 4)),
                     (img_out, 'img_out', torch.float32, (rows, cols, 4))):
-        _call('atvs_fusion_stage_f32', _p(depth), _p(prob), _p(bgr), rows, cols, int(bool(inverse_depth)),
-              ctypes.c_float(prob_thresh), _p(nd_out), _p(img_out), _stream())
+        _call('atvs_fusion_stage_f32', _p(depth), _p(prob), _p(bgr), rows, cols, int(bool(inverse_depth)), prob_thresh,
+              _p(nd_out), _p(img_out), _stream())
     return nd_out, img_out
 
 
@@ -121,20 +118,13 @@ def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num
     if not _fusion_args((cams, 'cams', torch.float32, (N, 28)), (normals_depths, 'normals_depths', torch.float32, (N, rows, cols, 4)),
                         (images, 'images', torch.float32, (N, rows, cols, 4))):
         raise RuntimeError('fusibile_scene: the number of points is only known after a launch (got meta tensors)')
-    lib = _lib.lib()
-    nbytes = ctypes.c_long(0)
-    rc = lib.atvs_fusibile_scene_scratch_size(N, rows, cols, ctypes.byref(nbytes))
-    if rc != 0:
-        raise RuntimeError('atvs_fusibile_scene_scratch_size failed: %s (%d) for %d maps of %dx%d' % (_ERR.get(rc, 'unknown'), rc, N,
-                                                                                                      cols, rows))
     dev = normals_depths.device
     capacity = N * rows * cols
-    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_size('atvs_fusibile_scene_scratch_size', N, rows, cols), dtype=torch.uint8, device=dev)
     points = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
     colors = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    _call('atvs_fusibile_scene', _p(cams), _p(normals_depths), _p(images), N, rows, cols, ctypes.c_float(disp_thresh),
-          ctypes.c_float(normal_thresh), int(num_consistent), _p(scratch), ctypes.c_long(scratch.numel()), _p(points), _p(colors),
-          ctypes.c_long(capacity), _p(count), _stream())
+    _call('atvs_fusibile_scene', _p(cams), _p(normals_depths), _p(images), N, rows, cols, disp_thresh, normal_thresh,
+          int(num_consistent), _p(scratch), scratch.numel(), _p(points), _p(colors), capacity, _p(count), _stream())
     m = int(count.item())
     return points[:m], colors[:m]

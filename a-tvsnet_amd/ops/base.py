@@ -138,12 +138,13 @@ def _dev_ok(*ts):
     return not meta
 
 
+# Argument types come from the header (`_lib.prototypes`): callers pass Python numbers, device addresses as int and None for NULL.
 def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
+    return t.data_ptr() if t is not None else None
 
 
 def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    return torch.cuda.current_stream().cuda_stream
 
 
 _side_pool = {}
@@ -161,6 +162,15 @@ def _call(name, *args):
     rc = getattr(_lib.lib(), name)(*args)
     if rc != 0:
         raise RuntimeError('%s failed: %s (%d)' % (name, _ERR.get(rc, 'unknown'), rc))
+
+
+def _size(name, *args):
+    """The value a `*_size` query writes through its trailing `long*`."""
+    n = ctypes.c_long(0)
+    rc = getattr(_lib.lib(), name)(*args, ctypes.byref(n))
+    if rc != 0:
+        raise RuntimeError('%s failed: %s (%d) for %s' % (name, _ERR.get(rc, 'unknown'), rc, args))
+    return n.value
 
 
 def _new(ref, shape):
@@ -239,7 +249,4 @@ def watch(tag):
 
 
 def _ptr_array(ts):
-    arr = (ctypes.c_void_p * len(ts))()
-    for i, t in enumerate(ts):
-        arr[i] = t.data_ptr()
-    return arr
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])

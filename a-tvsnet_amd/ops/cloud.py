@@ -24,8 +24,7 @@ import math
 import numpy as np
 import torch
 
-from .. import _lib
-from .base import _ERR, _call, _p, _stream
+from .base import _call, _p, _size, _stream
 
 CLOUD_MAX_POINTS = 1 << 30
 CLOUD_MAX_TOLERANCES = 16
@@ -61,14 +60,6 @@ def _radius(radius):
     return r
 
 
-def _size(name, *args):
-    nbytes = ctypes.c_long(0)
-    rc = getattr(_lib.lib(), name)(*(ctypes.c_long(int(a)) for a in args), ctypes.byref(nbytes))
-    if rc != 0:
-        raise RuntimeError('%s failed: %s (%d) for %s' % (name, _ERR.get(rc, 'unknown'), rc, args))
-    return int(nbytes.value)
-
-
 class CloudGrid(object):
     """A reference cloud sorted into a uniform grid (atvs_cloud_grid_build).  Owns its device buffer; reusable for any number of
     cloud_nearest calls.  n: reference points, radius: the float32 search radius (as a Python float), nbytes: the buffer's size."""
@@ -88,7 +79,7 @@ def cloud_grid(points, radius):
     _cloud_arg(points, 'points', torch.float32, (3,))
     n = int(points.shape[0])
     buf = torch.empty(_size('atvs_cloud_grid_scratch_size', n), dtype=torch.uint8, device=points.device)
-    _call('atvs_cloud_grid_build', _p(points), ctypes.c_long(n), ctypes.c_float(r), _p(buf), ctypes.c_long(buf.numel()), _stream())
+    _call('atvs_cloud_grid_build', _p(points), n, r, _p(buf), buf.numel(), _stream())
     return CloudGrid(buf, n, r)
 
 
@@ -107,8 +98,8 @@ def cloud_nearest(grid, queries):
     if m == 0:
         return d2, idx
     scratch = torch.empty(_size('atvs_cloud_nearest_scratch_size', grid.n, m), dtype=torch.uint8, device=queries.device)
-    _call('atvs_cloud_nearest', _p(grid.buf), ctypes.c_long(grid.buf.numel()), ctypes.c_long(grid.n), _p(queries), ctypes.c_long(m),
-          _p(scratch), ctypes.c_long(scratch.numel()), _p(d2), _p(idx), _stream())
+    _call('atvs_cloud_nearest', _p(grid.buf), grid.buf.numel(), grid.n, _p(queries), m,
+          _p(scratch), scratch.numel(), _p(d2), _p(idx), _stream())
     return d2, idx
 
 
@@ -126,7 +117,7 @@ def cloud_counts(d2, tolerances, radius=None):
     _cloud_arg(d2, 'd2', torch.float32, ())
     counts = torch.empty(CLOUD_MAX_TOLERANCES, dtype=torch.int64, device=d2.device)
     arr = (ctypes.c_double * len(tol))(*tol)
-    _call('atvs_cloud_counts', _p(d2), ctypes.c_long(int(d2.shape[0])), arr, len(tol), ctypes.c_float(r), _p(counts), _stream())
+    _call('atvs_cloud_counts', _p(d2), int(d2.shape[0]), arr, len(tol), r, _p(counts), _stream())
     return counts[:len(tol)]
 
 
@@ -152,7 +143,7 @@ def cloud_transform(points, matrix, out=None):
         if out.shape != points.shape or out.device != points.device:
             raise ValueError('out: expected %s on %s, got %s on %s' % (tuple(points.shape), points.device, tuple(out.shape), out.device))
     arr = (ctypes.c_double * 12)(*T[:3].reshape(-1).tolist())
-    _call('atvs_cloud_transform', _p(points), ctypes.c_long(int(points.shape[0])), arr, _p(out), _stream())
+    _call('atvs_cloud_transform', _p(points), int(points.shape[0]), arr, _p(out), _stream())
     return out
 
 
@@ -179,8 +170,8 @@ def cloud_pair_moments(src, dst, idx, d2, trim=float('inf'), pivot_src=None, piv
             raise RuntimeError('%s on %s, src on %s' % (name, t.device, src.device))
     out = torch.empty(19, dtype=torch.int64, device=src.device)
     scratch = torch.empty(_size('atvs_cloud_pair_moments_scratch_size', m), dtype=torch.uint8, device=src.device)
-    _call('atvs_cloud_pair_moments', _p(src), _p(dst), ctypes.c_long(n), _p(idx), _p(d2), ctypes.c_long(m), ctypes.c_double(trim),
-          ps, pd, _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    _call('atvs_cloud_pair_moments', _p(src), _p(dst), n, _p(idx), _p(d2), m, trim, ps, pd,
+          _p(scratch), scratch.numel(), _p(out), _stream())
     words = out.cpu().numpy()
     return int(words[0]), words[1:].view(np.float64).copy()
 
@@ -205,8 +196,8 @@ def cloud_voxel_downsample(points, voxel, origin=None):
     first = torch.empty(n, dtype=torch.int32, device=points.device)
     count = torch.empty(1, dtype=torch.int64, device=points.device)
     scratch = torch.empty(_size('atvs_cloud_voxel_downsample_scratch_size', n), dtype=torch.uint8, device=points.device)
-    _call('atvs_cloud_voxel_downsample', _p(points), ctypes.c_long(n), ctypes.c_double(voxel), org, _p(scratch),
-          ctypes.c_long(scratch.numel()), _p(means), _p(count), _p(first), _stream())
+    _call('atvs_cloud_voxel_downsample', _p(points), n, voxel, org, _p(scratch), scratch.numel(),
+          _p(means), _p(count), _p(first), _stream())
     k = int(count.item())
     if k < 0:
         lo, hi = cloud_bounds(points)
@@ -225,7 +216,7 @@ def cloud_bounds(points):
     origin of cloud_voxel_downsample, the pivots and the box corners of register_cloud.register."""
     _cloud_arg(points, 'points', torch.float32, (3,))
     out = torch.empty(8, dtype=torch.int32, device=points.device)
-    _call('atvs_cloud_bounds', _p(points), ctypes.c_long(int(points.shape[0])), _p(out), _stream())
+    _call('atvs_cloud_bounds', _p(points), int(points.shape[0]), _p(out), _stream())
     words = out.cpu().numpy()
     if not words[6]:
         return None, None
@@ -266,9 +257,8 @@ def cloud_knn(grid, queries, k, exclude_same_index=False):
     if m == 0:
         return d2, idx
     scratch = torch.empty(_size('atvs_cloud_knn_scratch_size', grid.n, m), dtype=torch.uint8, device=queries.device)
-    _call('atvs_cloud_knn', _p(grid.buf), ctypes.c_long(grid.buf.numel()), ctypes.c_long(grid.n), _p(queries), ctypes.c_long(m),
-          ctypes.c_int(k), ctypes.c_int(1 if exclude_same_index else 0), _p(scratch), ctypes.c_long(scratch.numel()), _p(d2), _p(idx),
-          _stream())
+    _call('atvs_cloud_knn', _p(grid.buf), grid.buf.numel(), grid.n, _p(queries), m, k, 1 if exclude_same_index else 0,
+          _p(scratch), scratch.numel(), _p(d2), _p(idx), _stream())
     return d2, idx
 
 
@@ -280,9 +270,8 @@ def cloud_radius_count(grid, queries, exclude_same_index=False):
     if m == 0:
         return count
     scratch = torch.empty(_size('atvs_cloud_knn_scratch_size', grid.n, m), dtype=torch.uint8, device=queries.device)
-    _call('atvs_cloud_radius_count', _p(grid.buf), ctypes.c_long(grid.buf.numel()), ctypes.c_long(grid.n), _p(queries),
-          ctypes.c_long(m), ctypes.c_int(1 if exclude_same_index else 0), _p(scratch), ctypes.c_long(scratch.numel()), _p(count),
-          _stream())
+    _call('atvs_cloud_radius_count', _p(grid.buf), grid.buf.numel(), grid.n, _p(queries), m, 1 if exclude_same_index else 0,
+          _p(scratch), scratch.numel(), _p(count), _stream())
     return count
 
 
@@ -298,7 +287,7 @@ def cloud_knn_mean(d2):
     m = int(d2.shape[0])
     s = torch.empty(m, dtype=torch.float64, device=d2.device)
     if m:
-        _call('atvs_cloud_knn_mean', _p(d2), ctypes.c_long(m), ctypes.c_int(k), _p(s), _stream())
+        _call('atvs_cloud_knn_mean', _p(d2), m, k, _p(s), _stream())
     return s
 
 
@@ -310,7 +299,7 @@ def cloud_sor_stats(s):
     m = int(s.shape[0])
     out = torch.empty(3, dtype=torch.int64, device=s.device)
     scratch = torch.empty(_size('atvs_cloud_sor_stats_scratch_size', m), dtype=torch.uint8, device=s.device)
-    _call('atvs_cloud_sor_stats', _p(s), ctypes.c_long(m), _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    _call('atvs_cloud_sor_stats', _p(s), m, _p(scratch), scratch.numel(), _p(out), _stream())
     words = out.cpu().numpy()
     mean, std = words[1:].view(np.float64).tolist()
     return int(words[0]), mean, std
@@ -342,12 +331,9 @@ def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_t
     if n_cams * rows * cols >= 1 << 31:
         raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n_cams, rows, cols))
     depth = torch.empty((n_cams, rows, cols), dtype=torch.float32, device=points.device)
-    nbytes = ctypes.c_long(0)
-    _call('atvs_scan_render_scratch_size', ctypes.c_int(n_cams), ctypes.c_int(rows), ctypes.c_int(cols), ctypes.byref(nbytes))
-    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=points.device)
-    _call('atvs_scan_render', _p(points), ctypes.c_long(n), _p(cams), ctypes.c_int(n_cams), ctypes.c_int(rows), ctypes.c_int(cols),
-          ctypes.c_double(centre), ctypes.c_int(int(splat)), ctypes.c_double(tol), _p(scratch), ctypes.c_long(scratch.numel()),
-          _p(depth), _stream())
+    scratch = torch.empty(_size('atvs_scan_render_scratch_size', n_cams, rows, cols), dtype=torch.uint8, device=points.device)
+    _call('atvs_scan_render', _p(points), n, _p(cams), n_cams, rows, cols, centre, int(splat), tol,
+          _p(scratch), scratch.numel(), _p(depth), _stream())
     return depth
 
 
@@ -383,8 +369,8 @@ def cloud_scan_excess(points, cams, maps, pixel_centre=0.5, window=1):
     excess = torch.empty(m, dtype=torch.float32, device=points.device)
     scanner = torch.empty(m, dtype=torch.int32, device=points.device)
     if m:
-        _call('atvs_cloud_scan_excess', _p(points), ctypes.c_long(m), _p(cams), _p(maps), ctypes.c_int(n_cams // 6), ctypes.c_int(size),
-              ctypes.c_double(centre), ctypes.c_int(int(window)), _p(excess), _p(scanner), _stream())
+        _call('atvs_cloud_scan_excess', _p(points), m, _p(cams), _p(maps), n_cams // 6, size, centre, int(window),
+              _p(excess), _p(scanner), _stream())
     return excess, scanner
 
 
@@ -426,8 +412,8 @@ def cloud_voxel_shares(points, d2, excess, voxel, origin, tolerances, margin=0.0
     out = torch.empty((len(tol), 4), dtype=torch.int64, device=points.device)
     scratch = torch.empty(_size('atvs_cloud_voxel_shares_scratch_size', n), dtype=torch.uint8, device=points.device)
     arr = (ctypes.c_double * len(tol))(*tol)
-    _call('atvs_cloud_voxel_shares', _p(points), _p(d2), _p(excess), ctypes.c_long(n), ctypes.c_double(voxel), org, arr, len(tol),
-          ctypes.c_double(margin), _p(scratch), ctypes.c_long(scratch.numel()), _p(out), _stream())
+    _call('atvs_cloud_voxel_shares', _p(points), _p(d2), _p(excess), n, voxel, org, arr, len(tol), margin,
+          _p(scratch), scratch.numel(), _p(out), _stream())
     if int(out[0, 0].item()) < 0:
         lo, hi = cloud_bounds(points)
         o = np.array(list(org))

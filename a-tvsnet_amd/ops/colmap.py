@@ -8,8 +8,7 @@ import ctypes
 
 import torch
 
-from .. import _lib
-from .base import _ERR, _call, _p, _stream
+from .base import _call, _p, _size, _stream
 
 COVIS_MAX_IMAGES = 16384            # atvs_colmap_covisibility: an (images x images) int32 matrix of at most 1 GiB
 # atvs_undistort_map: COLMAP's camera model ids of the models it undistorts, and their parameter counts
@@ -43,16 +42,12 @@ def colmap_depth_range(points, cams, percentile):
     if not 0.0 < float(percentile) < 1.0:
         raise ValueError('percentile must lie in (0, 1), got %r' % percentile)
     n_images, dev = int(cams.shape[0]), cams.device
-    nbytes = ctypes.c_long(0)
-    rc = _lib.lib().atvs_colmap_depth_range_scratch_size(n_images, ctypes.byref(nbytes))
-    if rc != 0:
-        raise RuntimeError('atvs_colmap_depth_range_scratch_size failed: %s (%d) for %d images' % (_ERR.get(rc, 'unknown'), rc, n_images))
-    scratch = torch.empty(int(nbytes.value), dtype=torch.uint8, device=dev)
+    scratch = torch.empty(_size('atvs_colmap_depth_range_scratch_size', n_images), dtype=torch.uint8, device=dev)
     n = torch.empty(n_images, dtype=torch.int32, device=dev)
     d_lo = torch.empty(n_images, dtype=torch.float64, device=dev)
     d_hi = torch.empty(n_images, dtype=torch.float64, device=dev)
-    _call('atvs_colmap_depth_range', _p(points), ctypes.c_long(int(points.shape[0])), _p(cams), n_images,
-          ctypes.c_double(float(percentile)), _p(scratch), ctypes.c_long(scratch.numel()), _p(n), _p(d_lo), _p(d_hi), _stream())
+    _call('atvs_colmap_depth_range', _p(points), int(points.shape[0]), _p(cams), n_images,
+          float(percentile), _p(scratch), scratch.numel(), _p(n), _p(d_lo), _p(d_hi), _stream())
     return n, d_lo, d_hi
 
 

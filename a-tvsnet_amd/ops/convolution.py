@@ -2,8 +2,6 @@
 (`SplitVolume`), sibling launches, the refinement stems, the stride-2 transposed convolution.
 """
 
-import ctypes
-
 import torch
 
 from .. import _lib
@@ -354,7 +352,7 @@ def refine_stems(photo_raw, geo_var, geo_plane_bias, prob, hull, key, w_geo, w_p
         with _Timed(key, (D, H, W, 4), 24, B):
             _call('atvs_refine_stems_f32', _p(photo_raw if planar_out is None else None), _p(geo_var), _p(geo_plane_bias),
                   _p(prob), _p(hull), _p(pk.wp), _p(buf), _p(sbuf), B, D, H, W,
-                  ctypes.c_long(planar_stride(D, H, W) if planar_out is not None else 0), _stream())
+                  planar_stride(D, H, W) if planar_out is not None else 0, _stream())
     return buf, st
 
 

@@ -2,8 +2,6 @@
 (reference atvsnet/homography_warping.py, model.py:13-129,157-200,270-336).
 """
 
-import ctypes
-
 from .. import _lib
 from .base import _Timed, _call, _dev_ok, _new, _p, _ptr_array, _stream
 from .packing import planar_stride
@@ -53,7 +51,7 @@ def warp_planes(src, homographies, out=None, ld_out=None, c_off=0, mode=0, ref=N
         with _Timed(('warp', int(mode)), (D, h, w, C), width):
             _call('atvs_warp_planes', _p(src), _p(homographies), _p(ref), _p(depth_start), _p(depth_interval),
                   _p(out), _p(mask), D, h, w, C, int(ld_out), int(c_off), int(mode), int(rep),
-                  ctypes.c_long(planar_stride(D, h, w) if planar else 0), int(bool(pieces)), _stream())
+                  planar_stride(D, h, w) if planar else 0, int(bool(pieces)), _stream())
     return (out, mask) if want_mask else out
 
 
@@ -145,7 +143,7 @@ def interpolate(src, x, y, method='bilinear', want_mask=False):
     out = _new(src, (n, C))
     mask = _new(src, (n,)) if want_mask else None
     if _dev_ok(src, x, y):
-        _call('atvs_interpolate', _p(src), _p(x), _p(y), _p(out), _p(mask), ctypes.c_long(n), h, w, C,
+        _call('atvs_interpolate', _p(src), _p(x), _p(y), _p(out), _p(mask), n, h, w, C,
               1 if method == 'nearest' else 0, _stream())
     return (out, mask) if want_mask else out
 

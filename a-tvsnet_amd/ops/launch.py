@@ -216,12 +216,11 @@ def conv1x1(x, key, w_host, bias=None, residual=None, relu=False, want_stats=Fal
     y = _new(x, tuple(x.shape[:-1]) + (pk.cout,)) if out is None else out
     st, sbuf = None, None
     if want_stats:
-        st, sbuf = _stats(x, getattr(lib, 'atvs_conv1x1%s_rows' % kind)(ctypes.c_long(pixels)), pk.cout, pixels, G)
+        st, sbuf = _stats(x, getattr(lib, 'atvs_conv1x1%s_rows' % kind)(pixels), pk.cout, pixels, G)
     if _dev_ok(x, y, bias, residual, in_params):
         with _Timed(pk.key, (1, 1, pixels, cin), pk.cout, G):
             _call('atvs_conv1x1%s_f32' % kind, _p(x), _p(pk.wp), _p(bias), _p(residual), _p(in_params), int(bool(in_relu)),
-                  _p(y), _p(sbuf), G,
-                  ctypes.c_long(pixels), cin, pk.cout, int(y.shape[-1]), int(y_coff), int(bool(relu)), _stream())
+                  _p(y), _p(sbuf), G, pixels, cin, pk.cout, int(y.shape[-1]), int(y_coff), int(bool(relu)), _stream())
     return (y, st) if want_stats else y
 
 
@@ -303,16 +302,16 @@ def conv_xp_launch(x5, pk, y, y_coff, bias=None, relu=False, stats_buf=None, pla
         raise ValueError('conv_xp: a strided output / a prologue over a chunk-planar input belong to the split-fp16 kernel')
     if _dev_ok(x5, y, bias, plane_bias, y2, pb2, x2, ipa, ipb):
         with _Timed(pk.key, (D, H, W, Cin), pk.cout + (16 if pk2 is not None else 0), G):
-            yp = ctypes.c_void_p(y.data_ptr() + 4 * int(y_off))     # y_off: floats into a chunk-planar buffer (with ldy / y_gstride)
+            yp = y.data_ptr() + 4 * int(y_off)    # y_off: floats into a chunk-planar buffer (with ldy / y_gstride)
             args = [_p(x5), _p(pk.wp), _p(bias), _p(plane_bias), yp, _p(stats_buf), G, D, H, W, Cin,
                     ldy, int(y_coff), int(bool(relu)), _p(pk2.wp if pk2 is not None else None), _p(pb2), _p(y2),
                     _p(sbuf2), int(y2.shape[-1]) if y2 is not None else 0, int(y_coff2), _p(x2), _p(ipa), _p(ipb),
                     int(bool(relu_a)), int(bool(relu_b))]
             if kind == 'xb':
-                _call('atvs_conv_xb_f32', *(args + [ctypes.c_long(planar_stride(D, H, W) if planar else 0),
-                                                    ctypes.c_long(int(y_gstride)), int(bool(pieces)), _stream()]))
+                _call('atvs_conv_xb_f32', *(args + [planar_stride(D, H, W) if planar else 0, int(y_gstride), int(bool(pieces)),
+                                                    _stream()]))
             else:
-                _call('atvs_conv_xw_f32', *(args + [ctypes.c_long(planar_stride(D, H, W) if planar else 0), _stream()]))
+                _call('atvs_conv_xw_f32', *(args + [planar_stride(D, H, W) if planar else 0, _stream()]))
 
 
 def xp_blocks(D, H, W, groups=1):
@@ -368,12 +367,8 @@ def conv_tiled_launch(x5, pk, y, out_stride, out_off, y_coff, tile_y, bias=None,
                   Cin, Dy, Hy, Wy, int(out_stride), int(out_off[0]), int(out_off[1]), int(out_off[2]), ldy, int(y_coff),
                   8 if xpair else pk.cout, pk.ntaps, int(tile_y), int(bool(relu)), int(class_cout), int(class_base),
                   int(bool(xpair)),
-                  ctypes.c_void_p(fin.counter.data_ptr()) if fin is not None else ctypes.c_void_p(0),
-                  _p(fin.params) if fin is not None else ctypes.c_void_p(0),
-                  ctypes.c_void_p(fin.stats.data_ptr()) if fin is not None else ctypes.c_void_p(0),
-                  fin.rows if fin is not None else 0, fin.arrivals if fin is not None else 0,
-                  fin.channels if fin is not None else 0, fin.fold if fin is not None else 0,
-                  ctypes.c_long(fin.count if fin is not None else 0), ctypes.c_float(1e-3), _stream())
+                  *((_p(fin.counter), _p(fin.params), _p(fin.stats), fin.rows, fin.arrivals, fin.channels, fin.fold, fin.count)
+                    if fin is not None else (None, None, None, 0, 0, 0, 0, 0)), 1e-3, _stream())
 
 
 def tiled_blocks(D, H, W, tile_y, cin, cout, xpair=False, groups=1):

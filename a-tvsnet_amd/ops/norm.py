@@ -2,12 +2,10 @@
 convolution that normalises on load is never normalised on its own (`PendingBN`, `PendingSum`, `LazySlice`).
 """
 
-import ctypes
-
 import torch
 
 from .. import _lib
-from .base import _call, _dev_ok, _new, _p, _stats, _stream, cfg
+from .base import _call, _dev_ok, _new, _p, _ptr_array, _stats, _stream, cfg
 from .packing import _xkind, planar_view
 
 
@@ -16,10 +14,10 @@ def channel_stats(x, groups=None):
     C = x.shape[-1]
     G = 1 if groups is None else int(groups)
     rows = x.numel() // C // G
-    blocks = int(_lib.lib().atvs_channel_stats_num_blocks(ctypes.c_long(rows)))
+    blocks = int(_lib.lib().atvs_channel_stats_num_blocks(rows))
     st, sbuf = _stats(x, blocks, C, rows, G)
     if _dev_ok(x):
-        _call('atvs_channel_stats', _p(x), G, ctypes.c_long(rows), C, _p(sbuf), _stream())
+        _call('atvs_channel_stats', _p(x), G, rows, C, _p(sbuf), _stream())
     return st
 
 
@@ -53,9 +51,8 @@ def bn_params(st, C, ref, beta=None, eps=1e-3):
     G = st.groups
     params = _new(ref, (3, C) if G == 1 else (G, 3, C))
     if _dev_ok(ref, beta):
-        _call('atvs_bn_finalize', ctypes.c_void_p(st.partial.data_ptr()), int(G), ctypes.c_long(st.blocks), st.cpad,
-              int(st.fold), ctypes.c_long(st.count), _p(beta), ctypes.c_float(eps), _p(params), C,
-              ctypes.c_void_p(nonfinite_flag(ref.device).data_ptr()), _stream())
+        _call('atvs_bn_finalize', _p(st.partial), int(G), st.blocks, st.cpad, int(st.fold), st.count, _p(beta), eps,
+              _p(params), C, _p(nonfinite_flag(ref.device)), _stream())
     return params
 
 
@@ -71,7 +68,7 @@ def bn_apply(x, params, relu=False, out=None, C=None, c_off=0):
     y = x if out is None else out
     G = _param_groups(params)
     if _dev_ok(x, params, y):
-        _call('atvs_bn_apply', _p(x), _p(params), _p(y), G, ctypes.c_long(x.numel() // ld // G), int(C), int(ld),
+        _call('atvs_bn_apply', _p(x), _p(params), _p(y), G, x.numel() // ld // G, int(C), int(ld),
               int(c_off), int(bool(relu)), _stream())
     return y
 
@@ -281,11 +278,11 @@ def bn_add(items, plus=None, keep_sum=True):
         out = None if out2 is out else out
         if _dev_ok(*(xs + [p for p in ps if p is not None] + [plus])):
             _call('atvs_bn_add_plus', _p(xs[0]), _p(ps[0]), _p(xs[1]), _p(ps[1]), _p(x2), _p(p2), _p(out), _p(plus), _p(out2), G,
-                  ctypes.c_long(out2.numel() // C // G), C, int(mask), _stream())
+                  out2.numel() // C // G, C, int(mask), _stream())
         return out, out2
     if _dev_ok(*(xs + [p for p in ps if p is not None])):
         _call('atvs_bn_add', _p(xs[0]), _p(ps[0]), _p(xs[1]), _p(ps[1]), _p(x2), _p(p2), _p(out), G,
-              ctypes.c_long(out.numel() // C // G), C, int(mask), _stream())
+              out.numel() // C // G, C, int(mask), _stream())
     return out
 
 
@@ -300,7 +297,7 @@ def add_n(tensors, out=None):
         step = 2 if c is not None else 1
         dst = out if (out is not None and i + step >= len(tensors)) else _new(acc, acc.shape)
         if _dev_ok(acc, b, c, dst):
-            _call('atvs_add_n', _p(acc), _p(b), _p(c), _p(dst), ctypes.c_long(acc.numel()), _stream())
+            _call('atvs_add_n', _p(acc), _p(b), _p(c), _p(dst), acc.numel(), _stream())
         acc = dst
         i += step
         first = False
@@ -335,7 +332,7 @@ def resize_bilinear(x, size, out=None, c_off=0, groups=None):
 def copy_channels(src, dst, C, src_off=0, dst_off=0):
     rows = src.numel() // src.shape[-1]
     if _dev_ok(src, dst):
-        _call('atvs_copy_channels', _p(src), _p(dst), ctypes.c_long(rows), int(C), src.shape[-1], int(src_off),
+        _call('atvs_copy_channels', _p(src), _p(dst), rows, int(C), src.shape[-1], int(src_off),
               dst.shape[-1], int(dst_off), _stream())
     return dst
 
@@ -353,8 +350,7 @@ def stack(tensors, dim=0):
             copy_channels(t.reshape(1, -1), out.reshape(len(tensors), -1)[i:i + 1], n)
         return out
     if _dev_ok(out, *tensors):
-        arr = (ctypes.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors])
-        _call('atvs_stack', arr, len(tensors), ctypes.c_long(n), _p(out), _stream())
+        _call('atvs_stack', _ptr_array(tensors), len(tensors), n, _p(out), _stream())
     return out
 
 

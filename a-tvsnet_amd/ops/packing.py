@@ -8,7 +8,7 @@ import os
 import torch
 
 from .. import _lib
-from .base import cfg
+from .base import _size, cfg
 
 
 def same_pad(in_size, k, s, d=1):
@@ -70,19 +70,13 @@ def _abi_pack(tag, key, w_host, device, entry, size_args, pieces=False, **fields
     if entry is None:
         packed = ws[0]
     else:
-        L = _lib.lib()
         n = size_args
         if isinstance(size_args, tuple):
-            pf = ctypes.c_long()
-            rc = getattr(L, 'atvs_%s_size' % entry)(*(size_args + (ctypes.byref(pf),)))
-            if rc:
-                raise RuntimeError('atvs_%s_size failed (%d) for %s' % (entry, rc, size_args))
-            n = pf.value
+            n = _size('atvs_%s_size' % entry, *size_args)
         else:
             size_args = ()
         packed = np.empty(n, np.uint8 if pieces else np.float32)
-        rc = getattr(L, 'atvs_' + entry)(*([w.ctypes.data_as(ctypes.c_void_p) for w in ws] + list(size_args)
-                                           + [packed.ctypes.data_as(ctypes.c_void_p)]))
+        rc = getattr(_lib.lib(), 'atvs_' + entry)(*([w.ctypes.data for w in ws] + list(size_args) + [packed.ctypes.data]))
         if rc:
             raise RuntimeError('atvs_%s failed (%d)' % (entry, rc))
     pk = _Packed(key=key, **fields)
@@ -112,9 +106,8 @@ def pack_conv_weights(key, w_host, taps, transposed, device):
     packed = np.empty(pf.value, np.float32)
     table = np.empty(ti.value, np.int32)
     tp = np.ascontiguousarray(np.array(taps, dtype=np.int32).reshape(-1, 4))
-    rc = L.atvs_conv_pack(w.ctypes.data_as(ctypes.c_void_p), int(bool(transposed)), tp.ctypes.data_as(ctypes.c_void_p),
-                          ntaps, cin, cout, packed.ctypes.data_as(ctypes.c_void_p),
-                          table.ctypes.data_as(ctypes.c_void_p))
+    rc = L.atvs_conv_pack(w.ctypes.data, int(bool(transposed)), tp.ctypes.data, ntaps, cin, cout, packed.ctypes.data,
+                          table.ctypes.data)
     if rc:
         raise RuntimeError('atvs_conv_pack failed (%d)' % rc)
     pk = _Packed(key=key, ntaps=ntaps, vec=vec.value, ksteps=ks.value, ntiles=nt.value, cin=cin, cout=cout)
@@ -141,9 +134,8 @@ def pack_conv_weights_tiled(key, w_host, taps, transposed, device, tile_y, xpair
     packed = np.empty(pf.value, np.float32)
     table = np.empty(ti.value, np.int32)
     tp = np.ascontiguousarray(np.array(taps, dtype=np.int32).reshape(-1, 4))
-    rc = L.atvs_conv_tiled_pack(w.ctypes.data_as(ctypes.c_void_p), int(bool(transposed)),
-                                tp.ctypes.data_as(ctypes.c_void_p), ntaps, cin, cout, int(tile_y), int(bool(xpair)),
-                                packed.ctypes.data_as(ctypes.c_void_p), table.ctypes.data_as(ctypes.c_void_p))
+    rc = L.atvs_conv_tiled_pack(w.ctypes.data, int(bool(transposed)), tp.ctypes.data, ntaps, cin, cout, int(tile_y),
+                                int(bool(xpair)), packed.ctypes.data, table.ctypes.data)
     if rc:
         raise RuntimeError('atvs_conv_tiled_pack failed (%d)' % rc)
     pk = _Packed(key=key, ntaps=ntaps, ksteps=jc.value * nch.value, ntiles=nt.value, cin=cin, cout=cout)

@@ -7,12 +7,11 @@ against scale_image).  Centring: exact integer sums, mu and sd in double (center
 differ in the last bits of the output, DESIGN.md "Scene mode").
 """
 
-import ctypes
 
 import numpy as np
 import torch
 
-from .base import _call, _stream
+from .base import _call, _p, _stream
 
 _plans = {}
 
@@ -114,10 +113,9 @@ def prepare_view(image, scale, crop, sample_scale=0.25, out=None, taps=None):
         if a.shape != b.shape or a.dtype != torch.int32:
             raise ValueError('prepare_view: tap buffers do not match the plan')
     H, W = plan.shape[:2]
-    p = lambda t: ctypes.c_void_p(t.data_ptr())                 # noqa: E731
-    _call('atvs_prepare_resize_u8', p(image), h, w, p(cropped), H, W, p(my), p(mx), p(sums), _stream())
-    _call('atvs_prepare_center', p(cropped), ctypes.c_long(H * W), p(sums), p(centred), _stream())
+    _call('atvs_prepare_resize_u8', _p(image), h, w, _p(cropped), H, W, _p(my), _p(mx), _p(sums), _stream())
+    _call('atvs_prepare_center', _p(cropped), H * W, _p(sums), _p(centred), _stream())
     if quarter.numel():
-        _call('atvs_prepare_resize_u8', p(cropped), H, W, p(quarter), int(quarter.shape[0]), int(quarter.shape[1]), p(qy), p(qx),
-              ctypes.c_void_p(0), _stream())
+        _call('atvs_prepare_resize_u8', _p(cropped), H, W, _p(quarter), int(quarter.shape[0]), int(quarter.shape[1]), _p(qy),
+              _p(qx), None, _stream())
     return centred, quarter

@@ -107,7 +107,7 @@ def test_split16_entry_points_check_their_arguments_first():
     assert L.atvs_conv3d_s2b_f32(n, n, n, n, n, 1, 8, 8, 8, 16, 32, 32, 0, 0, n) == ERR_NULL
     assert L.atvs_deconv_up_b_f32(n, n, n, n, 1, 8, 8, 8, 16, 8, 8, 0, 0, 16, 0, n) == ERR_NULL
     assert L.atvs_conv1x1_b_f32(n, n, n, n, n, 0, n, n, 1, ctypes.c_long(64), 32, 32, 32, 0, 0, n) == ERR_NULL
-    assert L.atvs_refine_stems_f32(n, n, n, n, n, n, n, n, 1, 8, 8, 32, n) == ERR_NULL
+    assert L.atvs_refine_stems_f32(n, n, n, n, n, n, n, n, 1, 8, 8, 32, 0, n) == ERR_NULL
     assert L.atvs_conv3d_8to1(n, n, n, 1, 8, 8, 8, n) == ERR_NULL
     one = (ctypes.c_float * 4)()
     ptr = ctypes.cast(one, ctypes.c_void_p)
@@ -116,4 +116,4 @@ def test_split16_entry_points_check_their_arguments_first():
     assert L.atvs_conv3d_s2b_f32(ptr, ptr, n, ptr, n, 1, 8, 8, 8, 16, 48, 48, 0, 0, n) == ERR_SHAPE
     assert L.atvs_deconv_up_b_f32(ptr, ptr, ptr, n, 1, 8, 8, 8, 16, 32, 32, 0, 0, 32, 0, n) == ERR_SHAPE
     assert L.atvs_conv1x1_b_f32(ptr, ptr, n, n, n, 0, ptr, n, 1, ctypes.c_long(64), 48, 32, 32, 0, 0, n) == ERR_SHAPE
-    assert L.atvs_refine_stems_f32(ptr, ptr, n, ptr, ptr, ptr, ptr, n, 0, 8, 8, 32, n) == ERR_SHAPE
+    assert L.atvs_refine_stems_f32(ptr, ptr, n, ptr, ptr, ptr, ptr, n, 0, 8, 8, 32, 0, n) == ERR_SHAPE

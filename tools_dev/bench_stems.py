@@ -1,7 +1,6 @@
 """refine_stems at full size (4 volumes)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-import ctypes
 import numpy as np
 import torch
 import atvsnet_amd
@@ -18,8 +17,8 @@ w = torch.randn(27 * 32, device=dev) * 0.1
 y = torch.empty(G, D, H, W, 32, device=dev)
 rows = int(_lib.lib().atvs_conv_stem_rows(D, H, W))
 st = torch.empty(G * rows, 2, 24, dtype=torch.float64, device=dev)
-P = lambda t: ctypes.c_void_p(t.data_ptr())
-run = lambda: ops._call('atvs_refine_stems_f32', P(photo), P(geo), P(pb), P(prob), P(hull), P(w), P(y), P(st), G, D, H, W, ops._stream())
+P = ops._p
+run = lambda: ops._call('atvs_refine_stems_f32', P(photo), P(geo), P(pb), P(prob), P(hull), P(w), P(y), P(st), G, D, H, W, 0, ops._stream())
 for _ in range(3):
     run()
 torch.cuda.synchronize()
