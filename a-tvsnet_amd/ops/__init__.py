@@ -18,7 +18,7 @@ Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
 """
 from .base import (Config, Stats, _ERR, _Timed, _call, _dev_ok, _new, _p, _ptr_array, _side_pool, _side_stream, _size, _stats,
-    _stats_buffer, _stream, _watch, _watched, cfg, configure, watch)      # noqa: F401
+    _stats_buffer, _stream, _watch, _watched, cfg, configure, launches, watch)      # noqa: F401
 from .packing import (PLANAR_PAD, _Packed, _abi_pack, _fold_cache, _pack_cache, _virt_cache, _xkind, _xp_cache, cache_snapshot,
     clear_pack_cache, conv_taps, deconv_s2_class_taps, deconv_up_ok, invalidate_weights, pack_conv3d_b, pack_conv_c16,
     pack_conv_c16b, pack_conv_weights, pack_conv_weights_tiled, pack_conv_xp, pack_conv_xp_sibling, pack_deconv_up,

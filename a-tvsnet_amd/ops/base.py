@@ -159,6 +159,7 @@ def _side_stream(device, i):
 
 
 def _call(name, *args):
+    _watch['launches'] += 1
     rc = getattr(_lib.lib(), name)(*args)
     if rc != 0:
         raise RuntimeError('%s failed: %s (%d)' % (name, _ERR.get(rc, 'unknown'), rc))
@@ -200,7 +201,7 @@ def _stats(ref, rows, cpad, count, groups, fold=1):
     return st, st.partial
 
 
-_watch = {'tag': None, 'events': []}
+_watch = {'tag': None, 'events': [], 'launches': 0}
 
 
 def _watched(key):
@@ -245,7 +246,15 @@ def watch(tag):
             out = [e[0].elapsed_time(e[1]) for e in ev]
     _watch['tag'] = tag
     _watch['events'] = []
+    _watch['launches'] = 0
     return out
+
+
+def launches():
+    """Library launches of EVERY kind (convolutions and the glue: batch norm, adds, copies, pooling, resize ...) since the last
+    watch(...) call.  watch('*') times the convolutions only; a definition that differs from another in glue alone (a batch norm
+    applied on its own instead of on load, a concat that copies) shows here."""
+    return _watch['launches']
 
 
 def _ptr_array(ts):
