@@ -56,10 +56,16 @@ def divide(num, den):
 def fusibile(cams, normals_depths, images, ref, disp_thresh, normal_thresh, num_consistent):
     """The consistency-voting kernel of the reference's fusibile for reference camera `ref` (atvs_fusibile).
     cams (N,28), normals_depths / images (N,rows,cols,4) -> coord, normal, texture (rows,cols,4), created (rows,cols)."""
-    N, rows, cols, _ = normals_depths.shape
+    if not isinstance(normals_depths, torch.Tensor) or normals_depths.dim() != 4:
+        raise ValueError('fusibile: normals_depths must be a (N, rows, cols, 4) tensor')
+    N, rows, cols, _ = (int(s) for s in normals_depths.shape)
+    if not 0 <= int(ref) < N:
+        raise ValueError('fusibile: ref must be in 0 .. %d, got %d' % (N - 1, int(ref)))
+    launch = _fusion_args((cams, 'cams', torch.float32, (N, 28)), (normals_depths, 'normals_depths', torch.float32, (N, rows, cols, 4)),
+                          (images, 'images', torch.float32, (N, rows, cols, 4)))
     coord, normal, tex = (_new(images, (rows, cols, 4)) for _ in range(3))
     created = _new(images, (rows, cols))
-    if _dev_ok(cams, normals_depths, images):
+    if launch:
         _call('atvs_fusibile', _p(cams), _p(normals_depths), _p(images), N, int(ref), rows, cols, disp_thresh, normal_thresh,
               int(num_consistent), _p(coord), _p(normal), _p(tex), _p(created), _stream())
     return coord, normal, tex, created

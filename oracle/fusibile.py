@@ -64,42 +64,56 @@ def pack_cameras(Ps):
     return out
 
 
-def _tex(tex, x, y):
-    """tex2D<float4>(tex, x + 0.5, y + 0.5), see the module docstring.  tex (rows, cols, 4); x, y float32 arrays."""
+def _tex(tex, x, y, dt=F):
+    """tex2D<float4>(tex, x + 0.5, y + 0.5), see the module docstring.  tex (rows, cols, 4); x, y arrays of type dt."""
     rows, cols = tex.shape[:2]
     xf, yf = np.floor(x), np.floor(y)
-    ax = np.floor((x - xf) * F(256.0) + F(0.5)) / F(256.0)
-    ay = np.floor((y - yf) * F(256.0) + F(0.5)) / F(256.0)
+    ax = np.floor((x - xf) * dt(256.0) + dt(0.5)) / dt(256.0)
+    ay = np.floor((y - yf) * dt(256.0) + dt(0.5)) / dt(256.0)
     x0 = np.clip(xf.astype(np.int64), 0, cols - 1)
     y0 = np.clip(yf.astype(np.int64), 0, rows - 1)
     x1 = np.clip(xf.astype(np.int64) + 1, 0, cols - 1)
     y1 = np.clip(yf.astype(np.int64) + 1, 0, rows - 1)
-    ax, ay = ax[..., None].astype(F), ay[..., None].astype(F)
-    one = F(1.0)
+    ax, ay = ax[..., None].astype(dt), ay[..., None].astype(dt)
+    one = dt(1.0)
     top = (one - ax) * tex[y0, x0] + ax * tex[y0, x1]
     bot = (one - ax) * tex[y1, x0] + ax * tex[y1, x1]
-    return ((one - ay) * top + ay * bot).astype(F)
+    return ((one - ay) * top + ay * bot).astype(dt)
 
 
-def fuse_reference(cams, normals_depths, images, ref, disp_thresh, normal_thresh, num_consistent):
+def fuse_reference(cams, normals_depths, images, ref, disp_thresh, normal_thresh, num_consistent, dtype=np.float32, trace=None,
+                   full=False):
     """The kernel for one reference camera: -> (coord (rows,cols,3), normal (rows,cols,3), texture (rows,cols,4),
-    created (rows,cols) bool).  cams (N,28); normals_depths / images (N,rows,cols,4) float32."""
+    created (rows,cols) bool).  cams (N,28); normals_depths / images (N,rows,cols,4) float32.
+
+    full: coord and normal come back with their fourth component too, as the kernel stores them: 0 (the reference's float4
+    operators + and / write w = 0, vector_operations.h:29-40, so the depth that rides along in the reference pixel's normal.w
+    (:174) never reaches an output; get3Dpoint_cu leaves X.w unset, which this project's contract fixes to 0).
+    dtype: the type every operation is evaluated in (float64: the same definition without float32 rounding; the texture weights
+    keep their 8 fractional bits, they are part of the definition; the thresholds stay the float32 values the kernel is given).
+    trace: a dict that receives the per-view intermediates, trace['views'][i] = {px, py, tz, inb, other, rel, disp_ok, dot, ang, ok}
+    and trace['count']."""
+    dt = np.dtype(dtype).type
+    cams, normals_depths, images = (np.asarray(a).astype(dt) for a in (cams, normals_depths, images))
+    disp_thresh, normal_thresh = dt(F(disp_thresh)), dt(F(normal_thresh))
     N, rows, cols = normals_depths.shape[:3]
     with np.errstate(all='ignore'):
         cr = cams[ref]
         Pr, Mi, Cr, pc = cr[0:12], cr[12:21], cr[21:24], cr[24:27]
         f = cr[27]
-        ys, xs = np.meshgrid(np.arange(rows, dtype=F), np.arange(cols, dtype=F), indexing='ij')
+        ys, xs = np.meshgrid(np.arange(rows, dtype=dt), np.arange(cols, dtype=dt), indexing='ij')
         nd = normals_depths[ref]
         normal, depth = nd[..., :3], nd[..., 3]
         # get3Dpoint_cu (:53-62)
         ptx, pty, ptz = depth * xs - pc[0], depth * ys - pc[1], depth - pc[2]
         X = np.stack([Mi[0] * ptx + Mi[1] * pty + Mi[2] * ptz,
                       Mi[3] * ptx + Mi[4] * pty + Mi[5] * ptz,
-                      Mi[6] * ptx + Mi[7] * pty + Mi[8] * ptz], -1).astype(F)
+                      Mi[6] * ptx + Mi[7] * pty + Mi[8] * ptz], -1).astype(dt)
         cons_n = np.concatenate([normal, nd[..., 3:4]], -1).copy()      # float4 normal (w rides along, :164)
         cons_t = images[ref].copy()
         count = np.zeros((rows, cols), np.int32)
+        if trace is not None:
+            trace['views'] = {}
         for i in range(N):
             if i == ref:
                 continue
@@ -109,28 +123,37 @@ def fuse_reference(cams, normals_depths, images, ref, disp_thresh, normal_thresh
             tx = P[0] * X[..., 0] + P[1] * X[..., 1] + P[2] * X[..., 2] + P[3]
             ty = P[4] * X[..., 0] + P[5] * X[..., 1] + P[6] * X[..., 2] + P[7]
             tz = P[8] * X[..., 0] + P[9] * X[..., 1] + P[10] * X[..., 2] + P[11]
-            px, py, d = (tx / tz).astype(F), (ty / tz).astype(F), tz.astype(F)
+            px, py, d = (tx / tz).astype(dt), (ty / tz).astype(dt), tz.astype(dt)
             inb = (px >= 0) & (px < cols) & (py >= 0) & (py < rows)
-            pxs, pys = np.where(inb, px, F(0)), np.where(inb, py, F(0))
-            other = _tex(normals_depths[i], pxs, pys)
+            pxs, pys = np.where(inb, px, dt(0)), np.where(inb, py, dt(0))
+            other = _tex(normals_depths[i], pxs, pys, dt)
             dC = Cr - c[21:24]
-            base = np.sqrt(dC[0] * dC[0] + dC[1] * dC[1] + dC[2] * dC[2]).astype(F)
+            base = np.sqrt(dC[0] * dC[0] + dC[1] * dC[1] + dC[2] * dC[2]).astype(dt)
             fb = f * base
-            d_disp = (fb / d).astype(F)
-            o_disp = (fb / other[..., 3]).astype(F)
-            ok = inb & ((np.abs(d_disp - o_disp) / d_disp) < F(disp_thresh))
+            d_disp = (fb / d).astype(dt)
+            o_disp = (fb / other[..., 3]).astype(dt)
+            rel = (np.abs(d_disp - o_disp) / d_disp).astype(dt)
+            disp_ok = inb & (rel < disp_thresh)
             dot = other[..., 0] * normal[..., 0] + other[..., 1] * normal[..., 1] + other[..., 2] * normal[..., 2]
-            ang = np.arccos(dot.astype(F)).astype(F)
-            ang = np.where(ang != ang, F(0), ang)
-            ok &= ang < F(normal_thresh)
+            ang = np.arccos(dot.astype(dt)).astype(dt)
+            ang = np.where(ang != ang, dt(0), ang)
+            ok = disp_ok & (ang < normal_thresh)
             add4 = lambda a, b: np.concatenate([a[..., :3] + b[..., :3], np.zeros_like(a[..., :1])], -1)   # noqa: E731
             cons_n = np.where(ok[..., None], add4(cons_n, other), cons_n)
-            cons_t = np.where(ok[..., None], add4(cons_t, _tex(images[i], pxs, pys)), cons_t)
+            cons_t = np.where(ok[..., None], add4(cons_t, _tex(images[i], pxs, pys, dt)), cons_t)
             count += ok
-        k = count.astype(F) + F(1.0)
-        cons_n = (cons_n[..., :3] / k[..., None]).astype(F)
-        cons_t = np.concatenate([cons_t[..., :3] / k[..., None], np.zeros_like(cons_t[..., :1])], -1).astype(F)
+            if trace is not None:
+                trace['views'][i] = dict(px=px, py=py, tz=d, inb=inb, other=other, rel=rel, disp_ok=disp_ok, dot=dot.astype(dt), ang=ang,
+                                         ok=ok)
+        k = count.astype(dt) + dt(1.0)
+        cons_n = (cons_n[..., :3] / k[..., None]).astype(dt)
+        cons_t = np.concatenate([cons_t[..., :3] / k[..., None], np.zeros_like(cons_t[..., :1])], -1).astype(dt)
         created = count >= int(num_consistent)
+        if trace is not None:
+            trace['count'] = count
+    if full:
+        w0 = np.zeros((rows, cols, 1), dt)
+        return np.concatenate([X, w0], -1), np.concatenate([cons_n, w0], -1), cons_t, created
     return X, cons_n, cons_t, created
 
 

@@ -150,3 +150,36 @@ def test_ops_fusibile_scene_validates_before_launch(no_launch):
             call(**dict(good, **{name: bad}))
     with pytest.raises(RuntimeError):
         call(**{k: v.to('meta') for k, v in good.items()})       # the count needs a launch
+
+
+def test_ops_fusibile_validates_before_launch(no_launch):
+    n, r, c = 3, 6, 7
+    call = lambda **kw: ops.fusibile(kw['cams'], kw['nd'], kw['img'], kw['ref'], 0.01, 6.28, 2)      # noqa: E731
+    goods = {}
+    for dev in ('cpu', 'meta'):                                  # refused on any device, before the device is looked at
+        f32 = lambda *s: torch.zeros(s, dtype=torch.float32, device=dev)        # noqa: E731
+        u8 = lambda *s: torch.zeros(s, dtype=torch.uint8, device=dev)           # noqa: E731
+        good = goods[dev] = dict(cams=f32(n, 28), nd=f32(n, r, c, 4), img=f32(n, r, c, 4), ref=1)
+        for name, bad, exc in [('cams', f32(n, 27), ValueError), ('cams', f32(n + 1, 28), ValueError), ('cams', f32(n * 28), ValueError),
+                               ('img', f32(n - 1, r, c, 4), ValueError), ('img', f32(n + 1, r, c, 4), ValueError),
+                               ('img', f32(n, r, c + 1, 4), ValueError), ('img', f32(n, r, c, 3), ValueError),
+                               ('nd', f32(r, c, 4), ValueError), ('nd', f32(n, r, c, 3), ValueError),
+                               ('nd', f32(n, c, r, 4).transpose(1, 2), ValueError),
+                               ('img', f32(n, r, c, 8)[..., ::2], ValueError), ('cams', f32(n, 56)[:, ::2], ValueError),
+                               ('nd', f32(n, r, c, 4).double(), TypeError), ('img', f32(n, r, c, 4).double(), TypeError),
+                               ('cams', f32(n, 28).double(), TypeError), ('nd', u8(n, r, c, 4), TypeError),
+                               ('img', u8(n, r, c, 4), TypeError), ('nd', np.zeros((n, r, c, 4), np.float32), ValueError),
+                               ('ref', -1, ValueError), ('ref', n, ValueError)]:
+            if torch.is_tensor(bad) and name in ('nd', 'img', 'cams') and bad.dim() in (2, 4) and bad.dtype == torch.float32 \
+                    and tuple(bad.shape) == tuple(good[name].shape):
+                assert not bad.is_contiguous()
+            with pytest.raises(exc):
+                call(**dict(good, **{name: bad}))
+    with pytest.raises(RuntimeError):
+        call(**goods['cpu'])                                     # CPU tensors: no fallback
+    meta = goods['meta']
+    coord, normal, tex, created = call(**meta)                   # meta: shapes only, no launch
+    assert all(t.device.type == 'meta' and t.dtype == torch.float32 for t in (coord, normal, tex, created))
+    assert tuple(coord.shape) == tuple(normal.shape) == tuple(tex.shape) == (r, c, 4) and tuple(created.shape) == (r, c)
+    with pytest.raises(RuntimeError):
+        call(**dict(meta, cams=goods['cpu']['cams']))            # meta mixed with another device

@@ -11,6 +11,8 @@ import pytest
 import torch
 
 import atvsnet_amd  # noqa: F401
+import fusion_cases as FC
+import numerics
 from atvsnet_amd import FLAGS, ops, synthetic, variables
 from atvsnet_amd.atvsnet import depth_fusion as DF
 from atvsnet_amd.atvsnet import eval_pointcloud as E
@@ -120,6 +122,43 @@ def test_scene_fusion_is_fuse_views(cuda, n, rows, cols, ncons):
     from oracle import fusibile as F
     ora_p, ora_c = F.fuse(Ps, depths, normals, images, disp, nthr, ncons)
     assert got_p.tobytes() == ora_p.tobytes() and got_c.tobytes() == ora_c.tobytes()
+
+
+def _nan_canonical(a):
+    """The bytes of a float array with every NaN replaced by one NaN.  Only the sign and payload of a NaN are forgiven (which
+    NaN an invalid operation returns is the platform's choice: x86 sets the sign bit of a default NaN, the GPU does not); where
+    the NaNs are, and every other value, the sign of a zero included, is compared bit for bit.  For the comparison with the CPU
+    oracle only: the two device paths are compared on their raw bytes."""
+    return np.where(np.isnan(a), np.float32(np.nan), a).tobytes()
+
+
+@pytest.mark.parametrize('case', FC.SCENE_CASES, ids=FC.case_id)
+def test_scene_fusion_general_cases(cuda, case):
+    """general_scene with full cameras, occlusion and (where the case says so) hard_maps' special values: the whole-scene kernel
+    equals the per-camera path byte for byte, and both equal the oracle.  num_consistent = 0 keeps the NaN points and the points
+    at a camera centre (the host filter is != 0, reference fusibile.cu:309)."""
+    from oracle import fusibile as F
+    assert (case.rows, case.cols) in FC.FUSION_SHAPES['scene'], 'shape is not listed in fusion_cases.FUSION_SHAPES'
+    Ps, depths, normals, images, _ = FC.case_inputs(case)
+    nd, img4 = FC.textures(depths, normals, images)
+    disp, nthr = case.thresholds
+    dev = [numerics.nan_bordered(torch.from_numpy(a).to(cuda)) for a in (DF.pack_cameras(Ps), nd, img4)]
+    numerics.poison_allocator(cuda)
+    pts, cols = ops.fusibile_scene(dev[0], dev[1], dev[2], disp, nthr, case.ncons)
+    got_p, got_c = pts.cpu().numpy(), cols.cpu().numpy()
+    want_p, want_c = DF.fuse_views(Ps, depths, normals, images, disp, nthr, case.ncons, device=cuda)
+    if 0 < case.ncons < case.n:
+        assert 0 < len(want_p) < case.n * case.rows * case.cols             # the case decides something
+    elif case.ncons >= case.n:
+        assert len(want_p) == 0                                              # there are only n - 1 other views: an empty cloud
+    assert got_p.shape == want_p.shape and got_p.tobytes() == want_p.tobytes()
+    assert got_c.tobytes() == want_c.tobytes()
+    ora_p, ora_c = F.fuse(Ps, depths, normals, images, disp, nthr, case.ncons)
+    assert got_p.shape == ora_p.shape and _nan_canonical(got_p) == _nan_canonical(ora_p)
+    assert got_c.tobytes() == ora_c.tobytes()
+    if case.ncons == 0:
+        assert np.isnan(got_p).any(-1).sum() > 0                 # NaN points are kept
+        assert len(got_p) > 0.99 * case.n * case.rows * case.cols
 
 
 def test_created_point_with_a_zero_coordinate_is_dropped(cuda):
