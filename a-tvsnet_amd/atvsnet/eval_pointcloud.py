@@ -4,7 +4,7 @@ Mirror of /root/reference/atvsnet/eval_pointcloud.py (gen_data_list :60-94, load
 :206-397, main :400-424): the same on-disk inputs (<scene>/pair.txt, images/%08d.jpg, cams/%08d_cam.txt) and
 outputs (<savepath>/<scene>/depths_atvsnet/%08d.pfm, %08d_prob.pfm, %08d.jpg, %08d.txt, %08d.png,
 zz_runtime.txt).  The session.run sequence of the reference (base per source, AAM1, refinement per source,
-AAM2 with probability maps) is example.infer_multiview(out_prob_map=True), replayed from one HIP graph per
+AAM2 with probability maps) is pipeline.infer_multiview(out_prob_map=True), replayed from one HIP graph per
 input shape.  Not available here and therefore not done: the optional ground-truth depth range from
 depths/*.exr (:170-192, needs an EXR reader).
 """
@@ -25,7 +25,7 @@ from . import clean_cloud
 from . import depth_fusion
 from . import eval_cloud
 from . import eval_depth
-from . import example
+from . import example, graphs, pipeline, range_guard
 from . import scene
 from .preprocess import (center_image, crop_mvs_input, crop_window, gen_pipeline_mvs_list, load_cam, scale_camera, scale_image,
                          scale_mvs_camera, scale_mvs_input, scaled_size, write_cam, write_pfm)
@@ -255,17 +255,17 @@ class _Pipelines(object):
         key = tuple(images.shape)
         if not (split and key in self.cache):
             # (cu_split: the slot's own stream copies the HOST tensors -- an upload on the default stream would wait for the map in
-            # flight on the other half of the chip, example.PipelinedInference.submit; the first map of a shape still needs device
+            # flight on the other half of the chip, graphs.PipelinedInference.submit; the first map of a shape still needs device
             # tensors to capture the graphs from)
             images, cams = images.to(self.device), cams.to(self.device)
         if not self.use_graph:
             # eager: computed here, with the drivers' range guard (an fp16-range overflow reruns the map on the fp32 kernels)
-            self.pending.append((None, example.infer_checked(
-                lambda: example.infer_multiview(images, cams, FLAGS.max_d, out_prob_map=True), self.device)))
+            self.pending.append((None, range_guard.infer_checked(
+                lambda: pipeline.infer_multiview(images, cams, FLAGS.max_d, out_prob_map=True), self.device)))
             return
         p = self.cache.get(key)
         if p is None:
-            p = self.cache[key] = example.PipelinedInference(images, cams, FLAGS.max_d, slots=self.SLOTS,
+            p = self.cache[key] = graphs.PipelinedInference(images, cams, FLAGS.max_d, slots=self.SLOTS,
                                                                 co_resident=self.CO_RESIDENT, out_prob_map=True)
         self.pending.append((p, p.submit(images, cams)))
 
@@ -276,7 +276,7 @@ class _Pipelines(object):
         p, t = self.pending.pop(0)
         # result(): the fp32 rerun of a map whose split-operand replay overflowed; host=True: copied by the slot's own stream
         out = t if p is None else p.result(t, host=True)
-        return [example.check_finite(o.cpu().numpy(), 'a network output') for o in out]
+        return [range_guard.check_finite(o.cpu().numpy(), 'a network output') for o in out]
 
 
 def _write_map(output_folder, out_index, outputs, image_raw, cams, plt):
@@ -372,7 +372,7 @@ class _SceneSource(object):
         ticket, cam, out_index = self.queued.pop(0)
         if stage is None:
             # result() has read the non-finite flag on the slot's stream: no second (default-stream) read here
-            outputs = [example.check_finite(o.numpy(), 'a network output', flag=False) for o in self.run.result(ticket, host=True)]
+            outputs = [range_guard.check_finite(o.numpy(), 'a network output', flag=False) for o in self.run.result(ticket, host=True)]
             return out_index, outputs, self.run.reference_image(ticket), cam
         # the slot's output buffers are overwritten by its next submission: staged from what result() returned (an overflowed
         # map's fp32 rerun), on the slot's stream, before submit() can reuse the slot; the host copies under that stream too
@@ -380,7 +380,7 @@ class _SceneSource(object):
         st = self.run.slot_stream(ticket)
         stage(out_index, dev_out[0], dev_out[2], self.run.reference_image(ticket, host=False), cam, stream=st)
         with torch.cuda.stream(st):
-            outputs = [example.check_finite(o.cpu().numpy(), 'a network output', flag=False) for o in dev_out]
+            outputs = [range_guard.check_finite(o.cpu().numpy(), 'a network output', flag=False) for o in dev_out]
             return out_index, outputs, self.run.reference_image(ticket), cam
 
 

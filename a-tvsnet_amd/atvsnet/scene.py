@@ -7,11 +7,11 @@ appears in.  Here:
 
 * the image is decoded once and uploaded as uint8; ops.prepare_view resizes it by the map's adaptive scale, crops and centres it,
   and forms the 1/4-scale image (bit for bit scale_image; the centring may differ from center_image in the last bits, DESIGN.md);
-* one captured graph per (image shape, output shape, slot) runs preparation + both towers (example.multiview_towers at N = 1:
+* one captured graph per (image shape, output shape, slot) runs preparation + both towers (pipeline.multiview_towers at N = 1:
   every tower has per-image statistics, so a row does not depend on the other images of a launch);
 * the cache maps (image id, adaptive scale, crop window) -> (features, shallow features, 1/4 image), and image id -> the device
   uint8 image, bounded in bytes with LRU eviction;
-* each map replays a features-mode graph (example.GraphedInference(features=True)) from PipelinedInference's slots.
+* each map replays a features-mode graph (graphs.GraphedInference(features=True)) from PipelinedInference's slots.
 
 Range rule: a map whose replay or whose newly computed tower features raised the non-finite flag is
 recomputed entirely on the fp32 kernels from the uint8 images (what ops.configure(split16=False) computes for it), and the cache
@@ -31,7 +31,7 @@ import torch
 
 from .. import ops, variables
 from ..flags import FLAGS
-from . import example
+from . import graphs, pipeline, range_guard
 from .preprocess import crop_window, scaled_size
 
 
@@ -134,7 +134,7 @@ class _Entry(object):
 
 
 class _TowerGraph(object):
-    """ops.prepare_view + example.multiview_towers of one image, captured for one (source shape, output shape); the taps are
+    """ops.prepare_view + pipeline.multiview_towers of one image, captured for one (source shape, output shape); the taps are
     static inputs, so one graph serves every scale / crop with those shapes."""
 
     def __init__(self, plan, scale, crop, sample_scale, device):
@@ -144,21 +144,12 @@ class _TowerGraph(object):
         self.args = (scale, crop, sample_scale)
         torch.cuda.current_stream(device).wait_event(plan.ready)
         self.taps = [t.clone() for t in plan.taps]
-        side = torch.cuda.Stream(device)
-        side.wait_stream(torch.cuda.current_stream(device))
-        with torch.cuda.stream(side):           # warm-up: weight packing / uploads
-            self._run()
-        torch.cuda.current_stream(device).wait_stream(side)
-        torch.cuda.synchronize(device)
-        self.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self.graph, capture_error_mode='thread_local'):
-            self.out = self._run()
-        self._weights = (ops.cache_snapshot(), variables.default_store().device_snapshot())
+        self.graph, self.out, self._weights = graphs.capture(self._run, device)
 
     def _run(self):
         scale, crop, sample_scale = self.args
         centred, quarter = ops.prepare_view(self.image, scale, crop, sample_scale, out=self.ws, taps=self.taps)
-        feats, shallow = example.multiview_towers(centred.view((1, 1) + tuple(centred.shape)))
+        feats, shallow = pipeline.multiview_towers(centred.view((1, 1) + tuple(centred.shape)))
         return feats, shallow, quarter
 
     def __call__(self, image, plan):
@@ -167,6 +158,12 @@ class _TowerGraph(object):
             d.copy_(t)
         self.graph.replay()
         return self.out
+
+
+class _Slot(object):
+    """What a slot of a pipeline holds: the map's views, adaptive scale and crops, the cache keys its submission made (`new`),
+    the reference's 1/4-scale image (`quarter`) and the (start, end) timing events."""
+    __slots__ = ('views', 'scale', 'crops', 'new', 'quarter', 'events')
 
 
 class SceneInference(object):
@@ -199,12 +196,12 @@ class SceneInference(object):
         self.shapes = {}
         self.tower_runs = 0
         self.times, self.gpu_ms = {'upload': 0.0}, []
-        self.streams = example.cu_split_streams(self.device, slots) if co_resident == 'cu_split' else None
+        self.streams = graphs.cu_split_streams(self.device, slots) if co_resident == 'cu_split' else None
         self._reset()
 
     def _reset(self):
         self.towers, self.pipelines = {}, {}
-        self.slot_map, self.slot_new, self.slot_quarter, self.slot_events = {}, {}, {}, {}
+        self.slot = {}                                     # (id(pipeline), slot) -> _Slot
         self.last = None                                   # (pipeline, slot) of the latest submission
 
     def _check_weights(self):
@@ -227,7 +224,7 @@ class SceneInference(object):
         return scale, [crop_window(*scaled_size(h, w, scale)) for h, w in shapes]
 
     def room(self):
-        return sum(p.busy.count(True) for p in self.pipelines.values()) < self.slots
+        return sum(p.in_flight() for p in self.pipelines.values()) < self.slots
 
     # -- device images and cache entries ------------------------------------------------------------------------------------
     def _device_image(self, image_id, stream):
@@ -260,15 +257,14 @@ class SceneInference(object):
             gc.collect()                                    # no unreachable graph of an earlier run may be freed during the capture
             h, w = int(math.ceil(H / 4.0)), int(math.ceil(W / 4.0))
             feats = (torch.zeros((n, h, w, 32), device=self.device), torch.zeros((n, h, w, 16), device=self.device))
-            p = example.PipelinedInference(feats, cams.to(self.device, torch.float32), self.max_d, slots=self.slots,
-                                           co_resident=self.co_resident, out_prob_map=True, features=True)
-            if self.streams is not None:
-                p.streams = self.streams                    # every shape's slot k on the same CU share
             # weak references only: a cycle scene -> pipeline -> graph -> scene would leave the captured graphs to the cyclic garbage
             # collector, which may then destroy one in the middle of a later capture (not permitted while a stream is capturing)
-            me, pw = weakref.ref(self), weakref.ref(p)
-            for s, g in enumerate(p.graphs):
-                g.fp32_fn = (lambda s=s: me()._fp32_map(pw(), s))
+            me = weakref.ref(self)
+            p = graphs.PipelinedInference(feats, cams.to(self.device, torch.float32), self.max_d, slots=self.slots,
+                                          co_resident=self.co_resident, out_prob_map=True, features=True,
+                                          streams=self.streams,   # every shape's slot k on the same CU share
+                                          fp32_fn=lambda s: me()._fp32_map(pw(), s))
+            pw = weakref.ref(p)                             # what fp32_fn finds when a map is rerun
             self.pipelines[key] = p
         return p
 
@@ -284,8 +280,8 @@ class SceneInference(object):
             raise ValueError('SceneInference: the views of a map crop to different sizes %s' % sorted(sizes))
         cams = cams if isinstance(cams, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(cams, dtype=np.float32))
         p = self._pipeline(len(views), crops[0][2], crops[0][3], cams)
-        slot = p.next
-        with torch.cuda.stream(p.streams[slot]):            # a new (size, scale, crop) uploads its taps on the slot's stream
+        slot, stream = p.next_slot()
+        with torch.cuda.stream(stream):                     # a new (size, scale, crop) uploads its taps on the slot's stream
             plans = [ops.view_plan(self.shape(v)[0], self.shape(v)[1], scale, c, self.sample_scale, self.device)
                      for v, c in zip(views, crops)]
         for v, c, plan in zip(views, crops, plans):         # first use of a shape: capture now, not inside the slot's stream
@@ -302,7 +298,8 @@ class SceneInference(object):
             if host_cams is not None:                       # pinned: queued on the slot's stream, the host does not wait
                 p.graphs[s].cams.copy_(host_cams, non_blocking=True)
             feats, shallow = p.graphs[s].images
-            new, quarter = [], None
+            rec = self.slot[(id(p), s)] = _Slot()
+            rec.views, rec.scale, rec.crops, rec.new, rec.quarter = views, scale, crops, [], None
             for i, (v, c, plan) in enumerate(zip(views, crops, plans)):
                 key = view_key(v, scale, c)
                 e = self.cache.get(key)
@@ -312,21 +309,18 @@ class SceneInference(object):
                     f, sh, q = self._tower_graph(plan, scale, c, s)(img, plan)
                     e = _Entry((f.clone(), sh.clone(), q.clone()), st)
                     self.cache.put(key, e, tensor_bytes(*e.tensors))
-                    new.append(key)
+                    rec.new.append(key)
                     self.tower_runs += 1
                 f, sh, q = e.use(st)
                 feats[i].copy_(f[0])
                 shallow[i].copy_(sh[0])
                 if i == 0:
-                    quarter = q
-            self.slot_map[(id(p), s)] = (views, scale, crops)
-            self.slot_new[(id(p), s)] = new
-            self.slot_quarter[(id(p), s)] = quarter
+                    rec.quarter = q
 
         host_cams = None if cams.is_cuda else cams.to(torch.float32).contiguous().pin_memory()
         s = p.submit(None, cams if cams.is_cuda else None, fill=fill)
         end.record(p.streams[s])
-        self.slot_events[(id(p), s)] = (start, end)
+        self.slot[(id(p), s)].events = (start, end)
         self.last = (p, s)
         return (p, s)
 
@@ -338,20 +332,17 @@ class SceneInference(object):
         if not p.busy[s]:
             raise RuntimeError('SceneInference: nothing in flight on slot %d' % s)
         p.events[s].synchronize()
+        queues = list(self.pipelines.values())
+        if p not in queues:
+            queues.append(p)                                 # reset away (new weights) with this map still in flight
         with torch.cuda.stream(p.streams[s]):                # the flag read: on the slot's (idle) stream
-            if ops.nonfinite_seen(self.device):
-                torch.cuda.synchronize(self.device)
-                ops.nonfinite_seen(self.device)
-                for q in self.pipelines.values():
-                    q.suspect.update(t for t, b in enumerate(q.busy) if b)
-                if p not in self.pipelines.values():
-                    p.suspect.update(t for t, b in enumerate(p.busy) if b)
-        for q in list(self.pipelines.values()) + [p]:
+            range_guard.mark_suspects(self.device, queues)
+        for q in queues:
             for t in q.suspect:
-                for key in self.slot_new.pop((id(q), t), []):
-                    self.cache.drop(key)                   # made while the flag was up: never reused
+                self._drop_new(q, t)                         # made while the flag was up: never reused
         out = p.result(s, host=host)
-        start, end = self.slot_events.pop((id(p), s))
+        rec = self.slot[(id(p), s)]
+        (start, end), rec.events = rec.events, None
         end.synchronize()
         self.gpu_ms.append(start.elapsed_time(end))
         return out
@@ -361,25 +352,31 @@ class SceneInference(object):
         device tensor, valid until the slot's next submission -- use it on slot_stream(ticket)."""
         p, s = ticket
         if not host:
-            return self.slot_quarter[(id(p), s)]
+            return self.slot[(id(p), s)].quarter
         with torch.cuda.stream(p.streams[s]):
-            return self.slot_quarter[(id(p), s)].cpu().numpy()
+            return self.slot[(id(p), s)].quarter.cpu().numpy()
 
     def slot_stream(self, ticket):
         """The stream `ticket`'s map runs on: work enqueued there after result() precedes the slot's next submission."""
         p, s = ticket
         return p.streams[s]
 
+    def _drop_new(self, p, s):
+        """Forget the cache entries that the submission now in slot s of p made (once: the list is consumed)."""
+        rec = self.slot.get((id(p), s))
+        while rec is not None and rec.new:
+            self.cache.drop(rec.new.pop())
+
     def _fp32_map(self, p, s):
         """The map now in slot s, computed entirely on the fp32 kernels from the uint8 images (towers included)."""
-        views, scale, crops = self.slot_map[(id(p), s)]
-        for key in self.slot_new.pop((id(p), s), []):
-            self.cache.drop(key)                             # made while the flag was up
+        rec = self.slot[(id(p), s)]
+        views, scale, crops = rec.views, rec.scale, rec.crops
+        self._drop_new(p, s)                                 # made while the flag was up
         st = torch.cuda.current_stream(self.device)
         with ops.configure(split16=False):
             imgs = torch.stack([ops.prepare_view(self._device_image(v, st), scale, c, self.sample_scale)[0]
                                 for v, c in zip(views, crops)], 0)[None]
-            out = example.infer_multiview(imgs, p.graphs[s].cams, self.max_d, out_prob_map=True)
+            out = pipeline.infer_multiview(imgs, p.graphs[s].cams, self.max_d, out_prob_map=True)
         if ops.nonfinite_seen(self.device):
-            raise FloatingPointError('a batch norm saw non-finite moments on the fp32 kernels too: ' + example._NONFINITE_HINT)
+            raise range_guard.fp32_nonfinite('a batch norm saw non-finite moments')
         return out

@@ -32,6 +32,9 @@ import torch.distributed as dist
 
 from . import ops
 from . import variables
+from .atvsnet import model
+from .atvsnet.graphs import pinned_weights, warm_up
+from .atvsnet.pipeline import depth_range
 from .flags import FLAGS
 
 EXCHANGE = 'all-to-all of voxel shards of [S|R|X] + all-gather of the combined shard, per AANet'
@@ -247,7 +250,6 @@ class HipLocalStages(object):
     def base(self, images, cams, max_d, depth_start, depth_interval, fwd, rev):
         """Base stage (reference model.py:398-417) of the owned directions -> (filtered cost volumes (len(fwd),D,h,w,8) in
         `fwd` order or None, {v: depth_view (h,w) for v in rev})."""
-        from .atvsnet import model
         views = sorted(set(fwd) | set(rev))
         local = [0] + views                                    # the reference view and the owned sources
         index = {v: i for i, v in enumerate(local)}
@@ -259,13 +261,11 @@ class HipLocalStages(object):
 
     def head(self, cost_agg, max_d, depth_start, depth_interval):
         """AAM1's output conv + soft-argmin: (D,h,w,8) -> (prob_agg (1,D,h,w), depth_init (1,h,w,1))."""
-        from .atvsnet import model
         prob_agg = model.output_conv(cost_agg.unsqueeze(0), reuse=False)
         return prob_agg, model.prob2depth(prob_agg, max_d, depth_start, depth_interval)
 
     def refine(self, images, cams, max_d, depth_start, depth_interval, fwd, depth_init, dviews, prob_agg, cost_agg):
         """Refinement of the owned sources in one pass -> refined cost volumes (len(fwd),D,h,w,8) = cost_agg + residual."""
-        from .atvsnet import model
         local = [0] + list(fwd)
         index = {v: i for i, v in enumerate(local)}
         shallow = model.shallow_feature_batch(torch.cat([images[:, i] for i in local], 0).unsqueeze(0))
@@ -278,24 +278,22 @@ class HipLocalStages(object):
 
     def final(self, rcost_agg, max_d, depth_start, depth_interval):
         """AAM2's output conv, x4 upsample + soft-argmin: (D,h,w,8) -> (1,H,W,1)."""
-        from .atvsnet import model
         rprob_agg = model.output_conv_refine(rcost_agg.unsqueeze(0), reuse=False)
         return model.prob2depth_upsample(rprob_agg, max_d, depth_start, depth_interval)[1]
 
 
 def _sharded_steps(images, cams, max_d, world, rank, stages=None):
-    """example.infer_multiview for this rank's share of the source views, as a generator: local compute runs
+    """pipeline.infer_multiview for this rank's share of the source views, as a generator: local compute runs
     between the yields, every yield is a communication step all ranks of the group must perform.
     Returns the full-resolution inverse-depth map (1,H,W,1), identical on every rank of the group.
     A rank may own no forward direction (more ranks than sources with split directions) or nothing at all (more ranks
     than directions): it still takes part in every exchange and ends with the same map."""
-    from .atvsnet import example as ex
     stages = stages or HipLocalStages()
     n = images.shape[1]
     mine = plan(n, world)[rank]
     fwd = sorted(v for kind, v in mine if kind == 'fwd')
     rev = sorted(v for kind, v in mine if kind == 'rev')
-    depth_start, depth_interval = ex.depth_range(cams)
+    depth_start, depth_interval = depth_range(cams)
     dev = images.device
     h, w = images.shape[2] // 4, images.shape[3] // 4
     dv_all = torch.zeros((n - 1, h, w), dtype=torch.float32, device=dev)
@@ -327,7 +325,7 @@ def _sharded_steps(images, cams, max_d, world, rank, stages=None):
 
 
 def infer_multiview_sharded(images, cams, max_d=None, group=None, view_streams=True, stages=None):
-    """example.infer_multiview with the source views sharded over the process group (every launch issued from
+    """pipeline.infer_multiview with the source views sharded over the process group (every launch issued from
     Python).  Every rank returns the same full-resolution inverse-depth map (1,H,W,1).  (view_streams is accepted
     for compatibility: a rank evaluates its views in one batched pass.  stages: test hook, see HipLocalStages.)"""
     max_d = FLAGS.max_d if max_d is None else max_d
@@ -349,13 +347,8 @@ class ShardedGraphedInference(object):
         self.images, self.cams = images.clone(), cams.clone()
         world, rank = dist.get_world_size(group), dist.get_rank(group)
         dev = images.device
-        # warm-up on a side stream: weight packing / uploads, function attributes, communicator set-up
-        side = torch.cuda.Stream(dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            _drive(_sharded_steps(self.images, self.cams, self.max_d, world, rank), group)
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
+        # the warm-up sets up the communicator too
+        warm_up(lambda: _drive(_sharded_steps(self.images, self.cams, self.max_d, world, rank), group), dev)
         self.graphs, self.colls = [], []
         pool = torch.cuda.graph_pool_handle()
         gen = _sharded_steps(self.images, self.cams, self.max_d, world, rank)
@@ -386,7 +379,7 @@ class ShardedGraphedInference(object):
                 self._comm(item)
                 self.colls.append(item)
         torch.cuda.synchronize(dev)
-        self._weights = (ops.cache_snapshot(), variables.default_store().device_snapshot())
+        self._weights = pinned_weights()
 
     def _comm(self, item):
         if item[0] == 'comm':
