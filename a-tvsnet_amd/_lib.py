@@ -95,13 +95,18 @@ def build(force=False, verbose=False):
     return LIB_PATH
 
 
+def header_macro(name):
+    """The integer include/atvsnet_hip.h gives `name` with #define; a header without it raises."""
+    with open(HEADER) as f:
+        m = re.search(r'#define\s+%s\s+(\d+)' % re.escape(name), f.read())
+    if not m:
+        raise RuntimeError('%s defines no %s' % (HEADER, name))
+    return int(m.group(1))
+
+
 def header_abi_version():
     """ATVS_ABI_VERSION of include/atvsnet_hip.h."""
-    with open(HEADER) as f:
-        m = re.search(r'#define\s+ATVS_ABI_VERSION\s+(\d+)', f.read())
-    if not m:
-        raise RuntimeError('%s defines no ATVS_ABI_VERSION' % HEADER)
-    return int(m.group(1))
+    return header_macro('ATVS_ABI_VERSION')
 
 
 _ARG = {'int': ctypes.c_int, 'long': ctypes.c_long, 'float': ctypes.c_float, 'double': ctypes.c_double}

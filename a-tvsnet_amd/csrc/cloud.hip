@@ -12,8 +12,8 @@
 // order of the points inside a cell, launch shape) cannot be seen in it.  A tolerance tau (double) counts a query when
 // (double)d2min <= tau * tau (formed in double); tau > R is an argument error (distances beyond R are not known).
 //
-// THE GRID (cloud_grid.h: shared with cloud_knn.hip).  A uniform grid of cubic cells of edge h over the bounding box of the finite
-// reference points, built by counting sort:
+// THE GRID (cloud_grid.h: shared with cloud_knn.hip, as the walk over the 27 cells and the search's host side are).  A uniform grid
+// of cubic cells of edge h over the bounding box of the finite reference points, built by counting sort:
 //   bbox     per-wave minimum / maximum, then integer atomic max on order-preserving bit patterns (no float atomics anywhere);
 //   params   one thread: origin = the box's minimum corner, h, cells per axis (all in double, kept in the grid's header);
 //   count    cell of every point -> keys[i], one integer atomic add per point into the cell's counter;
@@ -51,7 +51,7 @@
 
 namespace {
 
-constexpr int kMaxTolerances = 16;
+constexpr int kMaxTolerances = ATVS_CLOUD_MAX_TOLERANCES;
 
 struct Tolerances {
   double t2[kMaxTolerances];
@@ -102,23 +102,10 @@ __global__ __launch_bounds__(kThreads) void cloud_nearest_kernel(const GridHeade
   const unsigned long long none = (0x7f800000ull << 32) | 0xffffffffull;
   unsigned long long best = none;
   if (j < (long)qS[g.ncells]) {                             // not in the bucket of far / non-finite queries
-    int cx, cy, cz;
-    cell_of(g, q.x, q.y, q.z, &cx, &cy, &cz);
-    const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dims[0] - 1);
-    for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dims[2] - 1); ++z) {
-      for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dims[1] - 1); ++y) {
-        const int row = (z * g.dims[1] + y) * g.dims[0];
-        const unsigned b = S[row + x0], e = S[row + x1 + 1];
-#pragma unroll 4
-        for (unsigned p = b; p < e; ++p) {
-          const float4 r = rec[p];
-          const float dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z;
-          const float d2 = (dx * dx + dy * dy) + dz * dz;
-          const unsigned long long key = ((unsigned long long)__float_as_uint(d2) << 32) | (unsigned)__float_as_int(r.w);
-          best = key < best ? key : best;
-        }
-      }
-    }
+    walk<4>(g, S, rec, q, [&](unsigned bits, unsigned i) {
+      const unsigned long long key = ((unsigned long long)bits << 32) | i;
+      best = key < best ? key : best;
+    });
   }
   float d2 = __uint_as_float((unsigned)(best >> 32));
   int idx = (int)(unsigned)(best & 0xffffffffull);
@@ -179,10 +166,7 @@ extern "C" int atvs_cloud_grid_build(const float* points, long n, float radius, 
 }
 
 extern "C" int atvs_cloud_nearest_scratch_size(long n, long m, long* bytes) {
-  if (!bytes) return ATVS_ERR_NULL;
-  if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
-  *bytes = (long)layout_for(cell_cap(n), m, 0).total;
-  return ATVS_OK;
+  return query_scratch_size(n, m, bytes);
 }
 
 extern "C" int atvs_cloud_nearest(const void* grid, long grid_bytes, long n, const float* queries, long m, void* scratch,
@@ -190,20 +174,12 @@ extern "C" int atvs_cloud_nearest(const void* grid, long grid_bytes, long n, con
   if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
   if (m == 0) return ATVS_OK;
   if (!grid || !queries || !scratch || !d2 || !idx) return ATVS_ERR_NULL;
-  const long cap = cell_cap(n);
-  const Layout G = layout_for(cap, n, kHeaderBytes), Q = layout_for(cap, m, 0);
-  if (grid_bytes < (long)G.total || scratch_bytes < (long)Q.total) return ATVS_ERR_SHAPE;
   hipStream_t st = as_stream(stream);
-  const char* g = static_cast<const char*>(grid);
-  const GridHeader* hdr = reinterpret_cast<const GridHeader*>(g);
-  char* s = static_cast<char*>(scratch);
-  const int rc = counting_sort(queries, m, hdr, s, Q, cap, st);
-  if (rc != ATVS_OK) return rc;
-  hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)cdiv(m, kThreads)), dim3(kThreads), 0, st, hdr,
-                     reinterpret_cast<const unsigned*>(g + G.S), reinterpret_cast<const float4*>(g + G.rec),
-                     reinterpret_cast<const unsigned*>(s + Q.S), reinterpret_cast<const float4*>(s + Q.rec), m, d2, idx);
-  ATVS_LAUNCH_CHECK();
-  return ATVS_OK;
+  return search(grid, grid_bytes, n, queries, m, scratch, scratch_bytes, st,
+                [&](const GridHeader* hdr, const unsigned* S, const float4* rec, const unsigned* qS, const float4* qrec) {
+                  hipLaunchKernelGGL(cloud_nearest_kernel, dim3((unsigned)cdiv(m, kThreads)), dim3(kThreads), 0, st, hdr, S, rec, qS, qrec,
+                                     m, d2, idx);
+                });
 }
 
 extern "C" int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, float radius, long long* counts,

@@ -1,7 +1,8 @@
 // The uniform grid of the point-cloud searches, shared by cloud.hip (the nearest reference point) and cloud_knn.hip (the k nearest,
 // the count inside the radius, the bounding box): the grid's header, the cell of a point, the buffers' layout, the bounding-box
-// reduction and the counting sort that orders the reference points and the queries by cell.  cloud.hip's header comment says what
-// the grid is and why 27 cells suffice; nothing here can be seen in a result.
+// reduction, the counting sort that orders the reference points and the queries by cell, THE WALK over the 27 cells around a query
+// (walk) and THE SEARCH every entry point launches through (search: the layout check, the queries' sort, the pointers).
+// cloud.hip's header comment says what the grid is and why 27 cells suffice; nothing here can be seen in a result.
 #pragma once
 #include <math.h>
 
@@ -10,7 +11,6 @@
 
 namespace {
 
-constexpr long kMaxPoints = 1L << 30;
 constexpr long kMinCells = 4096;
 constexpr long kMaxCells = 1L << 28;
 constexpr long kCellsPerPoint = 8;
@@ -26,9 +26,7 @@ struct GridHeader {                // the first kHeaderBytes of a grid
 };
 static_assert(sizeof(GridHeader) <= kHeaderBytes, "header");
 
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 inline long cell_cap(long n) { return n * kCellsPerPoint < kMinCells ? kMinCells : (n * kCellsPerPoint > kMaxCells ? kMaxCells : n * kCellsPerPoint); }
-inline long scan_tiles(long cap) { return (cap + 1 + kScanTile - 1) / kScanTile; }
 
 // One counting sort's buffers behind `front` bytes: S (cap + 2 counters), records (16 B per point), keys (4 B per point), tile sums.
 struct Layout {
@@ -40,7 +38,7 @@ inline Layout layout_for(long cap, long npts, size_t front) {
   L.rec = L.S + align256((size_t)(cap + 2) * sizeof(unsigned));
   L.keys = L.rec + align256((size_t)npts * sizeof(float4));
   L.tiles = L.keys + align256((size_t)npts * sizeof(int));
-  L.total = L.tiles + align256((size_t)scan_tiles(cap) * sizeof(unsigned));
+  L.total = L.tiles + align256((size_t)scan_tiles(cap + 1) * sizeof(unsigned));
   return L;
 }
 
@@ -50,11 +48,6 @@ __device__ __forceinline__ unsigned enc(float f) {
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 __device__ __forceinline__ float dec(unsigned e) { return __uint_as_float((e & 0x80000000u) ? (e ^ 0x80000000u) : ~e); }
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  const float big = __uint_as_float(0x7f800000u);
-  return fabsf(x) < big && fabsf(y) < big && fabsf(z) < big;        // NaN fails every comparison
-}
 
 // The quotient the margin argument speaks of; ONE definition for the grid's size, the reference points and the queries.
 __device__ __forceinline__ double cell_coord(float x, double origin, double h) { return floor(((double)x - origin) / h); }
@@ -120,30 +113,60 @@ inline int counting_sort(const float* pts, long npts, const GridHeader* hdr, cha
   const dim3 per_point((unsigned)cdiv(npts, kThreads));
   hipLaunchKernelGGL(cloud_count_kernel, per_point, dim3(kThreads), 0, st, pts, npts, hdr, keys, C);
   ATVS_LAUNCH_CHECK();
-  const long count = cap + 1, nt = scan_tiles(cap);
-  hipLaunchKernelGGL(cloud_scan_tile_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, C, count, tiles);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(1024), 0, st, tiles, nt);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_scan_add_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, C, count, (const unsigned*)tiles);
-  ATVS_LAUNCH_CHECK();
+  const int rc = exclusive_scan(C, cap + 1, tiles, st);
+  if (rc != ATVS_OK) return rc;
   hipLaunchKernelGGL(cloud_scatter_kernel, per_point, dim3(kThreads), 0, st, pts, npts, (const int*)keys, C, rec);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }
 
-// The query side of a search, the same for every kernel that walks the grid: the layouts of the grid and of the queries' sort
-// inside the caller's buffers, checked against their sizes.
-struct Search {
-  Layout G, Q;
-  long cap;
-};
-inline int search_layout(long n, long m, long grid_bytes, long scratch_bytes, Search* s) {
+// What atvs_cloud_nearest_scratch_size and atvs_cloud_knn_scratch_size report: the queries' sort.
+inline int query_scratch_size(long n, long m, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
   if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
-  s->cap = cell_cap(n);
-  s->G = layout_for(s->cap, n, kHeaderBytes);
-  s->Q = layout_for(s->cap, m, 0);
-  if (grid_bytes < (long)s->G.total || scratch_bytes < (long)s->Q.total) return ATVS_ERR_SHAPE;
+  *bytes = (long)layout_for(cell_cap(n), m, 0).total;
+  return ATVS_OK;
+}
+
+// Calls visit(d2 bits, reference index) for every finite reference point in the 27 cells around the sorted query q, 9 contiguous
+// runs of records; Unroll: of the loop over a run.  S and rec are the kernels' own __restrict__ parameters: not said again here.
+template <int Unroll, class Visit>
+__device__ __forceinline__ void walk(const GridHeader& g, const unsigned* S, const float4* rec, const float4& q, Visit visit) {
+  int cx, cy, cz;
+  cell_of(g, q.x, q.y, q.z, &cx, &cy, &cz);
+  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dims[0] - 1);
+  for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dims[2] - 1); ++z) {
+    for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dims[1] - 1); ++y) {
+      const int row = (z * g.dims[1] + y) * g.dims[0];
+      const unsigned b = S[row + x0], e = S[row + x1 + 1];
+#pragma unroll Unroll
+      for (unsigned p = b; p < e; ++p) {
+        const float4 r = rec[p];
+        const float dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z;
+        const float d2 = (dx * dx + dy * dy) + dz * dz;
+        visit(__float_as_uint(d2), (unsigned)__float_as_int(r.w));
+      }
+    }
+  }
+}
+
+// The query side of a search, the same for every kernel that walks the grid: the layouts of the grid and of the queries' sort
+// inside the caller's buffers, checked against their sizes; the queries' counting sort; then `launch(hdr, S, rec, qS, qrec)`.
+template <class Launch>
+int search(const void* grid, long grid_bytes, long n, const float* queries, long m, void* scratch, long scratch_bytes, hipStream_t st,
+           Launch launch) {
+  if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
+  const long cap = cell_cap(n);
+  const Layout G = layout_for(cap, n, kHeaderBytes), Q = layout_for(cap, m, 0);
+  if (grid_bytes < (long)G.total || scratch_bytes < (long)Q.total) return ATVS_ERR_SHAPE;
+  const char* g = static_cast<const char*>(grid);
+  const GridHeader* hdr = reinterpret_cast<const GridHeader*>(g);
+  char* q = static_cast<char*>(scratch);
+  const int rc = counting_sort(queries, m, hdr, q, Q, cap, st);
+  if (rc != ATVS_OK) return rc;
+  launch(hdr, reinterpret_cast<const unsigned*>(g + G.S), reinterpret_cast<const float4*>(g + G.rec),
+         reinterpret_cast<const unsigned*>(q + Q.S), reinterpret_cast<const float4*>(q + Q.rec));
+  ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }
 

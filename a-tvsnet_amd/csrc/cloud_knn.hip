@@ -3,10 +3,10 @@
 // The definitions are in include/atvsnet_hip.h; tests/cloud_knn_restated.py restates them with numpy.  Built with
 // -ffp-contract=off; integer atomics only (the counting sort, the bounding box), so every output is a function of its inputs.
 //
-// THE SEARCH is cloud.hip's: the grid of atvs_cloud_grid_build (cloud_grid.h), the queries sorted by the same cells, one lane per
-// query in cell order over the 9 contiguous record runs of its 27 cells, the float32 d2 = (dx*dx + dy*dy) + dz*dz and the key
-// (bits(d2) << 32) | index, whose unsigned order is the order of (d2, index).  cloud.hip's margin argument is about pairs with
-// (double)d2 <= R^2, so it covers every neighbour here as it covers the nearest one.
+// THE SEARCH is cloud_grid.h's (walk, search), the one cloud.hip runs: the grid of atvs_cloud_grid_build, the queries sorted by the
+// same cells, one lane per query in cell order over the 9 contiguous record runs of its 27 cells, the float32
+// d2 = (dx*dx + dy*dy) + dz*dz and the key (bits(d2) << 32) | index, whose unsigned order is the order of (d2, index).  cloud.hip's
+// margin argument is about pairs with (double)d2 <= R^2, so it covers every neighbour here as it covers the nearest one.
 //
 // THE RADIUS TEST AS A KEY.  d2 >= +0 orders as its bits do, so { d2 : (double)d2 <= R^2 } is { d2 : bits(d2) <= bits(r2f) } with r2f
 // the largest float32 whose double is <= R^2 (the header's r2 rounded to float32, one step down if that rounded up).  `limit` =
@@ -39,28 +39,6 @@ __device__ __forceinline__ unsigned radius_bits(double r2) {
   return b;
 }
 
-// Calls visit(d2 bits, reference index) for every finite reference point in the 27 cells around the sorted query j.
-template <class Visit>
-__device__ __forceinline__ void walk(const GridHeader& g, const unsigned* __restrict__ S, const float4* __restrict__ rec, const float4& q,
-                                     Visit visit) {
-  int cx, cy, cz;
-  cell_of(g, q.x, q.y, q.z, &cx, &cy, &cz);
-  const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.dims[0] - 1);
-  for (int z = max(cz - 1, 0); z <= min(cz + 1, g.dims[2] - 1); ++z) {
-    for (int y = max(cy - 1, 0); y <= min(cy + 1, g.dims[1] - 1); ++y) {
-      const int row = (z * g.dims[1] + y) * g.dims[0];
-      const unsigned b = S[row + x0], e = S[row + x1 + 1];
-#pragma unroll 2
-      for (unsigned p = b; p < e; ++p) {
-        const float4 r = rec[p];
-        const float dx = q.x - r.x, dy = q.y - r.y, dz = q.z - r.z;
-        const float d2 = (dx * dx + dy * dy) + dz * dz;
-        visit(__float_as_uint(d2), (unsigned)__float_as_int(r.w));
-      }
-    }
-  }
-}
-
 template <int K>
 __global__ __launch_bounds__(kThreads) void cloud_knn_kernel(const GridHeader* __restrict__ hdr, const unsigned* __restrict__ S,
                                                              const float4* __restrict__ rec, const unsigned* __restrict__ qS,
@@ -77,7 +55,7 @@ __global__ __launch_bounds__(kThreads) void cloud_knn_kernel(const GridHeader* _
 #pragma unroll
   for (int t = 0; t < K; ++t) a[t] = limit;
   if (j < (long)qS[g.ncells]) {                            // not in the bucket of far / non-finite queries
-    walk(g, S, rec, q, [&](unsigned bits, unsigned i) {
+    walk<2>(g, S, rec, q, [&](unsigned bits, unsigned i) {
       unsigned long long x = ((unsigned long long)bits << 32) | i;
       if (x < a[K - 1] && i != self) {
 #pragma unroll
@@ -114,7 +92,7 @@ __global__ __launch_bounds__(kThreads) void cloud_radius_count_kernel(const Grid
   const unsigned rb = radius_bits(g.r2);
   int c = 0;
   if (j < (long)qS[g.ncells])
-    walk(g, S, rec, q, [&](unsigned bits, unsigned i) { c += (bits <= rb && i != self) ? 1 : 0; });
+    walk<2>(g, S, rec, q, [&](unsigned bits, unsigned i) { c += (bits <= rb && i != self) ? 1 : 0; });
   count[orig] = c;
 }
 
@@ -203,31 +181,10 @@ inline StatLayout stat_layout(long m) {
   return L;
 }
 
-// The queries' counting sort, then `launch(hdr, S, rec, qS, qrec)`.
-template <class Launch>
-int search(const void* grid, long grid_bytes, long n, const float* queries, long m, void* scratch, long scratch_bytes, hipStream_t st,
-           Launch launch) {
-  Search s;
-  const int rc = search_layout(n, m, grid_bytes, scratch_bytes, &s);
-  if (rc != ATVS_OK) return rc;
-  const char* g = static_cast<const char*>(grid);
-  const GridHeader* hdr = reinterpret_cast<const GridHeader*>(g);
-  char* q = static_cast<char*>(scratch);
-  const int rs = counting_sort(queries, m, hdr, q, s.Q, s.cap, st);
-  if (rs != ATVS_OK) return rs;
-  launch(hdr, reinterpret_cast<const unsigned*>(g + s.G.S), reinterpret_cast<const float4*>(g + s.G.rec),
-         reinterpret_cast<const unsigned*>(q + s.Q.S), reinterpret_cast<const float4*>(q + s.Q.rec));
-  ATVS_LAUNCH_CHECK();
-  return ATVS_OK;
-}
-
 }  // namespace
 
 extern "C" int atvs_cloud_knn_scratch_size(long n, long m, long* bytes) {
-  if (!bytes) return ATVS_ERR_NULL;
-  if (n < 0 || n > kMaxPoints || m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
-  *bytes = (long)layout_for(cell_cap(n), m, 0).total;
-  return ATVS_OK;
+  return query_scratch_size(n, m, bytes);
 }
 
 extern "C" int atvs_cloud_knn(const void* grid, long grid_bytes, long n, const float* queries, long m, int k, int exclude_same_index,

@@ -28,14 +28,11 @@
 
 namespace {
 
-constexpr long kMaxPoints = 1L << 30;
 constexpr int kWords = 19;                             // pair count (int64) + 18 doubles
 constexpr long kMinSlots = 1024;
 constexpr size_t kVoxelHeader = 256;
 constexpr unsigned long long kEmpty = ~0ull;
 constexpr double kCellLimit = 2097152.0;               // 2^21 cells per axis
-
-__host__ __device__ inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 struct Matrix12 {
   double t[12];
@@ -94,7 +91,6 @@ struct VoxelLayout {
   long slots;
   int shift;                                                          // 64 - log2(slots)
 };
-inline long scan_tiles_for(long count) { return (count + kScanTile - 1) / kScanTile; }
 inline VoxelLayout voxel_layout(long n) {
   VoxelLayout L;
   long slots = kMinSlots;
@@ -113,13 +109,8 @@ inline VoxelLayout voxel_layout(long n) {
   L.flags = L.cnt + align256((size_t)slots * 4);
   L.slot = L.flags + align256((size_t)(n + 1) * 4);
   L.tiles = L.slot + align256((size_t)n * 4);
-  L.total = L.tiles + align256((size_t)scan_tiles_for(n + 1) * 4);
+  L.total = L.tiles + align256((size_t)scan_tiles(n + 1) * 4);
   return L;
-}
-
-__device__ __forceinline__ bool finite3(float x, float y, float z) {
-  const float big = __uint_as_float(0x7f800000u);
-  return fabsf(x) < big && fabsf(y) < big && fabsf(z) < big;
 }
 
 // cell c and fraction u of one coordinate; false when the cell leaves [0, 2^21)
@@ -147,30 +138,54 @@ __device__ __forceinline__ int voxel_find_slot(const unsigned long long* c, unsi
   return -1;
 }
 
+// The table's front end for point i (ONE definition for the down-sampler and the shares): the slot of its voxel and its fractions
+// u[] inside it; -1 for a non-finite point, and for one whose cell leaves [0, 2^21), which raises *err.
+__device__ __forceinline__ int voxel_slot_of(const float* __restrict__ pts, long i, const VoxelArgs& A, long slots, int shift,
+                                             unsigned long long* __restrict__ keys, int* __restrict__ err, unsigned long long* u) {
+  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
+  if (!finite3(x, y, z)) return -1;
+  unsigned long long c[3];
+  const bool ok = voxel_coord(x, A.origin[0], A.voxel, &c[0], &u[0]) & voxel_coord(y, A.origin[1], A.voxel, &c[1], &u[1]) &
+                  voxel_coord(z, A.origin[2], A.voxel, &c[2], &u[2]);
+  if (!ok) {
+    atomicOr(err, 1);
+    return -1;
+  }
+  return voxel_find_slot(c, keys, slots, shift);
+}
+
+// voxel and origin as the caller gave them -> A; false (voxel <= 0, or either not finite): ATVS_ERR_ARG
+inline bool voxel_args(double voxel, const double* origin, VoxelArgs* A) {
+  const double big = 1.7976931348623157e308;
+  *A = VoxelArgs{{origin[0], origin[1], origin[2]}, voxel};
+  return voxel > 0.0 && voxel <= big && fabs(origin[0]) <= big && fabs(origin[1]) <= big && fabs(origin[2]) <= big;
+}
+
+// An empty table in the scratch `s`: the header (the error word) zeroed, [keys, ones_end) all-ones (kEmpty); -> err, keys, slot_of
+struct VoxelTable {
+  int* err;
+  unsigned long long* keys;
+  int* slot_of;
+};
+inline bool voxel_table(char* s, size_t keys, size_t ones_end, size_t slot, hipStream_t st, VoxelTable* T) {
+  *T = VoxelTable{reinterpret_cast<int*>(s), reinterpret_cast<unsigned long long*>(s + keys), reinterpret_cast<int*>(s + slot)};
+  return hipMemsetAsync(s, 0, kVoxelHeader, st) == hipSuccess && hipMemsetAsync(s + keys, 0xff, ones_end - keys, st) == hipSuccess;
+}
+
 __global__ __launch_bounds__(kThreads) void cloud_voxel_insert_kernel(const float* __restrict__ pts, long n, VoxelArgs A, long slots, int shift,
                                                                       unsigned long long* __restrict__ keys, unsigned* __restrict__ first,
                                                                       unsigned long long* __restrict__ sums, unsigned* __restrict__ cnt,
                                                                       int* __restrict__ slot_of, int* __restrict__ err) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-  int s = -1;
-  if (finite3(x, y, z)) {
-    unsigned long long c[3], u[3];
-    const bool ok = voxel_coord(x, A.origin[0], A.voxel, &c[0], &u[0]) & voxel_coord(y, A.origin[1], A.voxel, &c[1], &u[1]) &
-                    voxel_coord(z, A.origin[2], A.voxel, &c[2], &u[2]);
-    if (!ok) {
-      atomicOr(err, 1);
-    } else {
-      s = voxel_find_slot(c, keys, slots, shift);
-      if (s >= 0) {
-        atomicAdd(cnt + s, 1u);
-        atomicAdd(sums + (long)s * 3 + 0, u[0]);
-        atomicAdd(sums + (long)s * 3 + 1, u[1]);
-        atomicAdd(sums + (long)s * 3 + 2, u[2]);
-        atomicMin(first + s, (unsigned)i);
-      }
-    }
+  unsigned long long u[3];
+  const int s = voxel_slot_of(pts, i, A, slots, shift, keys, err, u);
+  if (s >= 0) {
+    atomicAdd(cnt + s, 1u);
+    atomicAdd(sums + (long)s * 3 + 0, u[0]);
+    atomicAdd(sums + (long)s * 3 + 1, u[1]);
+    atomicAdd(sums + (long)s * 3 + 2, u[2]);
+    atomicMin(first + s, (unsigned)i);
   }
   slot_of[i] = s;
 }
@@ -246,19 +261,8 @@ __global__ __launch_bounds__(kThreads) void cloud_share_insert_kernel(const floa
                                                                       int* __restrict__ err) {
   const long i = (long)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
-  const float x = pts[i * 3 + 0], y = pts[i * 3 + 1], z = pts[i * 3 + 2];
-  int s = -1;
-  if (finite3(x, y, z)) {
-    unsigned long long c[3], u[3];
-    const bool ok = voxel_coord(x, A.origin[0], A.voxel, &c[0], &u[0]) & voxel_coord(y, A.origin[1], A.voxel, &c[1], &u[1]) &
-                    voxel_coord(z, A.origin[2], A.voxel, &c[2], &u[2]);
-    if (!ok) {
-      atomicOr(err, 1);
-    } else {
-      s = voxel_find_slot(c, keys, slots, shift);
-    }
-  }
-  slot_of[i] = s;
+  unsigned long long u[3];
+  slot_of[i] = voxel_slot_of(pts, i, A, slots, shift, keys, err, u);
 }
 
 __global__ __launch_bounds__(kThreads) void cloud_share_count_kernel(const int* __restrict__ slot_of, const float* __restrict__ d2,
@@ -379,45 +383,31 @@ extern "C" int atvs_cloud_voxel_downsample(const float* points, long n, double v
                                            float* out_points, long long* out_count, int* out_first, atvs_stream_t stream) {
   if (n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
   if (!origin || !out_count || (n > 0 && (!points || !scratch || !out_points || !out_first))) return ATVS_ERR_NULL;
-  if (!(voxel > 0.0) || !(voxel <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
   VoxelArgs A;
-  A.voxel = voxel;
-  for (int k = 0; k < 3; ++k) {
-    if (!(fabs(origin[k]) <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
-    A.origin[k] = origin[k];
-  }
+  if (!voxel_args(voxel, origin, &A)) return ATVS_ERR_ARG;
   hipStream_t st = as_stream(stream);
   if (n == 0) return hipMemsetAsync(out_count, 0, sizeof(long long), st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
   const VoxelLayout L = voxel_layout(n);
   if (scratch_bytes < (long)L.total) return ATVS_ERR_SHAPE;
   char* s = static_cast<char*>(scratch);
-  int* err = reinterpret_cast<int*>(s);
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s + L.keys);
+  VoxelTable T;
+  if (!voxel_table(s, L.keys, L.zero, L.slot, st, &T)) return ATVS_ERR_LAUNCH;      // `first` lies behind the keys: all-ones too
   unsigned* first = reinterpret_cast<unsigned*>(s + L.first);
   unsigned long long* sums = reinterpret_cast<unsigned long long*>(s + L.sums);
   unsigned* cnt = reinterpret_cast<unsigned*>(s + L.cnt);
   unsigned* flags = reinterpret_cast<unsigned*>(s + L.flags);
-  int* slot_of = reinterpret_cast<int*>(s + L.slot);
-  unsigned* tiles = reinterpret_cast<unsigned*>(s + L.tiles);
-  if (hipMemsetAsync(s, 0, kVoxelHeader, st) != hipSuccess) return ATVS_ERR_LAUNCH;
-  if (hipMemsetAsync(s + L.keys, 0xff, L.zero - L.keys, st) != hipSuccess) return ATVS_ERR_LAUNCH;
   if (hipMemsetAsync(s + L.zero, 0, L.slot - L.zero, st) != hipSuccess) return ATVS_ERR_LAUNCH;
   const dim3 per_point((unsigned)cdiv(n, kThreads));
-  hipLaunchKernelGGL(cloud_voxel_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, keys, first, sums, cnt,
-                     slot_of, err);
+  hipLaunchKernelGGL(cloud_voxel_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, T.keys, first, sums, cnt,
+                     T.slot_of, T.err);
   ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_voxel_flag_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, (const unsigned*)first, n, flags);
+  hipLaunchKernelGGL(cloud_voxel_flag_kernel, per_point, dim3(kThreads), 0, st, (const int*)T.slot_of, (const unsigned*)first, n, flags);
   ATVS_LAUNCH_CHECK();
-  const long count = n + 1, nt = scan_tiles_for(count);     // flags[n] = 0: after the scan it is the number of voxels
-  hipLaunchKernelGGL(cloud_scan_tile_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, flags, count, tiles);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(1024), 0, st, tiles, nt);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_scan_add_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, flags, count, (const unsigned*)tiles);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(cloud_voxel_emit_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, n, A,
-                     (const unsigned long long*)keys, (const unsigned*)first, (const unsigned long long*)sums, (const unsigned*)cnt,
-                     (const unsigned*)flags, (const int*)err, out_points, out_count, out_first);
+  const int rc = exclusive_scan(flags, n + 1, reinterpret_cast<unsigned*>(s + L.tiles), st);      // flags[n] = 0 -> the number of voxels
+  if (rc != ATVS_OK) return rc;
+  hipLaunchKernelGGL(cloud_voxel_emit_kernel, per_point, dim3(kThreads), 0, st, (const int*)T.slot_of, n, A,
+                     (const unsigned long long*)T.keys, (const unsigned*)first, (const unsigned long long*)sums, (const unsigned*)cnt,
+                     (const unsigned*)flags, (const int*)T.err, out_points, out_count, out_first);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }
@@ -432,15 +422,10 @@ extern "C" int atvs_cloud_voxel_shares_scratch_size(long n, long* bytes) {
 extern "C" int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* excess, long n, double voxel, const double* origin,
                                        const double* tolerances, int n_tolerances, double margin, void* scratch, long scratch_bytes,
                                        long long* out, atvs_stream_t stream) {
-  if (n < 0 || n > kMaxPoints || n_tolerances < 1 || n_tolerances > 16) return ATVS_ERR_SHAPE;
+  if (n < 0 || n > kMaxPoints || n_tolerances < 1 || n_tolerances > ATVS_CLOUD_MAX_TOLERANCES) return ATVS_ERR_SHAPE;
   if (!origin || !tolerances || !out || (n > 0 && (!points || !d2 || !scratch))) return ATVS_ERR_NULL;
-  if (!(voxel > 0.0) || !(voxel <= 1.7976931348623157e308) || margin != margin) return ATVS_ERR_ARG;
   VoxelArgs A;
-  A.voxel = voxel;
-  for (int k = 0; k < 3; ++k) {
-    if (!(fabs(origin[k]) <= 1.7976931348623157e308)) return ATVS_ERR_ARG;
-    A.origin[k] = origin[k];
-  }
+  if (!voxel_args(voxel, origin, &A) || margin != margin) return ATVS_ERR_ARG;
   for (int k = 0; k < n_tolerances; ++k)
     if (!(tolerances[k] >= 0.0)) return ATVS_ERR_ARG;        // NaN or negative; +inf is allowed
   const ShareLayout L = share_layout(n);
@@ -449,14 +434,11 @@ extern "C" int atvs_cloud_voxel_shares(const float* points, const float* d2, con
   if (hipMemsetAsync(out, 0, (size_t)n_tolerances * 4 * sizeof(long long), st) != hipSuccess) return ATVS_ERR_LAUNCH;
   if (n == 0) return ATVS_OK;
   char* s = static_cast<char*>(scratch);
-  int* err = reinterpret_cast<int*>(s);
-  unsigned long long* keys = reinterpret_cast<unsigned long long*>(s + L.keys);
+  VoxelTable T;
+  if (!voxel_table(s, L.keys, L.cnt, L.slot, st, &T)) return ATVS_ERR_LAUNCH;
   unsigned* cnt = reinterpret_cast<unsigned*>(s + L.cnt);
-  int* slot_of = reinterpret_cast<int*>(s + L.slot);
-  if (hipMemsetAsync(s, 0, kVoxelHeader, st) != hipSuccess) return ATVS_ERR_LAUNCH;
-  if (hipMemsetAsync(s + L.keys, 0xff, L.cnt - L.keys, st) != hipSuccess) return ATVS_ERR_LAUNCH;
   const dim3 per_point((unsigned)cdiv(n, kThreads)), per_slot((unsigned)cdiv(L.slots, kThreads));
-  hipLaunchKernelGGL(cloud_share_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, keys, slot_of, err);
+  hipLaunchKernelGGL(cloud_share_insert_kernel, per_point, dim3(kThreads), 0, st, points, n, A, L.slots, L.shift, T.keys, T.slot_of, T.err);
   ATVS_LAUNCH_CHECK();
   unsigned long long* res = reinterpret_cast<unsigned long long*>(out);
   for (int k0 = 0; k0 < n_tolerances; k0 += kSharePass) {
@@ -465,10 +447,10 @@ extern "C" int atvs_cloud_voxel_shares(const float* points, const float* d2, con
     S.count = n_tolerances - k0 < kSharePass ? n_tolerances - k0 : kSharePass;
     for (int k = 0; k < kSharePass; ++k) S.tau2[k] = k < S.count ? tolerances[k0 + k] * tolerances[k0 + k] : 0.0;
     if (hipMemsetAsync(s + L.cnt, 0, L.slot - L.cnt, st) != hipSuccess) return ATVS_ERR_LAUNCH;
-    hipLaunchKernelGGL(cloud_share_count_kernel, per_point, dim3(kThreads), 0, st, (const int*)slot_of, d2, excess, n, S, cnt);
+    hipLaunchKernelGGL(cloud_share_count_kernel, per_point, dim3(kThreads), 0, st, (const int*)T.slot_of, d2, excess, n, S, cnt);
     ATVS_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cloud_share_reduce_kernel, per_slot, dim3(kThreads), 0, st, (const unsigned long long*)keys, L.slots,
-                       (const unsigned*)cnt, S.count, n_tolerances, (const int*)err, res + 4 * k0, res);
+    hipLaunchKernelGGL(cloud_share_reduce_kernel, per_slot, dim3(kThreads), 0, st, (const unsigned long long*)T.keys, L.slots,
+                       (const unsigned*)cnt, S.count, n_tolerances, (const int*)T.err, res + 4 * k0, res);
     ATVS_LAUNCH_CHECK();
   }
   return ATVS_OK;

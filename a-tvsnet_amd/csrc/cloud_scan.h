@@ -1,16 +1,16 @@
-// The exclusive prefix sum of unsigned counters shared by the point-cloud kernels (cloud.hip: the counting sorts' cell starts;
-// cloud_register.hip: the output positions of the voxel down-sampler).  Three launches: tiles of kScanTile counters scanned in
-// place, the tile sums scanned by one workgroup, the sums added back.  Integer arithmetic only: exact in any launch shape.
+// The exclusive prefix sum of unsigned counters shared by the point-cloud kernels: exclusive_scan(), called by cloud_grid.h's
+// counting_sort (the cell starts) and cloud_register.hip's atvs_cloud_voxel_downsample (the output positions).  Three launches: tiles
+// of kScanTile counters scanned in place, the tile sums scanned by one workgroup, the sums added back.  Integer arithmetic only: exact
+// in any launch shape.  cloud_grid.h, cloud_tree.h and cloud_register.hip take cloud_common.h's constants through this file.
 #pragma once
 #include "common.h"
+#include "cloud_common.h"
 
 namespace {
 
-constexpr int kThreads = 256;
 constexpr int kScanItems = 8;                          // counters per thread of a scan tile
 constexpr int kScanTile = kThreads * kScanItems;       // 2048
 
-// Exclusive scan of `count` counters in place: tiles of kScanTile, the tile sums by one workgroup, then added back.
 __device__ __forceinline__ unsigned wave_inclusive(unsigned v, int lane) {
   for (int off = 1; off < 64; off <<= 1) {
     const unsigned y = (unsigned)__shfl_up((int)v, off);
@@ -74,6 +74,20 @@ __global__ __launch_bounds__(kThreads) void cloud_scan_add_kernel(unsigned* __re
     const long i = base + (long)k * kThreads + threadIdx.x;
     if (i < count) a[i] += add;
   }
+}
+
+inline long scan_tiles(long count) { return (count + kScanTile - 1) / kScanTile; }     // the words of a caller's `tiles` buffer
+
+// Exclusive scan of `count` counters in place: tiles of kScanTile, the tile sums by one workgroup, then added back.
+inline int exclusive_scan(unsigned* counters, long count, unsigned* tiles, hipStream_t st) {
+  const long nt = scan_tiles(count);
+  hipLaunchKernelGGL(cloud_scan_tile_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, counters, count, tiles);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_sums_kernel, dim3(1), dim3(1024), 0, st, tiles, nt);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(cloud_scan_add_kernel, dim3((unsigned)nt), dim3(kThreads), 0, st, counters, count, (const unsigned*)tiles);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
 }
 
 }  // namespace

@@ -21,12 +21,8 @@
 
 namespace {
 
-constexpr int kThreads = 256;          // points per workgroup (one lane per point)
-constexpr int kCam = 16;               // R (3x3 row-major), t (3), fx, fy, cx, cy
 constexpr int kFaces = 6;
-constexpr int kMaxWindow = 2;
-constexpr int kMaxCams = 65535;        // atvs_scan_render's limit
-constexpr long kMaxPoints = 1L << 30;
+constexpr int kMaxWindow = ATVS_CLOUD_SCAN_MAX_WINDOW;
 
 __global__ __launch_bounds__(kThreads) void scan_excess_kernel(const float* __restrict__ pts, long m, const double* __restrict__ cams,
                                                                const float* __restrict__ maps, int n_scanners, int size,
@@ -36,7 +32,7 @@ __global__ __launch_bounds__(kThreads) void scan_excess_kernel(const float* __re
   if (p >= m) return;
   const float xf = pts[p * 3 + 0], yf = pts[p * 3 + 1], zf = pts[p * 3 + 2];
   const float big = __uint_as_float(0x7f800000u);
-  const bool finite = fabsf(xf) < big && fabsf(yf) < big && fabsf(zf) < big;
+  const bool finite = finite3(xf, yf, zf);
   const double X = (double)xf, Y = (double)yf, Z = (double)zf;
   const double hi = (double)size;
   const size_t plane = (size_t)size * (size_t)size;
@@ -81,8 +77,8 @@ __global__ __launch_bounds__(kThreads) void scan_excess_kernel(const float* __re
 extern "C" int atvs_cloud_scan_excess(const float* points, long m, const double* cams, const float* maps, int n_scanners, int size,
                                       double pixel_centre, int window, float* excess, int* scanner, atvs_stream_t stream) {
   if (m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
-  if (n_scanners < 1 || n_scanners > kMaxCams / kFaces || size < 1) return ATVS_ERR_SHAPE;
-  if ((double)(n_scanners * kFaces) * (double)size * (double)size >= 2147483648.0) return ATVS_ERR_SHAPE;
+  if (n_scanners < 1 || n_scanners > kMaxCams / kFaces) return ATVS_ERR_SHAPE;              // before the product below can overflow
+  if (check_maps(n_scanners * kFaces, size, size) != ATVS_OK) return ATVS_ERR_SHAPE;
   if (!cams || !maps || (m > 0 && (!points || !excess || !scanner))) return ATVS_ERR_NULL;
   if (window < 0 || window > kMaxWindow) return ATVS_ERR_ARG;
   if (!(fabs(pixel_centre) < (double)INFINITY)) return ATVS_ERR_ARG;

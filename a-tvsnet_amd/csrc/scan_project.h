@@ -1,11 +1,20 @@
 // The projection of a point into one camera of atvs_scan_render's layout, shared by the renderer (scan_render.hip: where a scan
 // point lands) and the visibility query (cloud_visibility.hip: which pixel a reconstruction point looks at).  ONE definition: a scan
 // point and a query on the same ray reach the same pixel.  Float64, every operation rounded (-ffp-contract=off), in the order of
-// include/atvsnet_hip.h.
+// include/atvsnet_hip.h.  With it what both say of a set of cameras: a camera's length, their number's limit, the maps' shape check.
 #pragma once
 #include "common.h"
+#include "cloud_common.h"
 
 #include <math.h>
+
+constexpr int kCam = 16;               // R (3x3 row-major), t (3), fx, fy, cx, cy
+constexpr int kMaxCams = ATVS_SCAN_RENDER_MAX_CAMS;
+
+static inline int check_maps(int n_cams, int rows, int cols) {        // n_cams maps of rows x cols: pixels are indexed in 31 bits
+  if (n_cams <= 0 || rows <= 0 || cols <= 0 || n_cams > kMaxCams) return ATVS_ERR_SHAPE;
+  return (double)n_cams * (double)rows * (double)cols >= 2147483648.0 ? ATVS_ERR_SHAPE : ATVS_OK;
+}
 
 struct ScanProjection {
   double c0, c1, c2;      // the point in the camera's frame

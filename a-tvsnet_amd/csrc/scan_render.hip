@@ -27,11 +27,8 @@
 
 namespace {
 
-constexpr int kThreads = 256;          // points per workgroup (one lane per point)
-constexpr int kGroup = 8;              // cameras per workgroup
-constexpr int kCam = 16;               // R (3x3 row-major), t (3), fx, fy, cx, cy
-constexpr int kMaxSplat = 4;
-constexpr long kMaxPoints = 1L << 30;
+constexpr int kGroup = 8;              // cameras per workgroup (of kThreads points, one lane per point)
+constexpr int kMaxSplat = ATVS_SCAN_RENDER_MAX_SPLAT;
 constexpr unsigned kEmpty = 0xffffffffu;
 
 __host__ __device__ inline size_t plane_bytes(int n_cams, int rows, int cols) {
@@ -82,17 +79,11 @@ __global__ __launch_bounds__(kThreads) void resolve_kernel(const unsigned* __res
   depth[i] = d;
 }
 
-int check_shape(int n_cams, int rows, int cols) {
-  if (n_cams <= 0 || rows <= 0 || cols <= 0 || n_cams > 65535) return ATVS_ERR_SHAPE;
-  if ((double)n_cams * (double)rows * (double)cols >= 2147483648.0) return ATVS_ERR_SHAPE;
-  return ATVS_OK;
-}
-
 }  // namespace
 
 extern "C" int atvs_scan_render_scratch_size(int n_cams, int rows, int cols, long* bytes) {
   if (!bytes) return ATVS_ERR_NULL;
-  if (check_shape(n_cams, rows, cols) != ATVS_OK) return ATVS_ERR_SHAPE;
+  if (check_maps(n_cams, rows, cols) != ATVS_OK) return ATVS_ERR_SHAPE;
   *bytes = (long)(2 * plane_bytes(n_cams, rows, cols));
   return ATVS_OK;
 }
@@ -101,7 +92,7 @@ extern "C" int atvs_scan_render(const float* points, long n, const double* cams,
                                 double pixel_centre, int splat, double occlusion_tol, void* scratch, long scratch_bytes,
                                 float* depth_out, atvs_stream_t stream) {
   if (!cams || !scratch || !depth_out || (n > 0 && !points)) return ATVS_ERR_NULL;
-  if (check_shape(n_cams, rows, cols) != ATVS_OK || n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (check_maps(n_cams, rows, cols) != ATVS_OK || n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
   const size_t pb = plane_bytes(n_cams, rows, cols);
   if (scratch_bytes < (long)(2 * pb)) return ATVS_ERR_SHAPE;
   if (splat < 0 || splat > kMaxSplat) return ATVS_ERR_ARG;

@@ -24,14 +24,16 @@ import math
 import numpy as np
 import torch
 
+from .. import _lib
 from .base import _call, _p, _size, _stream
 
 CLOUD_MAX_POINTS = 1 << 30
-CLOUD_MAX_TOLERANCES = 16
-CLOUD_MAX_K = 32
-SCAN_RENDER_MAX_SPLAT = 4
-SCAN_RENDER_MAX_CAMS = 65535
-CLOUD_SCAN_MAX_WINDOW = 2
+# include/atvsnet_hip.h defines these limits; the kernels take them from there too
+CLOUD_MAX_TOLERANCES = _lib.header_macro('ATVS_CLOUD_MAX_TOLERANCES')
+CLOUD_MAX_K = _lib.header_macro('ATVS_CLOUD_MAX_K')
+SCAN_RENDER_MAX_SPLAT = _lib.header_macro('ATVS_SCAN_RENDER_MAX_SPLAT')
+SCAN_RENDER_MAX_CAMS = _lib.header_macro('ATVS_SCAN_RENDER_MAX_CAMS')
+CLOUD_SCAN_MAX_WINDOW = _lib.header_macro('ATVS_CLOUD_SCAN_MAX_WINDOW')
 
 
 def _cloud_arg(t, name, dtype, trailing):
@@ -58,6 +60,34 @@ def _radius(radius):
     if not (r > 0.0 and math.isfinite(r)):
         raise ValueError('radius must be a positive finite float32, got %r' % (radius,))
     return r
+
+
+def _int_in(v, name, lo, hi=None):
+    """int(v) for an integer (not a bool) in lo..hi; hi None: 1 or more."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < lo or (hi is not None and int(v) > hi):
+        raise ValueError('%s: expected %s, got %r' % (name, 'a positive integer' if hi is None else 'an integer in %d..%d' % (lo, hi), v))
+    return int(v)
+
+
+def _same_device(t, name, ref, ref_name):
+    if t.device != ref.device:
+        raise RuntimeError('%s on %s, %s on %s' % (name, t.device, ref_name, ref.device))
+
+
+def _tolerances(tolerances, bounded=False, radius=None):
+    """-> (tolerances as floats, r): each >= 0 and r None, or `bounded` by r = radius (None: the largest float32)."""
+    tol = [float(t) for t in tolerances]
+    if not 1 <= len(tol) <= CLOUD_MAX_TOLERANCES:
+        raise ValueError('1 to %d tolerances, got %d' % (CLOUD_MAX_TOLERANCES, len(tol)))
+    if not bounded:
+        if any(not t >= 0.0 for t in tol):
+            raise ValueError('tolerances must be >= 0, got %r' % (tol,))
+        return tol, None
+    r = float(np.finfo(np.float32).max) if radius is None else _radius(radius)
+    for t in tol:
+        if not 0.0 <= t <= r:
+            raise ValueError('tolerance %r outside [0, radius = %r]' % (t, r))
+    return tol, r
 
 
 class CloudGrid(object):
@@ -87,12 +117,7 @@ def cloud_nearest(grid, queries):
     """queries (m,3) float32 -> (d2 (m,) float32, idx (m,) int32): per query the smallest float32 squared distance
     (dx*dx + dy*dy) + dz*dz to a finite point of the grid's cloud and the lowest index attaining it; (+inf, -1) where that is
     beyond the grid's radius, the query is not finite, or the cloud has no finite point."""
-    if not isinstance(grid, CloudGrid):
-        raise TypeError('grid: expected a CloudGrid (ops.cloud_grid), got %s' % type(grid).__name__)
-    _cloud_arg(queries, 'queries', torch.float32, (3,))
-    if queries.device != grid.buf.device:
-        raise RuntimeError('queries on %s, the grid on %s' % (queries.device, grid.buf.device))
-    m = int(queries.shape[0])
+    m = _search_args(grid, queries, False)
     d2 = torch.empty(m, dtype=torch.float32, device=queries.device)
     idx = torch.empty(m, dtype=torch.int32, device=queries.device)
     if m == 0:
@@ -107,13 +132,7 @@ def cloud_counts(d2, tolerances, radius=None):
     """d2 (m,) float32 of cloud_nearest, up to 16 tolerances -> (len(tolerances),) int64 on the device: how many entries have
     double(d2) <= tau * tau.  radius: the radius d2 was computed with; a tolerance above it raises (distances beyond the radius
     are not known).  None: the caller vouches for that."""
-    tol = [float(t) for t in tolerances]
-    if not 1 <= len(tol) <= CLOUD_MAX_TOLERANCES:
-        raise ValueError('1 to %d tolerances, got %d' % (CLOUD_MAX_TOLERANCES, len(tol)))
-    r = float(np.finfo(np.float32).max) if radius is None else _radius(radius)
-    for t in tol:
-        if not 0.0 <= t <= r:
-            raise ValueError('tolerance %r outside [0, radius = %r]' % (t, r))
+    tol, r = _tolerances(tolerances, True, radius)
     _cloud_arg(d2, 'd2', torch.float32, ())
     counts = torch.empty(CLOUD_MAX_TOLERANCES, dtype=torch.int64, device=d2.device)
     arr = (ctypes.c_double * len(tol))(*tol)
@@ -166,8 +185,7 @@ def cloud_pair_moments(src, dst, idx, d2, trim=float('inf'), pivot_src=None, piv
     if int(idx.shape[0]) != m or int(d2.shape[0]) != m:
         raise ValueError('idx %s and d2 %s must have one entry per row of src %s' % (tuple(idx.shape), tuple(d2.shape), tuple(src.shape)))
     for t, name in ((dst, 'dst'), (idx, 'idx'), (d2, 'd2')):
-        if t.device != src.device:
-            raise RuntimeError('%s on %s, src on %s' % (name, t.device, src.device))
+        _same_device(t, name, src, 'src')
     out = torch.empty(19, dtype=torch.int64, device=src.device)
     scratch = torch.empty(_size('atvs_cloud_pair_moments_scratch_size', m), dtype=torch.uint8, device=src.device)
     _call('atvs_cloud_pair_moments', _p(src), _p(dst), n, _p(idx), _p(d2), m, trim, ps, pd,
@@ -176,22 +194,42 @@ def cloud_pair_moments(src, dst, idx, d2, trim=float('inf'), pivot_src=None, piv
     return int(words[0]), words[1:].view(np.float64).copy()
 
 
+def _voxel(voxel):
+    voxel = float(voxel)
+    if not (voxel > 0.0 and math.isfinite(voxel)):
+        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
+    return voxel
+
+
+def _default_origin(points):
+    """The floor of the finite points' minimum (0 when there is none) as _vec3 gives it."""
+    lo = cloud_bounds(points)[0] if int(points.shape[0]) else None
+    return _vec3(None if lo is None else np.floor(lo), 'origin')
+
+
+def _raise_cell_range(fn, points, org, voxel):
+    """What the device could only flag: a finite point whose cell leaves [0, 2^21) on an axis."""
+    lo, hi = cloud_bounds(points)
+    o = np.array(list(org))
+    if (lo < o).any():
+        raise ValueError('%s: a point lies below the origin %s (the finite minimum is %s)' % (fn, o.tolist(), lo.tolist()))
+    fit = float((hi - o).max()) / float(1 << 21) * (1.0 + 1e-5)          # a little above the limit, so that the printed digits fit too
+    raise ValueError('%s: voxel %r puts a point more than 2^21 voxels from the origin (bad shape); the '
+                     'smallest voxel that fits this cloud is %.8g' % (fn, voxel, fit))
+
+
 def cloud_voxel_downsample(points, voxel, origin=None):
     """points (n,3) float32, voxel > 0 -> (means (k,3) float32, first (k,) int32): one point per occupied cubic voxel of edge
     `voxel`, the exact mean of the voxel's finite points (integer sums of 32-bit fractions; include/atvsnet_hip.h), in ascending
     order of the voxel's lowest original index, which is `first`.  Non-finite points are dropped.  origin: 3 host numbers, the
     corner of voxel (0,0,0); None: the floor of the finite points' minimum (one small reduction and copy).  A point more than
     2^21 voxels from the origin, or below it, raises with the voxel size that would fit.  Synchronises once, to read k."""
-    voxel = float(voxel)
-    if not (voxel > 0.0 and math.isfinite(voxel)):
-        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
-    if origin is not None:
-        org = _vec3(origin, 'origin')
+    voxel = _voxel(voxel)
+    org = origin if origin is None else _vec3(origin, 'origin')
     _cloud_arg(points, 'points', torch.float32, (3,))
     n = int(points.shape[0])
-    if origin is None:
-        lo = cloud_bounds(points)[0] if n else None
-        org = _vec3(None if lo is None else np.floor(lo), 'origin')
+    if org is None:
+        org = _default_origin(points)
     means = torch.empty((n, 3), dtype=torch.float32, device=points.device)
     first = torch.empty(n, dtype=torch.int32, device=points.device)
     count = torch.empty(1, dtype=torch.int64, device=points.device)
@@ -200,13 +238,7 @@ def cloud_voxel_downsample(points, voxel, origin=None):
           _p(means), _p(count), _p(first), _stream())
     k = int(count.item())
     if k < 0:
-        lo, hi = cloud_bounds(points)
-        o = np.array(list(org))
-        if (lo < o).any():
-            raise ValueError('cloud_voxel_downsample: a point lies below the origin %s (the finite minimum is %s)' % (o.tolist(), lo.tolist()))
-        fit = float((hi - o).max()) / float(1 << 21) * (1.0 + 1e-5)          # a little above the limit, so that the printed digits fit too
-        raise ValueError('cloud_voxel_downsample: voxel %r puts a point more than 2^21 voxels from the origin (bad shape); the '
-                         'smallest voxel that fits this cloud is %.8g' % (voxel, fit))
+        _raise_cell_range('cloud_voxel_downsample', points, org, voxel)
     return means[:k], first[:k]
 
 
@@ -225,23 +257,15 @@ def cloud_bounds(points):
 
 
 def _search_args(grid, queries, exclude_same_index):
-    """The checks cloud_knn and cloud_radius_count share -> m."""
+    """The checks cloud_nearest, cloud_knn and cloud_radius_count share -> m."""
     if not isinstance(grid, CloudGrid):
         raise TypeError('grid: expected a CloudGrid (ops.cloud_grid), got %s' % type(grid).__name__)
     if exclude_same_index and isinstance(queries, torch.Tensor) and queries.dim() == 2 and int(queries.shape[0]) != grid.n:
         raise ValueError('exclude_same_index: the queries must be the grid\'s own cloud, row for row (%d queries, %d reference '
                          'points)' % (int(queries.shape[0]), grid.n))
     _cloud_arg(queries, 'queries', torch.float32, (3,))
-    if queries.device != grid.buf.device:
-        raise RuntimeError('queries on %s, the grid on %s' % (queries.device, grid.buf.device))
-    m = int(queries.shape[0])
-    return m
-
-
-def _check_k(k):
-    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= int(k) <= CLOUD_MAX_K:
-        raise ValueError('k: expected an integer in 1..%d, got %r' % (CLOUD_MAX_K, k))
-    return int(k)
+    _same_device(queries, 'queries', grid.buf, 'the grid')
+    return int(queries.shape[0])
 
 
 def cloud_knn(grid, queries, k, exclude_same_index=False):
@@ -250,7 +274,7 @@ def cloud_knn(grid, queries, k, exclude_same_index=False):
     of (d2, index), padded with (+inf, -1); a non-finite query has none.  exclude_same_index: the queries are the grid's own cloud
     and row j is no neighbour of itself (index j alone: a duplicate at another index is a neighbour at distance 0).  With k = 1
     and the flag clear it is cloud_nearest bit for bit."""
-    k = _check_k(k)
+    k = _int_in(k, 'k', 1, CLOUD_MAX_K)
     m = _search_args(grid, queries, exclude_same_index)
     d2 = torch.empty((m, k), dtype=torch.float32, device=queries.device)
     idx = torch.empty((m, k), dtype=torch.int32, device=queries.device)
@@ -311,11 +335,8 @@ def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_t
     float64, by u = floor((x - pixel_centre) + 0.5); 0 where none does, and 0 where that depth is further than (1 + occlusion_tol)
     times the nearest depth landing within `splat` pixels (a background point seen through a hole).  splat 0..4; splat = 0 keeps
     every pixel.  include/atvsnet_hip.h has the definition in full; the same inputs give the same bits (integer atomics)."""
-    for name, v in (('rows', rows), ('cols', cols)):
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or int(v) < 1:
-            raise ValueError('%s: expected a positive integer, got %r' % (name, v))
-    if isinstance(splat, bool) or not isinstance(splat, (int, np.integer)) or not 0 <= int(splat) <= SCAN_RENDER_MAX_SPLAT:
-        raise ValueError('splat: expected an integer in 0..%d, got %r' % (SCAN_RENDER_MAX_SPLAT, splat))
+    rows, cols = _int_in(rows, 'rows', 1), _int_in(cols, 'cols', 1)
+    splat = _int_in(splat, 'splat', 0, SCAN_RENDER_MAX_SPLAT)
     tol, centre = float(occlusion_tol), float(pixel_centre)
     if not (tol >= 0.0 and math.isfinite(tol)):
         raise ValueError('occlusion_tol must be >= 0 and finite, got %r' % (occlusion_tol,))
@@ -323,16 +344,15 @@ def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_t
         raise ValueError('pixel_centre must be finite, got %r' % (pixel_centre,))
     _cloud_arg(points, 'points', torch.float32, (3,))
     _cloud_arg(cams, 'cams', torch.float64, (16,))
-    if cams.device != points.device:
-        raise RuntimeError('cams on %s, points on %s' % (cams.device, points.device))
-    n, n_cams, rows, cols = int(points.shape[0]), int(cams.shape[0]), int(rows), int(cols)
+    _same_device(cams, 'cams', points, 'points')
+    n, n_cams = int(points.shape[0]), int(cams.shape[0])
     if not 1 <= n_cams <= SCAN_RENDER_MAX_CAMS:
         raise ValueError('cams: 1 to %d cameras, got %d' % (SCAN_RENDER_MAX_CAMS, n_cams))
     if n_cams * rows * cols >= 1 << 31:
         raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n_cams, rows, cols))
     depth = torch.empty((n_cams, rows, cols), dtype=torch.float32, device=points.device)
     scratch = torch.empty(_size('atvs_scan_render_scratch_size', n_cams, rows, cols), dtype=torch.uint8, device=points.device)
-    _call('atvs_scan_render', _p(points), n, _p(cams), n_cams, rows, cols, centre, int(splat), tol,
+    _call('atvs_scan_render', _p(points), n, _p(cams), n_cams, rows, cols, centre, splat, tol,
           _p(scratch), scratch.numel(), _p(depth), _stream())
     return depth
 
@@ -344,8 +364,7 @@ def cloud_scan_excess(points, cams, maps, pixel_centre=0.5, window=1):
     front of it (free space), positive behind -- minimised over the scanners that observe the point, and the lowest scanner
     attaining it; (+inf, -1) where none does or the point is not finite.  The face is the first of the six in view; a window stays
     inside its face.  window 0..2.  include/atvsnet_hip.h has the definition in full; the output is a function of the inputs."""
-    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 0 <= int(window) <= CLOUD_SCAN_MAX_WINDOW:
-        raise ValueError('window: expected an integer in 0..%d, got %r' % (CLOUD_SCAN_MAX_WINDOW, window))
+    window = _int_in(window, 'window', 0, CLOUD_SCAN_MAX_WINDOW)
     centre = float(pixel_centre)
     if not math.isfinite(centre):
         raise ValueError('pixel_centre must be finite, got %r' % (pixel_centre,))
@@ -363,13 +382,12 @@ def cloud_scan_excess(points, cams, maps, pixel_centre=0.5, window=1):
     if n_cams * size * size >= 1 << 31:
         raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n_cams, size, size))
     for t, name in ((cams, 'cams'), (maps, 'maps')):
-        if t.device != points.device:
-            raise RuntimeError('%s on %s, points on %s' % (name, t.device, points.device))
+        _same_device(t, name, points, 'points')
     m = int(points.shape[0])
     excess = torch.empty(m, dtype=torch.float32, device=points.device)
     scanner = torch.empty(m, dtype=torch.int32, device=points.device)
     if m:
-        _call('atvs_cloud_scan_excess', _p(points), m, _p(cams), _p(maps), n_cams // 6, size, centre, int(window),
+        _call('atvs_cloud_scan_excess', _p(points), m, _p(cams), _p(maps), n_cams // 6, size, centre, window,
               _p(excess), _p(scanner), _stream())
     return excess, scanner
 
@@ -383,17 +401,11 @@ def cloud_voxel_shares(points, d2, excess, voxel, origin, tolerances, margin=0.0
     sum q / (voxels * 2^32).  Integer atomics only: the same inputs give the same words.  A point more than 2^21 voxels from the
     origin, or below it, raises as cloud_voxel_downsample does.  Synchronises once, to read the error word."""
     voxel, margin = float(voxel), float(margin)
-    if not (voxel > 0.0 and math.isfinite(voxel)):
-        raise ValueError('voxel must be positive and finite, got %r' % (voxel,))
+    voxel = _voxel(voxel)
     if math.isnan(margin):
         raise ValueError('margin must be a number, got %r' % (margin,))
-    tol = [float(t) for t in tolerances]
-    if not 1 <= len(tol) <= CLOUD_MAX_TOLERANCES:
-        raise ValueError('1 to %d tolerances, got %d' % (CLOUD_MAX_TOLERANCES, len(tol)))
-    if any(not t >= 0.0 for t in tol):
-        raise ValueError('tolerances must be >= 0, got %r' % (tol,))
-    if origin is not None:
-        org = _vec3(origin, 'origin')
+    tol, _ = _tolerances(tolerances)
+    org = origin if origin is None else _vec3(origin, 'origin')
     _cloud_arg(points, 'points', torch.float32, (3,))
     _cloud_arg(d2, 'd2', torch.float32, ())
     n = int(points.shape[0])
@@ -404,22 +416,14 @@ def cloud_voxel_shares(points, d2, excess, voxel, origin, tolerances, margin=0.0
             _cloud_arg(excess, 'excess', torch.float32, ())
         if int(t.shape[0]) != n:
             raise ValueError('%s %s must have one entry per row of points %s' % (name, tuple(t.shape), tuple(points.shape)))
-        if t.device != points.device:
-            raise RuntimeError('%s on %s, points on %s' % (name, t.device, points.device))
-    if origin is None:
-        lo = cloud_bounds(points)[0] if n else None
-        org = _vec3(None if lo is None else np.floor(lo), 'origin')
+        _same_device(t, name, points, 'points')
+    if org is None:
+        org = _default_origin(points)
     out = torch.empty((len(tol), 4), dtype=torch.int64, device=points.device)
     scratch = torch.empty(_size('atvs_cloud_voxel_shares_scratch_size', n), dtype=torch.uint8, device=points.device)
     arr = (ctypes.c_double * len(tol))(*tol)
     _call('atvs_cloud_voxel_shares', _p(points), _p(d2), _p(excess), n, voxel, org, arr, len(tol), margin,
           _p(scratch), scratch.numel(), _p(out), _stream())
     if int(out[0, 0].item()) < 0:
-        lo, hi = cloud_bounds(points)
-        o = np.array(list(org))
-        if (lo < o).any():
-            raise ValueError('cloud_voxel_shares: a point lies below the origin %s (the finite minimum is %s)' % (o.tolist(), lo.tolist()))
-        fit = float((hi - o).max()) / float(1 << 21) * (1.0 + 1e-5)
-        raise ValueError('cloud_voxel_shares: voxel %r puts a point more than 2^21 voxels from the origin (bad shape); the '
-                         'smallest voxel that fits this cloud is %.8g' % (voxel, fit))
+        _raise_cell_range('cloud_voxel_shares', points, org, voxel)
     return out

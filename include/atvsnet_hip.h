@@ -785,10 +785,13 @@ int atvs_undistort_remap(const unsigned char* src, int W, int H, const int* map,
  * grid afterwards, valid for any number of atvs_cloud_nearest calls with the same n.  No host synchronisation.
  * atvs_cloud_nearest: queries (m,3) -> d2 (m) float32, idx (m) int32 as defined above; the queries are sorted by cell and
  * answered in that order, the results written to their original positions.  scratch: atvs_cloud_nearest_scratch_size(n, m) bytes.
- * atvs_cloud_counts: counts (16 int64, zeroed on the stream) [t] = the number of i with (double)d2[i] <= tolerances[t]^2 (the
- * square formed in double), t < k <= 16; `tolerances` is a HOST array of k doubles; radius = the R d2 was computed with.
+ * atvs_cloud_counts: counts (ATVS_CLOUD_MAX_TOLERANCES int64, zeroed on the stream) [t] = the number of i with
+ * (double)d2[i] <= tolerances[t]^2 (the square formed in double), t < k <= ATVS_CLOUD_MAX_TOLERANCES; `tolerances` is a HOST array
+ * of k doubles; radius = the R d2 was computed with.
  * R <= 0 or not finite, a tolerance negative, NaN or above R: ATVS_ERR_ARG; n or m negative or beyond 2^30, a short grid or
- * scratch, k outside [1, 16]: ATVS_ERR_SHAPE.  n = 0 and m = 0 are valid (every query not found; nothing launched over no points). */
+ * scratch, k outside [1, ATVS_CLOUD_MAX_TOLERANCES]: ATVS_ERR_SHAPE.  n = 0 and m = 0 are valid (every query not found; nothing
+ * launched over no points). */
+#define ATVS_CLOUD_MAX_TOLERANCES 16
 int atvs_cloud_grid_scratch_size(long n, long* bytes);
 int atvs_cloud_grid_build(const float* points, long n, float radius, void* grid, long grid_bytes, atvs_stream_t stream);
 int atvs_cloud_nearest_scratch_size(long n, long m, long* bytes);
@@ -899,8 +902,11 @@ int atvs_cloud_bounds(const float* points, long n, void* out, atvs_stream_t stre
  *
  * atvs_scan_render: depth_out (n_cams, rows, cols) float32 as defined.  scratch: atvs_scan_render_scratch_size(n_cams, rows, cols)
  * bytes (the two planes), filled by hipMemsetAsync on the stream.  Two launches (one when n = 0: all-zero maps).
- * splat outside [0, 4], occlusion_tol negative or not finite, pixel_centre not finite: ATVS_ERR_ARG; n_cams * rows * cols >= 2^31,
- * n_cams outside [1, 65535], rows or cols < 1, n negative or beyond 2^30, a short scratch: ATVS_ERR_SHAPE. */
+ * splat outside [0, ATVS_SCAN_RENDER_MAX_SPLAT], occlusion_tol negative or not finite, pixel_centre not finite: ATVS_ERR_ARG;
+ * n_cams * rows * cols >= 2^31, n_cams outside [1, ATVS_SCAN_RENDER_MAX_CAMS], rows or cols < 1, n negative or beyond 2^30, a short
+ * scratch: ATVS_ERR_SHAPE. */
+#define ATVS_SCAN_RENDER_MAX_SPLAT 4
+#define ATVS_SCAN_RENDER_MAX_CAMS 65535
 int atvs_scan_render_scratch_size(int n_cams, int rows, int cols, long* bytes);
 int atvs_scan_render(const float* points, long n, const double* cams, int n_cams, int rows, int cols, double pixel_centre, int splat,
                      double occlusion_tol, void* scratch, long scratch_bytes, float* depth_out, atvs_stream_t stream);
@@ -911,10 +917,11 @@ int atvs_scan_render(const float* points, long n, const double* cams, int n_cams
  * host synchronisation, no allocation; every output is a function of the inputs alone, bit for bit on every run.
  * tests/cloud_eth3d_restated.py restates both definitions.
  *
- * atvs_cloud_scan_excess.  points (m,3) float32; S = n_scanners >= 1 scanners, 6 S <= 65535; cams (6 S,16) doubles in
- * atvs_scan_render's layout, six faces per scanner (a cube map: six 90-degree pinhole cameras at the scanner's origin); maps
- * (6 S, size, size) float32 as atvs_scan_render returns them for those cameras (0 = empty pixel); window w in 0..2.  Per (point,
- * scanner), in double, every operation rounded, nothing contracted: for the faces f = 0..5 in order, c, xs, ys are
+ * atvs_cloud_scan_excess.  points (m,3) float32; S = n_scanners >= 1 scanners, 6 S <= ATVS_SCAN_RENDER_MAX_CAMS; cams (6 S,16)
+ * doubles in atvs_scan_render's layout, six faces per scanner (a cube map: six 90-degree pinhole cameras at the scanner's origin);
+ * maps (6 S, size, size) float32 as atvs_scan_render returns them for those cameras (0 = empty pixel); window w in
+ * 0..ATVS_CLOUD_SCAN_MAX_WINDOW.  Per (point, scanner), in double, every operation rounded, nothing contracted: for the faces
+ * f = 0..5 in order, c, xs, ys are
  * atvs_scan_render's (csrc/scan_project.h is the one definition both use) and the face is IN VIEW under its rule at splat = 0 with
  * rows = cols = size: c_2 > 0, (float)c_2 finite and > 0, 0 <= xs < size, 0 <= ys < size.  The FIRST face in view is the point's
  * face (the tie rule on cube edges); with none the scanner does not observe the point (its own origin is such a point).
@@ -924,23 +931,25 @@ int atvs_scan_render(const float* points, long n, const double* cams, int n_cams
  * nearest scan sample along that ray by |e_s| (free space), positive = behind it.  excess (m) float32 = (float)min_s e_s over the
  * observing scanners, scanner (m) int32 = the lowest s attaining the minimum (compared in double); (+inf, -1) when no scanner
  * observes the point or the point is not finite.  One launch; m = 0 writes nothing.
- * w outside [0, 2], pixel_centre not finite: ATVS_ERR_ARG; size < 1, S < 1, 6 S > 65535, 6 S size size >= 2^31, m negative or
- * beyond 2^30: ATVS_ERR_SHAPE.
+ * w outside [0, ATVS_CLOUD_SCAN_MAX_WINDOW], pixel_centre not finite: ATVS_ERR_ARG; size < 1, S < 1,
+ * 6 S > ATVS_SCAN_RENDER_MAX_CAMS, 6 S size size >= 2^31, m negative or beyond 2^30: ATVS_ERR_SHAPE.
  *
  * atvs_cloud_voxel_shares.  points (n,3) float32, d2 (n) float32 of atvs_cloud_nearest, excess (n) float32 of
  * atvs_cloud_scan_excess or NULL, voxel and origin (HOST, 3 finite doubles) as for atvs_cloud_voxel_downsample, tolerances (HOST,
- * 1..16 doubles >= 0), margin (a double, not NaN).  A point's voxel is atvs_cloud_voxel_downsample's cell triple (one function in
- * csrc/cloud_register.hip); non-finite points belong to no voxel.  Per voxel and tolerance tau: hit = the number of its points
- * with (double)d2 <= tau * tau; den = all its points when excess is NULL, otherwise hit + the number of points that are not hit
- * and have (double)excess <= margin (the rest -- behind everything a scanner saw, or seen by none -- are UNOBSERVED and count
- * nowhere; a NaN is neither hit nor observed).  A voxel with den = 0 is left out at that tau; otherwise q = (hit * 2^32) / den
+ * 1..ATVS_CLOUD_MAX_TOLERANCES doubles >= 0), margin (a double, not NaN).  A point's voxel is atvs_cloud_voxel_downsample's cell
+ * triple (one function in csrc/cloud_register.hip); non-finite points belong to no voxel.  Per voxel and tolerance tau: hit = the
+ * number of its points with (double)d2 <= tau * tau; den = all its points when excess is NULL, otherwise hit + the number of
+ * points that are not hit and have (double)excess <= margin (the rest -- behind everything a scanner saw, or seen by none -- are
+ * UNOBSERVED and count nowhere; a NaN is neither hit nor observed).  A voxel with den = 0 is left out at that tau; otherwise q = (hit * 2^32) / den
  * in unsigned 64-bit integer division.  out (n_tolerances,4) int64: sum of q, the number of voxels counted, sum of hit, sum of
  * den.  The share is sum q / (voxels * 2^32), formed by the caller.  Unsigned integer atomics only.  A finite point whose cell
  * leaves [0, 2^21) on an axis makes the call a shape error that only the device can see: every word of out is -1 (ops/cloud.py
  * raises).  n = 0: zero words.  Tolerances are taken four at a time (count and reduce launches per pass).
  * scratch: atvs_cloud_voxel_shares_scratch_size(n) bytes: 40 B per slot of the table (capacity = the power of two >=
  * max(2 n, 1024)) and 4 B per point: 84 to 164 B per point.  voxel <= 0 or not finite, a non-finite origin, a negative or NaN
- * tolerance, a NaN margin: ATVS_ERR_ARG; n negative or beyond 2^30, n_tolerances outside [1, 16], a short scratch: ATVS_ERR_SHAPE. */
+ * tolerance, a NaN margin: ATVS_ERR_ARG; n negative or beyond 2^30, n_tolerances outside [1, ATVS_CLOUD_MAX_TOLERANCES], a short
+ * scratch: ATVS_ERR_SHAPE. */
+#define ATVS_CLOUD_SCAN_MAX_WINDOW 2
 int atvs_cloud_scan_excess(const float* points, long m, const double* cams, const float* maps, int n_scanners, int size,
                            double pixel_centre, int window, float* excess, int* scanner, atvs_stream_t stream);
 int atvs_cloud_voxel_shares_scratch_size(long n, long* bytes);

@@ -101,6 +101,9 @@ def test_voxel_downsample_equals_the_restatement_bit_for_bit(cuda):
     got = ops.cloud_voxel_downsample(torch.zeros((0, 3), device=cuda), 0.1)
     assert got[0].shape == (0, 3) and got[1].shape == (0,)
     _same_voxels(cuda, np.array([[0.3, 0.7, 0.2]], np.float32), 0.25, (0, 0, 0))
+    # the scan runs over n + 1 counters: 2048 fill one tile of it, 2049 begin a second
+    for n in (2047, 2048):
+        _same_voxels(cuda, pts[:n], 0.05, (0, 0, 0))
     # a permutation of the input gives the same SET of points
     perm = rng.permutation(len(pts))
     a = ops.cloud_voxel_downsample(_up(cuda, pts), 0.05, (0, 0, 0))[0].cpu().numpy()

@@ -219,6 +219,22 @@ def test_library_abi_version_matches_header():
     assert _lib.lib().atvs_abi_version() == _lib.header_abi_version() >= 2
 
 
+def test_the_point_cloud_limits_are_the_headers_macros():
+    """ops' five limits are what include/atvsnet_hip.h defines (read here from its text), and a macro it lacks raises."""
+    with open(_lib.HEADER) as f:
+        words = [line.split() for line in f.read().splitlines()]
+    for name, macro, value in (('CLOUD_MAX_TOLERANCES', 'ATVS_CLOUD_MAX_TOLERANCES', 16), ('CLOUD_MAX_K', 'ATVS_CLOUD_MAX_K', 32),
+                               ('SCAN_RENDER_MAX_SPLAT', 'ATVS_SCAN_RENDER_MAX_SPLAT', 4),
+                               ('SCAN_RENDER_MAX_CAMS', 'ATVS_SCAN_RENDER_MAX_CAMS', 65535),
+                               ('CLOUD_SCAN_MAX_WINDOW', 'ATVS_CLOUD_SCAN_MAX_WINDOW', 2)):
+        defined = [w[2] for w in words if w[:2] == ['#define', macro]]
+        assert defined == [str(value)], macro
+        assert getattr(ops, name) == _lib.header_macro(macro) == value, name
+    for missing in ('ATVS_NO_SUCH_LIMIT', 'ATVS_CLOUD_MAX'):                # a prefix of a macro's name is not the macro
+        with pytest.raises(RuntimeError, match='defines no %s' % missing):
+            _lib.header_macro(missing)
+
+
 def test_weight_reload_drops_arranged_copies():
     """The pack caches are keyed by variable NAME: setting a variable must drop every arranged copy."""
     import numpy as np

@@ -185,6 +185,7 @@ def test_ops_scan_render_refuses_bad_arguments_no_fallback():
     with pytest.raises(ValueError, match='points'):
         ops.scan_render(torch.zeros(5, 4), C, 4, 4)
     assert ops.SCAN_RENDER_MAX_SPLAT == 4 and ops.SCAN_RENDER_MAX_CAMS == 65535
+    assert (ops.CLOUD_MAX_TOLERANCES, ops.CLOUD_MAX_K, ops.CLOUD_SCAN_MAX_WINDOW, ops.CLOUD_MAX_POINTS) == (16, 32, 2, 1 << 30)
 
 
 def test_library_exports_the_renderer_and_checks_arguments_on_the_host():
