@@ -5,6 +5,7 @@ layout, function names) with the external ``fusibile`` executable replaced by th
 
     python -m atvsnet_amd.atvsnet.depth_fusion --dense_folder <scene> [--prob_threshold 0.8]
         [--disp_threshold 0.01] [--num_consistent 2]
+        [--normals {fake,depth}] [--normal_threshold DEG] [--normal_step S] [--normal_depth_gate G]
 
 reads  <dense_folder>/depths_atvsnet/{%08d.pfm, %08d_prob.pfm, %08d.jpg, %08d.txt}   (written by eval_pointcloud)
 writes <dense_folder>/depths_atvsnet/%08d_prob_filtered.pfm                          (probability_filter, :185-206)
@@ -14,6 +15,10 @@ writes <dense_folder>/depths_atvsnet/%08d_prob_filtered.pfm                     
 
 The gipuma-format intermediate files are kept (same bytes as the reference writes) so that either fusion back-end can
 consume them; ``--fusibile_exe_path`` is accepted and ignored.
+
+``--normals depth`` (not in the reference, whose normals are fake_colmap_normal's constant): every normals.dmb is estimated from
+its disp.dmb and camera on the MI355X (atvs_depth_normals_f32), the fusion's normal test runs with
+``--normal_threshold`` degrees (default 30) instead of 360, and the PLY carries the unit normal of every point.
 """
 from __future__ import print_function
 
@@ -94,8 +99,62 @@ def fake_colmap_normal(in_depth_path, out_normal_path):
     write_gipuma_dmb(out_normal_path, np.float32(normal_image * mask))
 
 
-def atvsnet_to_gipuma(dense_folder, gipuma_point_folder):
-    '''(reference :115-182)'''
+NORMAL_SOURCES = ('fake', 'depth')
+# --normals depth: the default normal threshold in degrees.  fusibile's own default neighbourhood (0.52 rad,
+# algorithmparameters.h:89), a default and not a measurement.
+DEPTH_NORMAL_THRESHOLD_DEG = 30.0
+
+
+def check_normal_options(normals='fake', normal_threshold=None, normal_step=1, normal_depth_gate=0.02):
+    """The normal options of SceneFusion / main, checked before any launch -> (normals, threshold in degrees, step, gate).
+    normal_threshold None: 360 (the reference's: the test rejects nothing) with 'fake', DEPTH_NORMAL_THRESHOLD_DEG with 'depth'."""
+    if normals not in NORMAL_SOURCES:
+        raise ValueError('normals must be one of %s, got %r' % (', '.join(NORMAL_SOURCES), normals))
+    if normal_threshold is None:
+        normal_threshold = 360.0 if normals == 'fake' else DEPTH_NORMAL_THRESHOLD_DEG
+    normal_threshold = float(normal_threshold)
+    if not (0.0 < normal_threshold <= 360.0):
+        raise ValueError('normal_threshold must be in (0, 360] degrees, got %r' % (normal_threshold,))
+    if int(normal_step) != normal_step or int(normal_step) < 1:
+        raise ValueError('normal_step must be an integer >= 1, got %r' % (normal_step,))
+    normal_depth_gate = float(normal_depth_gate)
+    if not (0.0 <= normal_depth_gate < float('inf')):
+        raise ValueError('normal_depth_gate must be >= 0 and finite, got %r' % (normal_depth_gate,))
+    return normals, normal_threshold, int(normal_step), normal_depth_gate
+
+
+def normal_threshold_radians(degrees):
+    """fusibile's --normal_thresh=<degrees> as it reaches the kernel (main.cpp:346-348): the float it scans, times pi / 180 in
+    double (rounded to float32 where it is passed on)."""
+    return float(np.float32(degrees)) * np.pi / 180.0
+
+
+def unit_normals(normals):
+    """(M,3) averaged normals of the fusion -> (M,3) float32 unit normals: the float64 norm, one division, one cast; a zero (or
+    non-finite) normal stays as it is.  The one place both pipelines restore unit length."""
+    n = np.asarray(normals, np.float32).reshape(-1, 3).astype(np.float64)
+    with np.errstate(all='ignore'):
+        length = np.sqrt((n * n).sum(-1, keepdims=True))
+        return np.where(length > 0, n / length, n).astype(np.float32)
+
+
+def depth_normal(in_depth_path, in_p_path, out_normal_path, normal_step=1, normal_depth_gate=0.02, device=None):
+    """normals.dmb of one map from its disp.dmb and its .P camera on the MI355X (atvs_depth_normals_f32): what
+    SceneFusion(normals='depth') computes for the map's slot of the slab."""
+    import torch
+    from .. import ops
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
+    depth = np.asarray(read_gipuma_dmb(in_depth_path), np.float32)
+    depth = depth.reshape(depth.shape[:2])
+    nd = np.zeros((1,) + depth.shape + (4,), np.float32)
+    nd[0, ..., 3] = depth
+    cams = torch.from_numpy(pack_cameras([read_p_file(in_p_path)])).to(dev)
+    out = ops.depth_normals(cams, torch.from_numpy(nd).to(dev), normal_step, normal_depth_gate)
+    write_gipuma_dmb(out_normal_path, out[0, ..., :3].cpu().numpy())
+
+
+def atvsnet_to_gipuma(dense_folder, gipuma_point_folder, normals='fake', normal_step=1, normal_depth_gate=0.02):
+    '''(reference :115-182)  normals='depth': normals.dmb from the map and its camera (depth_normal) instead of fake_colmap_normal'''
     depth_folder = os.path.join(dense_folder, 'depths_atvsnet')
     gipuma_cam_folder = os.path.join(gipuma_point_folder, 'cams')
     gipuma_image_folder = os.path.join(gipuma_point_folder, 'images')
@@ -131,7 +190,12 @@ def atvsnet_to_gipuma(dense_folder, gipuma_point_folder):
         in_depth_pfm = os.path.join(depth_folder, image_prefix + '_prob_filtered.pfm')
         out_depth_dmb = os.path.join(sub_depth_folder, 'disp.dmb')
         atvsnet_to_gipuma_dmb(in_depth_pfm, out_depth_dmb)
-        fake_colmap_normal(out_depth_dmb, os.path.join(sub_depth_folder, 'normals.dmb'))
+        out_normal_dmb = os.path.join(sub_depth_folder, 'normals.dmb')
+        if normals == 'depth':
+            depth_normal(out_depth_dmb, os.path.join(gipuma_cam_folder, image_name + '.P'), out_normal_dmb, normal_step,
+                         normal_depth_gate)
+        else:
+            fake_colmap_normal(out_depth_dmb, out_normal_dmb)
 
 
 def probability_filter(dense_folder, prob_threshold):
@@ -188,10 +252,11 @@ def read_p_file(path):
     return np.array(vals[:12], np.float64).reshape(3, 4)
 
 
-def fuse_views(Ps, depths, normals, images_bgr, disp_thresh, normal_thresh, num_consistent, device=None):
+def fuse_views(Ps, depths, normals, images_bgr, disp_thresh, normal_thresh, num_consistent, device=None, return_normals=False):
     """runcuda + copy_point_cloud_to_host (fusibile/fusibile.cu:279-325, 422-427) on the MI355X: every camera in turn
     is the reference of one atvs_fusibile launch; its created points whose three coordinates are all non-zero are
-    appended (camera-major, row-major).  -> (points (M,3) float32, colors (M,3) uint8 r,g,b)."""
+    appended (camera-major, row-major).  -> (points (M,3) float32, colors (M,3) uint8 r,g,b); return_normals: and the kernel's
+    averaged (not normalised) normal of every point, (M,3) float32."""
     import torch
     from .. import ops
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else device
@@ -200,16 +265,20 @@ def fuse_views(Ps, depths, normals, images_bgr, disp_thresh, normal_thresh, num_
     img = np.asarray(images_bgr)
     img4 = np.concatenate([img.astype(np.float32), np.zeros(img.shape[:3] + (1,), np.float32)], -1)
     nd_d, img_d = torch.from_numpy(np.ascontiguousarray(nd)).to(dev), torch.from_numpy(np.ascontiguousarray(img4)).to(dev)
-    pts, cols = [], []
+    pts, cols, nrms = [], [], []
     for ref in range(len(Ps)):
-        coord, _, tex, created = ops.fusibile(cams, nd_d, img_d, ref, float(disp_thresh), float(normal_thresh),
+        coord, normal, tex, created = ops.fusibile(cams, nd_d, img_d, ref, float(disp_thresh), float(normal_thresh),
                                               int(num_consistent))
         X = coord[..., :3]
         keep = (created > 0) & (X[..., 0] != 0) & (X[..., 1] != 0) & (X[..., 2] != 0)
         pts.append(X[keep].cpu().numpy())
+        if return_normals:
+            nrms.append(normal[..., :3][keep].cpu().numpy())
         t = tex[keep].cpu().numpy()
         # (char)(int) of channels 2, 1, 0 of the averaged texture (fusibile/displayUtils.h:109-111)
         cols.append(np.stack([t[:, 2], t[:, 1], t[:, 0]], -1).astype(np.int32).astype(np.uint8))
+    if return_normals:
+        return np.concatenate(pts, 0), np.concatenate(cols, 0), np.concatenate(nrms, 0)
     return np.concatenate(pts, 0), np.concatenate(cols, 0)
 
 
@@ -248,12 +317,19 @@ class SceneFusion(object):
 
     depth, prob: the network's outputs (host numpy or device tensors, any squeezable form of (rows, cols)); image_bgr_u8: the
     1/4-scale reference image (rows, cols, 3) uint8; cam: the (2,4,4) camera eval_pointcloud writes with write_cam.  `stream`:
-    the stream the staging is enqueued on (default: the current one); run() orders itself after every staging."""
+    the stream the staging is enqueued on (default: the current one); run() orders itself after every staging.
+
+    normals='depth' (default 'fake': the file pipeline's constant normal and its 360 degree threshold, which rejects nothing):
+    run() first estimates the normals of the staged slab from its depth planes (atvs_depth_normals_f32 with normal_step and
+    normal_depth_gate), fuses with normal_threshold degrees (default DEPTH_NORMAL_THRESHOLD_DEG) and keeps the
+    unit normal of every point for normals() and write_ply -- depth_fusion.main --normals depth on the same maps."""
 
     def __init__(self, n_maps, rows, cols, device=None, prob_threshold=0.8, disp_threshold=0.01, num_consistent=2,
-                 inverse_depth=None):
+                 inverse_depth=None, normals='fake', normal_threshold=None, normal_step=1, normal_depth_gate=0.02):
         import torch
         from ..flags import FLAGS
+        self.normal_source, self.normal_threshold, self.normal_step, self.normal_depth_gate = check_normal_options(
+            normals, normal_threshold, normal_step, normal_depth_gate)
         for name, v in (('n_maps', n_maps), ('rows', rows), ('cols', cols)):
             if int(v) != v or int(v) <= 0:
                 raise ValueError('SceneFusion: %s must be a positive integer, got %r' % (name, v))
@@ -269,7 +345,7 @@ class SceneFusion(object):
         self.img = torch.empty(shape, dtype=torch.float32, device=self.device)
         self.cams = np.zeros((self.n_maps, 28), np.float32)
         self.index, self.events = [], []          # out_index and staging event of each slot, in add() order
-        self.result = None
+        self.result = self.result_normals = None
 
     def _check_size(self, what, shape, want):
         if tuple(int(s) for s in shape) != want:
@@ -305,7 +381,7 @@ class SceneFusion(object):
         self.cams[slot] = row
         self.index.append(out_index)
         self.events.append(ev)
-        self.result = None
+        self.result = self.result_normals = None
 
     def order(self):
         """The slots in fusion order: by out_index ascending."""
@@ -324,18 +400,33 @@ class SceneFusion(object):
                 cur.wait_event(ev)
             order = self.order()
             nd, img = self.nd[:k], self.img[:k]
+            depth = self.normal_source == 'depth'
+            if depth:            # in slot order, in place: only the normal floats change, the staged depth planes stay
+                ops.depth_normals(torch.from_numpy(np.ascontiguousarray(self.cams[:k])).to(self.device), nd, self.normal_step,
+                                  self.normal_depth_gate)
             if not np.array_equal(order, np.arange(k)):
                 idx = torch.from_numpy(order).to(self.device)
                 nd, img = nd.index_select(0, idx), img.index_select(0, idx)
             cams = torch.from_numpy(np.ascontiguousarray(self.cams[:k][order])).to(self.device)
-            pts, cols = ops.fusibile_scene(cams, nd, img, self.disp_threshold, NORMAL_THRESHOLD, self.num_consistent)
-            self.result = (pts.cpu().numpy(), cols.cpu().numpy())
+            out = ops.fusibile_scene(cams, nd, img, self.disp_threshold, normal_threshold_radians(self.normal_threshold),
+                                     self.num_consistent, with_normals=depth)
+            self.result = (out[0].cpu().numpy(), out[1].cpu().numpy())
+            self.result_normals = unit_normals(out[2].cpu().numpy()) if depth else None
         return self.result
 
+    def normals(self):
+        """-> (M,3) float32: the unit normal of every point of run() (the fusion's average over the agreeing views, brought back to
+        unit length by unit_normals; a zero normal stays zero).  normals='depth' only."""
+        if self.normal_source != 'depth':
+            raise RuntimeError("SceneFusion.normals: the scene is fused with normals='fake', there are no normals to return")
+        self.run()
+        return self.result_normals
+
     def write_ply(self, path):
-        """run() into a binary PLY at `path` (the layout depth_fusion.main copies to <dense_folder>/final3d_model.ply)."""
+        """run() into a binary PLY at `path` (the layout depth_fusion.main copies to <dense_folder>/final3d_model.ply; with
+        normals='depth' every vertex carries its normal)."""
         pts, cols = self.run()
-        ply.write_ply(path, pts, cols)
+        ply.write_ply(path, pts, cols, self.result_normals)
         return len(pts)
 
 
@@ -344,12 +435,12 @@ def _imread_bgr(path):
     return np.asarray(Image.open(path).convert('RGB'))[:, :, ::-1].copy()
 
 
-def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consistent):
+def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consistent, normal_thresh=360, ply_normals=False):
     '''(reference :209-231 + fusibile/main.cpp:559-845) fuses the gipuma-format folder on the MI355X and writes
-    <point_folder>/consistencyCheck-<date>-<time>/final3d_model.ply'''
+    <point_folder>/consistencyCheck-<date>-<time>/final3d_model.ply.  normal_thresh: degrees, 360 as the reference passes it
+    (:216); ply_normals: the PLY carries the unit normal of every point (unit_normals of the fusion's average).'''
     cam_folder = os.path.join(point_folder, 'cams')
     image_folder = os.path.join(point_folder, 'images')
-    normal_thresh = 360            # degrees, as the reference passes it (:216)
     # sub-folders `<prefix>__<id>` whose name starts with '2' and has two underscores (main.cpp:619-649), sorted
     ids = []
     for sub in sorted(os.listdir(point_folder)):
@@ -369,11 +460,13 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
     normals = np.stack([read_gipuma_dmb(os.path.join(point_folder, sub, 'normals.dmb')) for sub, _, _ in ids], 0)
     if depths.shape[1:3] != images.shape[1:3]:
         raise RuntimeError('depth maps %s and images %s differ in size' % (depths.shape[1:3], images.shape[1:3]))
-    pts, cols = fuse_views(Ps, depths, normals, images, disp_thresh, normal_thresh * np.pi / 180.0, int(num_consistent))
+    fused = fuse_views(Ps, depths, normals, images, disp_thresh, normal_threshold_radians(normal_thresh), int(num_consistent),
+                       return_normals=ply_normals)
+    pts, cols = fused[:2]
     out = os.path.join(point_folder, 'consistencyCheck-' + time.strftime('%Y%m%d-%H%M%S'))
     os.makedirs(out, exist_ok=True)
     print('Found %.2f million points' % (len(pts) / 1e6))
-    ply.write_ply(os.path.join(out, 'final3d_model.ply'), pts, cols)
+    ply.write_ply(os.path.join(out, 'final3d_model.ply'), pts, cols, unit_normals(fused[2]) if ply_normals else None)
     return out
 
 
@@ -384,7 +477,21 @@ def main(argv=None):
     parser.add_argument('--prob_threshold', type=float, default=0.8)
     parser.add_argument('--disp_threshold', type=float, default=0.01)
     parser.add_argument('--num_consistent', type=float, default=2)
+    parser.add_argument('--normals', choices=NORMAL_SOURCES, default='fake',
+                        help='fake: the constant normal of the reference; depth: estimated from each depth map on the GPU, tested in '
+                             'the fusion and written into the PLY')
+    parser.add_argument('--normal_threshold', type=float, default=None, metavar='DEG',
+                        help='largest angle between the normals of two agreeing views (default: 360 with --normals fake, %g with '
+                             '--normals depth)' % DEPTH_NORMAL_THRESHOLD_DEG)
+    parser.add_argument('--normal_step', type=int, default=1, metavar='S', help='--normals depth: pixel distance of the neighbours')
+    parser.add_argument('--normal_depth_gate', type=float, default=0.02, metavar='G',
+                        help='--normals depth: a neighbour counts when its depth is within G * depth')
     args = parser.parse_args(argv)
+    try:
+        normals, normal_threshold, normal_step, normal_depth_gate = check_normal_options(
+            args.normals, args.normal_threshold, args.normal_step, args.normal_depth_gate)
+    except ValueError as e:
+        parser.error(str(e))
     dense_folder = args.dense_folder
     point_folder = os.path.join(dense_folder, 'points_atvsnet')
     if not os.path.isdir(point_folder):
@@ -392,9 +499,10 @@ def main(argv=None):
     print('filter depth map with probability map')
     probability_filter(dense_folder, args.prob_threshold)
     print('Convert atvsnet output to gipuma input')
-    atvsnet_to_gipuma(dense_folder, point_folder)
+    atvsnet_to_gipuma(dense_folder, point_folder, normals, normal_step, normal_depth_gate)
     print('Run depth map fusion & filter')
-    depth_map_fusion(point_folder, args.fusibile_exe_path, args.disp_threshold, args.num_consistent)
+    depth_map_fusion(point_folder, args.fusibile_exe_path, args.disp_threshold, args.num_consistent, normal_threshold,
+                     ply_normals=normals == 'depth')
     cloudlist = sorted(name for name in os.listdir(point_folder) if 'consistency' in name)
     shutil.copyfile(os.path.join(point_folder, cloudlist[-1], 'final3d_model.ply'),
                     os.path.join(dense_folder, 'final3d_model.ply'))

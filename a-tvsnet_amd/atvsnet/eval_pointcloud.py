@@ -519,9 +519,13 @@ def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register
 
 
 def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True, gt_ply=None, register=None,
-                  clean=None, score_maps=None):
-    """What each of run_eval_pc's options needs -> every rule as (broken by these values, message)."""
-    return [
+                  clean=None, score_maps=None, fuse_normals=None):
+    """What each of run_eval_pc's options needs -> every rule as (broken by these values, message).  The row of fuse_normals is
+    listed for a caller that gives fuse_normals: without it there is nothing the row could refuse."""
+    normals_row = [] if fuse_normals is None else [
+        (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
+                       '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
+    return normals_row + [
         (scene_cache and not use_graph, '--scene_cache replays captured graphs: it cannot be combined with --eager (use_graph=False)'),
         (not map_files and fuse is None, '--no_map_files needs --fuse (map_files=False needs fuse): the run would write nothing'),
         (bool(gt_ply) and fuse is None, '--gt_ply needs --fuse (gt_ply needs fuse): there is no point cloud to score'),
@@ -539,13 +543,17 @@ def _check_options(**options):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None, register=None, clean=None, score_maps=None):
+                gt_ply=None, register=None, clean=None, score_maps=None, fuse_normals=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
     fuse: None, or dict(prob_threshold=, disp_threshold=, num_consistent=): every map is also staged on the device as it is
     finished (depth_fusion.SceneFusion) and each scene ends with <savepath>/<scene>/final3d_model.ply, the point cloud
     depth_fusion.main makes from the written files.  map_files=False (with fuse only): no per-map files.
+    fuse_normals (with fuse only): None, or a dict of SceneFusion's normal options (normals=, normal_threshold=, normal_step=,
+    normal_depth_gate=): with normals='depth' the fusion estimates each map's normals from its depths, tests them and writes them
+    into final3d_model.ply -- what depth_fusion.main --normals depth makes from the written files.  Scoring and cleaning read the
+    points as before.
     gt_ply (with fuse only): ground-truth PLY paths; each scene's fused points, as the PLY stores them, are scored against them
     (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY.
     register (with gt_ply only): None, or dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned
@@ -562,7 +570,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     second fit).  Every other output is what it is without it."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
-                   clean=clean, score_maps=score_maps)
+                   clean=clean, score_maps=score_maps, fuse_normals=fuse_normals)
+    if fuse_normals is not None:
+        depth_fusion.check_normal_options(**fuse_normals)
+        fuse = dict(fuse, **fuse_normals)
     gt_points, register_args, init_cameras = None, {}, None
     if gt_ply:
         from ..tools.ply import read_ply_points
@@ -597,6 +608,14 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         source.close()
 
 
+def _normal_options(flags):
+    """run_eval_pc's fuse_normals from cli's --fuse_normal* options: those that were given, None when none was."""
+    names = dict(fuse_normals='normals', fuse_normal_threshold='normal_threshold', fuse_normal_step='normal_step',
+                 fuse_normal_depth_gate='normal_depth_gate')
+    given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
+    return given or None
+
+
 def _run_options(flags):
     """run_eval_pc's keyword arguments from a namespace of cli's options (FLAGS, cli's parsed arguments): one it lacks is off."""
     opt = lambda name, default=None: getattr(flags, name, default)          # noqa: E731
@@ -604,6 +623,7 @@ def _run_options(flags):
         use_graph=not opt('eager'), scene_cache=opt('scene_cache', False), write_thread=not opt('sync_write'),
         fuse=dict(prob_threshold=flags.prob_threshold, disp_threshold=flags.disp_threshold, num_consistent=flags.num_consistent)
         if opt('fuse') else None,
+        fuse_normals=_normal_options(flags),
         map_files=not opt('no_map_files'), gt_ply=opt('gt_ply') or None, clean=opt('clean') or None,
         register=dict(with_scale=opt('with_scale', False), init_cameras=opt('init_cameras') or None) if opt('register') else None,
         score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
@@ -654,6 +674,14 @@ def cli(argv=None):
     parser.add_argument('--num_consistent', type=float, default=2, help='--fuse: depth_fusion --num_consistent')
     parser.add_argument('--no_map_files', action='store_true',
                         help='--fuse: do not write the per-map files of depths_atvsnet/ (zz_runtime.txt is still written)')
+    parser.add_argument('--fuse_normals', choices=depth_fusion.NORMAL_SOURCES, default=None,
+                        help='--fuse: depth_fusion --normals (depth: normals estimated from each depth map on the GPU, tested in the '
+                             'fusion and written into final3d_model.ply; default fake)')
+    parser.add_argument('--fuse_normal_threshold', type=float, default=None, metavar='DEG',
+                        help='--fuse: depth_fusion --normal_threshold')
+    parser.add_argument('--fuse_normal_step', type=int, default=None, metavar='S', help='--fuse: depth_fusion --normal_step')
+    parser.add_argument('--fuse_normal_depth_gate', type=float, default=None, metavar='G',
+                        help='--fuse: depth_fusion --normal_depth_gate')
     parser.add_argument('--gt_ply', type=str, default=None, metavar='FILE[,FILE...]',
                         help='--fuse: score each scene\'s fused cloud against these ground-truth PLY file(s) (eval_cloud: accuracy, '
                              'completeness, F-score; not the official ETH3D evaluator) into <savepath>/<scene>/cloud_eval.json')
@@ -690,6 +718,7 @@ def cli(argv=None):
     args.clean = clean_cloud.options(parser, args, 'clean_') or None
     try:
         _check_options(**_run_options(args))
+        depth_fusion.check_normal_options(**(_normal_options(args) or {}))
     except ValueError as e:
         parser.error(str(e))
     scenes = args.scenes.split(',') if args.scenes else None

@@ -12,23 +12,27 @@
 //            and the total;
 //   scatter  one workgroup per count: its region to points / colours at its offset.
 // No workgroup waits on another, no atomics; the cameras are wave-uniform (one reference per workgroup).
+//
+// atvs_fusibile_scene_normals is the same three launches with kNormals = true: the count pass also keeps fuse_pixel's averaged
+// normal of every kept point in a second region of the scratch, the scatter pass writes it beside the point.
+#include "fusion_grid.h"
 #include "fusion_pixel.h"
 
 namespace {
 
-constexpr int kRun = 256;            // pixels per workgroup of the count pass (4 waves)
 constexpr int kScanThreads = 1024;
 
 struct ScratchLayout {               // byte offsets into the caller's scratch
-  size_t counts, offsets, slab, bytes;
+  size_t counts, offsets, slab, nslab, bytes;
 };
 
-__host__ __device__ inline ScratchLayout scratch_layout(long blocks) {
+__host__ __device__ inline ScratchLayout scratch_layout(long blocks, bool normals) {
   ScratchLayout s;
   s.counts = 0;
   s.offsets = ((size_t)blocks * 4 + 255) & ~(size_t)255;
   s.slab = s.offsets + (((size_t)blocks * 4 + 255) & ~(size_t)255);
-  s.bytes = s.slab + (size_t)blocks * kRun * sizeof(float4);
+  s.nslab = s.slab + (size_t)blocks * kRun * sizeof(float4);
+  s.bytes = s.nslab + (normals ? (size_t)blocks * kRun * sizeof(float4) : 0);
   return s;
 }
 
@@ -51,17 +55,18 @@ __global__ __launch_bounds__(256) void fusion_stage_kernel(const float* __restri
   img_out[i] = make_float4((float)p[0], (float)p[1], (float)p[2], 0.f);
 }
 
+template <bool kNormals>
 __global__ __launch_bounds__(kRun) void fusion_count_kernel(const float* __restrict__ cams, const float4* __restrict__ nd,
                                                             const float4* __restrict__ img, int nviews, int rows, int cols,
                                                             int runs_per_cam, float disp_thresh, float normal_thresh,
                                                             int num_consistent, int* __restrict__ counts,
-                                                            float4* __restrict__ slab) {
+                                                            float4* __restrict__ slab, float4* __restrict__ nslab) {
   __shared__ int wave_kept[kRun / 64];
   const int b = blockIdx.x;
   const int ref = b / runs_per_cam;                    // uniform over the workgroup
   const int p = (b - ref * runs_per_cam) * kRun + (int)threadIdx.x;
   bool keep = false;
-  float4 out = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 out = make_float4(0.f, 0.f, 0.f, 0.f), nout = out;
   if (p < rows * cols) {
     const int y = p / cols, x = p - y * cols;
     const FusedPixel o = fuse_pixel(cams, nd, img, nviews, ref, rows, cols, x, y, disp_thresh, normal_thresh, num_consistent);
@@ -69,6 +74,7 @@ __global__ __launch_bounds__(kRun) void fusion_count_kernel(const float* __restr
     // (char)(int) of channels 2, 1, 0 of the averaged texture (fusibile/displayUtils.h:109-111), packed r | g << 8 | b << 16
     const unsigned r = (unsigned char)(int)o.texture.z, g = (unsigned char)(int)o.texture.y, bl = (unsigned char)(int)o.texture.x;
     out = make_float4(o.coord.x, o.coord.y, o.coord.z, __uint_as_float(r | (g << 8) | (bl << 16)));
+    nout = o.normal;
   }
   const unsigned long long m = __ballot(keep);
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -80,6 +86,7 @@ __global__ __launch_bounds__(kRun) void fusion_count_kernel(const float* __restr
     total += wave_kept[w];
   }
   if (keep) slab[(size_t)b * kRun + before] = out;
+  if (kNormals && keep) nslab[(size_t)b * kRun + before] = nout;
   if (threadIdx.x == 0) counts[b] = total;
 }
 
@@ -105,9 +112,11 @@ __global__ __launch_bounds__(kScanThreads) void fusion_scan_kernel(const int* __
   if (threadIdx.x == 0) total[0] = carry;
 }
 
+template <bool kNormals>
 __global__ __launch_bounds__(kRun) void fusion_scatter_kernel(const int* __restrict__ counts, const int* __restrict__ offsets,
-                                                              const float4* __restrict__ slab, long capacity,
-                                                              float* __restrict__ points, unsigned char* __restrict__ colors) {
+                                                              const float4* __restrict__ slab, const float4* __restrict__ nslab,
+                                                              long capacity, float* __restrict__ points,
+                                                              unsigned char* __restrict__ colors, float* __restrict__ normals) {
   const int b = blockIdx.x, t = threadIdx.x;
   if (t >= counts[b]) return;
   const long dst = (long)offsets[b] + t;
@@ -120,18 +129,52 @@ __global__ __launch_bounds__(kRun) void fusion_scatter_kernel(const int* __restr
   colors[dst * 3 + 0] = (unsigned char)(rgb & 0xff);
   colors[dst * 3 + 1] = (unsigned char)((rgb >> 8) & 0xff);
   colors[dst * 3 + 2] = (unsigned char)((rgb >> 16) & 0xff);
+  if (kNormals) {
+    const float4 n = nslab[(size_t)b * kRun + t];
+    normals[dst * 3 + 0] = n.x;
+    normals[dst * 3 + 1] = n.y;
+    normals[dst * 3 + 2] = n.z;
+  }
 }
 
-// runs of kRun pixels per camera and workgroups of the count pass; false when the index types cannot hold the scene
-bool scene_grid(int nviews, int rows, int cols, int* runs_per_cam, long* blocks) {
-  if (nviews <= 0 || rows <= 0 || cols <= 0) return false;
-  const long long plane = (long long)rows * cols;
-  const long long runs = (plane + kRun - 1) / kRun;
-  // every pixel index of the slab (N * rows * cols), every slot of the scratch regions (blocks * kRun) and the point count: int
-  if (plane * nviews > 0x7fffffffLL || runs * kRun * nviews > 0x7fffffffLL) return false;
-  *runs_per_cam = (int)runs;
-  *blocks = (long)(runs * nviews);
-  return true;
+int scene_scratch_size(int nviews, int rows, int cols, bool normals, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  int runs = 0;
+  long blocks = 0;
+  if (!scene_grid(nviews, rows, cols, &runs, &blocks)) return ATVS_ERR_SHAPE;
+  *bytes = (long)scratch_layout(blocks, normals).bytes;
+  return ATVS_OK;
+}
+
+// count, scan, scatter on `stream`; kNormals: `normals` (capacity, 3) receives fuse_pixel's normal.xyz of every kept point
+template <bool kNormals>
+int fuse_scene(const float* cams, const float* normals_depths, const float* images, int nviews, int rows, int cols,
+               float disp_thresh, float normal_thresh, int num_consistent, void* scratch, long scratch_bytes, float* points,
+               unsigned char* colors, float* normals, long capacity, int* n_points, atvs_stream_t stream) {
+  if (!cams || !normals_depths || !images || !scratch || !points || !colors || !n_points || (kNormals && !normals))
+    return ATVS_ERR_NULL;
+  int runs = 0;
+  long blocks = 0;
+  if (!scene_grid(nviews, rows, cols, &runs, &blocks)) return ATVS_ERR_SHAPE;
+  const ScratchLayout L = scratch_layout(blocks, kNormals);
+  // every pixel may become a point: the outputs must hold N * rows * cols of them
+  if (scratch_bytes < (long)L.bytes || capacity < (long)nviews * rows * cols) return ATVS_ERR_SHAPE;
+  char* s = static_cast<char*>(scratch);
+  int* counts = reinterpret_cast<int*>(s + L.counts);
+  int* offsets = reinterpret_cast<int*>(s + L.offsets);
+  float4* slab = reinterpret_cast<float4*>(s + L.slab);
+  float4* nslab = kNormals ? reinterpret_cast<float4*>(s + L.nslab) : nullptr;
+  hipStream_t st = as_stream(stream);
+  hipLaunchKernelGGL(fusion_count_kernel<kNormals>, dim3((unsigned)blocks), dim3(kRun), 0, st, cams,
+                     reinterpret_cast<const float4*>(normals_depths), reinterpret_cast<const float4*>(images), nviews, rows, cols,
+                     runs, disp_thresh, normal_thresh, num_consistent, counts, slab, nslab);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fusion_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, (int)blocks, offsets, n_points);
+  ATVS_LAUNCH_CHECK();
+  hipLaunchKernelGGL(fusion_scatter_kernel<kNormals>, dim3((unsigned)blocks), dim3(kRun), 0, st, counts, offsets, slab, nslab,
+                     capacity, points, colors, normals);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
 }
 
 }  // namespace
@@ -149,38 +192,25 @@ extern "C" int atvs_fusion_stage_f32(const float* depth, const float* prob, cons
 }
 
 extern "C" int atvs_fusibile_scene_scratch_size(int nviews, int rows, int cols, long* bytes) {
-  if (!bytes) return ATVS_ERR_NULL;
-  int runs = 0;
-  long blocks = 0;
-  if (!scene_grid(nviews, rows, cols, &runs, &blocks)) return ATVS_ERR_SHAPE;
-  *bytes = (long)scratch_layout(blocks).bytes;
-  return ATVS_OK;
+  return scene_scratch_size(nviews, rows, cols, false, bytes);
+}
+
+extern "C" int atvs_fusibile_scene_normals_scratch_size(int nviews, int rows, int cols, long* bytes) {
+  return scene_scratch_size(nviews, rows, cols, true, bytes);
 }
 
 extern "C" int atvs_fusibile_scene(const float* cams, const float* normals_depths, const float* images, int nviews, int rows,
                                    int cols, float disp_thresh, float normal_thresh, int num_consistent, void* scratch,
                                    long scratch_bytes, float* points, unsigned char* colors, long capacity, int* n_points,
                                    atvs_stream_t stream) {
-  if (!cams || !normals_depths || !images || !scratch || !points || !colors || !n_points) return ATVS_ERR_NULL;
-  int runs = 0;
-  long blocks = 0;
-  if (!scene_grid(nviews, rows, cols, &runs, &blocks)) return ATVS_ERR_SHAPE;
-  const ScratchLayout L = scratch_layout(blocks);
-  // every pixel may become a point: the outputs must hold N * rows * cols of them
-  if (scratch_bytes < (long)L.bytes || capacity < (long)nviews * rows * cols) return ATVS_ERR_SHAPE;
-  char* s = static_cast<char*>(scratch);
-  int* counts = reinterpret_cast<int*>(s + L.counts);
-  int* offsets = reinterpret_cast<int*>(s + L.offsets);
-  float4* slab = reinterpret_cast<float4*>(s + L.slab);
-  hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(fusion_count_kernel, dim3((unsigned)blocks), dim3(kRun), 0, st, cams,
-                     reinterpret_cast<const float4*>(normals_depths), reinterpret_cast<const float4*>(images), nviews, rows, cols,
-                     runs, disp_thresh, normal_thresh, num_consistent, counts, slab);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fusion_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, (int)blocks, offsets, n_points);
-  ATVS_LAUNCH_CHECK();
-  hipLaunchKernelGGL(fusion_scatter_kernel, dim3((unsigned)blocks), dim3(kRun), 0, st, counts, offsets, slab, capacity, points,
-                     colors);
-  ATVS_LAUNCH_CHECK();
-  return ATVS_OK;
+  return fuse_scene<false>(cams, normals_depths, images, nviews, rows, cols, disp_thresh, normal_thresh, num_consistent, scratch,
+                           scratch_bytes, points, colors, nullptr, capacity, n_points, stream);
+}
+
+extern "C" int atvs_fusibile_scene_normals(const float* cams, const float* normals_depths, const float* images, int nviews,
+                                           int rows, int cols, float disp_thresh, float normal_thresh, int num_consistent,
+                                           void* scratch, long scratch_bytes, float* points, unsigned char* colors, float* normals,
+                                           long capacity, int* n_points, atvs_stream_t stream) {
+  return fuse_scene<true>(cams, normals_depths, images, nviews, rows, cols, disp_thresh, normal_thresh, num_consistent, scratch,
+                          scratch_bytes, points, colors, normals, capacity, n_points, stream);
 }

@@ -113,11 +113,32 @@ def fusion_stage(depth, prob, bgr, inverse_depth, prob_thresh, nd_out, img_out):
     return nd_out, img_out
 
 
-def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num_consistent):
+def depth_normals(cams, normals_depths, step=1, depth_gate=0.02):
+    """Normals of a scene's depth maps from the maps themselves (atvs_depth_normals_f32): cams (N,28), normals_depths
+    (N,rows,cols,4) float32 = (nx, ny, nz, depth), whose three normal floats are rewritten IN PLACE from its depth plane (which is
+    left as it is): the float64 cross products of the four neighbour quadrants at `step` pixels, a neighbour counting when its
+    depth is within depth_gate * depth, oriented towards the camera; (0,0,0) where there is no depth or no usable quadrant.
+    On the current stream.  -> normals_depths."""
+    if not isinstance(normals_depths, torch.Tensor) or normals_depths.dim() != 4:
+        raise ValueError('depth_normals: normals_depths must be a (N, rows, cols, 4) tensor')
+    if int(step) != step or int(step) < 1:
+        raise ValueError('depth_normals: step must be an integer >= 1, got %r' % (step,))
+    depth_gate = float(depth_gate)
+    if not (0.0 <= depth_gate < float('inf')):
+        raise ValueError('depth_normals: depth_gate must be >= 0 and finite, got %r' % (depth_gate,))
+    N, rows, cols, _ = (int(s) for s in normals_depths.shape)
+    if _fusion_args((cams, 'cams', torch.float32, (N, 28)), (normals_depths, 'normals_depths', torch.float32, (N, rows, cols, 4))):
+        _call('atvs_depth_normals_f32', _p(cams), _p(normals_depths), N, rows, cols, int(step), depth_gate, _stream())
+    return normals_depths
+
+
+def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num_consistent, with_normals=False):
     """Every reference camera of the slab fused in one pass, the host filter of fuse_views applied and the kept points compacted on
     the device (atvs_fusibile_scene).  cams (N,28), normals_depths / images (N,rows,cols,4) float32 -> (points (M,3) float32,
     colors (M,3) uint8 r,g,b) on the device, camera-major and row-major as fuse_views concatenates them.  Reads the count back
-    (one synchronisation of the current stream)."""
+    (one synchronisation of the current stream).
+    with_normals: -> (points, colors, normals (M,3) float32), the normal averaged over the reference and the agreeing views of
+    every point, not normalised (atvs_fusibile_scene_normals; points and colours are the same bits)."""
     if not isinstance(normals_depths, torch.Tensor) or normals_depths.dim() != 4:
         raise ValueError('fusibile_scene: normals_depths must be a (N, rows, cols, 4) tensor')
     N, rows, cols, _ = (int(s) for s in normals_depths.shape)
@@ -126,11 +147,13 @@ def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num
         raise RuntimeError('fusibile_scene: the number of points is only known after a launch (got meta tensors)')
     dev = normals_depths.device
     capacity = N * rows * cols
-    scratch = torch.empty(_size('atvs_fusibile_scene_scratch_size', N, rows, cols), dtype=torch.uint8, device=dev)
+    name = 'atvs_fusibile_scene_normals' if with_normals else 'atvs_fusibile_scene'
+    scratch = torch.empty(_size(name + '_scratch_size', N, rows, cols), dtype=torch.uint8, device=dev)
     points = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
     colors = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
     count = torch.empty(1, dtype=torch.int32, device=dev)
-    _call('atvs_fusibile_scene', _p(cams), _p(normals_depths), _p(images), N, rows, cols, disp_thresh, normal_thresh,
-          int(num_consistent), _p(scratch), scratch.numel(), _p(points), _p(colors), capacity, _p(count), _stream())
+    outputs = [points, colors] + ([torch.empty((capacity, 3), dtype=torch.float32, device=dev)] if with_normals else [])
+    _call(name, _p(cams), _p(normals_depths), _p(images), N, rows, cols, disp_thresh, normal_thresh, int(num_consistent),
+          _p(scratch), scratch.numel(), *([_p(t) for t in outputs] + [capacity, _p(count), _stream()]))
     m = int(count.item())
-    return points[:m], colors[:m]
+    return tuple(t[:m] for t in outputs)

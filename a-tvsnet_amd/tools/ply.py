@@ -1,39 +1,67 @@
 """Binary PLY point clouds in the layout the reference's fusibile writes (fusibile/displayUtils.h:80-135):
-`format binary_little_endian 1.0`, vertices of (float x, y, z, uchar red, green, blue)."""
+`format binary_little_endian 1.0`, vertices of (float x, y, z, uchar red, green, blue); with normals (not in the reference)
+(float x, y, z, nx, ny, nz, uchar red, green, blue)."""
 import numpy as np
 
 _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
 
 
-def write_ply(path, points, colors):
+_VERTEX_N = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
+                      ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
+_HEADER_TYPES = {'f4': 'float', 'u1': 'uchar'}
+
+
+def write_ply(path, points, colors, normals=None):
     """points (M,3) float32, colors (M,3) uint8 (r, g, b).  Non-finite coordinates are written as (0,0,0) like the
-    reference (:115-119)."""
+    reference (:115-119).  normals (M,3) float32: the vertex becomes (x, y, z, nx, ny, nz, red, green, blue); a non-finite
+    normal is written as (0,0,0)."""
     points = np.asarray(points, np.float32).reshape(-1, 3).copy()
     colors = np.asarray(colors, np.uint8).reshape(-1, 3)
     bad = ~np.isfinite(points).all(axis=1)
     points[bad] = 0.0
-    v = np.empty(len(points), _VERTEX)
+    v = np.empty(len(points), _VERTEX if normals is None else _VERTEX_N)
     v['x'], v['y'], v['z'] = points[:, 0], points[:, 1], points[:, 2]
     v['red'], v['green'], v['blue'] = colors[:, 0], colors[:, 1], colors[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, np.float32).reshape(-1, 3).copy()
+        if len(normals) != len(points):
+            raise ValueError('write_ply: %d normals for %d points' % (len(normals), len(points)))
+        normals[~np.isfinite(normals).all(axis=1)] = 0.0
+        v['nx'], v['ny'], v['nz'] = normals[:, 0], normals[:, 1], normals[:, 2]
     with open(path, 'wb') as f:
-        f.write(('ply\nformat binary_little_endian 1.0\nelement vertex %d\nproperty float x\nproperty float y\n'
-                 'property float z\nproperty uchar red\nproperty uchar green\nproperty uchar blue\nend_header\n'
-                 % len(points)).encode('ascii'))
+        f.write(('ply\nformat binary_little_endian 1.0\nelement vertex %d\n' % len(points)).encode('ascii'))
+        f.write(''.join('property %s %s\n' % (_HEADER_TYPES[v.dtype[name].str[1:]], name) for name in v.dtype.names).encode('ascii'))
+        f.write(b'end_header\n')
         v.tofile(f)
 
 
-def read_ply(path):
-    """-> (points (M,3) float32, colors (M,3) uint8) of a file written by write_ply / the reference."""
+def read_ply_normals(path):
+    """-> (points (M,3) float32, colors (M,3) uint8, normals (M,3) float32 or None) of a file written by write_ply / the reference,
+    by the vertex properties its header lists: with or without nx, ny, nz."""
     with open(path, 'rb') as f:
-        n = None
+        n, names = None, []
         while True:
-            line = f.readline().decode('ascii').strip()
+            raw = f.readline()
+            if not raw:
+                raise ValueError('%s: the header has no end_header' % path)
+            line = raw.decode('ascii').strip()
             if line.startswith('element vertex'):
                 n = int(line.split()[-1])
+            if line.startswith('property'):
+                names.append(line.split()[-1])
             if line == 'end_header':
                 break
-        v = np.fromfile(f, _VERTEX, n)
-    return np.stack([v['x'], v['y'], v['z']], -1), np.stack([v['red'], v['green'], v['blue']], -1)
+        layout = {_VERTEX.names: _VERTEX, _VERTEX_N.names: _VERTEX_N}.get(tuple(names))
+        if layout is None or n is None:
+            raise ValueError('%s: not a vertex layout write_ply writes: %s' % (path, ' '.join(names)))
+        v = np.fromfile(f, layout, n)
+    normals = np.stack([v['nx'], v['ny'], v['nz']], -1) if layout is _VERTEX_N else None
+    return np.stack([v['x'], v['y'], v['z']], -1), np.stack([v['red'], v['green'], v['blue']], -1), normals
+
+
+def read_ply(path):
+    """-> (points (M,3) float32, colors (M,3) uint8) of a file written by write_ply / the reference (with or without normals)."""
+    return read_ply_normals(path)[:2]
 
 
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 53
+#define ATVS_ABI_VERSION 54
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -654,6 +654,29 @@ int atvs_fusibile_scene_scratch_size(int nviews, int rows, int cols, long* bytes
 int atvs_fusibile_scene(const float* cams, const float* normals_depths, const float* images, int nviews, int rows, int cols,
                         float disp_thresh, float normal_thresh, int num_consistent, void* scratch, long scratch_bytes,
                         float* points, unsigned char* colors, long capacity, int* n_points, atvs_stream_t stream);
+
+/* atvs_fusibile_scene that also returns the normals: normals (capacity, 3) floats receives normal.xyz of atvs_fusibile for every
+ * kept point, in the order of the points (the average over the reference and the agreeing views, NOT normalised).  The same
+ * kernels with one more scratch region: atvs_fusibile_scene_normals_scratch_size bytes.  Points, colours and count are those of
+ * atvs_fusibile_scene bit for bit. */
+int atvs_fusibile_scene_normals_scratch_size(int nviews, int rows, int cols, long* bytes);
+int atvs_fusibile_scene_normals(const float* cams, const float* normals_depths, const float* images, int nviews, int rows,
+                                int cols, float disp_thresh, float normal_thresh, int num_consistent, void* scratch,
+                                long scratch_bytes, float* points, unsigned char* colors, float* normals, long capacity,
+                                int* n_points, atvs_stream_t stream);
+
+/* Normals of a scene's depth maps from the maps themselves (csrc/depth_normals.hip), one launch over the fusion slab
+ * normals_depths (nviews, rows, cols, 4) = (nx, ny, nz, depth), IN PLACE: only .w (the depth) is read, only the three normal
+ * floats are written.  cams (nviews, 28) as for atvs_fusibile.  Per pixel (x, y) with depth d, in float64:
+ *   d > 0 false -> (0,0,0).  X(x,y,d) = M_inv (d x - p0, d y - p1, d - p2).  Neighbours R = (x+step, y), D = (x, y+step),
+ *   L = (x-step, y), U = (x, y-step), valid when inside the image, dn > 0 and |dn - d| <= depth_gate * d.  For the quadrants
+ *   (R,D), (D,L), (L,U), (U,R) with both neighbours valid: c = (Xa - X) x (Xb - X), and c / |c| is added to a sum when |c| > 0.
+ *   |sum| = 0 -> (0,0,0); else n = sum / |sum|, negated when n . (C - X) < 0 (the surface faces its camera); stored as float.
+ * A zero normal is 90 degrees from every normal in atvs_fusibile (acosf(0)): under a normal threshold below 90 degrees such a
+ * pixel agrees with no view.
+ * step < 1, depth_gate negative or not finite: ATVS_ERR_ARG; nviews * rows * cols beyond int: ATVS_ERR_SHAPE. */
+int atvs_depth_normals_f32(const float* cams, float* normals_depths, int nviews, int rows, int cols, int step, float depth_gate,
+                           atvs_stream_t stream);
 
 
 /* ---- 3x3x3 stride-2 SAME transposed convolution to 8 or 16 channels, all 8 output parity classes per staged input tile
