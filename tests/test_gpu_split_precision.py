@@ -7,7 +7,14 @@ runs six operand regimes: randn, post-ReLU, scale 1e-3, log-uniform 1e-4 ... 1e2
 subnormal), and a few entries near 6e4 with finite outputs.  Every run is under poison_allocator with NaN-bordered inputs:
 a read past an input, an unwritten output or statistics row, or a write outside the output's channel slice turns up as a
 NaN or a changed bit.  The batch-norm moments of each output are checked against float64 moments of what was written, and
-must not raise the sticky non-finite flag.  Rows with G = 3 scale the samples 1e-3, 1, 1e3 (where the range allows)."""
+must not raise the sticky non-finite flag.  Rows with G = 3 scale the samples 1e-3, 1, 1e3 (where the range allows).
+
+Rows whose input is lazy (a pending batch norm, or a sum of two, formed while the kernel stages it) run a seventh regime,
+`offset` (tests/bn_ref.py): raw inputs whose channel means are 50 to 2e4 standard deviations, with each sample's own batch
+moments as parameters.  There the rounding of the on-load transform, about u |mean * rstd| and not u |value|, is what dominates,
+so cond is numerics.cond_on_load -- the same operator on bn_cond = |x s| + |m s| + |b| of each lazy term -- and rel is the row's
+own plus 2^-22: the transform moves a normalised input by at most 2u * bn_cond, a two-term sum adds u (cond_a + cond_b), and
+3u < 2^-22."""
 import collections
 
 import numpy as np
@@ -17,18 +24,22 @@ import torch
 from oracle import nets
 from oracle import tf_ops as T
 
+import bn_ref
 import numerics as N
 from numerics import FP32_MFMA, SPLIT
 
 pytestmark = pytest.mark.gpu
 
 REGIMES = ('randn', 'relu', 'small', 'loguniform', 'subnormal', 'near_max')
-_SCALE = {'randn': 1.0, 'relu': 1.0, 'small': 1e-3, 'loguniform': 1.0, 'subnormal': 2.0 ** -16, 'near_max': 1.0}
+OFFSET = 'offset'                  # the seventh regime, of the rows with a lazy input only
+OFFSET_REL = 2.0 ** -22
+_SCALE = {'randn': 1.0, 'relu': 1.0, 'small': 1e-3, 'loguniform': 1.0, 'subnormal': 2.0 ** -16, 'near_max': 1.0, OFFSET: 1.0}
 SAMPLE_SCALES = (1e-3, 1.0, 1e3)
 
 # family: what the row asserts it reaches; split: its split-operand family (the ops.split_on names, xb = conv_xb.hip,
 # aanet_b = aanet_b.hip) or None; cfg: the ops.configure switches it runs under
-Row = collections.namedtuple('Row', 'name family split bar run cfg')
+Row = collections.namedtuple('Row', 'name family split bar run cfg lazy')
+Row.__new__.__defaults__ = (False,)                  # lazy: the input is formed on load, the row runs the offset regime too
 FP32 = {'split16': False}
 
 
@@ -71,6 +82,21 @@ def _params(G, C, seed, regime):
 
 def _dev(t, dev):
     return N.nan_bordered(t.to(dev))
+
+
+def _pending(shape, seed_x, seed_p, regime, dev, relu):
+    """A lazy input of the regime: the operand and parameters of _input / _params, or in the offset regime a raw tensor with
+    large channel means and its own batch moments (bn_ref.operand)."""
+    from atvsnet_amd import ops
+    if regime == OFFSET:
+        x, par = bn_ref.operand(OFFSET, shape, seed_x)
+    else:
+        x, par = _input(shape, seed_x, regime, grouped=True), _params(shape[0], shape[-1], seed_p, regime)
+    return ops.PendingBN(_dev(x, dev), par.to(dev), relu=relu)
+
+
+def _cond(regime):
+    return N.cond_on_load if regime == OFFSET else N.cond
 
 
 def _relu(t, on=True):
@@ -123,7 +149,7 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
 
     def run(dev, regime):
         from atvsnet_amd import ops
-        x = _input((G,) + sp + (cin,), 1, regime, grouped=True)
+        x = None if lazy else _input((G,) + sp + (cin,), 1, regime, grouped=True)
         w = _weights(ks + (cin, cout), 2)
         b = torch.randn(cout, generator=_gen(3)) * 0.1 * _SCALE[regime] if bias else None
         padding = 'SAME' if explicit_pad is None else 'VALID'
@@ -145,12 +171,11 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
             xin = _dev(x, dev)
             terms = [x]
         else:
-            pa = ops.PendingBN(_dev(x, dev), _params(G, cin, 4, regime).to(dev), relu=True)
+            pa = _pending((G,) + sp + (cin,), 1, 4, regime, dev, True)
             kw.update(in_params=pa.params, in_relu=True)
             xin, terms = pa.raw, [pa]
             if lazy == 'sum':
-                x1 = _input((G,) + sp + (cin,), 5, regime, grouped=True)
-                pb = ops.PendingBN(_dev(x1, dev), _params(G, cin, 6, regime).to(dev), relu=False)
+                pb = _pending((G,) + sp + (cin,), 5, 6, regime, dev, False)
                 kw.update(in_sum=(pb.raw, pb.params, False))
                 terms.append(pb)
         buf = None
@@ -165,10 +190,10 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
             s = xs[0] if len(xs) == 1 else xs[0] + xs[1]
             return _relu(T.conv(s, wt, stride, padding, dilation, bias=bt, explicit_pad=explicit_pad), relu)
         bb = b if b is not None else torch.zeros(cout)
-        cnd = _winograd_cond(x, w) + bb.double().abs() if winograd else N.cond(op, *terms, w, bb)
+        cnd = _winograd_cond(x, w) + bb.double().abs() if winograd else _cond(regime)(op, *terms, w, bb)
         return [Case(ys.cpu(), N.ref64(op, *terms, w, bb), cnd, N.floor_of(w, bar),
                      stats=(st, ys, cout), kept=(buf, 4, 4 + cout) if slice_out else None)]
-    return Row(name, family, split, bar, run, cfg or {})
+    return Row(name, family, split, bar, run, cfg or {}, bool(lazy))
 
 
 # ------------------------------------------------------------------------------------------------ the other entry points
@@ -202,11 +227,10 @@ def bottleneck_row(name, G, H, W, C):
     def run(dev, regime):
         from atvsnet_amd import ops
         assert ops.bottleneck_ok(C, 1, H, W)
-        x = _input((G, H, W, C), 21, regime, grouped=True)
-        par = _params(G, C, 22, regime)
+        pend = _pending((G, H, W, C), 21, 22, regime, dev, True)
+        x = pend.raw.cpu()
         ws = [_weights(s, 23 + i) for i, s in enumerate(((1, 1, C, C), (3, 3, C, C), (1, 1, C, C)))]
         bs = [torch.randn(C, generator=_gen(26 + i)) * 0.1 * _SCALE[regime] for i in range(3)]
-        pend = ops.PendingBN(_dev(x, dev), par.to(dev), relu=True)
         y, st = ops.bottleneck(pend.raw, pend.params, tuple((name, i) for i in range(3)), ws[0].numpy(), bs[0].to(dev),
                                ws[1].numpy(), bs[1].to(dev), ws[2].numpy(), bs[2].to(dev))
 
@@ -216,26 +240,38 @@ def bottleneck_row(name, G, H, W, C):
             return T.conv(r, w3, 1, 'SAME', bias=b3)
         a = (pend, ws[0], bs[0], ws[1], bs[1], ws[2], bs[2])
         want = N.ref64(branch, *a) + x.double()
-        return [Case(y.cpu(), want, N.cond(branch, *a), _residual_floor(want, *ws), stats=(st, y, C))]
-    return Row(name, 'bottleneck', 'btl', SPLIT, run, {})
+        return [Case(y.cpu(), want, _cond(regime)(branch, *a), _residual_floor(want, *ws), stats=(st, y, C))]
+    return Row(name, 'bottleneck', 'btl', SPLIT, run, {}, True)
 
 
-def siblings_row(name, G, D, H, W, cin, bar, cfg=None):
+def siblings_row(name, G, D, H, W, cin, bar, cfg=None, lazy=None):
+    """lazy='bn': the input is one pending batch norm + ReLU, normalised while it is staged (Cin % 16 == 0); lazy='sum': the sum
+    of two pending batch norms, formed while it is staged (Cin == 8, the U-Net's stack inputs)."""
     def run(dev, regime):
         from atvsnet_amd import ops
         assert ops.siblings_ok((D, H, W), cin, 8, 16)
-        x = _input((G, D, H, W, cin), 31, regime, grouped=True)
         w1, w2 = _weights((3, 3, 3, cin, 8), 32), _weights((3, 3, 3, cin, 16), 33)
         assert ops.pack_conv_xp((name, 'probe'), w1.numpy(), dev).kind == ('xb' if bar is SPLIT else 'xw')
-        (y, st), (y2, st2) = ops.conv_siblings(_dev(x, dev), (name, 1), w1.numpy(), (name, 2), w2.numpy(), groups=G)
+        if lazy is None:
+            x = _input((G, D, H, W, cin), 31, regime, grouped=True)
+            src, terms = _dev(x, dev), [x]
+        else:
+            terms = [_pending((G, D, H, W, cin), 31, 34, regime, dev, True)]
+            if lazy == 'sum':
+                terms.append(_pending((G, D, H, W, cin), 35, 36, regime, dev, False))
+            src = terms[0] if lazy == 'bn' else ops.PendingSum(terms)
+            assert ops.siblings_prologue_ok(src)
+        (y, st), (y2, st2) = ops.conv_siblings(src, (name, 1), w1.numpy(), (name, 2), w2.numpy(), groups=G)
+        assert all(t._final is None for t in terms if lazy), '%s: the lazy input was materialised' % name
         out = []
         for yy, s, w, stride, c in ((y, st, w1, 1, 8), (y2, st2, w2, 2, 16)):
-            def op(x, w, stride=stride):
-                return T.conv(x, w, stride, 'SAME')
-            cnd = _winograd_cond(x, w) if (stride == 1 and bar is FP32_MFMA) else N.cond(op, x, w)
-            out.append(Case(yy.cpu(), N.ref64(op, x, w), cnd, N.floor_of(w, bar), stats=(s, yy, c)))
+            def op(*a, stride=stride):
+                xs, w = a[:-1], a[-1]
+                return T.conv(xs[0] if len(xs) == 1 else xs[0] + xs[1], w, stride, 'SAME')
+            cnd = _winograd_cond(terms[0], w) if (stride == 1 and bar is FP32_MFMA) else _cond(regime)(op, *terms, w)
+            out.append(Case(yy.cpu(), N.ref64(op, *terms, w), cnd, N.floor_of(w, bar), stats=(s, yy, c)))
         return out
-    return Row(name, 'xp_siblings', 'xb' if bar is SPLIT else None, bar, run, cfg or {})
+    return Row(name, 'xp_siblings', 'xb' if bar is SPLIT else None, bar, run, cfg or {}, bool(lazy))
 
 
 def plane_row(name, G, D, H, W, cv, cc, bar):
@@ -295,7 +331,6 @@ def into_plane_row(name, G, D, H, W, cv, cc, pieces, plane=2):
 def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cfg=None):
     def run(dev, regime):
         from atvsnet_amd import ops
-        x = _input((G, D, H, W, cin), 51, regime, grouped=True)
         w = _weights((3, 3, 3, cout, cin), 52)
         lib = ops._lib.lib()
         if family == 'deconv_halves':
@@ -303,24 +338,24 @@ def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cf
         else:
             assert ops.deconv_up_ok(cin, cout) and bool(lib.atvs_deconv_up_b_supported(cin, cout))
         assert ops.split_on('upb') == (bar is SPLIT)
-        terms = [x]
-        src = _dev(x, dev)
         if summed:
-            a = ops.PendingBN(src, _params(G, cin, 53, regime).to(dev), relu=True)
-            x1 = _input((G, D, H, W, cin), 54, regime, grouped=True)
-            b = ops.PendingBN(_dev(x1, dev), _params(G, cin, 55, regime).to(dev), relu=False)
+            a = _pending((G, D, H, W, cin), 51, 53, regime, dev, True)
+            b = _pending((G, D, H, W, cin), 54, 55, regime, dev, False)
             src = ops.PendingSum([a, b])
             assert ops.deconv_sum_ok(src, cout, G)
             terms = [a, b]
+        else:
+            x = _input((G, D, H, W, cin), 51, regime, grouped=True)
+            terms, src = [x], _dev(x, dev)
         y, st = ops.conv3d_transpose_s2(src, name, w.numpy(), relu=True, want_stats=True, groups=G)
 
         def op(*a):
             xs, w = a[:-1], a[-1]
             s = xs[0] if len(xs) == 1 else xs[0] + xs[1]
             return _relu(T.conv3d_transpose_same(s, w))
-        return [Case(y.cpu(), N.ref64(op, *terms, w), N.cond(op, *terms, w), N.floor_of(w.permute(0, 1, 2, 4, 3), bar),
+        return [Case(y.cpu(), N.ref64(op, *terms, w), _cond(regime)(op, *terms, w), N.floor_of(w.permute(0, 1, 2, 4, 3), bar),
                      stats=(st, y, cout))]
-    return Row(name, family, split, bar, run, cfg or {})
+    return Row(name, family, split, bar, run, cfg or {}, summed)
 
 
 def aanet_row(name, nv, D, H, W):
@@ -375,24 +410,23 @@ def refine_stems_row(name, G, D, H, W):
 def head_row(name, G, D, H, W, summed=False):
     def run(dev, regime):
         from atvsnet_amd import ops
-        x = _input((G, D, H, W, 8), 91, regime, grouped=True)
         w = _weights((3, 3, 3, 8, 1), 92)
-        terms = [x]
-        src = _dev(x, dev)
         if summed:
-            a = ops.PendingBN(src, _params(G, 8, 93, regime).to(dev), relu=True)
-            x1 = _input((G, D, H, W, 8), 94, regime, grouped=True)
-            b = ops.PendingBN(_dev(x1, dev), _params(G, 8, 95, regime).to(dev), relu=True)
+            a = _pending((G, D, H, W, 8), 91, 93, regime, dev, True)
+            b = _pending((G, D, H, W, 8), 94, 95, regime, dev, True)
             src = ops.PendingSum([a, b])
             assert src.two_pending() is not None and ops.cfg.head_sum and ops.cfg.sum_on_load
             terms = [a, b]
+        else:
+            x = _input((G, D, H, W, 8), 91, regime, grouped=True)
+            terms, src = [x], _dev(x, dev)
         y = ops.conv3d_8to1(src, w.reshape(-1).to(dev), groups=G)
 
         def op(*a):
             xs, w = a[:-1], a[-1]
             return T.conv(xs[0] if len(xs) == 1 else xs[0] + xs[1], w, 1, 'SAME')
-        return [Case(y.cpu(), N.ref64(op, *terms, w), N.cond(op, *terms, w), N.floor_of(w, FP32_MFMA))]
-    return Row(name, '8to1', None, FP32_MFMA, run, {})
+        return [Case(y.cpu(), N.ref64(op, *terms, w), _cond(regime)(op, *terms, w), N.floor_of(w, FP32_MFMA))]
+    return Row(name, '8to1', None, FP32_MFMA, run, {}, summed)
 
 
 ROWS = [
@@ -420,6 +454,8 @@ ROWS = [
     conv_row('xb_cin24_G2_W24', 'xp', 'xb', SPLIT, 2, (2, 5, 24), 24, 8),
     conv_row('xb_cin8_D1', 'xp', 'xb', SPLIT, 1, (1, 4, 25), 8, 8),
     siblings_row('xb_siblings', 2, 3, 6, 24, 16, SPLIT),
+    siblings_row('xb_siblings_norm', 2, 3, 6, 24, 16, SPLIT, lazy='bn'),
+    siblings_row('xb_siblings_sum', 2, 3, 5, 25, 8, SPLIT, lazy='sum'),
     plane_row('xb_plane_bias', 2, 3, 5, 26, 8, 3, SPLIT),
     into_plane_row('xb_into_plane', 2, 3, 5, 26, 16, 3, False),
     into_plane_row('xb_into_plane_pieces', 2, 3, 5, 26, 16, 3, True),
@@ -466,14 +502,14 @@ def test_elementwise_against_float64(cuda, row):
     from atvsnet_amd import ops
     with ops.configure(clear_pack_cache=True, **row.cfg):
         ops.nonfinite_seen(cuda)                           # reset the sticky flag
-        for regime in REGIMES:
+        for regime in REGIMES + ((OFFSET,) if row.lazy else ()):
             N.poison_allocator(cuda)
             cases = row.run(cuda, regime)
             torch.cuda.synchronize()
             for i, c in enumerate(cases):
                 what = '%s[%s]#%d' % (row.name, regime, i)
-                r = N.assert_elementwise(c.got, c.want64, c.cond64, row.bar.rel * (N.NEAR_MAX if regime == 'near_max' else 1.0),
-                                         c.floor, what)
+                rel = row.bar.rel * (N.NEAR_MAX if regime == 'near_max' else 1.0) + (OFFSET_REL if regime == OFFSET else 0.0)
+                r = N.assert_elementwise(c.got, c.want64, c.cond64, rel, c.floor, what)
                 key = (row.family, 'split' if row.bar is SPLIT else 'fp32', regime)
                 _WORST[key] = max(_WORST.get(key, 0.0), r)
                 print('%-28s %-10s err/cond %.2e' % (row.name, regime, r))
@@ -494,5 +530,5 @@ def _report():
             continue
         print('\n%s: largest err/cond %.2e' % (cls, max(_WORST[k] for k in keys)))
         for fam in sorted({k[0] for k in keys}):
-            print('  %-16s ' % fam + ' '.join('%s %.1e' % (reg, _WORST[(fam, cls, reg)]) for reg in REGIMES
+            print('  %-16s ' % fam + ' '.join('%s %.1e' % (reg, _WORST[(fam, cls, reg)]) for reg in REGIMES + (OFFSET,)
                                               if (fam, cls, reg) in _WORST))

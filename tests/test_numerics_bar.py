@@ -159,3 +159,6 @@ def test_the_gpu_table_covers_every_split_family_and_the_fp32_forms():
     assert {r.name for r in S.ROWS if r.bar is N.FP32_MFMA and r.family in ('xp', 'xp_siblings')} <= \
         {r.name for r in S.ROWS if r.cfg.get('split16') is False}
     assert len({r.name for r in S.ROWS}) == len(S.ROWS)
+    # the rows whose input is formed on load, which run the offset regime too
+    assert {r.name for r in S.ROWS if r.lazy} == {'c16b_sum', 'c3b_norm', 's2b_norm', 'c2b_on_load', 'c1b_on_load', 'btl_G2',
+                                                  'upb_sum', '8to1_sum', 'xb_siblings_norm', 'xb_siblings_sum'}
