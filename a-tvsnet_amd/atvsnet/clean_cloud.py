@@ -2,13 +2,14 @@
 remove points with too few neighbours.
 
     python -m atvsnet_amd.atvsnet.clean_cloud --in final3d_model.ply --out clean.ply [--voxel V] [--sor K,RATIO [--sor_radius R]]
-           [--radius_filter R,N] [--report clean.json] [--gpu_id 0]
+           [--radius_filter R,N] [--keep_normals] [--report clean.json] [--gpu_id 0]
 
 The cloud depth_fusion writes has one point per consistent pixel of every reference camera (a surface patch appears once per
 camera that saw it) and the isolated floaters that pass the consistency vote.  The steps run in this order, each optional:
 
     voxel V                one point per occupied voxel of edge V, the mean of its points (ops.cloud_voxel_downsample); its colour
-                           is the colour of the voxel's lowest row; non-finite rows drop out
+                           is the colour of the voxel's lowest row (and with --keep_normals its normal that row's);
+                           non-finite rows drop out
     sor (k, ratio, radius) statistical outlier removal as PCL and Open3D define it: s[j] = the mean distance of row j to its k
                            nearest other rows (ops.cloud_knn with exclude_same_index, ops.cloud_knn_mean), mu and sigma = the mean
                            and sample standard deviation of the finite s (ops.cloud_sor_stats); row j stays when
@@ -68,9 +69,11 @@ def _check(voxel, sor, radius_filter):
     return voxel, sor, radius_filter
 
 
-def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=None):
+def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=None, normals=None):
     """points (n,3) float32, colors (n,3) uint8 or None: host arrays -> (points, colors, report): the rows that stay, in their
-    order, as host arrays (colors None when none were given), and what every step did.  voxel, sor=(k, ratio, radius),
+    order, as host arrays (colors None when none were given), and what every step did.  normals (n,3) float32 (a fused cloud's
+    nx ny nz): -> (points, colors, normals, report) instead; the normals follow their rows as the colours do (a voxel's normal is
+    its lowest row's, not an average; a filter keeps rows).  voxel, sor=(k, ratio, radius),
     radius_filter=(radius, min_neighbours): the module's steps, None = skipped; at least one is needed.
     report: {'n_in', 'n_out', 'steps': [{'step', its arguments, 'rows_in', 'rows_out'}, ...]}; the sor step also carries `count`,
     `mean`, `std` (ops.cloud_sor_stats) and `threshold` = mean + ratio * std."""
@@ -82,14 +85,19 @@ def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=
         colors = np.ascontiguousarray(np.asarray(colors, np.uint8).reshape(-1, 3))
         if len(colors) != len(pts):
             raise ValueError('colors: %d rows for %d points' % (len(colors), len(pts)))
+    if normals is not None:
+        normals = np.ascontiguousarray(np.asarray(normals, np.float32).reshape(-1, 3))
+        if len(normals) != len(pts):
+            raise ValueError('normals: %d rows for %d points' % (len(normals), len(pts)))
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     report = {'n_in': int(len(pts)), 'steps': []}
     with torch.cuda.device(dev):
         p = torch.from_numpy(pts).to(dev)
         c = None if colors is None else torch.from_numpy(colors).to(dev)
+        nrm = None if normals is None else torch.from_numpy(normals).to(dev)
 
         def keep_rows(mask):
-            return p[mask].contiguous(), (None if c is None else c[mask].contiguous())
+            return tuple(None if t is None else t[mask].contiguous() for t in (p, c, nrm))
 
         if voxel is not None:
             rows_in = int(p.shape[0])
@@ -97,6 +105,8 @@ def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=
             p = p.contiguous()
             if c is not None:
                 c = c[first.long()].contiguous()
+            if nrm is not None:
+                nrm = nrm[first.long()].contiguous()
             report['steps'].append({'step': 'voxel', 'voxel': voxel, 'rows_in': rows_in, 'rows_out': int(p.shape[0])})
         if sor is not None:
             k, ratio, radius = sor
@@ -105,19 +115,22 @@ def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=
             s = ops.cloud_knn_mean(d2)
             count, mean, std = ops.cloud_sor_stats(s)
             threshold = mean + ratio * std
-            p, c = keep_rows(s <= threshold)
+            p, c, nrm = keep_rows(s <= threshold)
             report['steps'].append({'step': 'sor', 'k': k, 'ratio': ratio, 'radius': radius, 'rows_in': rows_in,
                                     'rows_out': int(p.shape[0]), 'count': count, 'mean': mean, 'std': std, 'threshold': threshold})
         if radius_filter is not None:
             radius, least = radius_filter
             rows_in = int(p.shape[0])
             found = ops.cloud_radius_count(ops.cloud_grid(p, radius), p, exclude_same_index=True)
-            p, c = keep_rows(found >= least)
+            p, c, nrm = keep_rows(found >= least)
             report['steps'].append({'step': 'radius_filter', 'radius': radius, 'min_neighbours': least, 'rows_in': rows_in,
                                     'rows_out': int(p.shape[0])})
         out_p = p.cpu().numpy()
         out_c = None if c is None else c.cpu().numpy()
+        out_n = None if nrm is None else nrm.cpu().numpy()
     report['n_out'] = int(len(out_p))
+    if normals is not None:
+        return out_p, out_c, out_n, report
     return out_p, out_c, report
 
 
@@ -184,6 +197,9 @@ def make_parser():
     parser.add_argument('--in', dest='input', required=True, help='the cloud (a PLY as depth_fusion writes it)')
     parser.add_argument('--out', required=True, help='the cleaned cloud (PLY)')
     add_options(parser)
+    parser.add_argument('--keep_normals', action='store_true',
+                        help='the input carries normals (nx ny nz, as `depth_fusion --normals depth` writes them): write those of '
+                             'the rows that stay into the cleaned cloud (a voxel keeps the normal of its first row)')
     parser.add_argument('--report', default=None, metavar='FILE.json', help='write what every step did here (default: print it)')
     parser.add_argument('--gpu_id', type=int, default=0)
     return parser
@@ -195,12 +211,24 @@ def cli(argv=None):
     steps = options(parser, args)
     if not steps:
         parser.error('nothing to do: give at least one of --voxel, --sor, --radius_filter')
+    if args.keep_normals:
+        try:
+            with_normals = ply.has_normals(args.input)
+        except (OSError, ValueError) as e:
+            parser.error('--keep_normals: cannot read %s: %s' % (args.input, e))
+        if not with_normals:
+            parser.error('--keep_normals: %s carries no normals (nx ny nz); `depth_fusion --normals depth` writes them' % args.input)
     import torch
     torch.cuda.set_device(args.gpu_id)
-    points, colors = ply.read_ply(args.input)
-    points, colors, report = clean(points, colors, **steps)
+    normals = None
+    if args.keep_normals:
+        points, colors, normals = ply.read_ply_normals(args.input)
+        points, colors, normals, report = clean(points, colors, normals=normals, **steps)
+    else:
+        points, colors = ply.read_ply(args.input)
+        points, colors, report = clean(points, colors, **steps)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    ply.write_ply(args.out, points, colors)
+    ply.write_ply(args.out, points, colors, normals)
     if args.report:
         write_json(args.report, report)
     else:

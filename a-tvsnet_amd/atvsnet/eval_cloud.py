@@ -3,7 +3,7 @@ distance tolerances.
 
     python -m atvsnet_amd.atvsnet.eval_cloud --recon final3d_model.ply --gt scan1.ply [scan2.ply ...]
            [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--radius R] [--gt_transform T.txt] [--out cloud_eval.json] [--distances PREFIX]
-           [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v]] [--init_transform T.txt |
+           [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v] [--register_icp plane]] [--init_transform T.txt |
             --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
            [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
             [--vis_window 1] [--free_space_margin 0]]
@@ -30,7 +30,8 @@ exactly: per point the smallest float32 squared distance (dx*dx + dy*dy) + dz*dz
 A reconstruction in another frame than the ground truth's (a COLMAP model: rotation, translation and scale are free) scores 0 as
 it stands.  --register aligns it first (atvsnet/register_cloud.py: voxel down-sampling, trimmed point-to-point ICP in stages, on the
 device), starting from --init_transform (a 4x4 matrix applied to the RECONSTRUCTION) or --init_cameras (the similarity between
-the camera centres of two COLMAP models of the same images); --save_transform keeps the matrix found.  --voxel scores the
+the camera centres of two COLMAP models of the same images); --save_transform keeps the matrix found.  --register_icp plane
+registers by point-to-plane ICP over the normals the reconstruction's PLY carries (depth_fusion --normals depth).  --voxel scores the
 voxel-down-sampled clouds (both sides), so that point density does not weight the shares.  Without these options the result is
 what it was before they existed.
 """
@@ -45,6 +46,8 @@ import numpy as np
 from ..tools import ply
 
 DEFAULT_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)
+NO_NORMALS = ('%s carries no normals (nx ny nz): point-to-plane registration needs the reconstruction\'s own; fuse it with '
+              '`depth_fusion --normals depth`, or use --register_icp point')
 
 
 def _check_tolerances(tolerances, radius):
@@ -113,7 +116,8 @@ def _matrix(T, name):
 
 def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None,
              register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None,
-             scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0):
+             scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0,
+             register_icp='point', recon_normals=None):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
     distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
@@ -121,8 +125,9 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     The rest changes nothing when left at its default.  init_transform: a 4x4 matrix applied to `recon` (on the device,
     ops.cloud_transform).  register: align `recon` to `gt` by register_cloud.register before scoring, starting from
     init_transform; with_scale, register_distances (default 4x, 2x, 1x the largest tolerance), register_voxel are its arguments;
-    the result gains `registration` (its dict; `matrix` includes init_transform).  Without register, init_transform is recorded
-    as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
+    the result gains `registration` (its dict; `matrix` includes init_transform).  register_icp = 'plane' registers by
+    point-to-plane ICP over recon_normals (M,3), the reconstruction's own normals, one per row of `recon`.  Without register,
+    init_transform is recorded as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
     result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds.
 
     scans: the ground truth as a list of (n_i,3) arrays, one per laser scan, with scanner_origins (S,3), each scanner's position
@@ -137,6 +142,13 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     import torch
     from .. import ops
     tol, radius = _check_tolerances(tolerances, radius)
+    if register_icp not in ('point', 'plane'):
+        raise ValueError("register_icp must be 'point' or 'plane', got %r" % (register_icp,))
+    if register_icp == 'plane' and not register:
+        raise ValueError("register_icp='plane' needs register=True")
+    if (register_icp == 'plane') != (recon_normals is not None):
+        raise ValueError("register_icp='plane' and recon_normals go together: the reconstruction's normals, one per point")
+    plane = {'icp': 'plane', 'normals': recon_normals} if register_icp == 'plane' else {}
     origins = None
     if scans is not None:
         from . import eval_eth3d
@@ -178,7 +190,7 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
             from . import register_cloud
             dist = [4.0 * max(tol), 2.0 * max(tol), max(tol)] if register_distances is None else list(register_distances)
             extra['registration'] = register_cloud.register(r, g, init=init, with_scale=with_scale, distances=dist,
-                                                            voxel=register_voxel, device=dev)
+                                                            voxel=register_voxel, device=dev, **plane)
             r = ops.cloud_transform(r, extra['registration']['matrix'])
         elif init is not None:
             extra['init_transform'] = init.tolist()
@@ -220,12 +232,18 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
     file of 16 numbers, the 4x4 matrix row-major.  init_transform_path: the same for evaluate's init_transform; init_cameras:
     (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
     result's `registration` / top level gains `init_cameras`: matched images and their rms).  save_transform_path: the matrix that
-    was applied to the reconstruction is written there.  options: evaluate's other keyword arguments.
+    was applied to the reconstruction is written there.  options: evaluate's other keyword arguments; with register_icp='plane'
+    the reconstruction's normals are read from its PLY (tools/ply.read_ply_normals; a file without them raises).
 
     The ETH3D-style score (evaluate's `scans`): gt_mlp_path, a MeshLab project (eval_eth3d.read_mlp) that replaces gt_paths -- each
     scan is moved by gt_transform times its own matrix (float64, rounded once) and that product's translation is its scanner's
     origin -- or gt_paths with scanner_origins_path, a text file of one `x y z` per scan in the frame after gt_transform."""
-    recon = ply.read_ply_points(recon_path)
+    if options.get('register_icp') == 'plane':
+        if not ply.has_normals(recon_path):
+            raise ValueError(NO_NORMALS % recon_path)
+        recon, _, options['recon_normals'] = ply.read_ply_normals(recon_path)
+    else:
+        recon = ply.read_ply_points(recon_path)
     T = None
     if gt_transform_path is not None:
         T = np.loadtxt(gt_transform_path, dtype=np.float64)
@@ -281,7 +299,7 @@ def register_options(parser, args):
     contradictory ones are argument errors."""
     if args.init_transform and args.init_cameras:
         parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
-    for name in ('with_scale', 'register_distances', 'register_voxel'):
+    for name in ('with_scale', 'register_distances', 'register_voxel', 'register_icp'):
         if getattr(args, name) not in (None, False) and not args.register:
             parser.error('--%s needs --register' % name)
     if args.save_transform and not (args.register or args.init_transform or args.init_cameras):
@@ -303,6 +321,14 @@ def register_options(parser, args):
             if not args.register_voxel >= 0.0:
                 parser.error('--register_voxel must be >= 0')
             options['register_voxel'] = args.register_voxel
+        if args.register_icp == 'plane':
+            try:
+                with_normals = ply.has_normals(args.recon)
+            except (OSError, ValueError) as e:
+                parser.error('--register_icp plane: cannot read %s: %s' % (args.recon, e))
+            if not with_normals:
+                parser.error('--register_icp plane: ' + NO_NORMALS % args.recon)
+            options['register_icp'] = 'plane'
     if args.init_transform:
         options['init_transform_path'] = args.init_transform
     if args.init_cameras:
@@ -367,6 +393,9 @@ def make_parser():
                         help='--register: the stages\' search distances, decreasing (default: 4, 2, 1 x the largest tolerance)')
     parser.add_argument('--register_voxel', type=float, default=None, metavar='V',
                         help='--register: voxel edge of the down-sampling before the fit (default: half the last distance; 0: none)')
+    parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
+                        help='--register: point-to-point ICP (the default) or point-to-plane over the normals the reconstruction\'s '
+                             'PLY carries (nx ny nz, as `depth_fusion --normals depth` writes them): far fewer iterations')
     parser.add_argument('--init_transform', default=None, metavar='FILE',
                         help='text file with a 4x4 row-major matrix applied to the RECONSTRUCTION (the start of --register)')
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),

@@ -455,10 +455,11 @@ def _write_cloud(scene_fusion, folder):
     return n_points
 
 
-def _score_cloud(points, folder, device, gt_points, register_args, init_cameras):
-    """cloud_eval.json -> the score."""
+def _score_cloud(points, folder, device, gt_points, register_args, init_cameras, normals=None):
+    """cloud_eval.json -> the score.  normals: the fused points' own, for a point-to-plane registration."""
     t0 = time.time()
-    score = eval_cloud.evaluate(points, gt_points, device=device, **register_args)
+    plane = {'recon_normals': normals} if register_args.get('register_icp') == 'plane' else {}
+    score = eval_cloud.evaluate(points, gt_points, device=device, **dict(register_args, **plane))
     if init_cameras is not None:
         score['init_cameras'] = init_cameras
     eval_cloud.write_json(os.path.join(folder, 'cloud_eval.json'), score)
@@ -480,12 +481,17 @@ def _score_maps(scene_fusion, map_cams, score, folder, device, gt_points, score_
     TIMES['depth_eval'] = time.time() - t0
 
 
-def _clean_cloud(points, colors, score, folder, device, gt_points, clean):
-    """final3d_model_clean.ply and cloud_clean.json, with a score cloud_eval_clean.json -> the cleaned point count."""
+def _clean_cloud(points, colors, score, folder, device, gt_points, clean, normals=None):
+    """final3d_model_clean.ply and cloud_clean.json, with a score cloud_eval_clean.json -> the cleaned point count.  normals: the
+    fused points' own; those of the rows that stay are written into the cleaned PLY."""
     from ..tools.ply import write_ply
     t0 = time.time()
-    clean_points, clean_colors, clean_report = clean_cloud.clean(points, colors, device=device, **clean)
-    write_ply(os.path.join(folder, 'final3d_model_clean.ply'), clean_points, clean_colors)
+    clean_normals = None
+    if normals is None:
+        clean_points, clean_colors, clean_report = clean_cloud.clean(points, colors, device=device, **clean)
+    else:
+        clean_points, clean_colors, clean_normals, clean_report = clean_cloud.clean(points, colors, device=device, normals=normals, **clean)
+    write_ply(os.path.join(folder, 'final3d_model_clean.ply'), clean_points, clean_colors, clean_normals)
     clean_cloud.write_json(os.path.join(folder, 'cloud_clean.json'), clean_report)
     TIMES['cloud_clean'] = time.time() - t0
     if score is not None:
@@ -500,31 +506,44 @@ def _clean_cloud(points, colors, score, folder, device, gt_points, clean):
     return len(clean_points)
 
 
-def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register_args, init_cameras, score_maps, clean):
+def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register_args, init_cameras, score_maps, clean,
+               clean_keep_normals=False):
     """A fused scene's files, each group by its own step: the PLY, the cloud's score, the maps' score, the cleaned cloud."""
     n_points = _write_cloud(scene_fusion, folder)
-    points, colors, score = None, None, None
+    points, colors, score, normals = None, None, None, None
     if gt_points is not None or clean:
         points, colors = scene_fusion.run()
         points = points.copy()
         points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
+        if register_args.get('register_icp') == 'plane' or clean_keep_normals:
+            normals = scene_fusion.normals().copy()
+            normals[~np.isfinite(normals).all(axis=1)] = 0.0     # likewise
     if gt_points is not None:
-        score = _score_cloud(points, folder, device, gt_points, register_args, init_cameras)
+        score = _score_cloud(points, folder, device, gt_points, register_args, init_cameras, normals)
     if score_maps is not None:
         _score_maps(scene_fusion, map_cams, score, folder, device, gt_points, score_maps)
     if clean:
-        n_clean = _clean_cloud(points, colors, score, folder, device, gt_points, clean)
+        n_clean = _clean_cloud(points, colors, score, folder, device, gt_points, clean, normals if clean_keep_normals else None)
         print(Notify.INFO, '%s: %d points after cleaning' % (name, n_clean), Notify.ENDC)
     print(Notify.INFO, '%s: %d fused points' % (name, n_points), Notify.ENDC)
 
 
 def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True, gt_ply=None, register=None,
-                  clean=None, score_maps=None, fuse_normals=None):
+                  clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False):
     """What each of run_eval_pc's options needs -> every rule as (broken by these values, message).  The row of fuse_normals is
-    listed for a caller that gives fuse_normals: without it there is nothing the row could refuse."""
+    listed for a caller that gives fuse_normals: without it there is nothing the row could refuse.  The rows of a point-to-plane
+    registration and of clean_keep_normals likewise, at the end."""
     normals_row = [] if fuse_normals is None else [
         (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
                        '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
+    no_normals = not (fuse_normals or {}).get('normals') == 'depth'
+    plane_row = [] if not (register or {}).get('icp') == 'plane' else [
+        (no_normals, '--register_icp plane needs --fuse_normals depth (register icp=plane needs fuse_normals normals=depth): '
+                     'point-to-plane registration runs over the fused cloud\'s own normals')]
+    keep_row = [] if not clean_keep_normals else [
+        (not clean, '--clean_keep_normals needs --clean_voxel, --clean_sor or --clean_radius_filter (clean_keep_normals needs clean)'),
+        (no_normals, '--clean_keep_normals needs --fuse_normals depth (clean_keep_normals needs fuse_normals normals=depth): there are '
+                     'no normals to keep')]
     return normals_row + [
         (scene_cache and not use_graph, '--scene_cache replays captured graphs: it cannot be combined with --eager (use_graph=False)'),
         (not map_files and fuse is None, '--no_map_files needs --fuse (map_files=False needs fuse): the run would write nothing'),
@@ -532,7 +551,8 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (register is not None and not gt_ply, '--register needs --gt_ply (register needs gt_ply): there is nothing to align to'),
         (bool(clean) and fuse is None, '--clean_voxel, --clean_sor and --clean_radius_filter need --fuse (clean needs fuse): there is no '
                                        'point cloud to clean'),
-        (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')]
+        (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')
+    ] + plane_row + keep_row
 
 
 def _check_options(**options):
@@ -543,7 +563,7 @@ def _check_options(**options):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None, register=None, clean=None, score_maps=None, fuse_normals=None):
+                gt_ply=None, register=None, clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
@@ -558,6 +578,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     (eval_cloud.evaluate, default tolerances) into <savepath>/<scene>/cloud_eval.json -- what eval_cloud's CLI gives on that PLY.
     register (with gt_ply only): None, or dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned
     to the ground truth before it is scored (eval_cloud --register [--init_cameras]); cloud_eval.json carries `registration`.
+    With icp='plane' in the dict (fuse_normals normals='depth' only) the registration is point-to-plane over the normals the
+    fusion returns (eval_cloud --register_icp plane).
+    clean_keep_normals (with clean and fuse_normals normals='depth' only): final3d_model_clean.ply carries the normals of the rows
+    that stay (clean_cloud --keep_normals).
     clean (with fuse only): None, or dict(voxel=, sor=(k, ratio, radius), radius_filter=(radius, min_neighbours)), the arguments of
     clean_cloud.clean: each scene's fused points, as the PLY stores them, are cleaned into <savepath>/<scene>/
     final3d_model_clean.ply with the report in cloud_clean.json; with gt_ply the cleaned cloud is scored too, into
@@ -570,7 +594,7 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     second fit).  Every other output is what it is without it."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
-                   clean=clean, score_maps=score_maps, fuse_normals=fuse_normals)
+                   clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals)
     if fuse_normals is not None:
         depth_fusion.check_normal_options(**fuse_normals)
         fuse = dict(fuse, **fuse_normals)
@@ -580,6 +604,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         gt_points = np.concatenate([read_ply_points(p) for p in gt_ply], 0)
     if register is not None:
         register_args = dict(register=True, with_scale=bool(register.get('with_scale')))
+        if register.get('icp') == 'plane':
+            register_args['register_icp'] = 'plane'
         if register.get('init_cameras'):
             from . import register_cloud
             init, matched, rms = register_cloud.init_from_cameras(*register['init_cameras'])
@@ -602,7 +628,7 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
                 writer.close()
             if scene_fusion is not None:
                 _end_scene(image_info[2], scene_fusion, map_cams, savepath_current, device, gt_points, register_args, init_cameras,
-                           score_maps, clean)
+                           score_maps, clean, clean_keep_normals)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
         source.close()
@@ -625,7 +651,9 @@ def _run_options(flags):
         if opt('fuse') else None,
         fuse_normals=_normal_options(flags),
         map_files=not opt('no_map_files'), gt_ply=opt('gt_ply') or None, clean=opt('clean') or None,
-        register=dict(with_scale=opt('with_scale', False), init_cameras=opt('init_cameras') or None) if opt('register') else None,
+        register=dict(dict(icp='plane') if opt('register_icp') == 'plane' else {}, with_scale=opt('with_scale', False),
+                      init_cameras=opt('init_cameras') or None) if opt('register') else None,
+        clean_keep_normals=bool(opt('clean_keep_normals')),
         score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
                         occlusion_tol=opt('map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
                         pixel_centre=opt('map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE)) if opt('score_maps') else None)
@@ -692,6 +720,9 @@ def cli(argv=None):
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
                         help='--register: two COLMAP sparse model folders of the same images (the scene\'s own and one in the '
                              'ground truth\'s frame); their camera centres give the initial similarity')
+    parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
+                        help='--register: point-to-point ICP (the default) or point-to-plane over the fused cloud\'s normals '
+                             '(eval_cloud --register_icp); plane needs --fuse_normals depth')
     parser.add_argument('--score_maps', action='store_true',
                         help='--gt_ply: render the ground truth into the scene\'s cameras and score the depth maps that entered the '
                              'cloud against it (eval_depth: mae, rmse, ..., inlier ratios per map; a point splat, not ETH3D\'s '
@@ -703,10 +734,15 @@ def cli(argv=None):
     parser.add_argument('--map_pixel_centre', type=float, default=eval_depth.DEFAULT_PIXEL_CENTRE,
                         help='--score_maps: image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5 (the plane sweep\'s)')
     clean_cloud.add_options(parser, 'clean_')
+    parser.add_argument('--clean_keep_normals', action='store_true',
+                        help='--fuse_normals depth with a cleaning step: final3d_model_clean.ply carries the normals of the rows that '
+                             'stay (clean_cloud --keep_normals)')
     args = parser.parse_args(argv)
     # what only the command line can break; the rest is _option_rules
     if (args.with_scale or args.init_cameras) and not args.register:
         parser.error('--with_scale and --init_cameras need --register')
+    if args.register_icp is not None and not args.register:
+        parser.error('--register_icp needs --register')
     if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
                                 or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
         parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')

@@ -5,20 +5,24 @@ a laser scan in the scanner's.  Three steps bring one into the other, as the Tan
 
     init_from_cameras        a similarity from the camera centres of two COLMAP models of the same images, matched by image name
     ops.cloud_voxel_downsample   both clouds thinned to one point per voxel, so that point density does not steer the fit
-    register                 trimmed point-to-point ICP in stages of decreasing distance
+    register                 trimmed ICP in stages of decreasing distance: point-to-point, or point-to-plane over the normals
+                             a fused cloud carries (icp='plane')
 
 The search (ops.cloud_grid / cloud_nearest), the move (ops.cloud_transform), the reduction of the matched pairs to 18 sums
 (ops.cloud_pair_moments) and the down-sampling run on the device; per iteration only 19 words cross to the host, where the
-closed form of Umeyama / Horn turns them into a 4x4 matrix in float64 (similarity_from_moments).  This module imports without a
-GPU; only `register` needs one.  Point-to-plane ICP, normals and a global (feature-based) registration are not here: without
-cameras or an initial matrix the clouds must already be within the first stage's distance of each other.
+closed form of Umeyama / Horn turns them into a 4x4 matrix in float64 (similarity_from_moments).  Point-to-plane reduces the
+pairs to 37 sums instead (ops.cloud_plane_moments; 38 words cross), and a 6x6 or 7x7 solve turns them into an increment of the
+matrix (motion_from_plane_moments).  This module imports without a GPU; only `register` needs one.  Not here: normals of an
+arbitrary cloud (only a fused cloud's own are used), target-side normals, a symmetric objective, and a global (feature-based)
+registration: without cameras or an initial matrix the clouds must already be within the first stage's distance of each other.
 """
 import numpy as np
 
 from . import colmap
 
 DEFAULT_DISTANCES = (2.0, 1.0, 0.5)          # 4x, 2x, 1x eval_cloud's largest default tolerance: a default, not a measurement
-RANK_TOLERANCE = 1e-10                       # second / first singular value of the cross-covariance below this: collinear pairs
+RANK_TOLERANCE = 1e-10                       # second / first singular value of the cross-covariance below this: collinear pairs;
+                                             # smallest / largest eigenvalue of the point-to-plane system below this: free motion
 
 
 def similarity_from_moments(count, moments, pivot_src=None, pivot_dst=None, with_scale=False):
@@ -68,6 +72,54 @@ def similarity_from_points(P, Q, with_scale=False):
     m = np.concatenate([a.sum(0), b.sum(0), (a[:, :, None] * b[:, None, :]).sum(0).reshape(-1),
                         [(a * a).sum(), (b * b).sum(), ((Q - P) ** 2).sum()]])
     return similarity_from_moments(len(P), m, ps, pd, with_scale)
+
+
+def _exp_so3(w):
+    """Rodrigues' formula: the rotation Exp(w) of the rotation vector w (3,), orthonormal to rounding for every |w|."""
+    K = np.array([[0.0, -w[2], w[1]], [w[2], 0.0, -w[0]], [-w[1], w[0], 0.0]])
+    theta = float(np.sqrt(w @ w))
+    if theta < 1e-8:                                             # sin t / t and (1 - cos t) / t^2 to within 1e-17 of their limits
+        return np.eye(3) + K + 0.5 * (K @ K)
+    return np.eye(3) + (np.sin(theta) / theta) * K + ((1.0 - np.cos(theta)) / (theta * theta)) * (K @ K)
+
+
+def motion_from_plane_moments(count, moments, pivot=None, with_scale=False, extent=1.0):
+    """One Gauss-Newton step of point-to-plane ICP from the 37 sums of `count` pairs (ops.cloud_plane_moments' layout: sum J_a J_b
+    for a <= b row-major (28), sum J_a r (7), sum r^2, sum d2; J = [g x n' (3), n' (3), q . n']) -> the 4x4 float64 increment
+    D: the current matrix T becomes D T.  The normal equations (sum J J^T) x = -sum J r are solved for x = (omega, t) (6 unknowns)
+    or (omega, t, sigma) (7, with_scale), and D is the EXACT motion x -> pivot + (1 + sigma) Exp(omega) (x - pivot) + t (Rodrigues'
+    formula), so the rotation stays orthonormal however many increments are composed.  extent: a length of the scene (register
+    passes half the diagonal of the target's box); the rotational and scale columns are divided by it before the system is judged
+    and solved, so that rotations and translations share a unit.  ValueError for fewer pairs than unknowns, and when the system's
+    smallest eigenvalue is below RANK_TOLERANCE of its largest: the pairs do not constrain the motion."""
+    k = int(count)
+    m = np.asarray(moments, np.float64).reshape(-1)
+    if m.shape != (37,):
+        raise ValueError('moments: expected 37 sums, got %d' % m.size)
+    dim = 7 if with_scale else 6
+    if k < dim:
+        raise ValueError('%d pairs: a point-to-plane step with %d unknowns needs at least %d' % (k, dim, dim))
+    extent = float(extent)
+    if not (extent > 0.0 and np.isfinite(extent)):
+        raise ValueError('extent must be positive and finite, got %r' % (extent,))
+    p = np.zeros(3) if pivot is None else np.asarray(pivot, np.float64).reshape(3)
+    A = np.zeros((7, 7))
+    A[np.triu_indices(7)] = m[:28]
+    A = A + np.triu(A, 1).T
+    unit = np.array([extent] * 3 + [1.0] * 3 + [extent])[:dim]
+    A, b = A[:dim, :dim] / np.outer(unit, unit), m[28:28 + dim] / unit
+    eig = np.linalg.eigvalsh(A)
+    if not (eig[-1] > 0.0 and eig[0] > RANK_TOLERANCE * eig[-1]):
+        raise ValueError('the %d pairs do not constrain the motion (eigenvalues of the point-to-plane system %s): a single plane '
+                         "leaves sliding along it free; use icp='point'" % (k, eig.tolist()))
+    x = np.linalg.solve(A, -b) / unit
+    s = 1.0 + float(x[6]) if with_scale else 1.0
+    if not s > 0.0:
+        raise ValueError('the point-to-plane step asks for the scale factor %r: the pairs do not constrain the motion' % s)
+    D = np.eye(4)
+    D[:3, :3] = s * _exp_so3(x[:3])
+    D[:3, 3] = (p + x[3:6]) - D[:3, :3] @ p
+    return D
 
 
 def apply(T, points):
@@ -120,8 +172,9 @@ def corner_move(T0, T1, corners):
 
 
 def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES, voxel=None, max_iterations=50, min_move=None,
-             device=None):
-    """Trimmed point-to-point ICP of `recon` (M,3) onto `gt` (N,3) (host arrays or device tensors, float32) on the device.
+             device=None, icp='point', normals=None):
+    """Trimmed ICP of `recon` (M,3) onto `gt` (N,3) (host arrays or device tensors, float32) on the device: point-to-point
+    (icp='point', the default) or point-to-plane over the reconstruction's normals (icp='plane').
 
     init: 4x4 starting matrix (None: identity).  with_scale: fit a similarity instead of a rigid motion.  distances: one search
     radius per stage, decreasing.  voxel: both clouds are first reduced by ops.cloud_voxel_downsample with this edge (None: half
@@ -132,7 +185,14 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
     it) or after max_iterations.
     -> dict: matrix (4x4 nested lists: moves the RECONSTRUCTION into the ground truth's frame, `init` included), scale, init,
     with_scale, voxel, n_recon / n_gt (points the fit used), stages [{distance, iterations, pairs, rmse, converged}] (pairs and
-    rmse: of the last search, i.e. under the matrix the last fit started from).  A stage with fewer than 3 pairs raises."""
+    rmse: of the last search, i.e. under the matrix the last fit started from).  A stage with fewer than 3 pairs raises.
+
+    icp='plane' needs normals (M,3), one per row of `recon` in recon's frame (a fused cloud's nx ny nz); they follow their points
+    through the down-sampling (a voxel's normal is its first row's); the ground truth needs none.  Per iteration the moments are
+    ops.cloud_plane_moments of the ORIGINAL source under the current T about the centre of the target's box, and T becomes
+    motion_from_plane_moments(...) T in float64 on the host; stop rule, stages and messages are the same.  The dict then also
+    holds icp = 'plane' and, per stage, plane_rmse = sqrt(sum r^2 / pairs) beside rmse; with icp='point' the dict is what it was
+    (no icp key), so that what is written from it keeps its bytes."""
     import torch
     from .. import ops
     dist = [float(d) for d in distances]
@@ -145,6 +205,13 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
         raise ValueError('voxel must be >= 0, got %r' % voxel)
     if int(max_iterations) < 1:
         raise ValueError('max_iterations must be at least 1')
+    if icp not in ('point', 'plane'):
+        raise ValueError("icp must be 'point' or 'plane', got %r" % (icp,))
+    plane = icp == 'plane'
+    if plane and normals is None:
+        raise ValueError("icp='plane' needs the reconstruction's normals (normals=, one row per point)")
+    if not plane and normals is not None:
+        raise ValueError("normals are used by icp='plane' only")
     T0 = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
 
@@ -155,14 +222,21 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
 
     with torch.cuda.device(dev):
         src, dst = upload(recon), upload(gt)
+        nrm = upload(normals) if plane else None
+        if plane and nrm.shape != src.shape:
+            raise ValueError('normals: %d rows for %d points' % (nrm.shape[0], src.shape[0]))
         if voxel > 0.0:
-            src, dst = ops.cloud_voxel_downsample(src, voxel)[0], ops.cloud_voxel_downsample(dst, voxel)[0]
+            src, first = ops.cloud_voxel_downsample(src, voxel)
+            if plane:
+                nrm = nrm[first.long()].contiguous()
+            dst = ops.cloud_voxel_downsample(dst, voxel)[0]
         s_lo, s_hi = ops.cloud_bounds(src)
         d_lo, d_hi = ops.cloud_bounds(dst)
         if s_lo is None or d_lo is None:
             raise ValueError('register: a cloud has no finite point')
         corners = box_corners(s_lo, s_hi)
         pivot_src, pivot_dst = (s_lo + s_hi) / 2.0, (d_lo + d_hi) / 2.0
+        extent = max(float(np.sqrt(((d_hi - d_lo) ** 2).sum())) / 2.0, np.finfo(np.float64).tiny)
         moved = torch.empty_like(src)
         T, stages = T0.copy(), []
         for k, r in enumerate(dist):
@@ -172,18 +246,29 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
             for _ in range(int(max_iterations)):
                 ops.cloud_transform(src, T, out=moved)
                 d2, idx = ops.cloud_nearest(grid, moved)
-                count, mom = ops.cloud_pair_moments(src, dst, idx, d2, pivot_src=pivot_src, pivot_dst=pivot_dst)
+                if plane:
+                    count, mom = ops.cloud_plane_moments(src, nrm, T, dst, idx, d2, pivot=pivot_dst)
+                else:
+                    count, mom = ops.cloud_pair_moments(src, dst, idx, d2, pivot_src=pivot_src, pivot_dst=pivot_dst)
                 if count < 3:
                     raise ValueError('register: %d pairs within %g in stage %d%s' % (
                         count, r, k, ': the initial alignment is too far off for the first distance (give --init_cameras, '
                         '--init_transform or larger --register_distances)' if k == 0 and stage['iterations'] == 0 else ''))
-                T_new = similarity_from_moments(count, mom, pivot_src, pivot_dst, with_scale)
+                if plane:
+                    T_new = motion_from_plane_moments(count, mom, pivot_dst, with_scale, extent) @ T
+                else:
+                    T_new = similarity_from_moments(count, mom, pivot_src, pivot_dst, with_scale)
                 move = corner_move(T, T_new, corners)
                 T = T_new
-                stage.update(iterations=stage['iterations'] + 1, pairs=count, rmse=float(np.sqrt(mom[17] / count)))
+                stage.update(iterations=stage['iterations'] + 1, pairs=count, rmse=float(np.sqrt(mom[-1] / count)))
+                if plane:
+                    stage['plane_rmse'] = float(np.sqrt(mom[35] / count))
                 if move <= move_tol:
                     stage['converged'] = True
                     break
             stages.append(stage)
-    return {'matrix': T.tolist(), 'scale': float(np.cbrt(np.linalg.det(T[:3, :3]))), 'init': T0.tolist(), 'with_scale': bool(with_scale),
-            'voxel': voxel, 'n_recon': int(src.shape[0]), 'n_gt': int(dst.shape[0]), 'stages': stages}
+    result = {'matrix': T.tolist(), 'scale': float(np.cbrt(np.linalg.det(T[:3, :3]))), 'init': T0.tolist(), 'with_scale': bool(with_scale),
+              'voxel': voxel, 'n_recon': int(src.shape[0]), 'n_gt': int(dst.shape[0]), 'stages': stages}
+    if plane:
+        result['icp'] = 'plane'
+    return result

@@ -11,6 +11,7 @@
 // 2^24 x L, three beyond.  An accumulator therefore sees at most L serial additions and then at most
 // 8 + ceil(log2(rows)) + (passes - 1) tree levels that round, rows = ceil(m / (256 L)) -- no more than L + ceil(log2 m) in all for
 // every m <= 2^30 (m > 256 L (rows - 1) gives log2 m > 8 + log2 L + log2(rows - 1), and log2 L = 4 pays for the passes).
+// The point-to-plane moments (atvs_cloud_plane_moments) are the same sum with rows of 38 words.
 //
 // VOXEL DOWN-SAMPLING.  insert: every finite point finds its voxel's slot in an open-addressing table (capacity = the power of two
 // >= max(2 n, 1024); linear probing from a multiplicative hash of the packed cell; one 64-bit compare-and-swap per probe) and adds
@@ -81,6 +82,63 @@ __global__ __launch_bounds__(kThreads) void cloud_pair_moments_kernel(const floa
     v[15] = v[15] + ((a0 * a0 + a1 * a1) + a2 * a2);
     v[16] = v[16] + ((b0 * b0 + b1 * b1) + b2 * b2);
     v[17] = v[17] + (double)dd;
+  }, rows, sh);
+}
+
+// ---- point-to-plane moments ----------------------------------------------------------------------------------------------------
+// The sums of a Gauss-Newton step of point-to-plane ICP over the source's normals (include/atvsnet_hip.h states the definition and
+// derives the Jacobian; tests/cloud_plane_restated.py restates it).  The same row shape and tree as the pair moments, 37 sums wide.
+
+constexpr int kPlaneSums = 37;                         // 28 J_a J_b (a <= b) + 7 J_a r + r^2 + d2
+constexpr int kPlaneWords = kPlaneSums + 1;
+
+struct PlaneArgs {
+  double t[12];          // T, rows 0-2
+  double rot[9];         // the rotation of T
+  double trim2;
+  double pivot[3];
+};
+
+// where J_a J_b (a <= b) lies among the 28 sums, row-major over the upper triangle of the 7 x 7 matrix
+__host__ __device__ constexpr int plane_at(int a, int b) { return a * 7 - a * (a - 1) / 2 + (b - a); }
+
+__global__ __launch_bounds__(kThreads) void cloud_plane_moments_kernel(const float* __restrict__ src, const float* __restrict__ normals,
+                                                                       const float* __restrict__ dst, long n, const int* __restrict__ idx,
+                                                                       const float* __restrict__ d2, long m, PlaneArgs A,
+                                                                       unsigned long long* __restrict__ rows) {
+  __shared__ MomentShared<kPlaneSums> sh;
+  moment_row<kPlaneSums>(m, [&](long i, long long& cnt, double* v) {
+    const int j = idx[i];
+    const float dd = d2[i];
+    if (j < 0 || (long)j >= n || !((double)dd <= A.trim2)) return;
+    const float fx = normals[i * 3 + 0], fy = normals[i * 3 + 1], fz = normals[i * 3 + 2];
+    if (!finite3(fx, fy, fz)) return;
+    const double nx = (double)fx, ny = (double)fy, nz = (double)fz;
+    if (!((nx * nx + ny * ny) + nz * nz > 0.0)) return;                      // the zero normal agrees with nothing
+    const double x = (double)src[i * 3 + 0], y = (double)src[i * 3 + 1], z = (double)src[i * 3 + 2];
+    const double* T = A.t;
+    const double* R = A.rot;
+    const double q0 = (((T[0] * x + T[1] * y) + T[2] * z) + T[3]) - A.pivot[0];
+    const double q1 = (((T[4] * x + T[5] * y) + T[6] * z) + T[7]) - A.pivot[1];
+    const double q2 = (((T[8] * x + T[9] * y) + T[10] * z) + T[11]) - A.pivot[2];
+    const double g0 = (double)dst[(long)j * 3 + 0] - A.pivot[0], g1 = (double)dst[(long)j * 3 + 1] - A.pivot[1],
+                 g2 = (double)dst[(long)j * 3 + 2] - A.pivot[2];
+    const double n0 = (R[0] * nx + R[1] * ny) + R[2] * nz;
+    const double n1 = (R[3] * nx + R[4] * ny) + R[5] * nz;
+    const double n2 = (R[6] * nx + R[7] * ny) + R[8] * nz;
+    const double e0 = q0 - g0, e1 = q1 - g1, e2 = q2 - g2;
+    const double r = (e0 * n0 + e1 * n1) + e2 * n2;
+    const double J[7] = {g1 * n2 - g2 * n1, g2 * n0 - g0 * n2, g0 * n1 - g1 * n0, n0, n1, n2, (q0 * n0 + q1 * n1) + q2 * n2};
+    cnt += 1;
+#pragma unroll
+    for (int a = 0; a < 7; ++a) {
+#pragma unroll
+      for (int b = a; b < 7; ++b) v[plane_at(a, b)] = v[plane_at(a, b)] + J[a] * J[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 7; ++a) v[28 + a] = v[28 + a] + J[a] * r;
+    v[35] = v[35] + r * r;
+    v[36] = v[36] + (double)dd;
   }, rows, sh);
 }
 
@@ -370,6 +428,48 @@ extern "C" int atvs_cloud_pair_moments(const float* src, const float* dst, long 
                      moment_first(m, level, res));
   ATVS_LAUNCH_CHECK();
   return moment_fold<kWords - 1>(m, level, res, st);
+}
+
+extern "C" int atvs_cloud_plane_moments_scratch_size(long m, long* bytes) {
+  if (!bytes) return ATVS_ERR_NULL;
+  if (m < 0 || m > kMaxPoints) return ATVS_ERR_SHAPE;
+  *bytes = (long)moment_scratch_bytes<kPlaneSums>(m);
+  return ATVS_OK;
+}
+
+extern "C" int atvs_cloud_plane_moments(const float* src, const float* normals, const double* matrix12, const double* rot9, const float* dst,
+                                        long n, const int* idx, const float* d2, long m, double trim, const double* pivot, void* scratch,
+                                        long scratch_bytes, void* out, atvs_stream_t stream) {
+  const double big = 1.7976931348623157e308;
+  if (m < 0 || m > kMaxPoints || n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!out || !matrix12 || !rot9 || !pivot || (m > 0 && (!src || !normals || !idx || !d2 || !scratch)) || (m > 0 && n > 0 && !dst))
+    return ATVS_ERR_NULL;
+  if (!(trim >= 0.0)) return ATVS_ERR_ARG;                  // NaN or negative; +inf is allowed
+  PlaneArgs A;
+  A.trim2 = trim * trim;
+  for (int k = 0; k < 12; ++k) {
+    if (!(fabs(matrix12[k]) <= big)) return ATVS_ERR_ARG;
+    A.t[k] = matrix12[k];
+  }
+  for (int k = 0; k < 9; ++k) {
+    if (!(fabs(rot9[k]) <= big)) return ATVS_ERR_ARG;
+    A.rot[k] = rot9[k];
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (!(fabs(pivot[k]) <= big)) return ATVS_ERR_ARG;
+    A.pivot[k] = pivot[k];
+  }
+  long need = 0;
+  atvs_cloud_plane_moments_scratch_size(m, &need);
+  if (m > 0 && scratch_bytes < need) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  unsigned long long* res = static_cast<unsigned long long*>(out);
+  if (m == 0) return hipMemsetAsync(out, 0, kPlaneWords * 8, st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
+  unsigned long long* level = static_cast<unsigned long long*>(scratch);
+  hipLaunchKernelGGL(cloud_plane_moments_kernel, dim3((unsigned)moment_rows(m)), dim3(kThreads), 0, st, src, normals, dst, n, idx, d2, m, A,
+                     moment_first(m, level, res));
+  ATVS_LAUNCH_CHECK();
+  return moment_fold<kPlaneSums>(m, level, res, st);
 }
 
 extern "C" int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes) {

@@ -1,5 +1,5 @@
-// The fixed-shape sum of the point-cloud kernels (cloud_register.hip: the 18 pair moments; cloud_knn.hip: the two passes of the
-// outlier statistics).  A row is one int64 count and N doubles.  Term i belongs to workgroup i / (256 L), thread (i mod 256),
+// The fixed-shape sum of the point-cloud kernels (cloud_register.hip: the 18 pair moments and the 37 point-to-plane moments;
+// cloud_knn.hip: the two passes of the outlier statistics).  A row is one int64 count and N doubles.  Term i belongs to workgroup i / (256 L), thread (i mod 256),
 // L = ATVS_CLOUD_MOMENT_RUN: a thread adds its at most L terms i, i + 256, ... in that order into accumulators that start at +0,
 // the 64 lanes of a wavefront fold in six steps (lane j takes lane j + 32, then + 16, ... + 1), the four wavefronts as
 // (w0 + w1) + (w2 + w3): one row per workgroup.  Rows are folded 256 at a time by the same tree (rows beyond the end are +0) until

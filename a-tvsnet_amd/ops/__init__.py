@@ -42,7 +42,7 @@ from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, d
 from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range      # noqa: F401
 from .colmap import UNDISTORT_MAX_SIDE, UNDISTORT_MODELS, undistort_map, undistort_remap      # noqa: F401
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401
-from .cloud import cloud_bounds, cloud_pair_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
+from .cloud import cloud_bounds, cloud_pair_moments, cloud_plane_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
 from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401
 from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401

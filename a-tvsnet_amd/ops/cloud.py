@@ -3,8 +3,8 @@ within a radius for every query, and tolerance counts.  The definition the kerne
 evaluator built on them is atvsnet/eval_cloud.py.
 
 Registration (csrc/cloud_register.hip; atvsnet/register_cloud.py is built on it): cloud_transform moves a cloud through a matrix,
-cloud_pair_moments reduces matched pairs to the 18 sums of a closed-form similarity fit, cloud_voxel_downsample keeps one mean
-point per occupied voxel.
+cloud_pair_moments reduces matched pairs to the 18 sums of a closed-form similarity fit, cloud_plane_moments to the 37 sums of a
+point-to-plane step over the source's normals, cloud_voxel_downsample keeps one mean point per occupied voxel.
 
 Neighbourhoods (csrc/cloud_knn.hip; atvsnet/clean_cloud.py is built on it): cloud_knn finds the k nearest reference points within
 the grid's radius, cloud_radius_count counts the reference points inside it, cloud_knn_mean and cloud_sor_stats reduce the k-NN
@@ -189,6 +189,46 @@ def cloud_pair_moments(src, dst, idx, d2, trim=float('inf'), pivot_src=None, piv
     out = torch.empty(19, dtype=torch.int64, device=src.device)
     scratch = torch.empty(_size('atvs_cloud_pair_moments_scratch_size', m), dtype=torch.uint8, device=src.device)
     _call('atvs_cloud_pair_moments', _p(src), _p(dst), n, _p(idx), _p(d2), m, trim, ps, pd,
+          _p(scratch), scratch.numel(), _p(out), _stream())
+    words = out.cpu().numpy()
+    return int(words[0]), words[1:].view(np.float64).copy()
+
+
+def cloud_plane_moments(src, normals, T, dst, idx, d2, trim=float('inf'), pivot=None):
+    """The sums of one Gauss-Newton step of point-to-plane ICP over the source's normals (atvs_cloud_plane_moments; the header
+    states every term).  src (m,3) float32: the ORIGINAL source; normals (m,3) float32: its normals in its own frame; T: the
+    current 4x4 (or 3x4) similarity as host numbers; dst (n,3) float32, idx (m,) int32, d2 (m,) float32: the searched cloud and
+    what cloud_nearest returned for cloud_transform(src, T); pivot: 3 host numbers in dst's frame (default 0).  A pair takes part
+    under cloud_pair_moments' rule when its normal is finite and not zero.  The rotation the normals turn by is T's 3x3 block
+    divided by the cube root of its determinant.  -> (count, moments): a Python int and a HOST numpy float64 (37,): sum J_a J_b
+    for a <= b (28, row-major), sum J_a r (7), sum r^2, sum double(d2), with J = [g x n' (3), n' (3), q . n'].  The 38 words are
+    what crosses to the host (one synchronising copy of 304 bytes); the same input gives the same words bit for bit."""
+    trim = float(trim)
+    if not trim >= 0.0:
+        raise ValueError('trim must be >= 0 (inf allowed), got %r' % (trim,))
+    p = _vec3(pivot, 'pivot')
+    M = np.asarray(T, np.float64)
+    if M.shape not in ((4, 4), (3, 4)) or not np.isfinite(M).all():
+        raise ValueError('T: expected a finite 4x4 (or 3x4) matrix, got %r' % (T,))
+    det = float(np.linalg.det(M[:3, :3]))
+    if not det > 0.0:
+        raise ValueError('T: the 3x3 block must have a positive determinant (a similarity), got %r' % det)
+    _cloud_arg(src, 'src', torch.float32, (3,))
+    _cloud_arg(normals, 'normals', torch.float32, (3,))
+    _cloud_arg(dst, 'dst', torch.float32, (3,))
+    _cloud_arg(idx, 'idx', torch.int32, ())
+    _cloud_arg(d2, 'd2', torch.float32, ())
+    m, n = int(src.shape[0]), int(dst.shape[0])
+    if int(normals.shape[0]) != m or int(idx.shape[0]) != m or int(d2.shape[0]) != m:
+        raise ValueError('normals %s, idx %s and d2 %s must have one entry per row of src %s' % (
+            tuple(normals.shape), tuple(idx.shape), tuple(d2.shape), tuple(src.shape)))
+    for t, name in ((normals, 'normals'), (dst, 'dst'), (idx, 'idx'), (d2, 'd2')):
+        _same_device(t, name, src, 'src')
+    m12 = (ctypes.c_double * 12)(*M[:3].reshape(-1).tolist())
+    rot = (ctypes.c_double * 9)(*(M[:3, :3] / np.cbrt(det)).reshape(-1).tolist())
+    out = torch.empty(38, dtype=torch.int64, device=src.device)
+    scratch = torch.empty(_size('atvs_cloud_plane_moments_scratch_size', m), dtype=torch.uint8, device=src.device)
+    _call('atvs_cloud_plane_moments', _p(src), _p(normals), m12, rot, _p(dst), n, _p(idx), _p(d2), m, trim, p,
           _p(scratch), scratch.numel(), _p(out), _stream())
     words = out.cpu().numpy()
     return int(words[0]), words[1:].view(np.float64).copy()

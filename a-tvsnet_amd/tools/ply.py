@@ -35,22 +35,33 @@ def write_ply(path, points, colors, normals=None):
         v.tofile(f)
 
 
+def _header(f, path):
+    """The header of an open file -> (vertex count or None, the property names in order); the file is left at the body."""
+    n, names = None, []
+    while True:
+        raw = f.readline()
+        if not raw:
+            raise ValueError('%s: the header has no end_header' % path)
+        line = raw.decode('ascii').strip()
+        if line.startswith('element vertex'):
+            n = int(line.split()[-1])
+        if line.startswith('property'):
+            names.append(line.split()[-1])
+        if line == 'end_header':
+            return n, names
+
+
+def has_normals(path):
+    """Whether read_ply_normals would return normals for this file: its header alone is read."""
+    with open(path, 'rb') as f:
+        return tuple(_header(f, path)[1]) == _VERTEX_N.names
+
+
 def read_ply_normals(path):
     """-> (points (M,3) float32, colors (M,3) uint8, normals (M,3) float32 or None) of a file written by write_ply / the reference,
     by the vertex properties its header lists: with or without nx, ny, nz."""
     with open(path, 'rb') as f:
-        n, names = None, []
-        while True:
-            raw = f.readline()
-            if not raw:
-                raise ValueError('%s: the header has no end_header' % path)
-            line = raw.decode('ascii').strip()
-            if line.startswith('element vertex'):
-                n = int(line.split()[-1])
-            if line.startswith('property'):
-                names.append(line.split()[-1])
-            if line == 'end_header':
-                break
+        n, names = _header(f, path)
         layout = {_VERTEX.names: _VERTEX, _VERTEX_N.names: _VERTEX_N}.get(tuple(names))
         if layout is None or n is None:
             raise ValueError('%s: not a vertex layout write_ply writes: %s' % (path, ' '.join(names)))

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 54
+#define ATVS_ABI_VERSION 55
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -825,7 +825,8 @@ int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, 
 
 /* Point-cloud registration (ops/cloud.py, atvsnet/register_cloud.py, csrc/cloud_register.hip).  Pointers are device pointers unless
  * named host.  Integer atomics only: every output is a function of the inputs alone, bit for bit on every run.  No host
- * synchronisation; scratch is the caller's.  tests/cloud_register_restated.py restates the three definitions.
+ * synchronisation; scratch is the caller's.  tests/cloud_register_restated.py restates the first three definitions,
+ * tests/cloud_plane_restated.py the plane moments.
  *
  * atvs_cloud_transform: out (n,3) float32 = points (n,3) through matrix12 (HOST, 12 doubles: rows 0-2 of a 4x4 matrix, row-major;
  * copied into the launch).  Per point and output coordinate k, in double: ((T[k][0] x + T[k][1] y) + T[k][2] z) + T[k][3], every
@@ -842,6 +843,31 @@ int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, 
  * (csrc/cloud_register.hip): an accumulator sees at most L = ATVS_CLOUD_MOMENT_RUN serial additions, then per-workgroup partial
  * rows are folded by fixed trees in index order, at most L + ceil(log2 m) rounding additions deep in all.  m = 0: 19 zero words.
  * scratch: atvs_cloud_pair_moments_scratch_size(m) bytes.  trim negative or NaN, a non-finite pivot: ATVS_ERR_ARG.
+ *
+ * atvs_cloud_plane_moments: the sums of one Gauss-Newton step of point-to-plane ICP over the SOURCE's normals.  src (m,3) float32 =
+ * the original, unmoved source; normals (m,3) float32 = its normals in its own frame; matrix12 (HOST, 12 doubles) = the current T
+ * as atvs_cloud_transform takes it; rot9 (HOST, 9 doubles, row-major) = the pure rotation of T (the caller divides a scale out);
+ * dst (n,3), idx (m), d2 (m) = the searched cloud and what atvs_cloud_nearest returned for atvs_cloud_transform(src, T); pivot
+ * (HOST, 3 finite doubles) in dst's frame.  Pair i takes part under atvs_cloud_pair_moments' rule (0 <= idx[i] < n, (double)d2[i]
+ * <= trim * trim, a NaN d2 takes no part) when in addition its three normal components are finite and (nx nx + ny ny) + nz nz > 0
+ * in double (a zero normal agrees with nothing).  Per pair, in double, every operation rounded on its own:
+ *   q_k  = (((T[k][0] x + T[k][1] y) + T[k][2] z) + T[k][3]) - pivot_k      (atvs_cloud_transform's order, NOT rounded to float32)
+ *   g_k  = (double)dst[idx[i]]_k - pivot_k
+ *   n'_k = (rot[k][0] nx + rot[k][1] ny) + rot[k][2] nz                       (not renormalised: a pair weighs by |n|^2)
+ *   r    = ((q_0 - g_0) n'_0 + (q_1 - g_1) n'_1) + (q_2 - g_2) n'_2
+ *   J    = [ g_1 n'_2 - g_2 n'_1,  g_2 n'_0 - g_0 n'_2,  g_0 n'_1 - g_1 n'_0,  n'_0,  n'_1,  n'_2,  (q_0 n'_0 + q_1 n'_1) + q_2 n'_2 ]
+ * J is the gradient of r under a small motion about the pivot, x -> pivot + (1 + sigma) Exp(omega) (x - pivot) + t, applied to the
+ * moved source AND to its normals (n' -> Exp(omega) n'), in the unknowns (omega, t, sigma).  To first order, with Exp(omega) v =
+ * v + omega x v:  r' = (q + omega x q + sigma q + t - g) . (n' + omega x n')
+ *                    = r + omega . (q x n') + omega . (n' x (q - g)) + t . n' + sigma q . n'
+ *                    = r + omega . (g x n') + t . n' + sigma q . n'
+ * (the q x n' of the moving point cancels against the turning normal: what is left is the TARGET's lever arm g x n').  `out`
+ * receives 38 8-byte words: [0] the pair count (int64), then 37 doubles: [1..28] sum J_a J_b for a <= b, row-major over the upper
+ * triangle ([1 + 7 a - a (a - 1) / 2 + (b - a)]), [29..35] sum J_a r, [36] sum r r, [37] sum (double)d2.  The normal equations of
+ * the step are (sum J J^T) (omega, t, sigma) = -sum J r; a rigid step takes their first six rows and columns.  The reduction is
+ * atvs_cloud_pair_moments' (no atomics; at most L + ceil(log2 m) rounding additions deep; the same input gives the same 38 words
+ * bit for bit).  m = 0: 38 zero words.  scratch: atvs_cloud_plane_moments_scratch_size(m) bytes.  trim negative or NaN, a
+ * non-finite pivot, matrix12 or rot9 entry: ATVS_ERR_ARG.
  *
  * atvs_cloud_voxel_downsample: one output point per occupied cubic voxel of edge `voxel` (double > 0): the mean of the voxel's
  * finite points; non-finite points are dropped.  origin: HOST, 3 finite doubles.  Per axis, in double: g = ((double)x - origin) /
@@ -860,6 +886,10 @@ int atvs_cloud_pair_moments_scratch_size(long m, long* bytes);
 int atvs_cloud_pair_moments(const float* src, const float* dst, long n, const int* idx, const float* d2, long m, double trim,
                             const double* pivot_src, const double* pivot_dst, void* scratch, long scratch_bytes, void* out,
                             atvs_stream_t stream);
+int atvs_cloud_plane_moments_scratch_size(long m, long* bytes);
+int atvs_cloud_plane_moments(const float* src, const float* normals, const double* matrix12, const double* rot9, const float* dst,
+                             long n, const int* idx, const float* d2, long m, double trim, const double* pivot, void* scratch,
+                             long scratch_bytes, void* out, atvs_stream_t stream);
 int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes);
 int atvs_cloud_voxel_downsample(const float* points, long n, double voxel, const double* origin, void* scratch, long scratch_bytes,
                                 float* out_points, long long* out_count, int* out_first, atvs_stream_t stream);
