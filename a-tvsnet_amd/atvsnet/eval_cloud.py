@@ -3,8 +3,9 @@ distance tolerances.
 
     python -m atvsnet_amd.atvsnet.eval_cloud --recon final3d_model.ply --gt scan1.ply [scan2.ply ...]
            [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--radius R] [--gt_transform T.txt] [--out cloud_eval.json] [--distances PREFIX]
-           [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v] [--register_icp plane]] [--init_transform T.txt |
-            --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
+           [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v]
+            [--register_icp plane [--register_normals target [--register_normal_k K] [--register_normal_radius R]]]]
+           [--init_transform T.txt | --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
            [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
             [--vis_window 1] [--free_space_margin 0]]
 
@@ -31,7 +32,8 @@ A reconstruction in another frame than the ground truth's (a COLMAP model: rotat
 it stands.  --register aligns it first (atvsnet/register_cloud.py: voxel down-sampling, trimmed point-to-point ICP in stages, on the
 device), starting from --init_transform (a 4x4 matrix applied to the RECONSTRUCTION) or --init_cameras (the similarity between
 the camera centres of two COLMAP models of the same images); --save_transform keeps the matrix found.  --register_icp plane
-registers by point-to-plane ICP over the normals the reconstruction's PLY carries (depth_fusion --normals depth).  --voxel scores the
+registers by point-to-plane ICP over the normals the reconstruction's PLY carries (depth_fusion --normals depth), or, with
+--register_normals target, over the ground truth's, estimated on the GPU (the reconstruction then needs none).  --voxel scores the
 voxel-down-sampled clouds (both sides), so that point density does not weight the shares.  Without these options the result is
 what it was before they existed.
 """
@@ -47,7 +49,8 @@ from ..tools import ply
 
 DEFAULT_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)
 NO_NORMALS = ('%s carries no normals (nx ny nz): point-to-plane registration needs the reconstruction\'s own; fuse it with '
-              '`depth_fusion --normals depth`, or use --register_icp point')
+              '`depth_fusion --normals depth`, or use --register_icp point, or --register_normals target (the planes of the ground '
+              'truth, whose normals are estimated on the GPU)')
 
 
 def _check_tolerances(tolerances, radius):
@@ -117,7 +120,8 @@ def _matrix(T, name):
 def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None,
              register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None,
              scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0,
-             register_icp='point', recon_normals=None):
+             register_icp='point', recon_normals=None, register_normals='source', register_normal_k=None,
+             register_normal_radius=None):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
     distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
@@ -126,7 +130,10 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     ops.cloud_transform).  register: align `recon` to `gt` by register_cloud.register before scoring, starting from
     init_transform; with_scale, register_distances (default 4x, 2x, 1x the largest tolerance), register_voxel are its arguments;
     the result gains `registration` (its dict; `matrix` includes init_transform).  register_icp = 'plane' registers by
-    point-to-plane ICP over recon_normals (M,3), the reconstruction's own normals, one per row of `recon`.  Without register,
+    point-to-plane ICP over recon_normals (M,3), the reconstruction's own normals, one per row of `recon`; with
+    register_normals = 'target' over the ground truth's instead, estimated on the device from register_normal_k neighbours
+    within register_normal_radius (register_cloud.register's normal_side, normal_k, normal_radius and their defaults), and
+    recon_normals is not used.  Without register,
     init_transform is recorded as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
     result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds.
 
@@ -146,9 +153,24 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
         raise ValueError("register_icp must be 'point' or 'plane', got %r" % (register_icp,))
     if register_icp == 'plane' and not register:
         raise ValueError("register_icp='plane' needs register=True")
-    if (register_icp == 'plane') != (recon_normals is not None):
+    if register_normals not in ('source', 'target'):
+        raise ValueError("register_normals must be 'source' or 'target', got %r" % (register_normals,))
+    target = register_normals == 'target'
+    if target and register_icp != 'plane':
+        raise ValueError("register_normals='target' needs register_icp='plane'")
+    if not target and (register_normal_k is not None or register_normal_radius is not None):
+        raise ValueError("register_normal_k and register_normal_radius need register_normals='target'")
+    if target and recon_normals is not None:
+        raise ValueError("register_normals='target' runs over the ground truth's normals: recon_normals is not used")
+    if (register_icp == 'plane' and not target) != (recon_normals is not None):
         raise ValueError("register_icp='plane' and recon_normals go together: the reconstruction's normals, one per point")
     plane = {'icp': 'plane', 'normals': recon_normals} if register_icp == 'plane' else {}
+    if target:
+        plane = {'icp': 'plane', 'normal_side': 'target'}
+        if register_normal_k is not None:
+            plane['normal_k'] = register_normal_k
+        if register_normal_radius is not None:
+            plane['normal_radius'] = register_normal_radius
     origins = None
     if scans is not None:
         from . import eval_eth3d
@@ -233,12 +255,13 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
     (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
     result's `registration` / top level gains `init_cameras`: matched images and their rms).  save_transform_path: the matrix that
     was applied to the reconstruction is written there.  options: evaluate's other keyword arguments; with register_icp='plane'
-    the reconstruction's normals are read from its PLY (tools/ply.read_ply_normals; a file without them raises).
+    the reconstruction's normals are read from its PLY (tools/ply.read_ply_normals; a file without them raises), unless
+    register_normals='target': then the plain reader is used and no normals are needed.
 
     The ETH3D-style score (evaluate's `scans`): gt_mlp_path, a MeshLab project (eval_eth3d.read_mlp) that replaces gt_paths -- each
     scan is moved by gt_transform times its own matrix (float64, rounded once) and that product's translation is its scanner's
     origin -- or gt_paths with scanner_origins_path, a text file of one `x y z` per scan in the frame after gt_transform."""
-    if options.get('register_icp') == 'plane':
+    if options.get('register_icp') == 'plane' and options.get('register_normals', 'source') != 'target':
         if not ply.has_normals(recon_path):
             raise ValueError(NO_NORMALS % recon_path)
         recon, _, options['recon_normals'] = ply.read_ply_normals(recon_path)
@@ -299,13 +322,23 @@ def register_options(parser, args):
     contradictory ones are argument errors."""
     if args.init_transform and args.init_cameras:
         parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
-    for name in ('with_scale', 'register_distances', 'register_voxel', 'register_icp'):
+    for name in ('with_scale', 'register_distances', 'register_voxel', 'register_icp', 'register_normals', 'register_normal_k',
+                 'register_normal_radius'):
         if getattr(args, name) not in (None, False) and not args.register:
             parser.error('--%s needs --register' % name)
     if args.save_transform and not (args.register or args.init_transform or args.init_cameras):
         parser.error('--save_transform needs --register, --init_transform or --init_cameras: no matrix is applied otherwise')
     if args.voxel is not None and not args.voxel > 0.0:
         parser.error('--voxel must be positive')
+    target = args.register_normals == 'target'
+    if target and args.register_icp != 'plane':
+        parser.error('--register_normals target needs --register_icp plane')
+    if not target and (args.register_normal_k is not None or args.register_normal_radius is not None):
+        parser.error('--register_normal_k and --register_normal_radius need --register_normals target')
+    if args.register_normal_k is not None and not 2 <= args.register_normal_k <= 32:
+        parser.error('--register_normal_k must be in 2..32')
+    if args.register_normal_radius is not None and not (args.register_normal_radius > 0.0 and np.isfinite(args.register_normal_radius)):
+        parser.error('--register_normal_radius must be positive and finite')
     options = {}
     if args.register:
         options.update(register=True, with_scale=bool(args.with_scale))
@@ -321,7 +354,13 @@ def register_options(parser, args):
             if not args.register_voxel >= 0.0:
                 parser.error('--register_voxel must be >= 0')
             options['register_voxel'] = args.register_voxel
-        if args.register_icp == 'plane':
+        if target:
+            options.update(register_icp='plane', register_normals='target')
+            if args.register_normal_k is not None:
+                options['register_normal_k'] = args.register_normal_k
+            if args.register_normal_radius is not None:
+                options['register_normal_radius'] = args.register_normal_radius
+        elif args.register_icp == 'plane':
             try:
                 with_normals = ply.has_normals(args.recon)
             except (OSError, ValueError) as e:
@@ -396,6 +435,14 @@ def make_parser():
     parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
                         help='--register: point-to-point ICP (the default) or point-to-plane over the normals the reconstruction\'s '
                              'PLY carries (nx ny nz, as `depth_fusion --normals depth` writes them): far fewer iterations')
+    parser.add_argument('--register_normals', default=None, choices=('source', 'target'),
+                        help='--register_icp plane: whose planes -- source (the default: the normals in the reconstruction\'s PLY) or '
+                             'target (the ground truth\'s, estimated on the GPU: the reconstruction needs none)')
+    parser.add_argument('--register_normal_k', type=int, default=None, metavar='K',
+                        help='--register_normals target: neighbours per estimated normal, 2..32 (default 16; a default, not a measurement)')
+    parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
+                        help='--register_normals target: their search radius (default: 4 edges of the registration\'s voxel, or twice '
+                             'the last distance without one; a default, not a measurement)')
     parser.add_argument('--init_transform', default=None, metavar='FILE',
                         help='text file with a 4x4 row-major matrix applied to the RECONSTRUCTION (the start of --register)')
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),

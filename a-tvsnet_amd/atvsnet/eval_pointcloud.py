@@ -455,10 +455,15 @@ def _write_cloud(scene_fusion, folder):
     return n_points
 
 
+def _source_planes(register_args):
+    """Whether the registration runs over the fused cloud's own normals (point-to-plane, not over the ground truth's)."""
+    return register_args.get('register_icp') == 'plane' and register_args.get('register_normals') != 'target'
+
+
 def _score_cloud(points, folder, device, gt_points, register_args, init_cameras, normals=None):
     """cloud_eval.json -> the score.  normals: the fused points' own, for a point-to-plane registration."""
     t0 = time.time()
-    plane = {'recon_normals': normals} if register_args.get('register_icp') == 'plane' else {}
+    plane = {'recon_normals': normals} if _source_planes(register_args) else {}
     score = eval_cloud.evaluate(points, gt_points, device=device, **dict(register_args, **plane))
     if init_cameras is not None:
         score['init_cameras'] = init_cameras
@@ -515,7 +520,7 @@ def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register
         points, colors = scene_fusion.run()
         points = points.copy()
         points[~np.isfinite(points).all(axis=1)] = 0.0          # as tools/ply.write_ply stores them
-        if register_args.get('register_icp') == 'plane' or clean_keep_normals:
+        if _source_planes(register_args) or clean_keep_normals:
             normals = scene_fusion.normals().copy()
             normals[~np.isfinite(normals).all(axis=1)] = 0.0     # likewise
     if gt_points is not None:
@@ -537,9 +542,17 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
                        '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
     no_normals = not (fuse_normals or {}).get('normals') == 'depth'
-    plane_row = [] if not (register or {}).get('icp') == 'plane' else [
+    target = (register or {}).get('normal_side') == 'target'
+    plane_row = [] if not (register or {}).get('icp') == 'plane' or target else [
         (no_normals, '--register_icp plane needs --fuse_normals depth (register icp=plane needs fuse_normals normals=depth): '
-                     'point-to-plane registration runs over the fused cloud\'s own normals')]
+                     'point-to-plane registration runs over the fused cloud\'s own normals; or give --register_normals target '
+                     '(register normal_side=target): the ground truth\'s planes, its normals estimated on the GPU')]
+    target_row = [] if not any(k in (register or {}) for k in ('normal_side', 'normal_k', 'normal_radius')) else [
+        (target and not register.get('icp') == 'plane', '--register_normals target needs --register_icp plane (register '
+                                                        'normal_side=target needs icp=plane)'),
+        (not target and ('normal_k' in register or 'normal_radius' in register),
+         '--register_normal_k and --register_normal_radius need --register_normals target (normal_k and normal_radius need '
+         'normal_side=target)')]
     keep_row = [] if not clean_keep_normals else [
         (not clean, '--clean_keep_normals needs --clean_voxel, --clean_sor or --clean_radius_filter (clean_keep_normals needs clean)'),
         (no_normals, '--clean_keep_normals needs --fuse_normals depth (clean_keep_normals needs fuse_normals normals=depth): there are '
@@ -552,7 +565,7 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (bool(clean) and fuse is None, '--clean_voxel, --clean_sor and --clean_radius_filter need --fuse (clean needs fuse): there is no '
                                        'point cloud to clean'),
         (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')
-    ] + plane_row + keep_row
+    ] + target_row + plane_row + keep_row
 
 
 def _check_options(**options):
@@ -579,7 +592,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     register (with gt_ply only): None, or dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned
     to the ground truth before it is scored (eval_cloud --register [--init_cameras]); cloud_eval.json carries `registration`.
     With icp='plane' in the dict (fuse_normals normals='depth' only) the registration is point-to-plane over the normals the
-    fusion returns (eval_cloud --register_icp plane).
+    fusion returns (eval_cloud --register_icp plane); with normal_side='target' too (and optionally normal_k, normal_radius) over
+    the ground truth's planes instead, its normals estimated on the device: no fuse_normals needed (eval_cloud --register_normals).
     clean_keep_normals (with clean and fuse_normals normals='depth' only): final3d_model_clean.ply carries the normals of the rows
     that stay (clean_cloud --keep_normals).
     clean (with fuse only): None, or dict(voxel=, sor=(k, ratio, radius), radius_filter=(radius, min_neighbours)), the arguments of
@@ -606,6 +620,11 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
         register_args = dict(register=True, with_scale=bool(register.get('with_scale')))
         if register.get('icp') == 'plane':
             register_args['register_icp'] = 'plane'
+        if register.get('normal_side') == 'target':
+            register_args['register_normals'] = 'target'
+            for key in ('normal_k', 'normal_radius'):
+                if register.get(key) is not None:
+                    register_args['register_' + key] = register[key]
         if register.get('init_cameras'):
             from . import register_cloud
             init, matched, rms = register_cloud.init_from_cameras(*register['init_cameras'])
@@ -642,6 +661,15 @@ def _normal_options(flags):
     return given or None
 
 
+def _target_options(flags):
+    """The entries of run_eval_pc's register dict from cli's --register_normal* options: those that were given."""
+    names = dict(register_normals='normal_side', register_normal_k='normal_k', register_normal_radius='normal_radius')
+    given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
+    if given.get('normal_side') == 'source':
+        del given['normal_side']                                    # the default: nothing new is passed on
+    return given
+
+
 def _run_options(flags):
     """run_eval_pc's keyword arguments from a namespace of cli's options (FLAGS, cli's parsed arguments): one it lacks is off."""
     opt = lambda name, default=None: getattr(flags, name, default)          # noqa: E731
@@ -652,7 +680,7 @@ def _run_options(flags):
         fuse_normals=_normal_options(flags),
         map_files=not opt('no_map_files'), gt_ply=opt('gt_ply') or None, clean=opt('clean') or None,
         register=dict(dict(icp='plane') if opt('register_icp') == 'plane' else {}, with_scale=opt('with_scale', False),
-                      init_cameras=opt('init_cameras') or None) if opt('register') else None,
+                      init_cameras=opt('init_cameras') or None, **_target_options(flags)) if opt('register') else None,
         clean_keep_normals=bool(opt('clean_keep_normals')),
         score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
                         occlusion_tol=opt('map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
@@ -722,7 +750,14 @@ def cli(argv=None):
                              'ground truth\'s frame); their camera centres give the initial similarity')
     parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
                         help='--register: point-to-point ICP (the default) or point-to-plane over the fused cloud\'s normals '
-                             '(eval_cloud --register_icp); plane needs --fuse_normals depth')
+                             '(eval_cloud --register_icp); plane needs --fuse_normals depth, or --register_normals target')
+    parser.add_argument('--register_normals', default=None, choices=('source', 'target'),
+                        help='--register_icp plane: the planes of the fused cloud (source, the default) or of the ground truth, whose '
+                             'normals are estimated on the GPU (target: no --fuse_normals depth needed; eval_cloud --register_normals)')
+    parser.add_argument('--register_normal_k', type=int, default=None, metavar='K',
+                        help='--register_normals target: eval_cloud --register_normal_k')
+    parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
+                        help='--register_normals target: eval_cloud --register_normal_radius')
     parser.add_argument('--score_maps', action='store_true',
                         help='--gt_ply: render the ground truth into the scene\'s cameras and score the depth maps that entered the '
                              'cloud against it (eval_depth: mae, rmse, ..., inlier ratios per map; a point splat, not ETH3D\'s '
@@ -743,6 +778,12 @@ def cli(argv=None):
         parser.error('--with_scale and --init_cameras need --register')
     if args.register_icp is not None and not args.register:
         parser.error('--register_icp needs --register')
+    if (args.register_normals, args.register_normal_k, args.register_normal_radius) != (None, None, None) and not args.register:
+        parser.error('--register_normals, --register_normal_k and --register_normal_radius need --register')
+    if args.register_normal_k is not None and not 2 <= args.register_normal_k <= 32:
+        parser.error('--register_normal_k must be in 2..32')
+    if args.register_normal_radius is not None and not (args.register_normal_radius > 0.0 and np.isfinite(args.register_normal_radius)):
+        parser.error('--register_normal_radius must be positive and finite')
     if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
                                 or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
         parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')

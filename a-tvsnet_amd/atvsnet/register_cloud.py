@@ -12,9 +12,11 @@ The search (ops.cloud_grid / cloud_nearest), the move (ops.cloud_transform), the
 (ops.cloud_pair_moments) and the down-sampling run on the device; per iteration only 19 words cross to the host, where the
 closed form of Umeyama / Horn turns them into a 4x4 matrix in float64 (similarity_from_moments).  Point-to-plane reduces the
 pairs to 37 sums instead (ops.cloud_plane_moments; 38 words cross), and a 6x6 or 7x7 solve turns them into an increment of the
-matrix (motion_from_plane_moments).  This module imports without a GPU; only `register` needs one.  Not here: normals of an
-arbitrary cloud (only a fused cloud's own are used), target-side normals, a symmetric objective, and a global (feature-based)
-registration: without cameras or an initial matrix the clouds must already be within the first stage's distance of each other.
+matrix (motion_from_plane_moments).  The planes are the source's (a fused cloud's own normals) or the target's
+(normal_side='target': the ground truth's normals, given or estimated by ops.cloud_knn + ops.cloud_normals, for a reconstruction
+that carries none; ops.cloud_plane_moments_target).  This module imports without a GPU; only `register` needs one.  Not here:
+orienting normals by propagation, a symmetric objective, and a global (feature-based) registration: without cameras or an initial
+matrix the clouds must already be within the first stage's distance of each other.
 """
 import numpy as np
 
@@ -172,7 +174,7 @@ def corner_move(T0, T1, corners):
 
 
 def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES, voxel=None, max_iterations=50, min_move=None,
-             device=None, icp='point', normals=None):
+             device=None, icp='point', normals=None, normal_side='source', gt_normals=None, normal_k=16, normal_radius=None):
     """Trimmed ICP of `recon` (M,3) onto `gt` (N,3) (host arrays or device tensors, float32) on the device: point-to-point
     (icp='point', the default) or point-to-plane over the reconstruction's normals (icp='plane').
 
@@ -192,7 +194,17 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
     ops.cloud_plane_moments of the ORIGINAL source under the current T about the centre of the target's box, and T becomes
     motion_from_plane_moments(...) T in float64 on the host; stop rule, stages and messages are the same.  The dict then also
     holds icp = 'plane' and, per stage, plane_rmse = sqrt(sum r^2 / pairs) beside rmse; with icp='point' the dict is what it was
-    (no icp key), so that what is written from it keeps its bytes."""
+    (no icp key), so that what is written from it keeps its bytes.
+
+    normal_side='target' (icp='plane' only) is the classical form of Chen and Medioni over the GROUND TRUTH's normals, for a
+    reconstruction that carries none: `normals` is refused, and the moments are ops.cloud_plane_moments_target.  gt_normals: (N,3),
+    one per row of `gt` in gt's frame; they follow their points through the down-sampling as the source's do.  None: they are
+    estimated once, after the down-sampling, by ops.cloud_grid(gt, normal_radius), ops.cloud_knn(k=normal_k,
+    exclude_same_index=True) and ops.cloud_normals(self_counts=True), unoriented -- the step does not see a normal's sign.
+    normal_radius None: 4 voxel edges, or twice the last distance when voxel == 0; like normal_k = 16 a default, not a
+    measurement.  A target point whose normal is zero (fewer than 3 samples within the radius, or samples along a line) pairs with
+    nothing.  The dict then also holds normal_side = 'target', normal_k and normal_radius (both None when gt_normals were given) and
+    n_gt_normals, the target points with a usable normal; with normal_side='source' it holds none of them."""
     import torch
     from .. import ops
     dist = [float(d) for d in distances]
@@ -208,7 +220,21 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
     if icp not in ('point', 'plane'):
         raise ValueError("icp must be 'point' or 'plane', got %r" % (icp,))
     plane = icp == 'plane'
-    if plane and normals is None:
+    if normal_side not in ('source', 'target'):
+        raise ValueError("normal_side must be 'source' or 'target', got %r" % (normal_side,))
+    target = normal_side == 'target'
+    if target and not plane:
+        raise ValueError("normal_side='target' is used by icp='plane' only")
+    if target and normals is not None:
+        raise ValueError("normal_side='target' uses the ground truth's normals (gt_normals=, or estimated): normals= is not used")
+    if gt_normals is not None and not target:
+        raise ValueError("gt_normals are used by normal_side='target' only")
+    if target and gt_normals is None:
+        if isinstance(normal_k, bool) or not isinstance(normal_k, (int, np.integer)) or not 2 <= int(normal_k) <= 32:
+            raise ValueError('normal_k: expected an integer in 2..32, got %r' % (normal_k,))
+        if normal_radius is not None and not (float(normal_radius) > 0.0 and np.isfinite(float(normal_radius))):
+            raise ValueError('normal_radius must be positive and finite, got %r' % (normal_radius,))
+    if plane and not target and normals is None:
         raise ValueError("icp='plane' needs the reconstruction's normals (normals=, one row per point)")
     if not plane and normals is not None:
         raise ValueError("normals are used by icp='plane' only")
@@ -222,14 +248,27 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
 
     with torch.cuda.device(dev):
         src, dst = upload(recon), upload(gt)
-        nrm = upload(normals) if plane else None
-        if plane and nrm.shape != src.shape:
+        nrm = upload(normals) if plane and not target else None
+        if nrm is not None and nrm.shape != src.shape:
             raise ValueError('normals: %d rows for %d points' % (nrm.shape[0], src.shape[0]))
+        gnrm = upload(gt_normals) if gt_normals is not None else None
+        if gnrm is not None and gnrm.shape != dst.shape:
+            raise ValueError('gt_normals: %d rows for %d points' % (gnrm.shape[0], dst.shape[0]))
         if voxel > 0.0:
             src, first = ops.cloud_voxel_downsample(src, voxel)
-            if plane:
+            if nrm is not None:
                 nrm = nrm[first.long()].contiguous()
-            dst = ops.cloud_voxel_downsample(dst, voxel)[0]
+            dst, first = ops.cloud_voxel_downsample(dst, voxel)
+            if gnrm is not None:
+                gnrm = gnrm[first.long()].contiguous()
+        if target and gnrm is None:
+            normal_k = int(normal_k)
+            normal_radius = float(normal_radius) if normal_radius is not None else (4.0 * voxel if voxel > 0.0 else 2.0 * dist[-1])
+            knn = ops.cloud_knn(ops.cloud_grid(dst, normal_radius), dst, normal_k, exclude_same_index=True)[1]
+            gnrm = ops.cloud_normals(dst, dst, knn, self_counts=True)
+        elif target:
+            normal_k = normal_radius = None
+        n_gt_normals = int((torch.isfinite(gnrm).all(dim=1) & (gnrm != 0).any(dim=1)).sum().item()) if target else None
         s_lo, s_hi = ops.cloud_bounds(src)
         d_lo, d_hi = ops.cloud_bounds(dst)
         if s_lo is None or d_lo is None:
@@ -246,7 +285,9 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
             for _ in range(int(max_iterations)):
                 ops.cloud_transform(src, T, out=moved)
                 d2, idx = ops.cloud_nearest(grid, moved)
-                if plane:
+                if target:
+                    count, mom = ops.cloud_plane_moments_target(src, T, dst, gnrm, idx, d2, pivot=pivot_dst)
+                elif plane:
                     count, mom = ops.cloud_plane_moments(src, nrm, T, dst, idx, d2, pivot=pivot_dst)
                 else:
                     count, mom = ops.cloud_pair_moments(src, dst, idx, d2, pivot_src=pivot_src, pivot_dst=pivot_dst)
@@ -271,4 +312,6 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
               'voxel': voxel, 'n_recon': int(src.shape[0]), 'n_gt': int(dst.shape[0]), 'stages': stages}
     if plane:
         result['icp'] = 'plane'
+    if target:
+        result.update(normal_side='target', normal_k=normal_k, normal_radius=normal_radius, n_gt_normals=n_gt_normals)
     return result

@@ -142,6 +142,50 @@ __global__ __launch_bounds__(kThreads) void cloud_plane_moments_kernel(const flo
   }, rows, sh);
 }
 
+// The same sums over the TARGET's normals (atvs_cloud_plane_moments_target): the normal belongs to the matched point and stays in
+// the target's frame, so nothing is rotated and the lever arm is the moved source's, q x n.
+struct PlaneTargetArgs {
+  double t[12];          // T, rows 0-2
+  double trim2;
+  double pivot[3];
+};
+
+__global__ __launch_bounds__(kThreads) void cloud_plane_moments_target_kernel(const float* __restrict__ src, const float* __restrict__ dst,
+                                                                              const float* __restrict__ dst_normals, long n,
+                                                                              const int* __restrict__ idx, const float* __restrict__ d2, long m,
+                                                                              PlaneTargetArgs A, unsigned long long* __restrict__ rows) {
+  __shared__ MomentShared<kPlaneSums> sh;
+  moment_row<kPlaneSums>(m, [&](long i, long long& cnt, double* v) {
+    const int j = idx[i];
+    const float dd = d2[i];
+    if (j < 0 || (long)j >= n || !((double)dd <= A.trim2)) return;
+    const float fx = dst_normals[(long)j * 3 + 0], fy = dst_normals[(long)j * 3 + 1], fz = dst_normals[(long)j * 3 + 2];
+    if (!finite3(fx, fy, fz)) return;
+    const double n0 = (double)fx, n1 = (double)fy, n2 = (double)fz;
+    if (!((n0 * n0 + n1 * n1) + n2 * n2 > 0.0)) return;                      // the zero normal agrees with nothing
+    const double x = (double)src[i * 3 + 0], y = (double)src[i * 3 + 1], z = (double)src[i * 3 + 2];
+    const double* T = A.t;
+    const double q0 = (((T[0] * x + T[1] * y) + T[2] * z) + T[3]) - A.pivot[0];
+    const double q1 = (((T[4] * x + T[5] * y) + T[6] * z) + T[7]) - A.pivot[1];
+    const double q2 = (((T[8] * x + T[9] * y) + T[10] * z) + T[11]) - A.pivot[2];
+    const double g0 = (double)dst[(long)j * 3 + 0] - A.pivot[0], g1 = (double)dst[(long)j * 3 + 1] - A.pivot[1],
+                 g2 = (double)dst[(long)j * 3 + 2] - A.pivot[2];
+    const double e0 = q0 - g0, e1 = q1 - g1, e2 = q2 - g2;
+    const double r = (e0 * n0 + e1 * n1) + e2 * n2;
+    const double J[7] = {q1 * n2 - q2 * n1, q2 * n0 - q0 * n2, q0 * n1 - q1 * n0, n0, n1, n2, (q0 * n0 + q1 * n1) + q2 * n2};
+    cnt += 1;
+#pragma unroll
+    for (int a = 0; a < 7; ++a) {
+#pragma unroll
+      for (int b = a; b < 7; ++b) v[plane_at(a, b)] = v[plane_at(a, b)] + J[a] * J[b];
+    }
+#pragma unroll
+    for (int a = 0; a < 7; ++a) v[28 + a] = v[28 + a] + J[a] * r;
+    v[35] = v[35] + r * r;
+    v[36] = v[36] + (double)dd;
+  }, rows, sh);
+}
+
 // ---- voxel down-sampling -------------------------------------------------------------------------------------------------------
 
 struct VoxelLayout {
@@ -468,6 +512,41 @@ extern "C" int atvs_cloud_plane_moments(const float* src, const float* normals, 
   unsigned long long* level = static_cast<unsigned long long*>(scratch);
   hipLaunchKernelGGL(cloud_plane_moments_kernel, dim3((unsigned)moment_rows(m)), dim3(kThreads), 0, st, src, normals, dst, n, idx, d2, m, A,
                      moment_first(m, level, res));
+  ATVS_LAUNCH_CHECK();
+  return moment_fold<kPlaneSums>(m, level, res, st);
+}
+
+extern "C" int atvs_cloud_plane_moments_target_scratch_size(long m, long* bytes) {
+  return atvs_cloud_plane_moments_scratch_size(m, bytes);                      // the same rows and tree
+}
+
+extern "C" int atvs_cloud_plane_moments_target(const float* src, const double* matrix12, const float* dst, const float* dst_normals, long n,
+                                               const int* idx, const float* d2, long m, double trim, const double* pivot, void* scratch,
+                                               long scratch_bytes, void* out, atvs_stream_t stream) {
+  const double big = 1.7976931348623157e308;
+  if (m < 0 || m > kMaxPoints || n < 0 || n > kMaxPoints) return ATVS_ERR_SHAPE;
+  if (!out || !matrix12 || !pivot || (m > 0 && (!src || !idx || !d2 || !scratch)) || (m > 0 && n > 0 && (!dst || !dst_normals)))
+    return ATVS_ERR_NULL;
+  if (!(trim >= 0.0)) return ATVS_ERR_ARG;                  // NaN or negative; +inf is allowed
+  PlaneTargetArgs A;
+  A.trim2 = trim * trim;
+  for (int k = 0; k < 12; ++k) {
+    if (!(fabs(matrix12[k]) <= big)) return ATVS_ERR_ARG;
+    A.t[k] = matrix12[k];
+  }
+  for (int k = 0; k < 3; ++k) {
+    if (!(fabs(pivot[k]) <= big)) return ATVS_ERR_ARG;
+    A.pivot[k] = pivot[k];
+  }
+  long need = 0;
+  atvs_cloud_plane_moments_target_scratch_size(m, &need);
+  if (m > 0 && scratch_bytes < need) return ATVS_ERR_SHAPE;
+  hipStream_t st = as_stream(stream);
+  unsigned long long* res = static_cast<unsigned long long*>(out);
+  if (m == 0) return hipMemsetAsync(out, 0, kPlaneWords * 8, st) == hipSuccess ? ATVS_OK : ATVS_ERR_LAUNCH;
+  unsigned long long* level = static_cast<unsigned long long*>(scratch);
+  hipLaunchKernelGGL(cloud_plane_moments_target_kernel, dim3((unsigned)moment_rows(m)), dim3(kThreads), 0, st, src, dst, dst_normals, n, idx,
+                     d2, m, A, moment_first(m, level, res));
   ATVS_LAUNCH_CHECK();
   return moment_fold<kPlaneSums>(m, level, res, st);
 }

@@ -11,7 +11,7 @@
     colmap    COLMAP model import: per-image depth range, co-visibility matrix; undistortion: sampling map, image gather
     cloud     point-cloud scoring: uniform grid, exact nearest neighbour within a radius, tolerance counts;
               registration: transform, pair moments, voxel down-sampling; neighbourhoods: k nearest neighbours, radius counts,
-              outlier statistics, bounding box; rendering: a scan splatted into cameras as nearest-depth maps; ETH3D-style
+              outlier statistics, bounding box, normals by PCA over the k nearest; rendering: a scan splatted into cameras as nearest-depth maps; ETH3D-style
               scoring: a point's free-space excess against scanner cube maps, voxel-averaged shares
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
@@ -44,6 +44,7 @@ from .colmap import UNDISTORT_MAX_SIDE, UNDISTORT_MODELS, undistort_map, undisto
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401
 from .cloud import cloud_bounds, cloud_pair_moments, cloud_plane_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
 from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401
+from .cloud import cloud_normals, cloud_plane_moments_target      # noqa: F401
 from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

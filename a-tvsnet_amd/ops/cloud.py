@@ -10,6 +10,10 @@ Neighbourhoods (csrc/cloud_knn.hip; atvsnet/clean_cloud.py is built on it): clou
 the grid's radius, cloud_radius_count counts the reference points inside it, cloud_knn_mean and cloud_sor_stats reduce the k-NN
 distances to the three numbers of statistical outlier removal, cloud_bounds is the bounding box of the finite rows.
 
+Normals (csrc/cloud_normals.hip): cloud_normals turns cloud_knn's neighbours into one PCA normal per query;
+cloud_plane_moments_target is the point-to-plane step over such normals of the TARGET (atvsnet/register_cloud.py
+normal_side='target', atvsnet/cloud_normals.py).
+
 Rendering (csrc/scan_render.hip; atvsnet/eval_depth.py is built on it): scan_render splats a scan into a set of cameras and keeps
 the nearest depth per pixel, the ground-truth depth maps the network's maps are scored against.
 
@@ -234,6 +238,42 @@ def cloud_plane_moments(src, normals, T, dst, idx, d2, trim=float('inf'), pivot=
     return int(words[0]), words[1:].view(np.float64).copy()
 
 
+def cloud_plane_moments_target(src, T, dst, dst_normals, idx, d2, trim=float('inf'), pivot=None):
+    """The sums of one Gauss-Newton step of point-to-plane ICP over the TARGET's normals (atvs_cloud_plane_moments_target; the
+    header states every term).  src (m,3) float32: the ORIGINAL source; T: the current 4x4 (or 3x4) matrix as host numbers; dst
+    (n,3) float32 and dst_normals (n,3) float32: the searched cloud and one normal per row of it, in its frame (used as they are:
+    nothing is rotated); idx (m,) int32, d2 (m,) float32: what cloud_nearest returned for cloud_transform(src, T); pivot: 3 host
+    numbers in dst's frame (default 0).  A pair takes part under cloud_pair_moments' rule when dst_normals[idx] is finite and not
+    zero.  -> (count, moments) in cloud_plane_moments' layout, with J = [q x n (3), n (3), q . n]; motion_from_plane_moments takes
+    them as they are.  Negating normals changes no bit of the result."""
+    trim = float(trim)
+    if not trim >= 0.0:
+        raise ValueError('trim must be >= 0 (inf allowed), got %r' % (trim,))
+    p = _vec3(pivot, 'pivot')
+    M = np.asarray(T, np.float64)
+    if M.shape not in ((4, 4), (3, 4)) or not np.isfinite(M).all():
+        raise ValueError('T: expected a finite 4x4 (or 3x4) matrix, got %r' % (T,))
+    _cloud_arg(src, 'src', torch.float32, (3,))
+    _cloud_arg(dst, 'dst', torch.float32, (3,))
+    _cloud_arg(dst_normals, 'dst_normals', torch.float32, (3,))
+    _cloud_arg(idx, 'idx', torch.int32, ())
+    _cloud_arg(d2, 'd2', torch.float32, ())
+    m, n = int(src.shape[0]), int(dst.shape[0])
+    if int(dst_normals.shape[0]) != n:
+        raise ValueError('dst_normals %s must have one row per row of dst %s' % (tuple(dst_normals.shape), tuple(dst.shape)))
+    if int(idx.shape[0]) != m or int(d2.shape[0]) != m:
+        raise ValueError('idx %s and d2 %s must have one entry per row of src %s' % (tuple(idx.shape), tuple(d2.shape), tuple(src.shape)))
+    for t, name in ((dst, 'dst'), (dst_normals, 'dst_normals'), (idx, 'idx'), (d2, 'd2')):
+        _same_device(t, name, src, 'src')
+    m12 = (ctypes.c_double * 12)(*M[:3].reshape(-1).tolist())
+    out = torch.empty(38, dtype=torch.int64, device=src.device)
+    scratch = torch.empty(_size('atvs_cloud_plane_moments_target_scratch_size', m), dtype=torch.uint8, device=src.device)
+    _call('atvs_cloud_plane_moments_target', _p(src), m12, _p(dst), _p(dst_normals), n, _p(idx), _p(d2), m, trim, p,
+          _p(scratch), scratch.numel(), _p(out), _stream())
+    words = out.cpu().numpy()
+    return int(words[0]), words[1:].view(np.float64).copy()
+
+
 def _voxel(voxel):
     voxel = float(voxel)
     if not (voxel > 0.0 and math.isfinite(voxel)):
@@ -367,6 +407,62 @@ def cloud_sor_stats(s):
     words = out.cpu().numpy()
     mean, std = words[1:].view(np.float64).tolist()
     return int(words[0]), mean, std
+
+
+def cloud_normals(points, queries, idx, self_counts=False, viewpoints=None, view_of=None, variation=False):
+    """points (n,3) float32: the searched cloud; queries (m,3) float32; idx (m,k) int32 as cloud_knn returned it for `queries` in
+    `points` (1 <= k <= 32, -1 padded) -> normals (m,3) float32: per row the unit eigenvector of the smallest eigenvalue of the
+    covariance of the samples points[idx] - query (atvs_cloud_normals: float64 throughout, a fixed 18-rotation Jacobi solver; the
+    header states every operation).  self_counts: the query is itself a sample (the self-search with exclude_same_index).  The
+    zero normal where a row has fewer than 3 samples, a non-finite one, an index >= n, or samples along one line.  viewpoints:
+    None, (v,3) host numbers, or a (v,3) float64 tensor on the device: row j's normal is turned towards viewpoint view_of[j]
+    (view_of (m,) int32 on the device; None: viewpoint 0 for every row; -1: not oriented).  A row that is not oriented has the
+    canonical sign: its component of largest magnitude is positive.  variation=True: -> (normals, variation (m,) float32 =
+    lambda_0 / (lambda_0 + lambda_1 + lambda_2), NaN where the normal is zero)."""
+    if not isinstance(self_counts, (bool, np.bool_)):
+        raise TypeError('self_counts: expected a bool, got %r' % (self_counts,))
+    if not isinstance(idx, torch.Tensor):
+        raise TypeError('idx: expected a tensor, got %s' % type(idx).__name__)
+    k = int(idx.shape[1]) if idx.dim() == 2 else 0
+    if not 1 <= k <= CLOUD_MAX_K:
+        raise ValueError('idx: expected shape (m,k) with k in 1..%d, got %s' % (CLOUD_MAX_K, tuple(idx.shape)))
+    views = viewpoints
+    if viewpoints is not None and not isinstance(viewpoints, torch.Tensor):
+        views = np.asarray(viewpoints, np.float64)
+        if views.shape == (3,):
+            views = views.reshape(1, 3)
+        if views.ndim != 2 or views.shape[1] != 3 or not len(views) or not np.isfinite(views).all():
+            raise ValueError('viewpoints: expected (v,3) finite numbers, v >= 1, got %r' % (viewpoints,))
+    if view_of is not None and views is None:
+        raise ValueError('view_of needs viewpoints')
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    _cloud_arg(queries, 'queries', torch.float32, (3,))
+    _cloud_arg(idx, 'idx', torch.int32, (k,))
+    n, m = int(points.shape[0]), int(queries.shape[0])
+    if int(idx.shape[0]) != m:
+        raise ValueError('idx %s must have one row per row of queries %s' % (tuple(idx.shape), tuple(queries.shape)))
+    for t, name in ((queries, 'queries'), (idx, 'idx')):
+        _same_device(t, name, points, 'points')
+    n_views = 0
+    if views is not None:
+        if not isinstance(views, torch.Tensor):
+            views = torch.from_numpy(np.ascontiguousarray(views)).to(points.device)
+        _cloud_arg(views, 'viewpoints', torch.float64, (3,))
+        _same_device(views, 'viewpoints', points, 'points')
+        n_views = int(views.shape[0])
+        if n_views < 1:
+            raise ValueError('viewpoints: at least one row')
+    if view_of is not None:
+        _cloud_arg(view_of, 'view_of', torch.int32, ())
+        if int(view_of.shape[0]) != m:
+            raise ValueError('view_of %s must have one entry per row of queries %s' % (tuple(view_of.shape), tuple(queries.shape)))
+        _same_device(view_of, 'view_of', points, 'points')
+    normals = torch.empty((m, 3), dtype=torch.float32, device=points.device)
+    var = torch.empty(m, dtype=torch.float32, device=points.device) if variation else None
+    if m:
+        _call('atvs_cloud_normals', _p(points), n, _p(queries), m, _p(idx), k, 1 if self_counts else 0, _p(views), n_views,
+              _p(view_of), _p(normals), _p(var), _stream())
+    return (normals, var) if variation else normals
 
 
 def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_tol=0.0):

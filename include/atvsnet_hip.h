@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 55
+#define ATVS_ABI_VERSION 56
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -869,6 +869,18 @@ int atvs_cloud_counts(const float* d2, long m, const double* tolerances, int k, 
  * bit for bit).  m = 0: 38 zero words.  scratch: atvs_cloud_plane_moments_scratch_size(m) bytes.  trim negative or NaN, a
  * non-finite pivot, matrix12 or rot9 entry: ATVS_ERR_ARG.
  *
+ * atvs_cloud_plane_moments_target: the same step over the TARGET's normals (Chen and Medioni's form).  dst_normals (n,3) float32 =
+ * one normal per row of dst, in dst's frame; the pair's normal is n = (double)dst_normals[idx[i]], used as it is: nothing is rotated,
+ * there is no rot9.  Pair i takes part under atvs_cloud_plane_moments' rule with that normal in the place of the source's (finite,
+ * (n_0 n_0 + n_1 n_1) + n_2 n_2 > 0 in double).  q_k and g_k are as above (q NOT rounded to float32), and
+ *   r    = ((q_0 - g_0) n_0 + (q_1 - g_1) n_1) + (q_2 - g_2) n_2
+ *   J    = [ q_1 n_2 - q_2 n_1,  q_2 n_0 - q_0 n_2,  q_0 n_1 - q_1 n_0,  n_0,  n_1,  n_2,  (q_0 n_0 + q_1 n_1) + q_2 n_2 ]
+ * The normal does not move with the source, so to first order r' = (q + omega x q + sigma q + t - g) . n =
+ * r + omega . (q x n) + t . n + sigma q . n: the lever arm is the moved SOURCE's, q x n.  r and every J_a change sign with n (negation is
+ * exact), so every product J_a J_b, J_a r and r r keeps its bits: negating any normals changes no bit of `out`.  The 38 words, their
+ * layout, the reduction, m = 0, the scratch size (atvs_cloud_plane_moments_target_scratch_size(m) = the source form's) and the error
+ * codes are atvs_cloud_plane_moments'.
+ *
  * atvs_cloud_voxel_downsample: one output point per occupied cubic voxel of edge `voxel` (double > 0): the mean of the voxel's
  * finite points; non-finite points are dropped.  origin: HOST, 3 finite doubles.  Per axis, in double: g = ((double)x - origin) /
  * voxel, c = floor(g), u = (uint64)floor((g - c) * 2^32) clamped to 2^32 - 1.  A voxel is the triple of c, packed 3 x 21 bits as
@@ -890,6 +902,10 @@ int atvs_cloud_plane_moments_scratch_size(long m, long* bytes);
 int atvs_cloud_plane_moments(const float* src, const float* normals, const double* matrix12, const double* rot9, const float* dst,
                              long n, const int* idx, const float* d2, long m, double trim, const double* pivot, void* scratch,
                              long scratch_bytes, void* out, atvs_stream_t stream);
+int atvs_cloud_plane_moments_target_scratch_size(long m, long* bytes);
+int atvs_cloud_plane_moments_target(const float* src, const double* matrix12, const float* dst, const float* dst_normals, long n,
+                                    const int* idx, const float* d2, long m, double trim, const double* pivot, void* scratch,
+                                    long scratch_bytes, void* out, atvs_stream_t stream);
 int atvs_cloud_voxel_downsample_scratch_size(long n, long* bytes);
 int atvs_cloud_voxel_downsample(const float* points, long n, double voxel, const double* origin, void* scratch, long scratch_bytes,
                                 float* out_points, long long* out_count, int* out_first, atvs_stream_t stream);
@@ -933,6 +949,49 @@ int atvs_cloud_knn_mean(const float* d2, long m, int k, double* s, atvs_stream_t
 int atvs_cloud_sor_stats_scratch_size(long m, long* bytes);
 int atvs_cloud_sor_stats(const double* s, long m, void* scratch, long scratch_bytes, void* out, atvs_stream_t stream);
 int atvs_cloud_bounds(const float* points, long n, void* out, atvs_stream_t stream);
+
+/* Normals of an arbitrary cloud (ops/cloud.py cloud_normals, atvsnet/register_cloud.py, atvsnet/cloud_normals.py,
+ * csrc/cloud_normals.hip): per query the direction of least variance of the neighbours atvs_cloud_knn found.  Pointers are device
+ * pointers.  No atomics, no host synchronisation, no allocation, one launch; a row's output is a function of that row's inputs alone,
+ * bit for bit on every run.  tests/cloud_normals_restated.py restates the definition.
+ *
+ * atvs_cloud_normals.  points P (n,3) float32 = the searched cloud, queries Q (m,3) float32, idx (m,k) int32 as atvs_cloud_knn
+ * returns it for Q in P (1 <= k <= ATVS_CLOUD_MAX_K; a negative entry is padding), self_counts 0 or 1, viewpoints (v,3) DOUBLES (or
+ * NULL with v = 0), view_of (m) int32 or NULL -> normals (m,3) float32 and, unless NULL, variation (m) float32.
+ * Per row j, in double, every operation rounded on its own, nothing contracted:
+ *   the samples   d_t = (double)P[idx[j,t]] - (double)Q[j] per component, for the t with idx[j,t] >= 0, in ascending t.  A
+ *                 difference of two float32 is exact in double when their exponents differ by at most 29 (53 - 24): for every finite
+ *                 pair whose larger magnitude is below 2^29 times the smaller one's last place -- any cloud whose extent is below
+ *                 2^29 times its float32 spacing, which a float32 cloud with a radius search always is; beyond that it is rounded once.
+ *   the sums      s = sum d_t (3) and S_ab = sum d_ta d_tb (6, a <= b), each from +0 in ascending t, product then addition.
+ *   the count     c = the number of samples, + 1 when self_counts (the query is itself a sample, d = 0: the self-search with
+ *                 exclude_same_index; PCL and Open3D count the point too).
+ *   the matrix    C_ab = S_ab - (s_a s_b) / c.  Shifting by the query keeps every term at the neighbourhood's own scale, so this
+ *                 one-pass form does not cancel however far the cloud lies from the origin: |d| is at most the search radius, so S_ab and
+ *                 s_a s_b / c are at most c radius^2, the size of C's own entries, not of the squared coordinates.
+ *   the normal    the unit eigenvector of the smallest eigenvalue of C, by cyclic Jacobi of FIXED shape: 6 sweeps of the rotations
+ *                 (p,q) = (0,1), (0,2), (1,2), all 18 always.  A rotation, r the third index: theta = (a_qq - a_pp) / (2 a_pq);
+ *                 t = sign(theta) / (|theta| + sqrt(theta theta + 1)), t = 0 when a_pq == 0; c = 1 / sqrt(t t + 1); s = t c;
+ *                 a_pp = a_pp - t a_pq; a_qq = a_qq + t a_pq; a_pq = 0; (a_pr, a_qr) = (c a_pr - s a_qr, s a_pr + c a_qr);
+ *                 columns p, q of V (the identity at first) turn the same way.  Afterwards lambda = the diagonal, the normal = the
+ *                 column of V under the smallest entry (the lowest index on ties), lambda_0 <= lambda_1 <= lambda_2 its order.
+ *                 At most 7 roundings reach an entry per rotation: the solver's backward error is at most S = 128 (>= 18 x 7) units
+ *                 of 2^-53 |C|, an allowance from the operation count.  The column is unit to that error and is not renormalised.
+ *   zero normal   (0, 0, 0), and variation NaN, when c < 3; when the query or a sample is not finite; when an idx[j,t] >= n (never
+ *                 read); when lambda_1 <= 1e-12 lambda_2 (fewer than two directions: collinear or coincident samples) or an
+ *                 eigenvalue is not finite.  This is the normal atvs_cloud_plane_moments(_target) skip.
+ *   the sign      with v = view_of ? view_of[j] : 0 and 0 <= v < the number of viewpoints: e = viewpoints[v] - (double)Q[j],
+ *                 dot = (n_0 e_0 + n_1 e_1) + n_2 e_2; negated when dot < 0, kept when dot > 0.  Otherwise (no viewpoints, v outside
+ *                 the range -- -1 means "do not orient" --, dot == 0 or NaN): the canonical sign, the component of largest
+ *                 magnitude (lowest index on ties) is made positive.  No propagation across the cloud.
+ *   the outputs   normals = the three doubles rounded once to float32; variation = (float)(lambda_0 / ((lambda_0 + lambda_1) +
+ *                 lambda_2)), the surface variation of Pauly et al. (it can be a rounding below 0 on an exact plane).
+ * One lane per query; a lane reads its own row of idx and gathers k x 12 bytes.  m = 0 is valid (nothing is written).
+ * n or m negative or beyond 2^30, k outside [1, ATVS_CLOUD_MAX_K], a negative number of viewpoints: ATVS_ERR_SHAPE; self_counts not
+ * 0 or 1, viewpoints NULL with a count or a count of 0 with viewpoints, view_of without viewpoints: ATVS_ERR_ARG. */
+int atvs_cloud_normals(const float* points, long n, const float* queries, long m, const int* idx, int k, int self_counts,
+                       const double* viewpoints, int n_viewpoints, const int* view_of, float* normals, float* variation,
+                       atvs_stream_t stream);
 
 /* A scan rendered into cameras (ops/cloud.py scan_render, atvsnet/eval_depth.py, csrc/scan_render.hip): the ground-truth depth
  * maps a set of depth maps is scored against.  Pointers are device pointers.  Integer atomics only: the output is a function of the
