@@ -17,15 +17,36 @@ The ratios below and the ones assert_elementwise returns are (err - floor) / con
 it); the floor is significant only in the below-2^-14 regime and on residual adds.
 
 Measured on one MI355X by tests/test_gpu_split_precision.py, largest err / cond over every row and regime except near_max:
-split-operand kernels 3.7e-7 (conv1x1_b, log-uniform), fp32 matrix-core / FMA kernels 5.1e-7 (conv_c16, log-uniform).  With a
+split-operand kernels 3.7e-7 (conv1x1_b, log-uniform), fp32 matrix-core / FMA kernels 7.9e-7 (conv2d_lds 128 -> 128 with
+dilation 2, log-uniform; 5.1e-7, conv_c16, before the fp32 twins of the split rows were added).  With a
 few entries near 6e4 one product dominates cond and every later fp32 add of the accumulator rounds at its ulp, so err / cond
-grows with the number of adds: 1.3e-6 split (conv2d_b), 2.8e-6 fp32 (conv_tiled); that regime is held to NEAR_MAX * rel.
+grows with the number of adds: 1.3e-6 split (conv2d_b), 3.3e-6 fp32 (conv2d_lds, dilation 2; conv_tiled 2.8e-6); that regime is
+held to NEAR_MAX * rel.
 The CPU emulation of the split with float64 accumulation (tests/test_numerics_bar.py) gives at most 2.0e-7 for the correct
 split and 3.1e-5 (3x3, Cin 128) for the mildest defect it checks, one tap's low pieces dropped.  SPLIT.rel is 8.1x the
-split maximum of the convolution rows and 1/10 of that defect; FP32_MFMA.rel 8.8x the fp32 maximum; near_max keeps 18x / 13x.
+split maximum of the convolution rows and 1/10 of that defect; FP32_MFMA.rel 8.8x the fp32 maximum it was set from (5.1e-7) and
+5.7x today's; near_max keeps 18x / 10.9x.
 Exception: the AANet module under its linearised bound (aanet_cond) measures 6.4e-7 with log-uniform views, 4.7x under
 SPLIT.rel; its cond leaves out the fp32 rounding of the scores and the softmax, which a wider SPLIT.rel may not absorb
 without losing the 8x above the one-tap defect.
+
+The fp32 forms of the overflow recompute (the rows under cfg=FP32, ops.configure(split16=False)), largest err / cond per family
+over the regimes except near_max | near_max: conv1x1 (plain, on load, G = 3, with a residual) 4.2e-7 | 5.1e-7; conv2d_lds (dilated,
+ragged) 7.9e-7 | 3.3e-6; c16 (8 / 16 / 48 -> 16 / 32, D = 1) 5.1e-7 | 2.3e-6; gather (stride 2, the tiny map, the strided conv2)
+4.9e-7 | 1.6e-6; tiled 3.8e-7 | 2.8e-6; deconv_up (16 -> 8, 32 -> 16 with G = 3) 3.8e-7 | 1.0e-6; the 64 -> 32 transposed
+convolution 4.4e-7 | 1.1e-6 as eight gather launches and 5.8e-7 | 1.3e-6 on conv_tiled (statistics folded by 4); the x-pair kernel
+conv_xw under its Winograd cond 7.9e-8 | 4.8e-7, with a plane bias 5.9e-8 | 4.8e-7, with its sibling (plain, a batch norm or a
+two-term sum formed on load) 4.2e-7 | 1.0e-6; the three-launch residual unit 6.1e-9 | 3.2e-8 (its cond is the propagated bound
+of three convolutions, as the fused unit's: 2.4e-8); offset regime at most 9.3e-9 (conv1x1).  The largest of the convolution
+families is conv2d_lds 128 -> 128 with dilation 2 (Cin chunks of a 1152-term sum): FP32_MFMA.rel keeps 5.7x over it, near_max 10.9x.
+The fp32 AANet module (conv_c16 scores + aanet_combine, nv = 1, 2, 5, 8, 16, and the three aanet_partial stages at 2 + 3 and
+4 + 4 views) measures 3.3e-7 | 2.8e-5 under aanet_cond.  The near_max figure, 0.78 of NEAR_MAX * FP32_MFMA.rel, is the fp32
+rounding of U_n = (R_n - S_n) + S_sum, which that cond leaves out: one view's 6e4 entry puts S_sum at up to 2.6e4 for EVERY
+view, so every score is rounded at the ulp of S_sum (2^-10) while the other views' own cond R_n + cond S_n is ~ 12 (aanet_b.hip,
+3.0e-7 there, takes the softmax of R_n - S_n alone from five views on: the shared sum cancels).  It is the reference's own
+arithmetic (fp32 R - S + S_sum): 2.82e-5 at five views and 2.79e-5 at eight, from the single launch and from the partial stages
+alike, 2.26e-5 at sixteen on the generic kernel -- and tests/test_numerics_bar.py gets the same three figures on the CPU from
+float64 scores with that one add rounded to fp32 (3.8e-9 without S_sum), so the kernels add nothing to it.
 
 A lazy input (a pending batch norm formed on load) enters `cond` as |its float64 normalised value|, which hides the rounding of
 the transform itself: about u |mean * rstd|, not u |value|.  The rows with such an input therefore also run the `offset` regime

@@ -14,7 +14,12 @@ Rows whose input is lazy (a pending batch norm, or a sum of two, formed while th
 moments as parameters.  There the rounding of the on-load transform, about u |mean * rstd| and not u |value|, is what dominates,
 so cond is numerics.cond_on_load -- the same operator on bn_cond = |x s| + |m s| + |b| of each lazy term -- and rel is the row's
 own plus 2^-22: the transform moves a normalised input by at most 2u * bn_cond, a two-term sum adds u (cond_a + cond_b), and
-3u < 2^-22."""
+3u < 2^-22.
+
+79 rows: 35 at the SPLIT bar and 44 at FP32_MFMA, of which 31 run under cfg=FP32 -- a twin of every split row whose fp32 form the
+fp32 path launches (tests/golden/conv_dispatch.json's split16=0 cases; tests/test_numerics_bar.py checks that each of their
+events has a row), the three-launch residual unit, and the AANet module as score convolutions + ops.aanet_combine / the
+ops.aanet_partial stages.  The one fp32 twin that is refused, a lazy input to conv2d_lds, is asserted below the table."""
 import collections
 
 import numpy as np
@@ -38,8 +43,9 @@ SAMPLE_SCALES = (1e-3, 1.0, 1e3)
 
 # family: what the row asserts it reaches; split: its split-operand family (the ops.split_on names, xb = conv_xb.hip,
 # aanet_b = aanet_b.hip) or None; cfg: the ops.configure switches it runs under
-Row = collections.namedtuple('Row', 'name family split bar run cfg lazy')
-Row.__new__.__defaults__ = (False,)                  # lazy: the input is formed on load, the row runs the offset regime too
+# maker: the function that built the row (tests/test_numerics_bar.py maps the entry points of conv_dispatch.json to it)
+Row = collections.namedtuple('Row', 'name family split bar run cfg lazy maker')
+Row.__new__.__defaults__ = (False, None)             # lazy: the input is formed on load, the row runs the offset regime too
 FP32 = {'split16': False}
 
 
@@ -111,25 +117,37 @@ def _winograd_cond(x, w):
     return T.conv(x.double().abs(), k5, 1, 'SAME')
 
 
+def _winograd_cond_terms(terms, w, regime):
+    """_winograd_cond of an input that is the sum of `terms` (tensors, or lazy inputs formed on load): |x| of a tensor, |its
+    float64 normalised value| of a lazy term, and in the offset regime its bn_cond (numerics.cond_on_load's rule)."""
+    def mag(t):
+        if not N._is_pending(t):
+            return t.double().abs()
+        return bn_ref.bn_cond(t.raw, t.params) if regime == OFFSET else N.term64(t).abs()
+    return _winograd_cond(sum(mag(t) for t in terms), w)
+
+
 class Case(object):
     """One launch's result: got (CPU) against want64 / cond64, the absolute floor, and what to check beside the values."""
 
-    def __init__(self, got, want64, cond64, floor, stats=None, kept=None):
+    def __init__(self, got, want64, cond64, floor, stats=None, kept=None, fold=(1,)):
         self.got, self.want64, self.cond64, self.floor = got, want64, cond64, floor
         self.stats = stats            # (Stats, device output of the same values, channels) or None
+        self.fold = fold              # the column folds the launch form may report (Stats.fold)
         self.kept = kept              # (NaN-filled device buffer, lo, hi) or None
 
 
-def _check_stats(st, y, C, what):
+def _check_stats(st, y, C, what, fold=(1,)):
     """The per-sample moments the launch wrote (all rows, the first C channels) against float64 moments of y; then
     bn_params must not raise the sticky non-finite flag."""
     from atvsnet_amd import ops
     G = st.groups
     part = st.partial.detach().cpu()
-    assert bool(torch.isfinite(part[..., :C]).all()), '%s: a statistics row holds a non-finite value' % what
-    # every launch form in this table writes its rows unfolded (fold > 1 is the tiled transposed-convolution fallback only)
-    assert st.fold == 1, '%s: statistics folded by %d' % (what, st.fold)
-    s = part.reshape(G, -1, 2, st.cpad).sum(1)[..., :C]
+    # every launch form in this table but one writes its rows unfolded; fold > 1 is the tiled transposed-convolution fallback
+    # (the fp32 64 -> 32 layer), whose column k * C + c holds the share of parity class k in channel c
+    assert st.fold in fold, '%s: statistics folded by %d' % (what, st.fold)
+    assert bool(torch.isfinite(part[..., :st.fold * C]).all()), '%s: a statistics row holds a non-finite value' % what
+    s = part.reshape(G, -1, 2, st.cpad).sum(1)[..., :st.fold * C].reshape(G, 2, st.fold, C).sum(2)
     v = y.detach().cpu().double().reshape(G, -1, C)
     for k, want in ((0, v.sum(1)), (1, (v * v).sum(1))):
         tol = 1e-5 * (v.abs() if k == 0 else v * v).sum(1) + 1e-30
@@ -143,7 +161,9 @@ def _check_stats(st, y, C, what):
 # ------------------------------------------------------------------------------------------------------- ops.conv rows
 
 def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation=1, explicit_pad=None, lazy=None, bias=True,
-             relu=True, cfg=None, slice_out=True, winograd=False):
+             relu=True, cfg=None, slice_out=True, winograd=False, residual=False):
+    """residual: a tensor of the output's shape added in the epilogue (a residual unit's conv3); it stays out of cond and the
+    floor gains the rounding of that add (_residual_floor)."""
     nsp = len(sp)
     ks = (k,) * nsp
 
@@ -155,7 +175,7 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
         padding = 'SAME' if explicit_pad is None else 'VALID'
         out_spec = (cout + 8, 4) if slice_out else None
         plan = ops.conv_plan(sp, k, cin, cout, stride, dilation, padding if explicit_pad is None else explicit_pad,
-                             bias, False, False, out_spec, lazy)
+                             bias, residual, False, out_spec, lazy)
         assert plan.family == family, '%s: conv_plan chose %s' % (name, plan.family)
         assert plan.on_load == bool(lazy), '%s: the lazy input is not formed on load' % name
         if family in ('conv2d_lds', 'conv1x1'):
@@ -182,6 +202,10 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
         if slice_out:
             buf = N.nan_output((G,) + plan.outs[3 - nsp:] + (cout + 8,), dev)
             kw.update(out=buf, y_coff=4)
+        res = None
+        if residual:
+            res = _input((G,) + plan.outs[3 - nsp:] + (cout,), 7, regime, grouped=True)
+            kw.update(residual=_dev(res, dev))
         y, st = ops.conv(xin, name, w.numpy(), **kw)
         ys = buf[..., 4:4 + cout] if slice_out else y
 
@@ -191,17 +215,20 @@ def conv_row(name, family, split, bar, G, sp, cin, cout, stride=1, k=3, dilation
             return _relu(T.conv(s, wt, stride, padding, dilation, bias=bt, explicit_pad=explicit_pad), relu)
         bb = b if b is not None else torch.zeros(cout)
         cnd = _winograd_cond(x, w) + bb.double().abs() if winograd else _cond(regime)(op, *terms, w, bb)
-        return [Case(ys.cpu(), N.ref64(op, *terms, w, bb), cnd, N.floor_of(w, bar),
-                     stats=(st, ys, cout), kept=(buf, 4, 4 + cout) if slice_out else None)]
-    return Row(name, family, split, bar, run, cfg or {}, bool(lazy))
+        want, floor = N.ref64(op, *terms, w, bb), N.floor_of(w, bar)
+        if residual:
+            want = want + res.double()
+            floor = _residual_floor(want, w, bar=bar)
+        return [Case(ys.cpu(), want, cnd, floor, stats=(st, ys, cout), kept=(buf, 4, 4 + cout) if slice_out else None)]
+    return Row(name, family, split, bar, run, cfg or {}, bool(lazy), 'conv_row')
 
 
 # ------------------------------------------------------------------------------------------------ the other entry points
 
-def _residual_floor(want, *ws):
-    """The floor of a fused residual unit: the weights' floors plus the fp32 rounding of the final residual add (2^-23 |y|).
+def _residual_floor(want, *ws, bar=SPLIT):
+    """The floor of a residual unit: the weights' floors plus the fp32 rounding of the final residual add (2^-23 |y|).
     The residual itself (exact fp32) stays out of cond, so a defect in the branch is measured against the branch alone."""
-    return sum(N.floor_of(w, SPLIT) for w in ws) + 2.0 ** -23 * want.abs()
+    return sum(N.floor_of(w, bar) for w in ws) + 2.0 ** -23 * want.abs()
 
 
 def tail_row(name, G, H, W, C, dil):
@@ -220,7 +247,7 @@ def tail_row(name, G, H, W, C, dil):
         a = (x, w2, b2, w3, b3)
         want = N.ref64(branch, *a) + res.double()
         return [Case(y.cpu(), want, N.cond(branch, *a), _residual_floor(want, w2, w3), stats=(st, y, C))]
-    return Row(name, 'conv2d_tail', 'btl', SPLIT, run, {})
+    return Row(name, 'conv2d_tail', 'btl', SPLIT, run, {}, False, 'tail_row')
 
 
 def bottleneck_row(name, G, H, W, C):
@@ -241,7 +268,40 @@ def bottleneck_row(name, G, H, W, C):
         a = (pend, ws[0], bs[0], ws[1], bs[1], ws[2], bs[2])
         want = N.ref64(branch, *a) + x.double()
         return [Case(y.cpu(), want, _cond(regime)(branch, *a), _residual_floor(want, *ws), stats=(st, y, C))]
-    return Row(name, 'bottleneck', 'btl', SPLIT, run, {}, True)
+    return Row(name, 'bottleneck', 'btl', SPLIT, run, {}, True, 'bottleneck_row')
+
+
+def residual_unit_row(name, G, H, W, C, dil):
+    """The identity-shortcut residual unit as the fp32 path runs it (cnn_wrapper/network.py bottleneck), three launches where the
+    split path runs ops.bottleneck (dil 1) or conv1 + ops.conv2d_tail (the 128-channel dilated units): conv1 1x1 with the
+    pre-activation batch norm formed on load, conv2 3x3 on conv2d_lds, conv3 1x1 with residual=.  bottleneck_row's operands and
+    float64 reference (with the dilation); r1 and r2 pass through memory as fp32, which the propagated cond covers as it does
+    the fused unit's registers."""
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        assert not ops.bottleneck_ok(C, dil, H, W) and not ops.conv2d_tail_ok(C, dil, H, W)
+        assert ops.conv_plan((H, W), 1, C, C, bias=True, lazy='bn')[:2] == ('conv1x1', True)
+        assert ops.conv_plan((H, W), 3, C, C, dilation=dil, bias=True)[:2] == ('conv2d_lds', False)
+        assert ops.conv_plan((H, W), 1, C, C, bias=True, residual=True)[:2] == ('conv1x1', False)
+        assert ops.pack_conv1x1((name, 'probe1'), np.zeros((C, C), np.float32), C, dev).kind == ''
+        assert ops.pack_conv2d_lds((name, 'probe2'), np.zeros((3, 3, C, C), np.float32), dev).kind == 'lds'
+        pend = _pending((G, H, W, C), 21, 22, regime, dev, True)
+        x = pend.raw.cpu()
+        ws = [_weights(s, 23 + i) for i, s in enumerate(((1, 1, C, C), (3, 3, C, C), (1, 1, C, C)))]
+        bs = [torch.randn(C, generator=_gen(26 + i)) * 0.1 * _SCALE[regime] for i in range(3)]
+        r1 = ops.conv(pend.raw, (name, 0), ws[0].numpy(), bias=bs[0].to(dev), relu=True, groups=G, in_params=pend.params,
+                      in_relu=True)
+        r2 = ops.conv(r1, (name, 1), ws[1].numpy(), dilation=dil, bias=bs[1].to(dev), relu=True, groups=G)
+        y, st = ops.conv(r2, (name, 2), ws[2].numpy(), bias=bs[2].to(dev), residual=pend.raw, want_stats=True, groups=G)
+
+        def branch(xn, w1, b1, w2, b2, w3, b3):
+            r = _relu(T.conv(xn, w1, 1, 'SAME', bias=b1))
+            r = _relu(T.conv(r, w2, 1, 'SAME', dil, bias=b2))
+            return T.conv(r, w3, 1, 'SAME', bias=b3)
+        a = (pend, ws[0], bs[0], ws[1], bs[1], ws[2], bs[2])
+        want = N.ref64(branch, *a) + x.double()
+        return [Case(y.cpu(), want, _cond(regime)(branch, *a), _residual_floor(want, *ws, bar=FP32_MFMA), stats=(st, y, C))]
+    return Row(name, 'residual_unit', None, FP32_MFMA, run, FP32, True, 'residual_unit_row')
 
 
 def siblings_row(name, G, D, H, W, cin, bar, cfg=None, lazy=None):
@@ -268,13 +328,14 @@ def siblings_row(name, G, D, H, W, cin, bar, cfg=None, lazy=None):
             def op(*a, stride=stride):
                 xs, w = a[:-1], a[-1]
                 return T.conv(xs[0] if len(xs) == 1 else xs[0] + xs[1], w, stride, 'SAME')
-            cnd = _winograd_cond(terms[0], w) if (stride == 1 and bar is FP32_MFMA) else _cond(regime)(op, *terms, w)
+            cnd = _winograd_cond_terms(terms, w, regime) if (stride == 1 and bar is FP32_MFMA) else \
+                _cond(regime)(op, *terms, w)
             out.append(Case(yy.cpu(), N.ref64(op, *terms, w), cnd, N.floor_of(w, bar), stats=(s, yy, c)))
         return out
-    return Row(name, 'xp_siblings', 'xb' if bar is SPLIT else None, bar, run, cfg or {}, bool(lazy))
+    return Row(name, 'xp_siblings', 'xb' if bar is SPLIT else None, bar, run, cfg or {}, bool(lazy), 'siblings_row')
 
 
-def plane_row(name, G, D, H, W, cv, cc, bar):
+def plane_row(name, G, D, H, W, cv, cc, bar, cfg=None):
     """conv_split: the D-varying channels on the x-pair kernel, the D-constant ones as a depth-plane bias (2-D convolution)."""
     def run(dev, regime):
         from atvsnet_amd import ops
@@ -284,14 +345,19 @@ def plane_row(name, G, D, H, W, cv, cc, bar):
         w = _weights((3, 3, 3, cc + cv, 8), 43)
         plan = ops.conv_plan((D, H, W), 3, cv, 8, plane_bias=True)
         assert plan.family == 'xp'
+        assert ops.pack_conv_xp((name, 'probe'), w[..., cc:, :].numpy(), dev).kind == ('xb' if bar is SPLIT else 'xw')
         sv = ops.SplitVolume(_dev(var, dev), _dev(const, dev), cmap)
         y, st = ops.conv_split(sv, name, w.numpy(), want_stats=True)
 
         def op(var, const, w):
             dense = torch.cat([const[:, None].expand(-1, D, -1, -1, -1), var], -1)
             return T.conv(dense, w, 1, 'SAME')
-        return [Case(y.cpu(), N.ref64(op, var, const, w), N.cond(op, var, const, w), N.floor_of(w, bar), stats=(st, y, 8))]
-    return Row(name, 'xp_plane_bias', 'xb', bar, run, {})
+        cnd = N.cond(op, var, const, w)
+        if bar is FP32_MFMA:
+            # conv_xw.hip's Winograd products for the D-varying channels (_winograd_cond), sum |x||w| for the plane bias
+            cnd = _winograd_cond(var, w[..., cc:, :]) + N.cond(op, torch.zeros_like(var), const, w)
+        return [Case(y.cpu(), N.ref64(op, var, const, w), cnd, N.floor_of(w, bar), stats=(st, y, 8))]
+    return Row(name, 'xp_plane_bias', 'xb' if bar is SPLIT else None, bar, run, cfg or {}, False, 'plane_row')
 
 
 def into_plane_row(name, G, D, H, W, cv, cc, pieces, plane=2):
@@ -325,7 +391,7 @@ def into_plane_row(name, G, D, H, W, cv, cc, pieces, plane=2):
             return T.conv(dense, w, 1, 'SAME')
         return [Case(got.cpu(), N.ref64(op, var, const, w), N.cond(op, var, const, w), N.floor_of(w, SPLIT),
                      stats=(st, got, 8))]
-    return Row(name, 'xp_into_plane', 'xb', SPLIT, run, {})
+    return Row(name, 'xp_into_plane', 'xb', SPLIT, run, {}, False, 'into_plane_row')
 
 
 def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cfg=None):
@@ -333,8 +399,17 @@ def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cf
         from atvsnet_amd import ops
         w = _weights((3, 3, 3, cout, cin), 52)
         lib = ops._lib.lib()
+        fold = (1,)
         if family == 'deconv_halves':
             assert not ops.deconv_up_ok(cin, cout) and cout == 32 and bool(lib.atvs_deconv_up_b_supported(cin, 16))
+        elif family in ('deconv_tiled', 'deconv_gather'):
+            # the fp32 64 -> 32 layer (no deconv_up form, and deconv_halves is the split path's): W >= 12 runs all parity classes
+            # of a class group from one staged tile of conv_tiled (its statistics folded by the classes per launch), a narrower
+            # map one gather launch per class
+            assert not ops.deconv_up_ok(cin, cout) and bar is FP32_MFMA and cout % 4 == 0 and cout <= 64
+            assert (W >= 12) == (family == 'deconv_tiled')
+            if family == 'deconv_tiled':
+                fold = (min(8, 128 // cout),)
         else:
             assert ops.deconv_up_ok(cin, cout) and bool(lib.atvs_deconv_up_b_supported(cin, cout))
         assert ops.split_on('upb') == (bar is SPLIT)
@@ -354,8 +429,8 @@ def deconv_row(name, family, split, bar, G, D, H, W, cin, cout, summed=False, cf
             s = xs[0] if len(xs) == 1 else xs[0] + xs[1]
             return _relu(T.conv3d_transpose_same(s, w))
         return [Case(y.cpu(), N.ref64(op, *terms, w), _cond(regime)(op, *terms, w), N.floor_of(w.permute(0, 1, 2, 4, 3), bar),
-                     stats=(st, y, cout))]
-    return Row(name, family, split, bar, run, cfg or {}, summed)
+                     stats=(st, y, cout), fold=fold)]
+    return Row(name, family, split, bar, run, cfg or {}, summed, 'deconv_row')
 
 
 def aanet_row(name, nv, D, H, W):
@@ -372,7 +447,40 @@ def aanet_row(name, nv, D, H, W):
         # softmax is identically 1 and the row checks the pass-through of X alone
         cnd, spread = N.aanet_cond(X, ws, wu)
         return [Case(y.cpu(), want, cnd, 2.0 * N.floor_of(torch.cat([ws, wu], -1), SPLIT) * spread)]
-    return Row(name, 'aanet_b', 'aanet_b', SPLIT, run, {})
+    return Row(name, 'aanet_b', 'aanet_b', SPLIT, run, {}, False, 'aanet_row')
+
+
+def aanet_fp32_row(name, nv, D, H, W, parts=None):
+    """The AANet module as the fp32 path runs it (cnn_wrapper/network.py attention_aggregation): the shared | unique 8 -> 16
+    score convolution of every view on conv_c16, then ops.aanet_combine (csrc/aanet.hip).  atvs_aanet_combine launches
+    aanet_combine_kernel<nv> (every operand read once, kept in registers) for nv <= 8 and aanet_combine_generic_kernel (the
+    operands re-read per pass) for 9 <= nv <= 16; neither the ABI nor a predicate says which ran, so the rows' view counts
+    1, 2, 5, 8 | 16 straddle that switch statement.  parts: the same views split over ranks, the three ops.aanet_partial
+    stages reduced as the all-reduces would (SUM, MAX, SUM) and ops.divide, held to the same bound."""
+    def run(dev, regime):
+        from atvsnet_amd import ops
+        X = _input((nv, D, H, W, 8), 61, regime)
+        ws, wu = _weights((3, 3, 3, 8, 8), 62), _weights((3, 3, 3, 8, 8), 63)
+        w16 = torch.cat([ws, wu], -1)
+        xs = [_dev(X[n], dev) for n in range(nv)]
+        assert not ops.aanet_fused_ok(xs)
+        assert ops.conv_plan((D, H, W), 3, 8, 16)[:2] == ('c16', False)
+        srs = [ops.conv(x, name, w16.numpy(), relu=True) for x in xs]
+        y = ops.aanet_combine(srs, xs)
+        Wd = {'a/attention_activation/weight_unique': wu.double(), 'a/attention_activation/weight_shared': ws.double()}
+        want = nets.attention_aggregation(X.double().permute(1, 2, 3, 4, 0).unsqueeze(0), Wd, 'a')[0]
+        cnd, spread = N.aanet_cond(X, ws, wu)
+        floor = 2.0 * N.floor_of(w16, FP32_MFMA) * spread
+        out = [Case(y.cpu(), want, cnd, floor)]
+        if parts:
+            assert sum(parts) == nv
+            sl = [slice(sum(parts[:i]), sum(parts[:i + 1])) for i in range(len(parts))]
+            ssum = torch.stack([ops.aanet_partial(srs[s], xs[s], 0) for s in sl], 0).sum(0)
+            umax = torch.stack([ops.aanet_partial(srs[s], xs[s], 1, ssum=ssum) for s in sl], 0).max(0).values
+            acc = torch.stack([ops.aanet_partial(srs[s], xs[s], 2, ssum=ssum, umax=umax) for s in sl], 0).sum(0)
+            out.append(Case(ops.divide(acc[1].contiguous(), acc[0].contiguous()).cpu(), want, cnd, floor))
+        return out
+    return Row(name, 'aanet_combine', None, FP32_MFMA, run, FP32, False, 'aanet_fp32_row')
 
 
 def stem_row(name, G, D, H, W, cin):
@@ -386,7 +494,7 @@ def stem_row(name, G, D, H, W, cin):
         def op(x, w):
             return T.conv(x, w, 1, 'SAME')
         return [Case(y.cpu(), N.ref64(op, x, w), N.cond(op, x, w), N.floor_of(w, FP32_MFMA), stats=(st, y, 8))]
-    return Row(name, 'stem', None, FP32_MFMA, run, {})
+    return Row(name, 'stem', None, FP32_MFMA, run, {}, False, 'stem_row')
 
 
 def refine_stems_row(name, G, D, H, W):
@@ -404,7 +512,7 @@ def refine_stems_row(name, G, D, H, W):
         a = (geo, prob, hull, wg, wp, wh)
         return [Case(buf[..., 8:].cpu(), N.ref64(op, *a), N.cond(op, *a), N.floor_of(wg, FP32_MFMA),
                      stats=(st, buf[..., 8:], 24))]
-    return Row(name, 'refine_stems', None, FP32_MFMA, run, {})
+    return Row(name, 'refine_stems', None, FP32_MFMA, run, {}, False, 'refine_stems_row')
 
 
 def head_row(name, G, D, H, W, summed=False):
@@ -426,7 +534,7 @@ def head_row(name, G, D, H, W, summed=False):
             xs, w = a[:-1], a[-1]
             return T.conv(xs[0] if len(xs) == 1 else xs[0] + xs[1], w, 1, 'SAME')
         return [Case(y.cpu(), N.ref64(op, *terms, w), _cond(regime)(op, *terms, w), N.floor_of(w, FP32_MFMA))]
-    return Row(name, '8to1', None, FP32_MFMA, run, {}, summed)
+    return Row(name, '8to1', None, FP32_MFMA, run, {}, summed, 'head_row')
 
 
 ROWS = [
@@ -488,6 +596,33 @@ ROWS = [
     conv_row('fp32_xw', 'xp', None, FP32_MFMA, 2, (2, 5, 24), 24, 8, cfg=FP32, winograd=True),
     siblings_row('fp32_xw_siblings', 2, 3, 6, 24, 16, FP32_MFMA, cfg=FP32),
     deconv_row('fp32_deconv_up', 'deconv_up', None, FP32_MFMA, 2, 3, 4, 6, 16, 8, cfg=FP32),
+    # the fp32 twins of the split rows above, at their shapes.  Where the fp32 plan sends a shape to another family than its
+    # split twin's (the tiny map and the strided conv2 go to gather: their conv2d_lds / conv2d_b_s2 forms are split-operand
+    # only), the row asserts the family the fp32 path launches
+    conv_row('fp32_conv1x1_on_load', 'conv1x1', None, FP32_MFMA, 1, (7, 9), 32, 128, k=1, lazy='bn', cfg=FP32),
+    conv_row('fp32_conv1x1_on_load_G3', 'conv1x1', None, FP32_MFMA, 3, (5, 13), 64, 32, k=1, lazy='bn', cfg=FP32),
+    conv_row('fp32_conv1x1_residual', 'conv1x1', None, FP32_MFMA, 2, (8, 16), 32, 32, k=1, relu=False, residual=True,
+             slice_out=False, cfg=FP32),          # the kernel takes a residual only with the output at channel 0
+    conv_row('fp32_conv2d_lds_dil2', 'conv2d_lds', None, FP32_MFMA, 1, (10, 18), 128, 128, dilation=2, cfg=FP32),
+    conv_row('fp32_conv2d_lds_ragged', 'conv2d_lds', None, FP32_MFMA, 1, (9, 37), 64, 64, cfg=FP32),
+    conv_row('fp32_tiny_gather', 'gather', None, FP32_MFMA, 2, (3, 5), 32, 32, cfg=FP32),
+    conv_row('fp32_stride2_gather', 'gather', None, FP32_MFMA, 1, (16, 32), 32, 64, stride=2, explicit_pad=((1, 1), (1, 1)),
+             slice_out=False, cfg=FP32),
+    conv_row('fp32_c16_cin8_16', 'c16', None, FP32_MFMA, 1, (2, 5, 12), 8, 16, cfg=FP32),
+    conv_row('fp32_c16_G3_D1', 'c16', None, FP32_MFMA, 3, (1, 7, 13), 16, 16, cfg=FP32),
+    deconv_row('fp32_deconv_up_32_16_G3', 'deconv_up', None, FP32_MFMA, 3, 2, 3, 5, 32, 16, cfg=FP32),
+    deconv_row('fp32_deconv_64_32', 'deconv_gather', None, FP32_MFMA, 1, 2, 3, 4, 64, 32, cfg=FP32),
+    deconv_row('fp32_deconv_64_32_W12', 'deconv_tiled', None, FP32_MFMA, 1, 2, 3, 12, 64, 32, cfg=FP32),
+    plane_row('fp32_xw_plane_bias', 2, 3, 5, 26, 8, 3, FP32_MFMA, cfg=FP32),
+    siblings_row('fp32_xw_siblings_norm', 2, 3, 6, 24, 16, FP32_MFMA, cfg=FP32, lazy='bn'),
+    siblings_row('fp32_xw_siblings_sum', 2, 3, 5, 25, 8, FP32_MFMA, cfg=FP32, lazy='sum'),
+    residual_unit_row('fp32_unit_G2', 2, 8, 16, 32, 1),
+    residual_unit_row('fp32_unit_dil2', 1, 8, 16, 128, 2),
+    aanet_fp32_row('fp32_aanet_nv1', 1, 2, 5, 12),
+    aanet_fp32_row('fp32_aanet_nv2', 2, 3, 4, 13),
+    aanet_fp32_row('fp32_aanet_nv5', 5, 2, 3, 12, parts=(2, 3)),
+    aanet_fp32_row('fp32_aanet_nv8', 8, 2, 3, 14, parts=(4, 4)),
+    aanet_fp32_row('fp32_aanet_nv16', 16, 2, 3, 13),
     stem_row('stem_cin2_G3', 3, 3, 5, 12, 2),
     stem_row('stem_cin1', 1, 2, 9, 33, 1),
     refine_stems_row('refine_stems_G2', 2, 3, 9, 35),
@@ -516,7 +651,22 @@ def test_elementwise_against_float64(cuda, row):
                 if c.kept is not None:
                     N.assert_bits_kept(*c.kept)
                 if c.stats is not None:
-                    _check_stats(c.stats[0], c.stats[1], c.stats[2], what)
+                    _check_stats(c.stats[0], c.stats[1], c.stats[2], what, c.fold)
+    ops.clear_pack_cache()
+
+
+def test_fp32_conv2d_lds_refuses_a_lazy_input(cuda):
+    """The fp32 twin of c2b_on_load, (8, 20), 32 -> 64: conv2d_lds.hip has no on-load form (conv2d_b.hip's is split-operand
+    only), so the plan keeps the family and says so, norm_on_load_2d_ok sends the network to a bn_apply pass, and ops.conv
+    refuses the pending input instead of convolving the raw one."""
+    from atvsnet_amd import ops
+    with ops.configure(clear_pack_cache=True, **FP32):
+        pend = _pending((2, 8, 20, 32), 1, 4, 'randn', cuda, True)
+        assert ops.conv_plan((8, 20), 3, 32, 64, bias=True, lazy='bn')[:2] == ('conv2d_lds', False)
+        assert not ops.norm_on_load_2d_ok(pend, 3, 64)
+        with pytest.raises(ValueError, match='no normalise-on-load form'):
+            ops.conv(pend.raw, 'fp32_conv2d_lds_on_load', _weights((3, 3, 32, 64), 2).numpy(), groups=2,
+                     in_params=pend.params, in_relu=True)
     ops.clear_pack_cache()
 
 

@@ -114,6 +114,26 @@ def test_aanet_bound_passes_the_split_and_fails_a_dropped_tap(nv):
             N.assert_elementwise(N.aanet64(X, ws, wu, conv=conv), want, cnd, N.SPLIT.rel, floor, 'aanet ' + name)
 
 
+@pytest.mark.parametrize('nv,shape', [(5, (2, 3, 12)), (8, (2, 3, 14)), (16, (2, 3, 13))])
+def test_the_fp32_aanet_rows_near_max_figure_is_the_rounding_of_the_shared_sum(nv, shape):
+    """The near-6e4 regime of the fp32_aanet rows (tests/test_gpu_split_precision.py, the same operands): float64 scores with
+    the one add U_n = (R_n - S_n) + S_sum rounded to fp32, as csrc/aanet.hip and the reference form it, give the err / cond the
+    rows measure on the GPU (2.8e-5, 2.8e-5, 2.3e-5: tests/numerics.py) and stay inside NEAR_MAX * FP32_MFMA.rel; the softmax of
+    R_n - S_n alone, rounded the same way, is four orders below -- the figure is that rounding at the ulp of S_sum, not a kernel's."""
+    import test_gpu_split_precision as S
+    X = S._input((nv,) + shape + (8,), 61, 'near_max').double()
+    ws, wu = S._weights((3, 3, 3, 8, 8), 62), S._weights((3, 3, 3, 8, 8), 63)
+    want = N.aanet64(X, ws, wu)
+    cnd, _ = N.aanet_cond(X, ws, wu)
+    s, r = (T.conv(X, w.double(), 1, 'SAME').clamp(min=0) for w in (ws, wu))
+    u32 = ((r - s).float() + s.sum(0, keepdim=True).float()).double()
+    with_sum = float((((torch.softmax(u32, 0) * X).sum(0) - want).abs() / cnd).max())
+    alone = float((((torch.softmax((r - s).float().double(), 0) * X).sum(0) - want).abs() / cnd).max())
+    print('aanet nv %d near 6e4: U rounded to fp32 err/cond %.2e, R - S alone %.2e' % (nv, with_sum, alone))
+    assert 2.0e-5 <= with_sum <= N.NEAR_MAX * N.FP32_MFMA.rel
+    assert alone <= 1e-7
+
+
 def test_the_bar_names_the_worst_element():
     want = torch.zeros(2, 3, 4, dtype=torch.float64)
     cnd = torch.ones_like(want)
@@ -161,4 +181,55 @@ def test_the_gpu_table_covers_every_split_family_and_the_fp32_forms():
     assert len({r.name for r in S.ROWS}) == len(S.ROWS)
     # the rows whose input is formed on load, which run the offset regime too
     assert {r.name for r in S.ROWS if r.lazy} == {'c16b_sum', 'c3b_norm', 's2b_norm', 'c2b_on_load', 'c1b_on_load', 'btl_G2',
-                                                  'upb_sum', '8to1_sum', 'xb_siblings_norm', 'xb_siblings_sum'}
+                                                  'upb_sum', '8to1_sum', 'xb_siblings_norm', 'xb_siblings_sum',
+                                                  'fp32_conv1x1_on_load', 'fp32_conv1x1_on_load_G3', 'fp32_xw_siblings_norm',
+                                                  'fp32_xw_siblings_sum', 'fp32_unit_G2', 'fp32_unit_dil2'}
+
+
+# the convolution entry points conv_dispatch.json names beside ops.conv -> the maker of their rows
+ENTRY_POINT_MAKERS = {'conv_siblings': 'siblings_row', 'conv3d_transpose_s2': 'deconv_row', 'conv3d_8to1': 'head_row',
+                      'aanet_combine': 'aanet_fp32_row', 'refine_stems': 'refine_stems_row'}
+PASSES = ('bn_apply', 'bn_add')          # the materialising passes of the table: no convolution (tests/test_gpu_batch_norm.py)
+NO_SPLIT_FORM = ('gather', 'tiled', 'stem', '8to1', 'refine_stems')       # one kernel, whatever split16 says
+
+
+def fp32_rows_of(event, rows):
+    """The rows of the GPU table that hold what one event of a split16=0 dispatch case launches: 'conv:<family>[+]' -> the
+    ops.conv rows of that family whose input is (+) / is not formed on load, a named entry point -> the rows of its maker; of
+    those, the rows that run under cfg=FP32 or whose family has no split-operand form."""
+    if event.startswith('conv:'):
+        fam, on_load = event[5:].rstrip('+'), event.endswith('+')
+        hits = [r for r in rows if r.maker in ('conv_row', 'stem_row') and r.family == fam and r.lazy == on_load]
+    else:
+        hits = [r for r in rows if r.maker == ENTRY_POINT_MAKERS[event]]
+    return [r for r in hits if r.bar is N.FP32_MFMA and (r.cfg.get('split16') is False or r.family in NO_SPLIT_FORM)]
+
+
+def _fp32_events():
+    import json
+    import test_conv_dispatch as CD
+    table = json.load(open(CD.GOLDEN))
+    cases = [k for k in table if k.endswith('/split16=0')]
+    assert len(cases) == 4
+    return sorted({e for k in cases for e in table[k].split()} - set(PASSES))
+
+
+def test_the_fp32_rows_cover_what_the_fp32_path_launches():
+    """Every convolution event of the four split16=0 cases of tests/golden/conv_dispatch.json (both pipelines, both sizes)
+    has a row of the GPU table that runs the fp32 form it names: a family the fp32 dispatch starts to use fails here until
+    it has one."""
+    import test_gpu_split_precision as S
+    events = _fp32_events()
+    assert {'conv:conv1x1+', 'conv:conv2d_lds', 'conv:c16', 'conv:tiled', 'conv:gather', 'conv:xp', 'aanet_combine'} <= set(events)
+    for e in events:
+        assert e.startswith('conv:') or e in ENTRY_POINT_MAKERS, 'conv_dispatch.json names %r: map it to its row maker' % e
+        assert fp32_rows_of(e, S.ROWS), 'no fp32 row of tests/test_gpu_split_precision.py holds %r' % e
+
+
+@pytest.mark.parametrize('event,names', [('conv:conv1x1+', ('fp32_conv1x1_on_load', 'fp32_conv1x1_on_load_G3')),
+                                         ('aanet_combine', tuple('fp32_aanet_nv%d' % n for n in (1, 2, 5, 8, 16)))])
+def test_the_coverage_check_sees_a_deleted_row(event, names):
+    """Without its rows an event has nothing left: the check above would fail."""
+    import test_gpu_split_precision as S
+    assert {r.name for r in fp32_rows_of(event, S.ROWS)} == set(names)
+    assert not fp32_rows_of(event, [r for r in S.ROWS if r.name not in names])
