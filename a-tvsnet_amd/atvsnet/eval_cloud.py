@@ -4,7 +4,8 @@ distance tolerances.
     python -m atvsnet_amd.atvsnet.eval_cloud --recon final3d_model.ply --gt scan1.ply [scan2.ply ...]
            [--tolerances 0.01,0.02,0.05,0.1,0.2,0.5] [--radius R] [--gt_transform T.txt] [--out cloud_eval.json] [--distances PREFIX]
            [--register [--with_scale] [--register_distances a,b,c] [--register_voxel v]
-            [--register_icp plane [--register_normals target [--register_normal_k K] [--register_normal_radius R]]]]
+            [--register_icp plane [--register_normals target [--register_normal_k K] [--register_normal_radius R]]]
+            [--register_global [--global_voxel V] [--global_hypotheses H] [--global_seed S] [--global_tau T] [--global_no_mutual]]]
            [--init_transform T.txt | --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
            [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
             [--vis_window 1] [--free_space_margin 0]]
@@ -31,7 +32,9 @@ exactly: per point the smallest float32 squared distance (dx*dx + dy*dy) + dz*dz
 A reconstruction in another frame than the ground truth's (a COLMAP model: rotation, translation and scale are free) scores 0 as
 it stands.  --register aligns it first (atvsnet/register_cloud.py: voxel down-sampling, trimmed point-to-point ICP in stages, on the
 device), starting from --init_transform (a 4x4 matrix applied to the RECONSTRUCTION) or --init_cameras (the similarity between
-the camera centres of two COLMAP models of the same images); --save_transform keeps the matrix found.  --register_icp plane
+the camera centres of two COLMAP models of the same images), or, with --register_global, from a start found from the clouds alone
+(register_cloud.global_init: FPFH descriptors, exact matching in feature space and RANSAC over triples of matches, on the device --
+for a cloud that comes without cameras in the ground truth's frame); --save_transform keeps the matrix found.  --register_icp plane
 registers by point-to-plane ICP over the normals the reconstruction's PLY carries (depth_fusion --normals depth), or, with
 --register_normals target, over the ground truth's, estimated on the GPU (the reconstruction then needs none).  --voxel scores the
 voxel-down-sampled clouds (both sides), so that point density does not weight the shares.  Without these options the result is
@@ -121,7 +124,7 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
              register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None,
              scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0,
              register_icp='point', recon_normals=None, register_normals='source', register_normal_k=None,
-             register_normal_radius=None):
+             register_normal_radius=None, register_global=False, global_options=None):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
     distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
@@ -133,7 +136,9 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     point-to-plane ICP over recon_normals (M,3), the reconstruction's own normals, one per row of `recon`; with
     register_normals = 'target' over the ground truth's instead, estimated on the device from register_normal_k neighbours
     within register_normal_radius (register_cloud.register's normal_side, normal_k, normal_radius and their defaults), and
-    recon_normals is not used.  Without register,
+    recon_normals is not used.  register_global: the start is found from the clouds alone (register_cloud.global_init: FPFH
+    matching and RANSAC on the device; global_options: its keyword arguments) instead of init_transform, which is then an argument
+    error; `registration` gains `global`.  Without register,
     init_transform is recorded as `init_transform`.  voxel: both clouds are scored after ops.cloud_voxel_downsample with this edge (after the alignment); the
     result gains `voxel`, `n_recon_full`, `n_gt_full`, and the distances refer to the down-sampled clouds.
 
@@ -164,6 +169,12 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
         raise ValueError("register_normals='target' runs over the ground truth's normals: recon_normals is not used")
     if (register_icp == 'plane' and not target) != (recon_normals is not None):
         raise ValueError("register_icp='plane' and recon_normals go together: the reconstruction's normals, one per point")
+    if (register_global or global_options is not None) and not register:
+        raise ValueError('register_global and global_options need register=True')
+    if global_options is not None and not register_global:
+        raise ValueError('global_options need register_global=True')
+    if register_global and init_transform is not None:
+        raise ValueError('register_global finds the starting matrix itself: init_transform is not used')
     plane = {'icp': 'plane', 'normals': recon_normals} if register_icp == 'plane' else {}
     if target:
         plane = {'icp': 'plane', 'normal_side': 'target'}
@@ -211,8 +222,10 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
         if register:
             from . import register_cloud
             dist = [4.0 * max(tol), 2.0 * max(tol), max(tol)] if register_distances is None else list(register_distances)
-            extra['registration'] = register_cloud.register(r, g, init=init, with_scale=with_scale, distances=dist,
-                                                            voxel=register_voxel, device=dev, **plane)
+            if register_global:
+                plane = dict(plane, global_options=global_options)
+            extra['registration'] = register_cloud.register(r, g, init='global' if register_global else init, with_scale=with_scale,
+                                                            distances=dist, voxel=register_voxel, device=dev, **plane)
             r = ops.cloud_transform(r, extra['registration']['matrix'])
         elif init is not None:
             extra['init_transform'] = init.tolist()
@@ -317,15 +330,52 @@ def write_json(path, result):
         f.write('\n')
 
 
+GLOBAL_FLAGS = {'global_voxel': 'feature_voxel', 'global_hypotheses': 'hypotheses', 'global_seed': 'seed', 'global_tau': 'tau',
+                'global_no_mutual': 'mutual'}                      # command-line option -> register_cloud.global_init's argument
+
+
+def add_global_arguments(parser):
+    """--register_global and its options (eval_pointcloud's command line has the same)."""
+    parser.add_argument('--register_global', action='store_true',
+                        help='--register: find the starting matrix from the clouds alone (FPFH descriptors matched in feature space, '
+                             'RANSAC over triples of matches, on the GPU) instead of --init_transform / --init_cameras')
+    parser.add_argument('--global_voxel', type=float, default=None, metavar='V',
+                        help='--register_global: voxel edge of the clouds the descriptors are computed on (default: twice the '
+                             'registration\'s voxel; with --with_scale 1/64 of each cloud\'s bounding-box diagonal; defaults, not '
+                             'measurements)')
+    parser.add_argument('--global_hypotheses', type=int, default=None, metavar='H',
+                        help='--register_global: triples of matches tried (default 65536; a default, not a measurement)')
+    parser.add_argument('--global_seed', type=int, default=None, metavar='S',
+                        help='--register_global: seed of the triples (default 0): the same seed gives the same matrix')
+    parser.add_argument('--global_tau', type=float, default=None, metavar='T',
+                        help='--register_global: a match agrees with a hypothesis within this distance, in the ground truth\'s units '
+                             '(default: 1.5 feature voxels; a default, not a measurement)')
+    parser.add_argument('--global_no_mutual', action='store_true',
+                        help='--register_global: keep every source-to-target match, not only those the target matches back')
+
+
 def register_options(parser, args):
     """The registration options of a parsed command line as evaluate_files' keyword arguments ({} when none is given);
     contradictory ones are argument errors."""
     if args.init_transform and args.init_cameras:
         parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
     for name in ('with_scale', 'register_distances', 'register_voxel', 'register_icp', 'register_normals', 'register_normal_k',
-                 'register_normal_radius'):
+                 'register_normal_radius', 'register_global'):
         if getattr(args, name) not in (None, False) and not args.register:
             parser.error('--%s needs --register' % name)
+    for name in GLOBAL_FLAGS:
+        if getattr(args, name) not in (None, False) and not args.register_global:
+            parser.error('--%s needs --register_global' % name)
+    if args.register_global and (args.init_transform or args.init_cameras):
+        parser.error('--register_global finds the initial matrix from the clouds alone: give it, --init_transform or --init_cameras')
+    if args.global_voxel is not None and not (args.global_voxel > 0.0 and np.isfinite(args.global_voxel)):
+        parser.error('--global_voxel must be positive and finite')
+    if args.global_tau is not None and not (args.global_tau > 0.0 and np.isfinite(args.global_tau)):
+        parser.error('--global_tau must be positive and finite')
+    if args.global_hypotheses is not None and not 1 <= args.global_hypotheses <= 1 << 24:
+        parser.error('--global_hypotheses must be in 1..2^24')
+    if args.global_seed is not None and args.global_seed < 0:
+        parser.error('--global_seed must be >= 0')
     if args.save_transform and not (args.register or args.init_transform or args.init_cameras):
         parser.error('--save_transform needs --register, --init_transform or --init_cameras: no matrix is applied otherwise')
     if args.voxel is not None and not args.voxel > 0.0:
@@ -368,6 +418,13 @@ def register_options(parser, args):
             if not with_normals:
                 parser.error('--register_icp plane: ' + NO_NORMALS % args.recon)
             options['register_icp'] = 'plane'
+        if args.register_global:
+            options['register_global'] = True
+            chosen = {key: getattr(args, name) for name, key in GLOBAL_FLAGS.items() if getattr(args, name) not in (None, False)}
+            if 'mutual' in chosen:
+                chosen['mutual'] = False
+            if chosen:
+                options['global_options'] = chosen
     if args.init_transform:
         options['init_transform_path'] = args.init_transform
     if args.init_cameras:
@@ -443,6 +500,7 @@ def make_parser():
     parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
                         help='--register_normals target: their search radius (default: 4 edges of the registration\'s voxel, or twice '
                              'the last distance without one; a default, not a measurement)')
+    add_global_arguments(parser)
     parser.add_argument('--init_transform', default=None, metavar='FILE',
                         help='text file with a 4x4 row-major matrix applied to the RECONSTRUCTION (the start of --register)')
     parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),

@@ -553,6 +553,9 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (not target and ('normal_k' in register or 'normal_radius' in register),
          '--register_normal_k and --register_normal_radius need --register_normals target (normal_k and normal_radius need '
          'normal_side=target)')]
+    global_row = [] if (register or {}).get('global') is None else [
+        (bool(register.get('init_cameras')), '--register_global finds the initial matrix from the clouds alone: give it or '
+                                             '--init_cameras (register global= or init_cameras=)')]
     keep_row = [] if not clean_keep_normals else [
         (not clean, '--clean_keep_normals needs --clean_voxel, --clean_sor or --clean_radius_filter (clean_keep_normals needs clean)'),
         (no_normals, '--clean_keep_normals needs --fuse_normals depth (clean_keep_normals needs fuse_normals normals=depth): there are '
@@ -565,7 +568,7 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (bool(clean) and fuse is None, '--clean_voxel, --clean_sor and --clean_radius_filter need --fuse (clean needs fuse): there is no '
                                        'point cloud to clean'),
         (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')
-    ] + target_row + plane_row + keep_row
+    ] + target_row + plane_row + global_row + keep_row
 
 
 def _check_options(**options):
@@ -594,6 +597,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     With icp='plane' in the dict (fuse_normals normals='depth' only) the registration is point-to-plane over the normals the
     fusion returns (eval_cloud --register_icp plane); with normal_side='target' too (and optionally normal_k, normal_radius) over
     the ground truth's planes instead, its normals estimated on the device: no fuse_normals needed (eval_cloud --register_normals).
+    With global= in the dict ({} or register_cloud.global_init's keyword arguments) the start is found from the clouds alone
+    (eval_cloud --register_global); init_cameras is then refused.
     clean_keep_normals (with clean and fuse_normals normals='depth' only): final3d_model_clean.ply carries the normals of the rows
     that stay (clean_cloud --keep_normals).
     clean (with fuse only): None, or dict(voxel=, sor=(k, ratio, radius), radius_filter=(radius, min_neighbours)), the arguments of
@@ -625,6 +630,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
             for key in ('normal_k', 'normal_radius'):
                 if register.get(key) is not None:
                     register_args['register_' + key] = register[key]
+        if register.get('global') is not None:
+            register_args['register_global'] = True
+            if register['global']:
+                register_args['global_options'] = dict(register['global'])
         if register.get('init_cameras'):
             from . import register_cloud
             init, matched, rms = register_cloud.init_from_cameras(*register['init_cameras'])
@@ -670,6 +679,17 @@ def _target_options(flags):
     return given
 
 
+def _global_options(flags):
+    """The entry `global` of run_eval_pc's register dict from cli's --register_global options: absent without --register_global,
+    else register_cloud.global_init's keyword arguments that were given."""
+    if not getattr(flags, 'register_global', False):
+        return {}
+    given = {key: getattr(flags, option) for option, key in eval_cloud.GLOBAL_FLAGS.items() if getattr(flags, option, None) not in (None, False)}
+    if 'mutual' in given:
+        given['mutual'] = False
+    return {'global': given}
+
+
 def _run_options(flags):
     """run_eval_pc's keyword arguments from a namespace of cli's options (FLAGS, cli's parsed arguments): one it lacks is off."""
     opt = lambda name, default=None: getattr(flags, name, default)          # noqa: E731
@@ -680,7 +700,8 @@ def _run_options(flags):
         fuse_normals=_normal_options(flags),
         map_files=not opt('no_map_files'), gt_ply=opt('gt_ply') or None, clean=opt('clean') or None,
         register=dict(dict(icp='plane') if opt('register_icp') == 'plane' else {}, with_scale=opt('with_scale', False),
-                      init_cameras=opt('init_cameras') or None, **_target_options(flags)) if opt('register') else None,
+                      init_cameras=opt('init_cameras') or None, **dict(_target_options(flags), **_global_options(flags)))
+        if opt('register') else None,
         clean_keep_normals=bool(opt('clean_keep_normals')),
         score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
                         occlusion_tol=opt('map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
@@ -758,6 +779,7 @@ def cli(argv=None):
                         help='--register_normals target: eval_cloud --register_normal_k')
     parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
                         help='--register_normals target: eval_cloud --register_normal_radius')
+    eval_cloud.add_global_arguments(parser)
     parser.add_argument('--score_maps', action='store_true',
                         help='--gt_ply: render the ground truth into the scene\'s cameras and score the depth maps that entered the '
                              'cloud against it (eval_depth: mae, rmse, ..., inlier ratios per map; a point splat, not ETH3D\'s '
@@ -784,6 +806,17 @@ def cli(argv=None):
         parser.error('--register_normal_k must be in 2..32')
     if args.register_normal_radius is not None and not (args.register_normal_radius > 0.0 and np.isfinite(args.register_normal_radius)):
         parser.error('--register_normal_radius must be positive and finite')
+    if args.register_global and not args.register:
+        parser.error('--register_global needs --register')
+    for name in eval_cloud.GLOBAL_FLAGS:
+        if getattr(args, name) not in (None, False) and not args.register_global:
+            parser.error('--%s needs --register_global' % name)
+    if any(v is not None and not (v > 0.0 and np.isfinite(v)) for v in (args.global_voxel, args.global_tau)):
+        parser.error('--global_voxel and --global_tau must be positive and finite')
+    if args.global_hypotheses is not None and not 1 <= args.global_hypotheses <= 1 << 24:
+        parser.error('--global_hypotheses must be in 1..2^24')
+    if args.global_seed is not None and args.global_seed < 0:
+        parser.error('--global_seed must be >= 0')
     if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
                                 or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
         parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')

@@ -14,9 +14,13 @@ closed form of Umeyama / Horn turns them into a 4x4 matrix in float64 (similarit
 pairs to 37 sums instead (ops.cloud_plane_moments; 38 words cross), and a 6x6 or 7x7 solve turns them into an increment of the
 matrix (motion_from_plane_moments).  The planes are the source's (a fused cloud's own normals) or the target's
 (normal_side='target': the ground truth's normals, given or estimated by ops.cloud_knn + ops.cloud_normals, for a reconstruction
-that carries none; ops.cloud_plane_moments_target).  This module imports without a GPU; only `register` needs one.  Not here:
-orienting normals by propagation, a symmetric objective, and a global (feature-based) registration: without cameras or an initial
-matrix the clouds must already be within the first stage's distance of each other.
+that carries none; ops.cloud_plane_moments_target).
+
+Without cameras or a matrix, global_init (register's init='global'; eval_cloud --register_global) finds
+the start from the clouds alone: FPFH descriptors of both down-sampled clouds (ops.cloud_fpfh), matched exactly in feature space
+(ops.cloud_feature_nearest), three-point hypotheses over the matches scored on the device (ops.cloud_ransac), the best few verified
+against the whole down-sampled clouds.  This module imports without a GPU; only `register` and `global_init` need one.  Not here:
+orienting normals by propagation, a symmetric objective, Fast Global Registration and a learned descriptor.
 """
 import numpy as np
 
@@ -173,8 +177,123 @@ def corner_move(T0, T1, corners):
     return float(np.sqrt((d * d).sum(axis=1)).max())
 
 
+def _pair_of(value, name):
+    """One positive number for both clouds, or (source's, target's) -> a tuple of two floats."""
+    pair = tuple(float(v) for v in value) if np.ndim(value) else (float(value), float(value))
+    if len(pair) != 2 or any(not (v > 0.0 and np.isfinite(v)) for v in pair):
+        raise ValueError('%s: expected a positive number or (source, target), got %r' % (name, value))
+    return pair
+
+
+def global_init(recon, gt, with_scale=False, voxel=None, feature_voxel=None, normal_k=16, feature_k=32, feature_radius=None, tau=None,
+                hypotheses=65536, seed=0, mutual=True, edge_ratio=0.9, best=4, device=None):
+    """A starting matrix for `register` from the clouds alone: recon (M,3) and gt (N,3) (host arrays or device tensors, float32),
+    however far apart, -> dict.  On the device, in this order:
+
+      1  both clouds are thinned by ops.cloud_voxel_downsample to feature_voxel (a number, or (source's, target's)); None: twice
+         `voxel`, the registration's; with_scale: 1/64 of each cloud's OWN bounding-box diagonal (ops.cloud_bounds), since a
+         length means nothing across two clouds of unknown scale -- which presumes that both cover about the same extent;
+      2  per cloud one ops.cloud_grid of feature_radius (None: 5 feature voxels), ops.cloud_knn in itself, and unoriented normals
+         from the first normal_k neighbours (ops.cloud_normals, self_counts=True);
+      3  FPFH over the first feature_k neighbours (ops.cloud_fpfh);
+      4  every source descriptor finds its nearest target descriptor (ops.cloud_feature_nearest); mutual: the pairs whose target
+         finds that source back are kept, unless fewer than a third survive (then all are kept, as Open3D does);
+      5  `hypotheses` triples of matches drawn by numpy.random.Generator(PCG64(seed)), on the host;
+      6  ops.cloud_ransac: the `best` hypotheses by the number of matches within tau (None: 1.5 of the target's feature voxels; in
+         the target's units), pruned by edge_ratio;
+      7  each of them moves the whole down-sampled source (ops.cloud_transform), which is searched in a grid of radius tau over
+         the down-sampled target (ops.cloud_nearest, ops.cloud_counts): its fitness is the share of source points within tau;
+      8  the highest fitness wins, RANSAC's order on ties.
+
+    -> matrix (4x4 nested lists: moves recon towards gt), fitness, scale, candidates [{index, count, sum, fitness}], n_recon /
+    n_gt (points after step 1), n_recon_normals / n_gt_normals (usable normals), n_recon_features / n_gt_features (descriptors
+    that are not zero), n_matches, n_mutual (None without mutual), mutual_used, n_valid_hypotheses, seed, and every parameter as
+    it was used (feature_voxel, feature_radius: pairs).  ValueError naming the step when fewer than 3 matches remain or no
+    hypothesis is valid.  Every default is a default, not a measurement."""
+    import torch
+    from .. import ops
+    if voxel is None and feature_voxel is None and not with_scale:
+        raise ValueError('global_init: give voxel (the registration\'s) or feature_voxel')
+    for value, name, lo, hi in ((normal_k, 'normal_k', 2, 32), (feature_k, 'feature_k', 1, 32), (hypotheses, 'hypotheses', 1, 1 << 24),
+                                (best, 'best', 1, 8), (seed, 'seed', 0, (1 << 63) - 1)):
+        if isinstance(value, bool) or not isinstance(value, (int, np.integer)) or not lo <= int(value) <= hi:
+            raise ValueError('%s: expected an integer in %d..%d, got %r' % (name, lo, hi, value))
+    if not 0.0 < float(edge_ratio) <= 1.0:
+        raise ValueError('edge_ratio must be in (0, 1], got %r' % (edge_ratio,))
+    if tau is not None and not (float(tau) > 0.0 and np.isfinite(float(tau))):
+        raise ValueError('tau must be positive and finite, got %r' % (tau,))
+    if feature_voxel is not None:
+        fv = _pair_of(feature_voxel, 'feature_voxel')
+    elif not with_scale:
+        fv = _pair_of(2.0 * float(voxel), 'voxel')
+    radius_given = None if feature_radius is None else _pair_of(feature_radius, 'feature_radius')
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+
+    def upload(x):
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1, 3))).to(dev)
+
+    def describe(cloud, edge, radius):
+        down = ops.cloud_voxel_downsample(cloud, edge)[0].contiguous()
+        knn = ops.cloud_knn(ops.cloud_grid(down, radius), down, max(int(normal_k), int(feature_k)), exclude_same_index=True)[1]
+        nrm = ops.cloud_normals(down, down, knn[:, :int(normal_k)].contiguous(), self_counts=True)     # the first k of a longer list
+        feat = ops.cloud_fpfh(down, knn[:, :int(feature_k)].contiguous(), nrm)
+        return down, int((nrm != 0).any(dim=1).sum().item()), feat, int((feat != 0).any(dim=1).sum().item())
+
+    with torch.cuda.device(dev):
+        src, dst = upload(recon), upload(gt)
+        if feature_voxel is None and with_scale:
+            boxes = [ops.cloud_bounds(c) for c in (src, dst)]
+            if any(lo is None for lo, _ in boxes):
+                raise ValueError('global_init: a cloud has no finite point')
+            fv = _pair_of([float(np.sqrt(((hi - lo) ** 2).sum())) / 64.0 for lo, hi in boxes], 'the clouds\' extent')
+        radius = radius_given or (5.0 * fv[0], 5.0 * fv[1])
+        tau = 1.5 * fv[1] if tau is None else float(tau)
+        src, n_src_normals, f_src, n_src_feat = describe(src, fv[0], radius[0])
+        dst, n_dst_normals, f_dst, n_dst_feat = describe(dst, fv[1], radius[1])
+        fwd = ops.cloud_feature_nearest(f_dst, f_src)[1].long()
+        rows = torch.nonzero(fwd >= 0).reshape(-1)
+        n_matches, n_mutual, mutual_used = int(rows.numel()), None, False
+        if mutual and n_matches:
+            back = ops.cloud_feature_nearest(f_src, f_dst)[1].long()
+            agree = rows[back[fwd[rows]] == rows]
+            n_mutual = int(agree.numel())
+            if 3 * n_mutual >= n_matches:
+                rows, mutual_used = agree, True
+        if int(rows.numel()) < 3:
+            raise ValueError('global_init: the feature matching left %d matches (%d source and %d target descriptors): at least 3 '
+                             'are needed' % (int(rows.numel()), n_src_feat, n_dst_feat))
+        a, b = src[rows].contiguous(), dst[fwd[rows]].contiguous()
+        triples = np.random.Generator(np.random.PCG64(int(seed))).integers(0, int(rows.numel()), size=(int(hypotheses), 3), dtype=np.int32)
+        cands, n_valid = ops.cloud_ransac(a, b, torch.from_numpy(triples).to(dev), tau, bool(with_scale), float(edge_ratio), int(best),
+                                          return_valid=True)
+        if n_valid == 0:
+            raise ValueError('global_init: RANSAC found no valid hypothesis among %d triples of %d matches (every triangle '
+                             'degenerate or its edges unequal beyond edge_ratio = %g)' % (int(hypotheses), int(rows.numel()), float(edge_ratio)))
+        reach = np.float32(tau)                                       # the grid's radius is a float32: the next one up where tau rounds down
+        reach = float(reach if float(reach) >= tau else np.nextafter(reach, np.float32(np.inf)))
+        grid, moved, found = ops.cloud_grid(dst, reach), torch.empty_like(src), []
+        for cand in cands:
+            if cand['count'] < 0:
+                continue
+            T = np.vstack([cand['matrix'], [0.0, 0.0, 0.0, 1.0]])
+            ops.cloud_transform(src, T, out=moved)
+            inside = int(ops.cloud_counts(ops.cloud_nearest(grid, moved)[0], [tau], reach).cpu()[0])
+            found.append((inside / float(src.shape[0]), T, cand))
+    fitness, T, _ = max(found, key=lambda f: f[0])                    # the first of equals: RANSAC's order
+    return {'matrix': T.tolist(), 'fitness': fitness, 'scale': float(np.cbrt(np.linalg.det(T[:3, :3]))),
+            'candidates': [{'index': c['index'], 'count': c['count'], 'sum': c['sum'], 'fitness': f} for f, _, c in found],
+            'n_recon': int(src.shape[0]), 'n_gt': int(dst.shape[0]), 'n_recon_normals': n_src_normals, 'n_gt_normals': n_dst_normals,
+            'n_recon_features': n_src_feat, 'n_gt_features': n_dst_feat, 'n_matches': n_matches, 'n_mutual': n_mutual,
+            'mutual_used': mutual_used, 'n_valid_hypotheses': n_valid, 'seed': int(seed), 'with_scale': bool(with_scale),
+            'feature_voxel': list(fv), 'feature_radius': list(radius), 'normal_k': int(normal_k), 'feature_k': int(feature_k),
+            'tau': tau, 'hypotheses': int(hypotheses), 'mutual': bool(mutual), 'edge_ratio': float(edge_ratio), 'best': int(best)}
+
+
 def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES, voxel=None, max_iterations=50, min_move=None,
-             device=None, icp='point', normals=None, normal_side='source', gt_normals=None, normal_k=16, normal_radius=None):
+             device=None, icp='point', normals=None, normal_side='source', gt_normals=None, normal_k=16, normal_radius=None,
+             global_options=None):
     """Trimmed ICP of `recon` (M,3) onto `gt` (N,3) (host arrays or device tensors, float32) on the device: point-to-point
     (icp='point', the default) or point-to-plane over the reconstruction's normals (icp='plane').
 
@@ -204,7 +323,12 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
     normal_radius None: 4 voxel edges, or twice the last distance when voxel == 0; like normal_k = 16 a default, not a
     measurement.  A target point whose normal is zero (fewer than 3 samples within the radius, or samples along a line) pairs with
     nothing.  The dict then also holds normal_side = 'target', normal_k and normal_radius (both None when gt_normals were given) and
-    n_gt_normals, the target points with a usable normal; with normal_side='source' it holds none of them."""
+    n_gt_normals, the target points with a usable normal; with normal_side='source' it holds none of them.
+
+    init='global': the start is found from the clouds alone by global_init(recon, gt, with_scale, voxel, **global_options)
+    (global_options: its other keyword arguments, e.g. dict(hypotheses=..., seed=..., tau=..., feature_voxel=..., mutual=...)),
+    and the loop goes on from its matrix.  The dict then also holds `global`, global_init's dict, and `init` is its matrix; with
+    any other init the dict is what it was."""
     import torch
     from .. import ops
     dist = [float(d) for d in distances]
@@ -238,8 +362,17 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
         raise ValueError("icp='plane' needs the reconstruction's normals (normals=, one row per point)")
     if not plane and normals is not None:
         raise ValueError("normals are used by icp='plane' only")
-    T0 = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
+    if isinstance(init, str) and init != 'global':
+        raise ValueError("init: a 4x4 matrix, None or 'global', got %r" % (init,))
+    if global_options is not None and not isinstance(init, str):
+        raise ValueError("global_options are used by init='global' only")
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    found = None
+    if isinstance(init, str):
+        found = global_init(recon, gt, with_scale=with_scale, voxel=voxel if voxel > 0.0 else dist[-1] / 2.0, device=dev,
+                            **(global_options or {}))
+        init = found['matrix']
+    T0 = np.eye(4) if init is None else np.array(init, np.float64).reshape(4, 4)
 
     def upload(x):
         if isinstance(x, torch.Tensor):
@@ -294,7 +427,8 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
                 if count < 3:
                     raise ValueError('register: %d pairs within %g in stage %d%s' % (
                         count, r, k, ': the initial alignment is too far off for the first distance (give --init_cameras, '
-                        '--init_transform or larger --register_distances)' if k == 0 and stage['iterations'] == 0 else ''))
+                        '--init_transform or larger --register_distances, or find the start from the clouds alone with '
+                        "--register_global / init='global')" if k == 0 and stage['iterations'] == 0 else ''))
                 if plane:
                     T_new = motion_from_plane_moments(count, mom, pivot_dst, with_scale, extent) @ T
                 else:
@@ -314,4 +448,6 @@ def register(recon, gt, init=None, with_scale=False, distances=DEFAULT_DISTANCES
         result['icp'] = 'plane'
     if target:
         result.update(normal_side='target', normal_k=normal_k, normal_radius=normal_radius, n_gt_normals=n_gt_normals)
+    if found is not None:
+        result['global'] = found
     return result

@@ -45,6 +45,7 @@ from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_coun
 from .cloud import cloud_bounds, cloud_pair_moments, cloud_plane_moments, cloud_transform, cloud_voxel_downsample      # noqa: F401
 from .cloud import CLOUD_MAX_K, cloud_knn, cloud_knn_mean, cloud_radius_count, cloud_sor_stats      # noqa: F401
 from .cloud import cloud_normals, cloud_plane_moments_target      # noqa: F401
+from .cloud import cloud_feature_nearest, cloud_fpfh, cloud_ransac      # noqa: F401
 from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

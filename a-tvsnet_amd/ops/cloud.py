@@ -14,6 +14,10 @@ Normals (csrc/cloud_normals.hip): cloud_normals turns cloud_knn's neighbours int
 cloud_plane_moments_target is the point-to-plane step over such normals of the TARGET (atvsnet/register_cloud.py
 normal_side='target', atvsnet/cloud_normals.py).
 
+Global registration (csrc/cloud_features.hip, csrc/cloud_ransac.hip; register_cloud.global_init is built on it): cloud_fpfh turns
+cloud_knn's neighbours and cloud_normals' normals into one 33-bin descriptor per point, cloud_feature_nearest matches descriptors
+exactly, cloud_ransac scores three-point hypotheses over the matches and returns the best few.
+
 Rendering (csrc/scan_render.hip; atvsnet/eval_depth.py is built on it): scan_render splats a scan into a set of cameras and keeps
 the nearest depth per pixel, the ground-truth depth maps the network's maps are scored against.
 
@@ -463,6 +467,99 @@ def cloud_normals(points, queries, idx, self_counts=False, viewpoints=None, view
         _call('atvs_cloud_normals', _p(points), n, _p(queries), m, _p(idx), k, 1 if self_counts else 0, _p(views), n_views,
               _p(view_of), _p(normals), _p(var), _stream())
     return (normals, var) if variation else normals
+
+
+CLOUD_FPFH_BINS = _lib.header_macro('ATVS_CLOUD_FPFH_BINS')
+CLOUD_RANSAC_MAX_BEST = _lib.header_macro('ATVS_CLOUD_RANSAC_MAX_BEST')
+CLOUD_RANSAC_MAX_HYPOTHESES = 1 << 24
+
+
+def cloud_fpfh(points, idx, normals):
+    """points (n,3) float32; idx (n,k) int32 as cloud_knn(grid, points, k, exclude_same_index=True) returned it for the cloud in
+    itself (1 <= k <= 32, -1 padded); normals (n,3) float32 as cloud_normals returned them (unoriented, zero rows allowed) ->
+    (n,33) float32: the FPFH descriptor of every point (atvs_cloud_fpfh: float64 throughout, no transcendental function; the
+    header states every operation).  The normal's sign is made intrinsic first: a point's normal is turned towards the centroid
+    of its neighbours, a neighbour's to the side of the point's.  Three features (alpha, phi, theta) of 11 bins each, every part
+    scaled to sum 1, so that moving, turning or scaling the cloud and negating any normal leave the descriptor as it is.  The zero
+    row where no pair counts (a zero or non-finite normal, no neighbour, duplicates only)."""
+    if not isinstance(idx, torch.Tensor):
+        raise TypeError('idx: expected a tensor, got %s' % type(idx).__name__)
+    k = int(idx.shape[1]) if idx.dim() == 2 else 0
+    if not 1 <= k <= CLOUD_MAX_K:
+        raise ValueError('idx: expected shape (n,k) with k in 1..%d, got %s' % (CLOUD_MAX_K, tuple(idx.shape)))
+    _cloud_arg(points, 'points', torch.float32, (3,))
+    _cloud_arg(idx, 'idx', torch.int32, (k,))
+    _cloud_arg(normals, 'normals', torch.float32, (3,))
+    n = int(points.shape[0])
+    if int(idx.shape[0]) != n or int(normals.shape[0]) != n:
+        raise ValueError('idx %s and normals %s must have one row per row of points %s' % (
+            tuple(idx.shape), tuple(normals.shape), tuple(points.shape)))
+    for t, name in ((idx, 'idx'), (normals, 'normals')):
+        _same_device(t, name, points, 'points')
+    out = torch.empty((n, 3 * CLOUD_FPFH_BINS), dtype=torch.float32, device=points.device)
+    if n:
+        scratch = torch.empty(_size('atvs_cloud_fpfh_scratch_size', n), dtype=torch.uint8, device=points.device)
+        _call('atvs_cloud_fpfh', _p(points), n, _p(idx), k, _p(normals), _p(scratch), scratch.numel(), _p(out), _stream())
+    return out
+
+
+def cloud_feature_nearest(feat_ref, feat_query):
+    """feat_ref (n,33) float32, feat_query (m,33) float32 -> (d2 (m,) float32, idx (m,) int32): per query row the smallest
+    float32 sum of the 33 squared differences (added in ascending bin order, nothing fused) over the reference rows that are not
+    all zero, and the lowest index attaining it; (+inf, -1) for an all-zero query row or when no reference row qualifies.  Exact
+    brute force (atvs_cloud_feature_nearest)."""
+    width = 3 * CLOUD_FPFH_BINS
+    _cloud_arg(feat_ref, 'feat_ref', torch.float32, (width,))
+    _cloud_arg(feat_query, 'feat_query', torch.float32, (width,))
+    _same_device(feat_query, 'feat_query', feat_ref, 'feat_ref')
+    n, m = int(feat_ref.shape[0]), int(feat_query.shape[0])
+    d2 = torch.empty(m, dtype=torch.float32, device=feat_ref.device)
+    idx = torch.empty(m, dtype=torch.int32, device=feat_ref.device)
+    if m:
+        _call('atvs_cloud_feature_nearest', _p(feat_ref), n, _p(feat_query), m, _p(d2), _p(idx), _stream())
+    return d2, idx
+
+
+def cloud_ransac(src, dst, triples, tau, with_scale, edge_ratio=0.9, best=4, return_valid=False):
+    """src, dst (c,3) float32: row i of one matches row i of the other; triples (h,3) int32: one hypothesis per row, the similarity
+    (with_scale) or rigid motion through the three pairs it names (two orthonormal frames, the perimeters' ratio, the centroids;
+    no SVD) -> a list of `best` (1..8) dicts in the order larger count, smaller sum, lower index: matrix (3x4 numpy float64: moves
+    src onto dst), count (the pairs with |M a - b|^2 <= tau^2, of all c), sum (of those squared distances, float64, in ascending
+    pair order), index (the row of `triples`).  A triple is invalid (never returned) when it repeats or leaves 0..c-1, has a
+    degenerate triangle, or an edge whose lengths, after the scale, differ by more than the factor edge_ratio.  Slots beyond the
+    valid hypotheses have count -1, index -1.  atvs_cloud_ransac_score: the same input gives the same words bit for bit; best x 15
+    words cross to the host (one synchronising copy).  return_valid: -> (that list, the number of valid hypotheses), counted on the
+    device from the scores the selection read (one more word crosses)."""
+    tau, edge_ratio = float(tau), float(edge_ratio)
+    if not (tau > 0.0 and math.isfinite(tau)):
+        raise ValueError('tau must be positive and finite, got %r' % (tau,))
+    if not 0.0 < edge_ratio <= 1.0:
+        raise ValueError('edge_ratio must be in (0, 1], got %r' % (edge_ratio,))
+    if not isinstance(with_scale, (bool, np.bool_)):
+        raise TypeError('with_scale: expected a bool, got %r' % (with_scale,))
+    best = _int_in(best, 'best', 1, CLOUD_RANSAC_MAX_BEST)
+    _cloud_arg(src, 'src', torch.float32, (3,))
+    _cloud_arg(dst, 'dst', torch.float32, (3,))
+    _cloud_arg(triples, 'triples', torch.int32, (3,))
+    c, h = int(src.shape[0]), int(triples.shape[0])
+    if int(dst.shape[0]) != c:
+        raise ValueError('dst %s must have one row per row of src %s' % (tuple(dst.shape), tuple(src.shape)))
+    if c < 3:
+        raise ValueError('%d pairs: a hypothesis needs 3' % c)
+    if not 1 <= h <= CLOUD_RANSAC_MAX_HYPOTHESES:
+        raise ValueError('triples: 1 to 2^24 rows, got %d' % h)
+    for t, name in ((dst, 'dst'), (triples, 'triples')):
+        _same_device(t, name, src, 'src')
+    out = torch.empty(best * 15, dtype=torch.int64, device=src.device)
+    scratch = torch.empty(_size('atvs_cloud_ransac_scratch_size', h), dtype=torch.uint8, device=src.device)
+    _call('atvs_cloud_ransac_score', _p(src), _p(dst), c, _p(triples), h, tau, 1 if with_scale else 0, edge_ratio, best,
+          _p(scratch), scratch.numel(), _p(out), _stream())
+    words = out.cpu().numpy().reshape(best, 15)
+    found = [{'matrix': w[:12].view(np.float64).reshape(3, 4).copy(), 'count': int(w[12]), 'sum': float(w[13:14].view(np.float64)[0]),
+              'index': int(w[14])} for w in words]
+    if not return_valid:
+        return found
+    return found, int((scratch[:4 * h].view(torch.int32) >= 0).sum().item())         # the scratch begins with the h counts
 
 
 def scan_render(points, cams, rows, cols, pixel_centre=0.0, splat=0, occlusion_tol=0.0):

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 56
+#define ATVS_ABI_VERSION 57
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -992,6 +992,88 @@ int atvs_cloud_bounds(const float* points, long n, void* out, atvs_stream_t stre
 int atvs_cloud_normals(const float* points, long n, const float* queries, long m, const int* idx, int k, int self_counts,
                        const double* viewpoints, int n_viewpoints, const int* view_of, float* normals, float* variation,
                        atvs_stream_t stream);
+
+/* Global registration (ops/cloud.py cloud_fpfh / cloud_feature_nearest / cloud_ransac, atvsnet/register_cloud.py global_init,
+ * csrc/cloud_features.hip, csrc/cloud_ransac.hip): FPFH descriptors (Rusu, Blodow and Beetz 2009), their exact nearest neighbour in
+ * feature space, and the scoring of three-point hypotheses.  Pointers are device pointers unless named host.  No atomics, no host
+ * synchronisation, no allocation, no transcendental function; every operation is rounded on its own, nothing is contracted; the
+ * same input gives the same bits on every run.  tests/cloud_global_restated.py restates all three definitions.
+ *
+ * atvs_cloud_fpfh.  points P (n,3) float32, idx (n,k) int32 = atvs_cloud_knn of the cloud in itself with exclude_same_index
+ * (1 <= k <= ATVS_CLOUD_MAX_K; a negative entry is padding), normals N (n,3) float32 = atvs_cloud_normals' (unoriented; a zero row
+ * is allowed) -> out (n,33) float32.  Two launches, one lane per point.  Per point j, in double:
+ *   a neighbour   t is VALID when 0 <= i = idx[j,t] < n and P[i] is finite; d_t = (double)P[i] - (double)P[j] per component.
+ *   the sign      c = sum of d_t over the valid t, from +0 in ascending t (the direction to the neighbours' centroid);
+ *                 u = -N[j] when (N_0 c_0 + N_1 c_1) + N_2 c_2 < 0, else N[j] (kept when the dot is 0 or NaN): the normal points
+ *                 to the concave side, whatever sign atvs_cloud_normals gave it.  Per neighbour, e = (u_0 m_0 + u_1 m_1) + u_2 m_2
+ *                 with m = N[i]; m is negated when e < 0, so that u . m >= 0.
+ *   a pair counts when t is valid, N[j] and N[i] are finite with (m_0 m_0 + m_1 m_1) + m_2 m_2 > 0, P[j] is finite,
+ *                 dd = (d_0 d_0 + d_1 d_1) + d_2 d_2 > 0, and with g = u x d (g_0 = u_1 d_2 - u_2 d_1, cyclic),
+ *                 gg = (g_0 g_0 + g_1 g_1) + g_2 g_2 > 0.
+ *   the frame     v = g / sqrt(gg) per component; w = u x v.
+ *   the features  alpha = (v_0 m_0 + v_1 m_1) + v_2 m_2;  phi = ((u_0 d_0 + u_1 d_1) + u_2 d_2) / sqrt(dd);
+ *                 x = (u_0 m_0 + u_1 m_1) + u_2 m_2 (>= 0 by the sign rule), y = (w_0 m_0 + w_1 m_1) + w_2 m_2, theta = atan2(y, x),
+ *                 which the sign rule keeps in [-pi/2, pi/2].
+ *   the bins      11 per feature.  alpha: the number of e in 1..10 with 11 alpha >= 2 e - 11 (the edges -9/11 .. 9/11); phi the
+ *                 same.  theta: the number of e in 1..10 with C_e y - S_e x >= 0, where (C_e, S_e) = (cos, sin) of the edge
+ *                 (2 e - 11) pi / 22, tabulated below; no angle is ever formed.  An exact tie goes to the UPPER bin.
+ *   SPFH          33 integer counts h_b (alpha 0..10, phi 11..21, theta 22..32) and the number of counting pairs c_j, kept as 36
+ *                 bytes per point (33 counts, c_j, two zero bytes) in scratch: the second launch gathers k x 36 bytes per lane.
+ *   FPFH          c_j = 0: the zero row.  Else g_b from +0: for every valid t in ascending order with dd > 0 (recomputed, PCL's
+ *                 weight 1 / dd) and c_i > 0: r = 1 / ((double)c_i dd), g_b = g_b + (double)h_b(i) r.
+ *   the output    per 11-bin part s = the sum of its g_b from +0 in ascending b; with the point's own f_b = (double)h_b / (double)c_j:
+ *                 out_b = (float)((f_b + g_b / s) 0.5), and (float)f_b when s is not > 0 (no neighbour has a histogram).  The
+ *                 neighbours' sum is scaled to 1 BEFORE the point's own part joins it (Open3D's order): SPFH(p) + sum SPFH(q) / dd
+ *                 as it stands would weigh the two by the cloud's unit of length.  Each part sums to 1, and the descriptor is
+ *                 unchanged when the cloud is scaled, moved or turned, and when any normal is negated.
+ * scratch: atvs_cloud_fpfh_scratch_size(n) bytes.  n = 0 is valid.  n negative or beyond 2^30, k outside [1, ATVS_CLOUD_MAX_K], a
+ * short scratch: ATVS_ERR_SHAPE.
+ *
+ * atvs_cloud_feature_nearest.  ref (n,33) float32, query (m,33) float32 -> d2 (m) float32, idx (m) int32: per query the smallest
+ * d2 = the float32 sum of (q_b - r_b)(q_b - r_b) over b = 0..32, the first product taken as it is, the others added in ascending b,
+ * over the reference rows that are not all zero, and the lowest index attaining it.  (+inf, -1) for a query whose 33 entries are
+ * all zero, and when no reference row qualifies (a NaN distance never wins).  Exact brute force on the vector unit: reference
+ * rows pass through LDS in tiles of ATVS_CLOUD_FEATURE_TILE, each lane owns one query.  n and m up to 2^30; beyond, or negative:
+ * ATVS_ERR_SHAPE.  m = 0 is valid.
+ *
+ * atvs_cloud_ransac_score.  src (c,3) and dst (c,3) float32: row i of one matches row i of the other; triples (h,3) int32; tau > 0,
+ * edge_ratio in (0, 1], with_scale 0 or 1, best in 1..ATVS_CLOUD_RANSAC_MAX_BEST -> out, best x 15 8-byte words.  One lane per
+ * hypothesis, in double.  With a_k = (double)src[i_k], b_k = (double)dst[i_k] for the triple (i_0, i_1, i_2):
+ *   the edges     of each triangle: p = x_1 - x_0, q = x_2 - x_0, r = x_2 - x_1; lengths l_01, l_02, l_12 = sqrt((e_0 e_0 + e_1 e_1) + e_2 e_2).
+ *   the frame     X = p / l_01; z = q - ((q_0 X_0 + q_1 X_1) + q_2 X_2) X; zz = (z_0 z_0 + z_1 z_1) + z_2 z_2; Y = z / sqrt(zz);
+ *                 Z = X x Y.  R[r][c] = (Xd_r Xs_c + Yd_r Ys_c) + Zd_r Zs_c (d: dst's frame, s: src's): a rotation to rounding.
+ *   the scale     s = ((ld_01 + ld_02) + ld_12) / ((ls_01 + ls_02) + ls_12) when with_scale, else 1.
+ *   the matrix    M[r][c] = s R[r][c]; with the centroids g = ((x_0 + x_1) + x_2) / 3 per component,
+ *                 M[r][3] = gd_r - ((M[r][0] gs_0 + M[r][1] gs_1) + M[r][2] gs_2).
+ *   invalid       (count -1) unless all of: 0 <= i_k < c, the three indices differ; every squared edge length of both triangles
+ *                 >= ATVS_CLOUD_RANSAC_MIN_EDGE2 (1e-60: the floor that keeps the divisions finite); zz > 1e-12 (q . q) in both
+ *                 triangles (the sine of the angle at x_0 above 1e-6: not a zero area); and for each of the three edges
+ *                 ld >= edge_ratio (s ls) and edge_ratio ld <= s ls.  Every test is written so that a NaN fails it.
+ *   the score     over ALL c pairs in ascending i (the triple's own included): x = (double)src[i];
+ *                 e_r = (((M[r][0] x_0 + M[r][1] x_1) + M[r][2] x_2) + M[r][3]) - (double)dst[i]; d = (e_0 e_0 + e_1 e_1) + e_2 e_2; the
+ *                 pair counts when d <= tau tau, and the sum takes d in that order from +0.  Pairs pass through LDS in tiles of
+ *                 256; every lane reads the same address.
+ *   the selection the order is larger count, then smaller sum, then lower index; invalid hypotheses never enter.  One workgroup
+ *                 finds the first `best` of that order in `best` rounds, each a fold of the fixed shape of the moments' tree (a
+ *                 lane takes lane + 32, + 16, .. + 1; the wavefronts as (w0, w1), (w2, w3)); the order is total, so the answer
+ *                 does not depend on the shape.  Slot r of out: M (12 doubles, row-major 3 x 4), the count (int64), the sum
+ *                 (double), the hypothesis' index (int64); a slot beyond the number of valid hypotheses: zeros, -1, +0, -1.
+ * scratch: atvs_cloud_ransac_scratch_size(h) bytes; afterwards it begins with the h counts (int32, -1 for an invalid hypothesis)
+ * and holds the h sums (double) from the next multiple of 256 bytes on.  c in 3..2^30, h in 1..2^24, else ATVS_ERR_SHAPE; tau or
+ * edge_ratio outside their range or NaN, with_scale not 0 or 1, best outside its range: ATVS_ERR_ARG. */
+#define ATVS_CLOUD_FPFH_BINS 11
+#define ATVS_CLOUD_FPFH_THETA_COS { 0.28173255684142978, 0.54064081745559767, 0.75574957435425827, 0.90963199535451844, 0.98982144188093268, 0.98982144188093268, 0.90963199535451844, 0.75574957435425827, 0.54064081745559767, 0.28173255684142978 }
+#define ATVS_CLOUD_FPFH_THETA_SIN { -0.95949297361449737, -0.84125353283118109, -0.6548607339452851, -0.41541501300188638, -0.14231483827328514, 0.14231483827328514, 0.41541501300188638, 0.6548607339452851, 0.84125353283118109, 0.95949297361449737 }
+#define ATVS_CLOUD_FEATURE_TILE 128
+#define ATVS_CLOUD_RANSAC_MAX_BEST 8
+#define ATVS_CLOUD_RANSAC_MIN_EDGE2 1e-60
+int atvs_cloud_fpfh_scratch_size(long n, long* bytes);
+int atvs_cloud_fpfh(const float* points, long n, const int* idx, int k, const float* normals, void* scratch, long scratch_bytes,
+                    float* out, atvs_stream_t stream);
+int atvs_cloud_feature_nearest(const float* ref, long n, const float* query, long m, float* d2, int* idx, atvs_stream_t stream);
+int atvs_cloud_ransac_scratch_size(long h, long* bytes);
+int atvs_cloud_ransac_score(const float* src, const float* dst, long c, const int* triples, long h, double tau, int with_scale,
+                      double edge_ratio, int best, void* scratch, long scratch_bytes, void* out, atvs_stream_t stream);
 
 /* A scan rendered into cameras (ops/cloud.py scan_render, atvsnet/eval_depth.py, csrc/scan_render.hip): the ground-truth depth
  * maps a set of depth maps is scored against.  Pointers are device pointers.  Integer atomics only: the output is a function of the
