@@ -511,10 +511,23 @@ def _clean_cloud(points, colors, score, folder, device, gt_points, clean, normal
     return len(clean_points)
 
 
+def _write_mesh(scene_fusion, map_cams, folder, mesh):
+    """final3d_mesh.ply and mesh.json -> the face count.  After the cloud: the fusion's result bounds the volume."""
+    from . import mesh_fusion
+    t0 = time.time()
+    scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
+    n_faces = scene_mesh.write_ply(os.path.join(folder, 'final3d_mesh.ply'))
+    mesh_fusion.write_json(os.path.join(folder, 'mesh.json'), scene_mesh.report())
+    TIMES['mesh'] = time.time() - t0
+    return n_faces
+
+
 def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register_args, init_cameras, score_maps, clean,
-               clean_keep_normals=False):
-    """A fused scene's files, each group by its own step: the PLY, the cloud's score, the maps' score, the cleaned cloud."""
+               clean_keep_normals=False, mesh=None):
+    """A fused scene's files, each group by its own step: the PLY, the mesh, the cloud's score, the maps' score, the cleaned cloud."""
     n_points = _write_cloud(scene_fusion, folder)
+    if mesh is not None:
+        print(Notify.INFO, '%s: %d mesh faces' % (name, _write_mesh(scene_fusion, map_cams, folder, mesh)), Notify.ENDC)
     points, colors, score, normals = None, None, None, None
     if gt_points is not None or clean:
         points, colors = scene_fusion.run()
@@ -534,10 +547,14 @@ def _end_scene(name, scene_fusion, map_cams, folder, device, gt_points, register
 
 
 def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True, gt_ply=None, register=None,
-                  clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False):
+                  clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False, mesh=None):
     """What each of run_eval_pc's options needs -> every rule as (broken by these values, message).  The row of fuse_normals is
     listed for a caller that gives fuse_normals: without it there is nothing the row could refuse.  The rows of a point-to-plane
-    registration and of clean_keep_normals likewise, at the end."""
+    registration, of clean_keep_normals and of mesh likewise, at the end."""
+    mesh_row = [] if mesh is None else [
+        (fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
+                       'mesh is integrated from the maps the fusion stages and bounded by its cloud'),
+        (mesh.get('voxel') is None, '--mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --mesh_voxel (mesh needs voxel=)')]
     normals_row = [] if fuse_normals is None else [
         (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
                        '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
@@ -568,7 +585,7 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (bool(clean) and fuse is None, '--clean_voxel, --clean_sor and --clean_radius_filter need --fuse (clean needs fuse): there is no '
                                        'point cloud to clean'),
         (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')
-    ] + target_row + plane_row + global_row + keep_row
+    ] + target_row + plane_row + global_row + keep_row + mesh_row
 
 
 def _check_options(**options):
@@ -579,7 +596,7 @@ def _check_options(**options):
 
 
 def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_thread=True, fuse=None, map_files=True,
-                gt_ply=None, register=None, clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False):
+                gt_ply=None, register=None, clean=None, score_maps=None, fuse_normals=None, clean_keep_normals=False, mesh=None):
     """(reference :206-397) image_infos: [[[dense_path, image_folder, scene_name], format], ...]
     scene_cache: every image prepared and run through the towers once per scene (atvsnet/scene.py), the files written by one
     background thread (write_thread=False: in this thread, same bytes).
@@ -610,10 +627,18 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     after the scene's fusion the ground truth is rendered into the scene's cameras (in SceneFusion.order()) and the staged,
     probability-filtered depth planes -- what enters the cloud -- are scored against it (eval_depth.score_maps) into
     <savepath>/<scene>/depth_eval.json.  With register the ground truth is moved by the inverse of the matrix already found (no
-    second fit).  Every other output is what it is without it."""
+    second fit).  Every other output is what it is without it.
+    mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=), the arguments of mesh_fusion.SceneMesh:
+    after the scene's fusion the staged depth planes and images are integrated into a TSDF volume bounded by the fused cloud and
+    meshed by marching tetrahedra into <savepath>/<scene>/final3d_mesh.ply, with the report in mesh.json.  Every other output is
+    what it is without it."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
-                   clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals)
+                   clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals,
+                   **({} if mesh is None else {'mesh': mesh}))
+    if mesh is not None:
+        from . import mesh_fusion
+        mesh_fusion.check_options(**mesh)
     if fuse_normals is not None:
         depth_fusion.check_normal_options(**fuse_normals)
         fuse = dict(fuse, **fuse_normals)
@@ -651,12 +676,12 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
             writer = _Writer(scene_cache and write_thread, timed=scene_cache)
             try:
                 scene_fusion, map_cams, scene_runtime = _run_scene(source, mvs_list, savepath_current, writer, map_files, fuse,
-                                                                   score_maps is not None, device)
+                                                                   score_maps is not None or mesh is not None, device)
             finally:
                 writer.close()
             if scene_fusion is not None:
                 _end_scene(image_info[2], scene_fusion, map_cams, savepath_current, device, gt_points, register_args, init_cameras,
-                           score_maps, clean, clean_keep_normals)
+                           score_maps, clean, clean_keep_normals, mesh)
             print(Notify.INFO, '%s: %d depth maps, %.2f s' % (image_info[2], len(mvs_list), scene_runtime), Notify.ENDC)
     finally:
         source.close()
@@ -690,10 +715,19 @@ def _global_options(flags):
     return {'global': given}
 
 
+def _mesh_options(flags):
+    """run_eval_pc's mesh from cli's --mesh_* options: those that were given, None when none was."""
+    names = dict(mesh_voxel='voxel', mesh_trunc_voxels='trunc_voxels', mesh_min_weight='min_weight', mesh_max_blocks='max_blocks')
+    given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
+    return given or None
+
+
 def _run_options(flags):
     """run_eval_pc's keyword arguments from a namespace of cli's options (FLAGS, cli's parsed arguments): one it lacks is off."""
     opt = lambda name, default=None: getattr(flags, name, default)          # noqa: E731
+    mesh = _mesh_options(flags)
     return dict(
+        {} if mesh is None else {'mesh': mesh},
         use_graph=not opt('eager'), scene_cache=opt('scene_cache', False), write_thread=not opt('sync_write'),
         fuse=dict(prob_threshold=flags.prob_threshold, disp_threshold=flags.disp_threshold, num_consistent=flags.num_consistent)
         if opt('fuse') else None,
@@ -794,6 +828,15 @@ def cli(argv=None):
     parser.add_argument('--clean_keep_normals', action='store_true',
                         help='--fuse_normals depth with a cleaning step: final3d_model_clean.ply carries the normals of the rows that '
                              'stay (clean_cloud --keep_normals)')
+    parser.add_argument('--mesh_voxel', type=float, default=None, metavar='V',
+                        help='--fuse: also mesh each scene (mesh_fusion.SceneMesh: TSDF fusion of the staged maps with voxels of this '
+                             'edge, marching tetrahedra) into <savepath>/<scene>/final3d_mesh.ply and mesh.json')
+    parser.add_argument('--mesh_trunc_voxels', type=float, default=None, metavar='T',
+                        help='--mesh_voxel: the band either side of a depth, in voxels (default 4: a default, not a measurement)')
+    parser.add_argument('--mesh_min_weight', type=float, default=None, metavar='W',
+                        help='--mesh_voxel: views a voxel needs to be meshed (default 2, the fusion\'s num_consistent)')
+    parser.add_argument('--mesh_max_blocks', type=int, default=None, metavar='N',
+                        help='--mesh_voxel: blocks of 8^3 voxels the maps may mark (default 131072)')
     args = parser.parse_args(argv)
     # what only the command line can break; the rest is _option_rules
     if (args.with_scale or args.init_cameras) and not args.register:
@@ -829,6 +872,9 @@ def cli(argv=None):
     try:
         _check_options(**_run_options(args))
         depth_fusion.check_normal_options(**(_normal_options(args) or {}))
+        if _mesh_options(args) is not None:
+            from . import mesh_fusion
+            mesh_fusion.check_options(**_mesh_options(args))
     except ValueError as e:
         parser.error(str(e))
     scenes = args.scenes.split(',') if args.scenes else None

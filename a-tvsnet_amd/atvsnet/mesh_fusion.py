@@ -1,0 +1,283 @@
+"""A triangle mesh of a scene from its depth maps, on the device: the probability-filtered depth maps and
+the images a scene's fusion holds are integrated into a block-sparse TSDF volume (ops.tsdf_integrate) and the volume is meshed by
+marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
+
+    mesh_maps      depth maps, cameras, images and a box -> the volume, the mesh, seconds per stage
+    SceneMesh      the mesh of a depth_fusion.SceneFusion: its staged planes in fusion order, the box of its fused points
+    mesh_report    blocks, valid voxels, vertices, faces, zero-area faces, boundary edges
+
+What this is not: there is no free-space carving (a view adds to a voxel only inside the narrow band around its depth), no per-view
+weight, no consistency mask on the depths beyond the probability filter, no mesh simplification, no hole filling, and the PLY
+carries no normals.  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports without a GPU.
+
+    python -m atvsnet_amd.atvsnet.mesh_fusion --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --voxel V
+        [--trunc_voxels 4 --min_weight 2 --prob_threshold 0.8 --pixel_centre 0 --max_blocks N --report mesh.json] --out mesh.ply
+"""
+import argparse
+import json
+import os
+import time
+
+import numpy as np
+
+from . import eval_depth
+
+DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
+DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
+DEFAULT_MAX_BLOCKS = 131072        # 64 Mi voxels: 1.3 GB of tsdf, weight and colour while the volume is built
+DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel coordinates: the convention that places the cloud
+
+
+def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
+                  pixel_centre=DEFAULT_PIXEL_CENTRE):
+    """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError."""
+    voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
+    if not (voxel > 0.0 and np.isfinite(voxel)):
+        raise ValueError('mesh voxel must be positive and finite, got %r' % (voxel,))
+    if not (trunc_voxels >= 1.0 and np.isfinite(trunc_voxels)):
+        raise ValueError('mesh trunc_voxels must be at least 1 and finite, got %r' % (trunc_voxels,))
+    if not (min_weight >= 1.0 and np.isfinite(min_weight)):
+        raise ValueError('mesh min_weight must be at least 1 and finite, got %r' % (min_weight,))
+    if int(max_blocks) != max_blocks or int(max_blocks) < 1:
+        raise ValueError('mesh max_blocks must be a positive integer, got %r' % (max_blocks,))
+    if not np.isfinite(pixel_centre):
+        raise ValueError('mesh pixel_centre must be finite, got %r' % (pixel_centre,))
+    return voxel, trunc_voxels, min_weight, int(max_blocks), pixel_centre
+
+
+def box_of(lo, hi, voxel, trunc):
+    """The volume's box around the points' bounds lo, hi (3 numbers each), padded by trunc plus one block -> (origin (3,) float64,
+    dims (bx, by, bz))."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
+    if lo.shape != (3,) or hi.shape != (3,) or not (np.isfinite(lo).all() and np.isfinite(hi).all()) or (hi < lo).any():
+        raise ValueError('box_of: bad bounds %r, %r' % (lo, hi))
+    pad = float(trunc) + 8.0 * float(voxel)
+    origin = lo - pad
+    dims = tuple(int(d) for d in np.maximum(np.ceil(((hi + pad) - origin) / (8.0 * float(voxel))), 1.0))
+    return origin, dims
+
+
+def depth_bounds(depths, cams16, pixel_centre=DEFAULT_PIXEL_CENTRE):
+    """The bounds of the maps' own back-projected samples, on the host -> (lo, hi) float64 (3,), or (None, None) without a sample.
+    depths (n,rows,cols), cams16 (n,16) as eval_depth.camera_rows gives them."""
+    depths = np.asarray(depths, np.float32)
+    lo, hi = None, None
+    v, u = np.meshgrid(np.arange(depths.shape[1], dtype=np.float64), np.arange(depths.shape[2], dtype=np.float64), indexing='ij')
+    for d, c in zip(depths, np.asarray(cams16, np.float64)):
+        ok = np.isfinite(d) & (d > 0)
+        if not ok.any():
+            continue
+        z = d[ok].astype(np.float64)
+        cam = np.stack([(u[ok] + pixel_centre - c[14]) / c[12] * z, (v[ok] + pixel_centre - c[15]) / c[13] * z, z], axis=1) - c[9:12]
+        world = cam @ c[:9].reshape(3, 3)                # R^T (c - t), per row
+        world = world[np.isfinite(world).all(axis=1)]
+        if len(world):
+            lo = world.min(axis=0) if lo is None else np.minimum(lo, world.min(axis=0))
+            hi = world.max(axis=0) if hi is None else np.maximum(hi, world.max(axis=0))
+    return lo, hi
+
+
+def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
+              max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE):
+    """depths (n,rows,cols) float32 and images (n,rows,cols,C>=3) float32 (b, g, r first) or None on the device, cams16 (n,16)
+    float64 host rows (eval_depth.camera_rows), lo / hi the bounds of what is to be meshed -> (volume, (vertices, colors, faces)
+    device tensors, {'integrate': s, 'extract': s}, each ended by a device synchronisation)."""
+    import torch
+    from .. import ops
+    voxel, trunc_voxels, min_weight, max_blocks, pixel_centre = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
+    trunc = trunc_voxels * voxel
+    origin, dims = box_of(lo, hi, voxel, trunc)
+    if dims[0] * dims[1] * dims[2] > ops.TSDF_MAX_DIRECTORY:
+        raise ValueError('mesh voxel %r gives a box of %s blocks, more than 2^26: the scene spans %s' % (voxel, dims, (np.asarray(hi) - lo).tolist()))
+    cams = torch.from_numpy(np.ascontiguousarray(cams16, np.float64)).to(depths.device)
+    torch.cuda.synchronize(depths.device)
+    t0 = time.time()
+    volume = ops.tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=images, pixel_centre=pixel_centre, max_blocks=max_blocks)
+    torch.cuda.synchronize(depths.device)
+    t1 = time.time()
+    mesh = ops.tsdf_mesh(volume, min_weight)
+    torch.cuda.synchronize(depths.device)
+    return volume, mesh, {'integrate': t1 - t0, 'extract': time.time() - t1}
+
+
+def mesh_report(volume, mesh, min_weight, seconds=None):
+    """-> a dict: the box, blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (edges of one face), seconds."""
+    vertices, _, faces = mesh
+    v = vertices.cpu().numpy().astype(np.float64)
+    f = faces.cpu().numpy().astype(np.int64)
+    zero = boundary = 0
+    if len(f):
+        normal = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
+        zero = int((np.abs(normal).max(axis=1) == 0.0).sum())
+        e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+        _, counts = np.unique(e[:, 0] * (len(v) + 1) + e[:, 1], return_counts=True)
+        boundary = int((counts == 1).sum())
+    return {'origin': [float(o) for o in volume.origin], 'voxel': volume.voxel, 'trunc': volume.trunc, 'dims': list(volume.dims),
+            'min_weight': float(min_weight), 'blocks': volume.num_blocks,
+            'valid_voxels': int((volume.weight >= float(min_weight)).sum().item()) if volume.num_blocks else 0,
+            'vertices': int(len(v)), 'faces': int(len(f)), 'zero_area_faces': zero, 'boundary_edges': boundary,
+            'seconds': dict(seconds or {})}
+
+
+def write_json(path, result):
+    with open(path, 'w') as f:
+        json.dump(result, f, indent=1, sort_keys=True)
+        f.write('\n')
+
+
+class SceneMesh(object):
+    """The mesh of a scene whose maps a depth_fusion.SceneFusion holds.
+
+        mesh = SceneMesh(scene_fusion, cams, voxel)     # cams: {out_index: (2,4,4) camera}, or (n,2,4,4) in the order of add()
+        mesh.write_ply(path)                            # = run() + tools/ply.write_mesh
+        mesh.report()
+
+    The box is the ops.cloud_bounds of the fused points of scene_fusion.run(), padded by trunc = trunc_voxels * voxel plus one
+    block: the consistent points bound the volume, so a stray depth cannot inflate it.  The staged, probability-filtered depth
+    planes (nd[..., 3]) and images (img) are integrated in scene_fusion.order().  run() -> (vertices (V,3) float32, colors (V,3)
+    uint8 r, g, b, faces (F,3) int32) as numpy arrays."""
+
+    def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
+                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE):
+        self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
+        self.fusion = scene_fusion
+        k = len(scene_fusion.index)
+        if isinstance(cams, dict):
+            missing = [i for i in scene_fusion.index if i not in cams]
+            if missing:
+                raise ValueError('SceneMesh: no camera for map %d' % missing[0])
+            cams = [cams[i] for i in scene_fusion.index]
+        self.cams16 = eval_depth.camera_rows(np.asarray(cams, np.float64))
+        if len(self.cams16) != k:
+            raise ValueError('SceneMesh: %d cameras for %d staged maps' % (len(self.cams16), k))
+        self.volume = self.result = self._report = None
+
+    def run(self):
+        import torch
+        from .. import ops
+        if self.result is None:
+            voxel, trunc_voxels, min_weight, max_blocks, pixel_centre = self.options
+            fusion = self.fusion
+            t0 = time.time()
+            points, _ = fusion.run()                      # orders this stream after every staging
+            dev = fusion.device
+            lo, hi = ops.cloud_bounds(torch.from_numpy(np.ascontiguousarray(points, np.float32)).to(dev)) if len(points) else (None, None)
+            seconds = {'bounds': time.time() - t0}
+            if lo is None:
+                raise RuntimeError('SceneMesh: the fusion has no finite point: there is nothing to bound the volume with')
+            order = fusion.order()
+            k = len(order)
+            idx = torch.from_numpy(order).to(dev)
+            depths = fusion.nd[:k, :, :, 3].index_select(0, idx).contiguous()
+            images = fusion.img[:k] if np.array_equal(order, np.arange(k)) else fusion.img[:k].index_select(0, idx)
+            self.volume, mesh, stage = mesh_maps(depths, self.cams16[order], images, lo, hi, voxel, trunc_voxels, min_weight, max_blocks,
+                                                 pixel_centre)
+            seconds.update(stage)
+            t0 = time.time()
+            self.result = tuple(None if t is None else t.cpu().numpy() for t in mesh)
+            seconds['download'] = time.time() - t0
+            t0 = time.time()
+            self._report = mesh_report(self.volume, mesh, min_weight, seconds)
+            seconds['report'] = self._report['seconds']['report'] = time.time() - t0          # on the host: the edge census
+        return self.result
+
+    def report(self):
+        self.run()
+        return self._report
+
+    def write_ply(self, path):
+        """run() into a binary PLY at `path` (tools/ply.write_mesh) -> the number of faces."""
+        from ..tools import ply
+        vertices, colors, faces = self.run()
+        ply.write_mesh(path, vertices, colors, faces)
+        return len(faces)
+
+
+def make_parser():
+    parser = argparse.ArgumentParser(description='mesh the written depth maps of a scene: TSDF fusion and marching tetrahedra on the GPU '
+                                                 '(no free-space carving, no simplification, no hole filling)')
+    parser.add_argument('--scene', default=None, help='<data_root>/eth3d/<scene>: its pair.txt names the maps (default: every map under --maps)')
+    parser.add_argument('--maps', required=True, help='<savepath>/<scene> of eval_pointcloud: depths_atvsnet/%%08d.pfm, _prob.pfm, .jpg, .txt')
+    parser.add_argument('--voxel', type=float, required=True, help='the voxel\'s edge in the scene\'s unit')
+    parser.add_argument('--trunc_voxels', type=float, default=DEFAULT_TRUNC_VOXELS, help='the band either side of a depth, in voxels (a default, not a measurement)')
+    parser.add_argument('--min_weight', type=float, default=DEFAULT_MIN_WEIGHT, help='views a voxel needs to be meshed (a default: the fusion\'s num_consistent)')
+    parser.add_argument('--prob_threshold', type=float, default=0.8, help='a depth whose probability is below this is no sample (depth_fusion --prob_threshold)')
+    parser.add_argument('--pixel_centre', type=float, default=DEFAULT_PIXEL_CENTRE, help='image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5')
+    parser.add_argument('--max_blocks', type=int, default=DEFAULT_MAX_BLOCKS, help='blocks of 8^3 voxels the maps may mark')
+    parser.add_argument('--bounds', default=None, metavar='PLY', help='bound the volume by this cloud (the scene\'s final3d_model.ply) instead of '
+                                                                      'by the maps\' own back-projected depths')
+    parser.add_argument('--report', default=None, metavar='FILE', help='write the report as JSON here')
+    parser.add_argument('--out', required=True, help='the mesh, a binary PLY')
+    parser.add_argument('--gpu_id', type=int, default=0)
+    return parser
+
+
+def _load_side_maps(maps_folder, indices, shape):
+    """The probability maps and images that stand beside the depth maps: (prob (n,rows,cols) or None, bgr (n,rows,cols,3) or None)."""
+    from .preprocess import load_pfm
+    folder = os.path.join(maps_folder, 'depths_atvsnet')
+    if not os.path.isdir(folder):
+        folder = maps_folder
+    probs, images = [], []
+    for i in indices:
+        stem = os.path.join(folder, '%08d' % i)
+        if probs is not None and os.path.exists(stem + '_prob.pfm'):
+            with open(stem + '_prob.pfm', 'rb') as f:
+                probs.append(np.asarray(load_pfm(f), np.float32))
+        else:
+            probs = None
+        if images is not None and os.path.exists(stem + '.jpg'):
+            from PIL import Image
+            images.append(np.asarray(Image.open(stem + '.jpg').convert('RGB'))[:, :, ::-1].astype(np.float32))
+            if images[-1].shape[:2] != shape:
+                images = None
+        else:
+            images = None
+    return (None if probs is None else np.stack(probs)), (None if images is None else np.stack(images))
+
+
+def cli(argv=None):
+    parser = make_parser()
+    args = parser.parse_args(argv)
+    try:
+        check_options(args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre)
+    except ValueError as e:
+        parser.error(str(e))
+    if not os.path.isdir(args.maps):
+        parser.error('--maps %s: no such folder' % args.maps)
+    if args.scene is not None and not os.path.isfile(os.path.join(args.scene, 'pair.txt')):
+        parser.error('--scene %s: no pair.txt' % args.scene)
+    if args.bounds is not None and not os.path.isfile(args.bounds):
+        parser.error('--bounds %s: no such file' % args.bounds)
+    from ..tools import ply
+    indices, depths, cams = eval_depth.load_maps(args.maps, eval_depth.scene_indices(args.scene) if args.scene is not None else None)
+    probs, images = _load_side_maps(args.maps, indices, depths.shape[1:])
+    depths = depths.copy()
+    if probs is not None:
+        depths[probs < args.prob_threshold] = 0          # depth_fusion.probability_filter
+    cams16 = eval_depth.camera_rows(cams)
+    if args.bounds is not None:
+        points = ply.read_ply_points(args.bounds)
+        points = points[np.isfinite(points).all(axis=1)]
+        lo, hi = (points.min(axis=0), points.max(axis=0)) if len(points) else (None, None)
+    else:
+        lo, hi = depth_bounds(depths, cams16, args.pixel_centre)
+    if lo is None:
+        parser.error('there is no depth sample (or no point in --bounds) to bound the volume with')
+    import torch
+    torch.cuda.set_device(args.gpu_id)
+    dev = torch.device('cuda', args.gpu_id)
+    volume, mesh, seconds = mesh_maps(torch.from_numpy(depths).to(dev), cams16, None if images is None else torch.from_numpy(images).to(dev),
+                                      lo, hi, args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre)
+    vertices, colors, faces = (None if t is None else t.cpu().numpy() for t in mesh)
+    ply.write_mesh(args.out, vertices, colors, faces)
+    result = dict(mesh_report(volume, mesh, args.min_weight, seconds), maps=[int(i) for i in indices], colored=images is not None,
+                  probability_filtered=probs is not None)
+    if args.report:
+        write_json(args.report, result)
+    print(json.dumps({k: result[k] for k in ('blocks', 'valid_voxels', 'vertices', 'faces', 'zero_area_faces', 'boundary_edges')}))
+    return result
+
+
+if __name__ == '__main__':
+    cli()

@@ -1,6 +1,7 @@
 """Binary PLY point clouds in the layout the reference's fusibile writes (fusibile/displayUtils.h:80-135):
 `format binary_little_endian 1.0`, vertices of (float x, y, z, uchar red, green, blue); with normals (not in the reference)
-(float x, y, z, nx, ny, nz, uchar red, green, blue)."""
+(float x, y, z, nx, ny, nz, uchar red, green, blue).  Triangle meshes (write_mesh / read_mesh): the same vertex element followed by
+`element face` with `property list uchar int vertex_indices`."""
 import numpy as np
 
 _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
@@ -9,6 +10,7 @@ _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('g
 _VERTEX_N = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('nx', '<f4'), ('ny', '<f4'), ('nz', '<f4'),
                       ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
 _HEADER_TYPES = {'f4': 'float', 'u1': 'uchar'}
+_FACE = np.dtype([('n', 'u1'), ('v', '<i4', (3,))])
 
 
 def write_ply(path, points, colors, normals=None):
@@ -36,16 +38,19 @@ def write_ply(path, points, colors, normals=None):
 
 
 def _header(f, path):
-    """The header of an open file -> (vertex count or None, the property names in order); the file is left at the body."""
-    n, names = None, []
+    """The header of an open file -> (vertex count or None, the vertex element's property names in order: the properties of a
+    later element, a mesh's faces, are not collected); the file is left at the body."""
+    n, names, element = None, [], None
     while True:
         raw = f.readline()
         if not raw:
             raise ValueError('%s: the header has no end_header' % path)
         line = raw.decode('ascii').strip()
+        if line.startswith('element'):
+            element = line.split()[1] if len(line.split()) > 1 else None
         if line.startswith('element vertex'):
             n = int(line.split()[-1])
-        if line.startswith('property'):
+        if line.startswith('property') and element in (None, 'vertex'):
             names.append(line.split()[-1])
         if line == 'end_header':
             return n, names
@@ -73,6 +78,56 @@ def read_ply_normals(path):
 def read_ply(path):
     """-> (points (M,3) float32, colors (M,3) uint8) of a file written by write_ply / the reference (with or without normals)."""
     return read_ply_normals(path)[:2]
+
+
+def write_mesh(path, vertices, colors, faces):
+    """vertices (V,3) float32, colors (V,3) uint8 (r, g, b) or None (white), faces (F,3) int32 -> a binary little-endian PLY:
+    `element vertex` as write_ply writes it (x y z red green blue), then `element face` with
+    `property list uchar int vertex_indices`.  A face index outside the vertices raises."""
+    vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
+    faces = np.asarray(faces).reshape(-1, 3)
+    if colors is None:
+        colors = np.full((len(vertices), 3), 255, np.uint8)
+    colors = np.asarray(colors, np.uint8).reshape(-1, 3)
+    if len(colors) != len(vertices):
+        raise ValueError('write_mesh: %d colors for %d vertices' % (len(colors), len(vertices)))
+    if len(faces) and (faces.min() < 0 or faces.max() >= len(vertices)):
+        raise ValueError('write_mesh: a face index outside 0..%d' % (len(vertices) - 1))
+    v = np.empty(len(vertices), _VERTEX)
+    v['x'], v['y'], v['z'] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
+    v['red'], v['green'], v['blue'] = colors[:, 0], colors[:, 1], colors[:, 2]
+    t = np.empty(len(faces), _FACE)
+    t['n'] = 3
+    t['v'] = faces
+    with open(path, 'wb') as f:
+        f.write(('ply\nformat binary_little_endian 1.0\nelement vertex %d\n' % len(vertices)).encode('ascii'))
+        f.write(''.join('property %s %s\n' % (_HEADER_TYPES[v.dtype[name].str[1:]], name) for name in v.dtype.names).encode('ascii'))
+        f.write(('element face %d\nproperty list uchar int vertex_indices\nend_header\n' % len(faces)).encode('ascii'))
+        v.tofile(f)
+        t.tofile(f)
+
+
+def read_mesh(path):
+    """-> (vertices (V,3) float32, colors (V,3) uint8, faces (F,3) int32) of a file written by write_mesh."""
+    with open(path, 'rb') as f:
+        lines = []
+        while not lines or lines[-1] != 'end_header':
+            raw = f.readline()
+            if not raw:
+                raise ValueError('%s: the header has no end_header' % path)
+            lines.append(raw.decode('ascii').strip())
+        elements = [ln.split() for ln in lines if ln.startswith('element')]
+        props = [ln for ln in lines if ln.startswith('property')]
+        if ([e[1] for e in elements] != ['vertex', 'face'] or lines[1] != 'format binary_little_endian 1.0' or
+                [p.split()[-1] for p in props[:-1]] != list(_VERTEX.names) or props[-1] != 'property list uchar int vertex_indices'):
+            raise ValueError('%s: not a mesh layout write_mesh writes' % path)
+        nv, nf = int(elements[0][2]), int(elements[1][2])
+        v = np.fromfile(f, _VERTEX, nv)
+        t = np.fromfile(f, _FACE, nf)
+    if len(v) != nv or len(t) != nf or (nf and (t['n'] != 3).any()):
+        raise ValueError('%s: truncated body, or a face that is no triangle' % path)
+    return (np.stack([v['x'], v['y'], v['z']], -1).reshape(-1, 3), np.stack([v['red'], v['green'], v['blue']], -1).reshape(-1, 3),
+            t['v'].astype(np.int32).reshape(-1, 3))
 
 
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',

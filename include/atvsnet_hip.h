@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 57
+#define ATVS_ABI_VERSION 58
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1150,6 +1150,79 @@ int atvs_cloud_voxel_shares_scratch_size(long n, long* bytes);
 int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* excess, long n, double voxel, const double* origin,
                             const double* tolerances, int n_tolerances, double margin, void* scratch, long scratch_bytes,
                             long long* out, atvs_stream_t stream);
+
+/* A surface from depth maps (ops/tsdf.py tsdf_integrate / tsdf_mesh, atvsnet/mesh_fusion.py, csrc/tsdf.hip): a block-sparse
+ * truncated-signed-distance (TSDF) volume integrated from depth maps, and a marching-tetrahedra extractor.  Pointers are device
+ * pointers unless marked HOST.  No float atomics, no allocation; every output is a function of the inputs alone, bit for bit on
+ * every run.  tests/tsdf_restated.py restates both definitions on a dense grid.
+ *
+ * The box.  origin (HOST, 3 finite doubles), voxel > 0, bx x by x bz blocks of 8^3 voxels, bx by bz <= ATVS_TSDF_MAX_DIRECTORY.
+ * Voxel (i, j, k) has its centre at origin[a] + ((double)i_a + 0.5) * voxel, every operation rounded.  A block's linear index is
+ * (z by + y) bx + x; inside a block voxels are indexed [z][y][x].
+ *
+ * Integration.  depths (n, rows, cols) float32 z-depth (0 or non-finite: no sample), cams (n,16) doubles in atvs_scan_render's
+ * layout, images (n, rows, cols, channels >= 3) float32 with b, g, r in channels 0..2, or NULL.  Per voxel, views ascending, in
+ * double, nothing contracted: the centre is projected by atvs_scan_render's projection (csrc/scan_project.h; in view when c_2 > 0,
+ * (float)c_2 finite and > 0, 0 <= xs < cols, 0 <= ys < rows); the pixel is (floor(xs), floor(ys)), d its depth; the view
+ * contributes when d > 0, d is finite and sdf = (double)d - c_2 lies in [-trunc, trunc]; then S += sdf / trunc, W += 1,
+ * C[c] += (double)image[c].  tsdf = (float)(S / W), weight = (float)W, color[c] = (float)(C[c] / W); all 0 where W = 0.  A view
+ * outside the narrow band adds nothing (no free-space carving), so a voxel's values do not depend on which blocks exist.
+ *   atvs_tsdf_mark: directory (bx by bz unsigned words) = 1 for every block that the padded box of some pixel's frustum segment
+ *   [d - trunc, d + trunc] meets, 0 elsewhere -- a superset of the blocks with a contributing voxel; err (one int) = 1 when a
+ *   pixel's box meets more than ATVS_TSDF_MAX_PIXEL_BLOCKS blocks (the voxel is too small for these maps), else 0.
+ *   atvs_tsdf_scan: counters (count unsigned words) -> their exclusive prefix sum in place, total[0] (device, 64-bit) = their sum.
+ *   scratch: atvs_tsdf_scan_scratch_size(count) bytes.  count = 0 writes total alone.  count beyond 2^31: ATVS_ERR_SHAPE.
+ *   atvs_tsdf_assign: slots = the scanned directory, count its total -> coords (count,3) int32 (x, y, z of each slot's block,
+ *   ascending in the linear index) and masks (count, ceil(n / 64)) 64-bit words: bit v of a slot is set when a pixel of view v
+ *   marked the block.
+ *   atvs_tsdf_integrate: one workgroup per slot over the views of its mask -> tsdf, weight (count,8,8,8), color (count,8,8,8,3) or
+ *   NULL with images NULL, any (count unsigned words) = 1 where the slot has a voxel of weight > 0.
+ *   atvs_tsdf_gather: keep = the scanned `any`, kept its total -> the kept slots, in order, in coords_out, tsdf_out, weight_out,
+ *   color_out: exactly the blocks that have a voxel of weight > 0.
+ * trunc <= 0 or not finite, voxel <= 0 or not finite, a non-finite origin or pixel_centre: ATVS_ERR_ARG; n rows cols >= 2^31,
+ * n outside [1, ATVS_SCAN_RENDER_MAX_CAMS], a box beyond the limit, count beyond the directory, channels < 3: ATVS_ERR_SHAPE.
+ *
+ * Extraction.  blocks (nb,3) int32 ascending in the linear index, each at most once, nb <= ATVS_TSDF_MAX_MESH_BLOCKS; tsdf, weight
+ * (nb,8,8,8), color (nb,8,8,8,3) or NULL.  A voxel is VALID when weight >= min_weight (a voxel of a missing block or outside the
+ * box is not); INSIDE means tsdf < 0.  The cube of voxel (i, j, k) has the 8 centres (i..i+1, j..j+1, k..k+1) and is meshed when
+ * all 8 are valid.  Its six Kuhn tetrahedra are taken in the lexicographic order of the axis permutations; for (a, b, c) the local
+ * vertices are 0 = corner 000, 1 = +e_a, 2 = +e_a + e_b, 3 = corner 111.  One local vertex s on one side: the triangle over the
+ * edges (s, o_0), (s, o_1), (s, o_2), the others ascending.  Two and two, inside {a < b}, outside {c < d}: (ac, ad, bd), then
+ * (ac, bd, bc).  A triangle's last two vertices are swapped when its normal, with every crossing at its edge's midpoint, points
+ * against (centroid of the outside corners - centroid of the inside corners): normals point into free space.  Then it is rotated
+ * so that its smallest vertex index comes first.  A vertex lives on an edge, owned by the edge's lower voxel; the seven edge types
+ * are the offsets (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1).  An edge has a vertex when its endpoints differ in
+ * INSIDE and a meshed cube has both among its corners.  With fa, fb the endpoints' tsdf as doubles: t = fa / (fa - fb),
+ * p = pa + t * (pb - pa) per coordinate in double, cast to float32; colour = floor((ca + t * (cb - ca)) + 0.5) clamped to 0..255,
+ * stored r, g, b.  Vertices are ordered by owning voxel (blocks ascending, x fastest inside a block), then edge type; faces by
+ * cube in that order, then tetrahedron, then the two triangles.  Zero-area triangles (tsdf == 0 at a corner) are kept.
+ *   atvs_tsdf_mesh_count: cube_ok, emask (nb 512 bytes each), vcount, fcount (nb 512 unsigned words each): per voxel whether its
+ *   cube is meshed, the set of its edge types that carry a vertex, their number, its cube's triangles.
+ *   atvs_tsdf_mesh_emit: vstart, fstart = vcount, fcount after atvs_tsdf_scan, n_vertices, n_faces their totals -> vertices
+ *   (n_vertices,3) float32, colors (n_vertices,3) bytes or NULL with color NULL, faces (n_faces,3) int32.
+ * A NaN min_weight: ATVS_ERR_ARG; nb negative, beyond the limit or the box: ATVS_ERR_SHAPE. */
+#define ATVS_TSDF_MAX_DIRECTORY 67108864
+#define ATVS_TSDF_MAX_MESH_BLOCKS 262144
+#define ATVS_TSDF_MAX_PIXEL_BLOCKS 4096
+int atvs_tsdf_scan_scratch_size(long count, long* bytes);
+int atvs_tsdf_scan(void* counters, long count, void* scratch, long scratch_bytes, long long* total, atvs_stream_t stream);
+int atvs_tsdf_mark(const float* depths, const double* cams, int n, int rows, int cols, double voxel, double trunc,
+                   const double* origin, int bx, int by, int bz, double pixel_centre, void* directory, int* err,
+                   atvs_stream_t stream);
+int atvs_tsdf_assign(const float* depths, const double* cams, int n, int rows, int cols, double voxel, double trunc,
+                     const double* origin, int bx, int by, int bz, double pixel_centre, const void* slots, long count, int* coords,
+                     void* masks, int* err, atvs_stream_t stream);
+int atvs_tsdf_integrate(const float* depths, const float* images, int channels, const double* cams, int n, int rows, int cols,
+                        double voxel, double trunc, const double* origin, int bx, int by, int bz, double pixel_centre,
+                        const int* coords, const void* masks, long count, float* tsdf, float* weight, float* color, void* any,
+                        atvs_stream_t stream);
+int atvs_tsdf_gather(const int* coords, const float* tsdf, const float* weight, const float* color, const void* keep, long count,
+                     long kept, int* coords_out, float* tsdf_out, float* weight_out, float* color_out, atvs_stream_t stream);
+int atvs_tsdf_mesh_count(const int* blocks, int nb, int bx, int by, int bz, const float* tsdf, const float* weight,
+                         float min_weight, void* cube_ok, void* emask, void* vcount, void* fcount, atvs_stream_t stream);
+int atvs_tsdf_mesh_emit(const int* blocks, int nb, int bx, int by, int bz, double voxel, const double* origin, const float* tsdf,
+                        const float* color, const void* emask, const void* vstart, const void* fstart, long n_vertices,
+                        long n_faces, float* vertices, void* colors, int* faces, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
