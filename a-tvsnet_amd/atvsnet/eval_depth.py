@@ -7,15 +7,20 @@ reference's own metrics (eval_errors.calc_error, on the host: a map is a few 10^
 
     camera_rows          the driver's (2,4,4) cameras -> the 16 doubles per camera the kernel reads
     inverse_similarity   the inverse of a recon -> scan matrix (eval_cloud --register / --save_transform)
-    render_scan          the scan, moved into the reconstruction's frame, rendered into the cameras
+    render_scan          the scan, moved into the reconstruction's frame, rendered into the cameras; with occlusion meshes, the
+                         pixels whose scan depth lies behind a mesh are taken out
+    render_mesh          a triangle mesh rendered into the cameras (ops.mesh_render): an occluder, or the ground truth itself
     score_maps           calc_error per map, valid-pixel counts, coverage, the mean over the scored maps
 
-This is NOT ETH3D's renderer: the scan's own visibility (which scanner position saw which point) and ETH3D's occlusion meshes are
-not used; a point splat with a depth test stands in for them.  `splat` and `occlusion_tol` have defaults, not measurements.
-This module imports without a GPU; only render_scan needs one.
+This is NOT ETH3D's renderer: the scan's own visibility (which scanner position saw which point) and ETH3D's splat-file occluders
+are not used; a point splat with a depth test stands in for the former.  Occlusion meshes (--occlusion_mesh) are rasterised exactly
+(csrc/mesh_render.hip), and a mesh can be the ground truth itself (--gt_mesh).  `splat`, `occlusion_tol`
+and `occlusion_mesh_tol` have defaults, not measurements.  This module imports without a GPU; only the renderers need one.
 
     python -m atvsnet_amd.atvsnet.eval_depth --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --gt scan.ply[,...]
         [--transform T.txt] [--splat S --occlusion_tol E --pixel_centre C] --out depth_eval.json [--save_gt DIR]
+        [--occlusion_mesh mesh.ply[,...] [--occlusion_mesh_tol E]]
+    python -m atvsnet_amd.atvsnet.eval_depth --scene ... --maps ... --gt_mesh surface.ply[,...] [--occlusion_mesh ...] --out ...
 """
 import argparse
 import json
@@ -27,6 +32,7 @@ from . import eval_errors
 
 DEFAULT_SPLAT = 2                  # a default, not a measurement: a 5 x 5 window closes the gaps of a scan about as dense as the map
 DEFAULT_OCCLUSION_TOL = 0.05       # a default, not a measurement: 5 % of the depth
+DEFAULT_OCCLUDER_TOL = 0.01        # a default, not a measurement: an occluder modelled ON the scan lies within 1 % of the scan's own depth
 DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel coordinates: the convention that places the cloud
 DEFAULT_MIN_VALID = 100            # as many jointly valid pixels as calc_error has depth bins
 SIMILARITY_TOLERANCE = 1e-9
@@ -80,27 +86,94 @@ def inverse_similarity(T):
     return inv
 
 
-def render_scan(points, cams, rows, cols, transform=None, pixel_centre=DEFAULT_PIXEL_CENTRE, splat=DEFAULT_SPLAT,
-                occlusion_tol=DEFAULT_OCCLUSION_TOL, device=None):
-    """points (n,3) float32 (host array or device tensor): the scan; cams: (n_cams,2,4,4) driver cameras or (n_cams,16) rows.
-    transform: None, or the 4x4 recon -> scan matrix that eval_cloud --register found (--save_transform): the scan is moved by its
-    inverse (ops.cloud_transform: float64, rounded once to float32) into the reconstruction's frame before it is rendered, so the
-    depths come out in the reconstruction's units.  -> (n_cams, rows, cols) float32 on the device (ops.scan_render)."""
+def _camera_rows16(cams):
+    c = np.asarray(cams, np.float64)
+    return c if c.ndim == 2 and c.shape[1] == 16 else camera_rows(c)
+
+
+def _points_on(points, dev, inv):
+    """points (host array or tensor) -> (n,3) float32 on `dev`, moved by the 4x4 `inv` (ops.cloud_transform) unless it is None."""
     import torch
     from .. import ops
-    c = np.asarray(cams, np.float64)
-    c = c if c.ndim == 2 and c.shape[1] == 16 else camera_rows(c)
+    if isinstance(points, torch.Tensor):
+        p = points.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    else:
+        p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
+    return p if inv is None else ops.cloud_transform(p, inv)
+
+
+def concat_meshes(meshes):
+    """[(vertices (V,3), faces (F,3)), ...] host arrays -> one (vertices float32, faces int32), face indices offset."""
+    vs, fs, base = [], [], 0
+    for v, f in meshes:
+        v = np.asarray(v, np.float32).reshape(-1, 3)
+        vs.append(v)
+        fs.append(np.asarray(f, np.int64).reshape(-1, 3) + base)
+        base += len(v)
+    if not vs:
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.int32)
+    return np.concatenate(vs, 0), np.concatenate(fs, 0).astype(np.int32)
+
+
+def load_meshes(paths):
+    """PLY triangle meshes (tools/ply.read_mesh where the file is this project's, ply.read_mesh_any otherwise) -> concat_meshes of
+    them."""
+    from ..tools import ply
+    meshes = []
+    for p in paths:
+        try:
+            v, _, f = ply.read_mesh(p)
+        except (ValueError, IndexError):
+            v, f = ply.read_mesh_any(p)
+        meshes.append((v, f))
+    return concat_meshes(meshes)
+
+
+def render_mesh(vertices, faces, cams, rows, cols, transform=None, pixel_centre=DEFAULT_PIXEL_CENTRE, device=None):
+    """vertices (V,3) float32 and faces (F,3) int32 (host arrays or device tensors); cams: (n_cams,2,4,4) driver cameras or
+    (n_cams,16) rows.  transform: None, or the 4x4 recon -> scan matrix: the vertices are moved by its inverse exactly as render_scan
+    moves the scan.  -> (depth (n_cams, rows, cols) float32, face (n_cams, rows, cols) int32) on the device (ops.mesh_render): the
+    nearest depth of the mesh at every pixel centre and the face that gives it, (0, -1) where there is none."""
+    import torch
+    from .. import ops
+    c = _camera_rows16(cams)
     inv = None if transform is None else inverse_similarity(transform)
     dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
     with torch.cuda.device(dev):
-        if isinstance(points, torch.Tensor):
-            p = points.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+        v = _points_on(vertices, dev, inv)
+        if isinstance(faces, torch.Tensor):
+            f = faces.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
         else:
-            p = torch.from_numpy(np.ascontiguousarray(np.asarray(points, np.float32).reshape(-1, 3))).to(dev)
-        if inv is not None:
-            p = ops.cloud_transform(p, inv)
+            f = torch.from_numpy(np.ascontiguousarray(np.asarray(faces, np.int32).reshape(-1, 3))).to(dev)
         rows_d = torch.from_numpy(np.ascontiguousarray(c)).to(dev)
-        return ops.scan_render(p, rows_d, int(rows), int(cols), pixel_centre=pixel_centre, splat=splat, occlusion_tol=occlusion_tol)
+        return ops.mesh_render(v, f, rows_d, int(rows), int(cols), pixel_centre=pixel_centre)
+
+
+def render_scan(points, cams, rows, cols, transform=None, pixel_centre=DEFAULT_PIXEL_CENTRE, splat=DEFAULT_SPLAT,
+                occlusion_tol=DEFAULT_OCCLUSION_TOL, device=None, occluders=None, occluder_tol=DEFAULT_OCCLUDER_TOL):
+    """points (n,3) float32 (host array or device tensor): the scan; cams: (n_cams,2,4,4) driver cameras or (n_cams,16) rows.
+    transform: None, or the 4x4 recon -> scan matrix that eval_cloud --register found (--save_transform): the scan is moved by its
+    inverse (ops.cloud_transform: float64, rounded once to float32) into the reconstruction's frame before it is rendered, so the
+    depths come out in the reconstruction's units.  -> (n_cams, rows, cols) float32 on the device (ops.scan_render).
+
+    occluders: None, or a list of (vertices, faces) occlusion meshes in the scan's frame.  They are concatenated, rendered by
+    render_mesh under the same transform, and a pixel of the resolved scan map whose depth is further than the mesh's times
+    (1 + occluder_tol) becomes 0 (ops.depth_occlude).  Applied after the scan is resolved, this is the test of every scan point
+    against the occluder at its pixel: where the nearest point of a pixel is occluded, every farther one is too."""
+    import torch
+    from .. import ops
+    c = _camera_rows16(cams)
+    inv = None if transform is None else inverse_similarity(transform)
+    dev = torch.device('cuda', torch.cuda.current_device()) if device is None else torch.device(device)
+    with torch.cuda.device(dev):
+        p = _points_on(points, dev, inv)
+        rows_d = torch.from_numpy(np.ascontiguousarray(c)).to(dev)
+        depth = ops.scan_render(p, rows_d, int(rows), int(cols), pixel_centre=pixel_centre, splat=splat, occlusion_tol=occlusion_tol)
+        if occluders:
+            v, f = concat_meshes(occluders)
+            wall, _ = render_mesh(v, f, c, rows, cols, transform=transform, pixel_centre=pixel_centre, device=dev)
+            ops.depth_occlude(depth, wall, tol=occluder_tol, out=depth)
+        return depth
 
 
 def _valid(a):
@@ -144,11 +217,17 @@ def score_maps(pred, gt, min_valid=DEFAULT_MIN_VALID, indices=None):
 
 
 def report(pred, gt, indices=None, min_valid=DEFAULT_MIN_VALID, transform=None, pixel_centre=DEFAULT_PIXEL_CENTRE,
-           splat=DEFAULT_SPLAT, occlusion_tol=DEFAULT_OCCLUSION_TOL):
-    """score_maps plus the rendering's parameters: what depth_eval.json holds."""
+           splat=DEFAULT_SPLAT, occlusion_tol=DEFAULT_OCCLUSION_TOL, occlusion_mesh_tol=None, occlusion_faces=None, gt_mesh=None):
+    """score_maps plus the rendering's parameters: what depth_eval.json holds.  occlusion_mesh_tol and occlusion_faces (the
+    occluders' tolerance and face count) and gt_mesh (the face count of a mesh that WAS the ground truth) appear only when given."""
     out = score_maps(pred, gt, min_valid=min_valid, indices=indices)
     out.update(rows=int(np.shape(pred)[1]), cols=int(np.shape(pred)[2]), pixel_centre=float(pixel_centre), splat=int(splat),
                occlusion_tol=float(occlusion_tol), transform=None if transform is None else np.asarray(transform, np.float64).reshape(4, 4).tolist())
+    if occlusion_faces is not None or occlusion_mesh_tol is not None:
+        out.update(occlusion_mesh_tol=float(DEFAULT_OCCLUDER_TOL if occlusion_mesh_tol is None else occlusion_mesh_tol),
+                   occlusion_faces=int(occlusion_faces or 0))
+    if gt_mesh is not None:
+        out.update(gt_mesh=int(gt_mesh))
     return out
 
 
@@ -205,7 +284,14 @@ def make_parser():
     parser.add_argument('--scene', default=None, help='<data_root>/eth3d/<scene>: its pair.txt names the maps to score '
                                                       '(default: every map found under --maps)')
     parser.add_argument('--maps', required=True, help='<savepath>/<scene> of eval_pointcloud: depths_atvsnet/%%08d.pfm and %%08d.txt')
-    parser.add_argument('--gt', required=True, metavar='FILE[,FILE...]', help='the scan: PLY file(s), concatenated')
+    parser.add_argument('--gt', default=None, metavar='FILE[,FILE...]', help='the scan: PLY file(s), concatenated')
+    parser.add_argument('--gt_mesh', default=None, metavar='FILE[,FILE...]',
+                        help='instead of --gt: triangle-mesh PLY file(s); the ground-truth maps are the rendered mesh itself '
+                             '(--splat and --occlusion_tol do not apply)')
+    parser.add_argument('--occlusion_mesh', default=None, metavar='FILE[,FILE...]',
+                        help='triangle-mesh PLY file(s) in the ground truth\'s frame: a ground-truth pixel behind them is taken out')
+    parser.add_argument('--occlusion_mesh_tol', type=float, default=None,
+                        help='a pixel is kept when its depth is within (1 + this) of the occlusion mesh\'s (default %g)' % DEFAULT_OCCLUDER_TOL)
     parser.add_argument('--transform', default=None, metavar='FILE',
                         help='text file with the 4x4 recon -> scan matrix (eval_cloud --save_transform); the scan is moved by its inverse')
     parser.add_argument('--splat', type=int, default=DEFAULT_SPLAT, help='half-width of the occlusion window in pixels, 0..4')
@@ -231,10 +317,19 @@ def cli(argv=None):
         parser.error('--pixel_centre must be finite')
     if args.min_valid < 1:
         parser.error('--min_valid must be at least 1')
-    gt_paths = [p for p in args.gt.split(',') if p]
+    if (args.gt is None) == (args.gt_mesh is None):
+        parser.error('exactly one of --gt and --gt_mesh is required')
+    gt_paths = [p for p in (args.gt if args.gt is not None else args.gt_mesh).split(',') if p]
     if not gt_paths:
-        parser.error('--gt names no file')
-    for p in gt_paths + ([args.transform] if args.transform else []):
+        parser.error('%s names no file' % ('--gt' if args.gt is not None else '--gt_mesh'))
+    if args.occlusion_mesh_tol is not None and args.occlusion_mesh is None:
+        parser.error('--occlusion_mesh_tol needs --occlusion_mesh')
+    if args.occlusion_mesh_tol is not None and not (args.occlusion_mesh_tol >= 0.0 and np.isfinite(args.occlusion_mesh_tol)):
+        parser.error('--occlusion_mesh_tol must be >= 0 and finite')
+    occ_paths = [p for p in (args.occlusion_mesh or '').split(',') if p]
+    if args.occlusion_mesh is not None and not occ_paths:
+        parser.error('--occlusion_mesh names no file')
+    for p in gt_paths + occ_paths + ([args.transform] if args.transform else []):
         if not os.path.isfile(p):
             parser.error('%s: no such file' % p)
     if not os.path.isdir(args.maps):
@@ -251,16 +346,36 @@ def cli(argv=None):
         except ValueError as e:
             parser.error('--transform %s: %s' % (args.transform, e))
     indices, pred, cams = load_maps(args.maps, scene_indices(args.scene) if args.scene is not None else None)
-    scan = np.concatenate([ply.read_ply_points(p) for p in gt_paths], 0)
+    extra = {}
+    try:
+        occluder = load_meshes(occ_paths) if occ_paths else None
+        surface = load_meshes(gt_paths) if args.gt_mesh is not None else None
+    except ValueError as e:
+        parser.error(str(e))
+    occ_tol = DEFAULT_OCCLUDER_TOL if args.occlusion_mesh_tol is None else args.occlusion_mesh_tol
+    if occluder is not None:
+        extra.update(occlusion_mesh_tol=occ_tol, occlusion_faces=len(occluder[1]))
     import torch
     torch.cuda.set_device(args.gpu_id)
     options = dict(pixel_centre=args.pixel_centre, splat=args.splat, occlusion_tol=args.occlusion_tol)
-    gt = render_scan(scan, cams, pred.shape[1], pred.shape[2], transform=transform, **options).cpu().numpy()
+    if surface is None:
+        scan = np.concatenate([ply.read_ply_points(p) for p in gt_paths], 0)
+        gt = render_scan(scan, cams, pred.shape[1], pred.shape[2], transform=transform, occluders=occluder and [occluder],
+                         occluder_tol=occ_tol, **options).cpu().numpy()
+    else:
+        from .. import ops
+        extra.update(gt_mesh=len(surface[1]))
+        gt, _ = render_mesh(surface[0], surface[1], cams, pred.shape[1], pred.shape[2], transform=transform, pixel_centre=args.pixel_centre)
+        if occluder is not None:
+            wall, _ = render_mesh(occluder[0], occluder[1], cams, pred.shape[1], pred.shape[2], transform=transform,
+                                  pixel_centre=args.pixel_centre)
+            ops.depth_occlude(gt, wall, tol=occ_tol, out=gt)
+        gt = gt.cpu().numpy()
     if args.save_gt:
         os.makedirs(args.save_gt, exist_ok=True)
         for i, g in zip(indices, gt):
             np.save(os.path.join(args.save_gt, '%08d_gt.npy' % i), g)
-    result = report(pred, gt, indices=indices, min_valid=args.min_valid, transform=transform, **options)
+    result = report(pred, gt, indices=indices, min_valid=args.min_valid, transform=transform, **dict(options, **extra))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_json(args.out, result)

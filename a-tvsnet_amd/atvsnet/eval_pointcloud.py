@@ -478,11 +478,20 @@ def _score_maps(scene_fusion, map_cams, score, folder, device, gt_points, score_
     order = scene_fusion.order()
     indices = [scene_fusion.index[k] for k in order]
     moved = score['registration']['matrix'] if 'registration' in score else None
+    score_maps = dict(score_maps)
+    files, tol = score_maps.pop('occlusion_mesh', None), score_maps.pop('occlusion_mesh_tol', None)
+    occlude, extra = {}, {}
+    if files:                                                            # the occluded maps, and what occluded them in the report
+        occluder = eval_depth.load_meshes(files)
+        tol = eval_depth.DEFAULT_OCCLUDER_TOL if tol is None else tol
+        occlude = dict(occluders=[occluder], occluder_tol=tol)
+        extra = dict(occlusion_mesh_tol=tol, occlusion_faces=len(occluder[1]))
     gt_maps = eval_depth.render_scan(gt_points, np.stack([map_cams[i] for i in indices]), scene_fusion.rows, scene_fusion.cols,
-                                     transform=moved, device=device, **score_maps)
+                                     transform=moved, device=device, **dict(score_maps, **occlude))
     pred = scene_fusion.nd[:len(indices), :, :, 3][torch.from_numpy(order).to(device)]
     eval_depth.write_json(os.path.join(folder, 'depth_eval.json'),
-                          eval_depth.report(pred.cpu().numpy(), gt_maps.cpu().numpy(), indices=indices, transform=moved, **score_maps))
+                          eval_depth.report(pred.cpu().numpy(), gt_maps.cpu().numpy(), indices=indices, transform=moved,
+                                            **dict(score_maps, **extra)))
     TIMES['depth_eval'] = time.time() - t0
 
 
@@ -517,6 +526,8 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
     t0 = time.time()
     scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
     n_faces = scene_mesh.write_ply(os.path.join(folder, 'final3d_mesh.ply'))
+    if mesh.get('render'):
+        scene_mesh.render(os.path.join(folder, 'depths_mesh'))
     mesh_fusion.write_json(os.path.join(folder, 'mesh.json'), scene_mesh.report())
     TIMES['mesh'] = time.time() - t0
     return n_faces
@@ -627,11 +638,14 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     after the scene's fusion the ground truth is rendered into the scene's cameras (in SceneFusion.order()) and the staged,
     probability-filtered depth planes -- what enters the cloud -- are scored against it (eval_depth.score_maps) into
     <savepath>/<scene>/depth_eval.json.  With register the ground truth is moved by the inverse of the matrix already found (no
-    second fit).  Every other output is what it is without it.
+    second fit).  With occlusion_mesh= (a list of triangle-mesh PLY files in the ground truth's frame) and occlusion_mesh_tol= in
+    the dict, a rendered pixel that lies behind those meshes is taken out first (eval_depth.render_scan's occluders).  Every other
+    output is what it is without it.
     mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=), the arguments of mesh_fusion.SceneMesh:
     after the scene's fusion the staged depth planes and images are integrated into a TSDF volume bounded by the fused cloud and
-    meshed by marching tetrahedra into <savepath>/<scene>/final3d_mesh.ply, with the report in mesh.json.  Every other output is
-    what it is without it."""
+    meshed by marching tetrahedra into <savepath>/<scene>/final3d_mesh.ply, with the report in mesh.json; with render=True the
+    mesh is also rendered into the scene's map cameras as <savepath>/<scene>/depths_mesh/%08d_mesh.pfm (SceneMesh.render).  Every
+    other output is what it is without it."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
                    clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals,
@@ -719,7 +733,19 @@ def _mesh_options(flags):
     """run_eval_pc's mesh from cli's --mesh_* options: those that were given, None when none was."""
     names = dict(mesh_voxel='voxel', mesh_trunc_voxels='trunc_voxels', mesh_min_weight='min_weight', mesh_max_blocks='max_blocks')
     given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
+    if getattr(flags, 'mesh_render', False):
+        given['render'] = True
     return given or None
+
+
+def _map_occlusion_options(flags):
+    """score_maps' occlusion_mesh (a list of files) and occlusion_mesh_tol from cli's --map_occlusion_mesh options: those given."""
+    files = getattr(flags, 'map_occlusion_mesh', None)
+    if not files:
+        return {}
+    files = [p for p in files.split(',') if p] if isinstance(files, str) else list(files)
+    tol = getattr(flags, 'map_occlusion_mesh_tol', None)
+    return dict({'occlusion_mesh': files}, **({} if tol is None else {'occlusion_mesh_tol': tol}))
 
 
 def _run_options(flags):
@@ -739,7 +765,8 @@ def _run_options(flags):
         clean_keep_normals=bool(opt('clean_keep_normals')),
         score_maps=dict(splat=opt('map_splat', eval_depth.DEFAULT_SPLAT),
                         occlusion_tol=opt('map_occlusion_tol', eval_depth.DEFAULT_OCCLUSION_TOL),
-                        pixel_centre=opt('map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE)) if opt('score_maps') else None)
+                        pixel_centre=opt('map_pixel_centre', eval_depth.DEFAULT_PIXEL_CENTRE),
+                        **_map_occlusion_options(flags)) if opt('score_maps') else None)
 
 
 def main(scene_list=None, base_path='eth3d/'):
@@ -824,6 +851,12 @@ def cli(argv=None):
                         help='--score_maps: a pixel is kept when its depth is within (1 + this) of the nearest in its window')
     parser.add_argument('--map_pixel_centre', type=float, default=eval_depth.DEFAULT_PIXEL_CENTRE,
                         help='--score_maps: image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5 (the plane sweep\'s)')
+    parser.add_argument('--map_occlusion_mesh', default=None, metavar='FILE[,FILE...]',
+                        help='--score_maps: triangle-mesh PLY file(s) in the ground truth\'s frame; a rendered ground-truth pixel that '
+                             'lies behind them is taken out (eval_depth --occlusion_mesh)')
+    parser.add_argument('--map_occlusion_mesh_tol', type=float, default=None, metavar='E',
+                        help='--map_occlusion_mesh: a pixel is kept when its depth is within (1 + this) of the mesh\'s (default %g)'
+                             % eval_depth.DEFAULT_OCCLUDER_TOL)
     clean_cloud.add_options(parser, 'clean_')
     parser.add_argument('--clean_keep_normals', action='store_true',
                         help='--fuse_normals depth with a cleaning step: final3d_model_clean.ply carries the normals of the rows that '
@@ -837,6 +870,9 @@ def cli(argv=None):
                         help='--mesh_voxel: views a voxel needs to be meshed (default 2, the fusion\'s num_consistent)')
     parser.add_argument('--mesh_max_blocks', type=int, default=None, metavar='N',
                         help='--mesh_voxel: blocks of 8^3 voxels the maps may mark (default 131072)')
+    parser.add_argument('--mesh_render', action='store_true',
+                        help='--mesh_voxel: render the mesh into the scene\'s map cameras (ops.mesh_render) as '
+                             '<savepath>/<scene>/depths_mesh/%%08d_mesh.pfm; mesh.json gains `render`')
     args = parser.parse_args(argv)
     # what only the command line can break; the rest is _option_rules
     if (args.with_scale or args.init_cameras) and not args.register:
@@ -863,6 +899,16 @@ def cli(argv=None):
     if not args.score_maps and (args.map_splat != eval_depth.DEFAULT_SPLAT or args.map_occlusion_tol != eval_depth.DEFAULT_OCCLUSION_TOL
                                 or args.map_pixel_centre != eval_depth.DEFAULT_PIXEL_CENTRE):
         parser.error('--map_splat, --map_occlusion_tol and --map_pixel_centre need --score_maps')
+    if not args.score_maps and (args.map_occlusion_mesh is not None or args.map_occlusion_mesh_tol is not None):
+        parser.error('--map_occlusion_mesh and --map_occlusion_mesh_tol need --score_maps')
+    if args.map_occlusion_mesh_tol is not None and args.map_occlusion_mesh is None:
+        parser.error('--map_occlusion_mesh_tol needs --map_occlusion_mesh')
+    if args.map_occlusion_mesh_tol is not None and not (args.map_occlusion_mesh_tol >= 0.0 and np.isfinite(args.map_occlusion_mesh_tol)):
+        parser.error('--map_occlusion_mesh_tol must be >= 0 and finite')
+    if args.map_occlusion_mesh is not None and not [p for p in args.map_occlusion_mesh.split(',') if p]:
+        parser.error('--map_occlusion_mesh names no file')
+    if args.mesh_render and args.mesh_voxel is None:
+        parser.error('--mesh_render needs --mesh_voxel')
     if not 0 <= args.map_splat <= 4:
         parser.error('--map_splat must be in 0..4')
     if not (args.map_occlusion_tol >= 0.0 and np.isfinite(args.map_occlusion_tol)) or not np.isfinite(args.map_pixel_centre):

@@ -5,6 +5,7 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     mesh_maps      depth maps, cameras, images and a box -> the volume, the mesh, seconds per stage
     SceneMesh      the mesh of a depth_fusion.SceneFusion: its staged planes in fusion order, the box of its fused points
     mesh_report    blocks, valid voxels, vertices, faces, zero-area faces, boundary edges
+    render_views   the mesh rendered into cameras (ops.mesh_render), one %08d_mesh.pfm per map
 
 What this is not: there is no free-space carving (a view adds to a voxel only inside the narrow band around its depth), no per-view
 weight, no consistency mask on the depths beyond the probability filter, no mesh simplification, no hole filling, and the PLY
@@ -12,6 +13,7 @@ carries no normals.  `trunc_voxels` and `min_weight` have defaults, not measurem
 
     python -m atvsnet_amd.atvsnet.mesh_fusion --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --voxel V
         [--trunc_voxels 4 --min_weight 2 --prob_threshold 0.8 --pixel_centre 0 --max_blocks N --report mesh.json] --out mesh.ply
+        [--render DIR]
 """
 import argparse
 import json
@@ -29,8 +31,9 @@ DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel 
 
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
-                  pixel_centre=DEFAULT_PIXEL_CENTRE):
-    """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError."""
+                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False):
+    """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
+    the driver also renders the mesh) has nothing to check."""
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
     if not (voxel > 0.0 and np.isfinite(voxel)):
         raise ValueError('mesh voxel must be positive and finite, got %r' % (voxel,))
@@ -119,6 +122,24 @@ def mesh_report(volume, mesh, min_weight, seconds=None):
             'seconds': dict(seconds or {})}
 
 
+def render_views(vertices, faces, cams16, rows, cols, folder, indices, pixel_centre=DEFAULT_PIXEL_CENTRE):
+    """The mesh (device tensors, as ops.tsdf_mesh returns them) rendered into the cameras cams16 (n,16) by ops.mesh_render and
+    written as folder/%08d_mesh.pfm, one per index -> {'maps': n, 'covered_fraction': share of pixels that see the mesh,
+    'seconds': render and download, ended by a device synchronisation}."""
+    import torch
+    from .preprocess import write_pfm
+    torch.cuda.synchronize(vertices.device)
+    t0 = time.time()
+    depth, _ = eval_depth.render_mesh(vertices, faces, np.asarray(cams16, np.float64).reshape(-1, 16), rows, cols,
+                                      pixel_centre=pixel_centre, device=vertices.device)
+    depth = depth.cpu().numpy()
+    seconds = time.time() - t0
+    os.makedirs(folder, exist_ok=True)
+    for i, d in zip(indices, depth):
+        write_pfm(os.path.join(folder, '%08d_mesh.pfm' % int(i)), np.ascontiguousarray(d, np.float32))
+    return {'maps': int(len(depth)), 'covered_fraction': float((depth > 0).mean()) if depth.size else 0.0, 'seconds': seconds}
+
+
 def write_json(path, result):
     with open(path, 'w') as f:
         json.dump(result, f, indent=1, sort_keys=True)
@@ -138,7 +159,7 @@ class SceneMesh(object):
     uint8 r, g, b, faces (F,3) int32) as numpy arrays."""
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE):
+                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
         self.fusion = scene_fusion
         k = len(scene_fusion.index)
@@ -150,7 +171,7 @@ class SceneMesh(object):
         self.cams16 = eval_depth.camera_rows(np.asarray(cams, np.float64))
         if len(self.cams16) != k:
             raise ValueError('SceneMesh: %d cameras for %d staged maps' % (len(self.cams16), k))
-        self.volume = self.result = self._report = None
+        self.volume = self.result = self._report = self._device_mesh = None
 
     def run(self):
         import torch
@@ -175,6 +196,7 @@ class SceneMesh(object):
             seconds.update(stage)
             t0 = time.time()
             self.result = tuple(None if t is None else t.cpu().numpy() for t in mesh)
+            self._device_mesh = mesh
             seconds['download'] = time.time() - t0
             t0 = time.time()
             self._report = mesh_report(self.volume, mesh, min_weight, seconds)
@@ -184,6 +206,17 @@ class SceneMesh(object):
     def report(self):
         self.run()
         return self._report
+
+    def render(self, folder):
+        """run(), then the mesh -- still on the device -- rendered into the scene's map cameras as folder/%08d_mesh.pfm
+        (render_views); report() gains `render`."""
+        self.run()
+        fusion = self.fusion
+        order = fusion.order()
+        vertices, _, faces = self._device_mesh
+        self._report['render'] = render_views(vertices, faces, self.cams16[order], fusion.rows, fusion.cols, folder,
+                                              [fusion.index[k] for k in order], self.options[4])
+        return self._report['render']
 
     def write_ply(self, path):
         """run() into a binary PLY at `path` (tools/ply.write_mesh) -> the number of faces."""
@@ -207,6 +240,8 @@ def make_parser():
     parser.add_argument('--bounds', default=None, metavar='PLY', help='bound the volume by this cloud (the scene\'s final3d_model.ply) instead of '
                                                                       'by the maps\' own back-projected depths')
     parser.add_argument('--report', default=None, metavar='FILE', help='write the report as JSON here')
+    parser.add_argument('--render', default=None, metavar='DIR', help='render the mesh into the maps\' cameras (ops.mesh_render) as '
+                                                                      'DIR/%%08d_mesh.pfm; the report gains `render`')
     parser.add_argument('--out', required=True, help='the mesh, a binary PLY')
     parser.add_argument('--gpu_id', type=int, default=0)
     return parser
@@ -273,6 +308,8 @@ def cli(argv=None):
     ply.write_mesh(args.out, vertices, colors, faces)
     result = dict(mesh_report(volume, mesh, args.min_weight, seconds), maps=[int(i) for i in indices], colored=images is not None,
                   probability_filtered=probs is not None)
+    if args.render:
+        result['render'] = render_views(mesh[0], mesh[2], cams16, depths.shape[1], depths.shape[2], args.render, indices, args.pixel_centre)
     if args.report:
         write_json(args.report, result)
     print(json.dumps({k: result[k] for k in ('blocks', 'valid_voxels', 'vertices', 'faces', 'zero_area_faces', 'boundary_edges')}))

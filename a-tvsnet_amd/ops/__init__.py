@@ -1,4 +1,4 @@
-"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in eleven modules --
+"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in twelve modules --
 
     base      ctypes plumbing, the dispatch switches (`cfg`, `configure`), launch timing
     packing   weights in operand order + their cache, tap lists, the chunk-planar layout
@@ -14,6 +14,7 @@
               outlier statistics, bounding box, normals by PCA over the k nearest; rendering: a scan splatted into cameras as nearest-depth maps; ETH3D-style
               scoring: a point's free-space excess against scanner cube maps, voxel-averaged shares
     tsdf      a surface from depth maps: a block-sparse TSDF volume integrated from them, a marching-tetrahedra mesh of it
+    mesh      a triangle mesh rendered into cameras (nearest depth and face per pixel), depth maps occluded by such a rendering
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -50,4 +51,5 @@ from .cloud import cloud_feature_nearest, cloud_fpfh, cloud_ransac      # noqa: 
 from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401
 from .tsdf import TSDF_MAX_DIRECTORY, TSDF_MAX_MESH_BLOCKS, TSDF_MAX_PIXEL_BLOCKS, TsdfVolume, tsdf_integrate, tsdf_mesh      # noqa: F401
+from .mesh import MESH_RENDER_SMALL_PIXELS, depth_occlude, mesh_render      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

@@ -201,3 +201,106 @@ def read_ply_points(path):
             raise bad('truncated body: %d bytes for %d vertices of %d bytes' % (len(body), count, dtype.itemsize))
         v = np.frombuffer(body, dtype, count)
         return np.stack([v['x'].astype(np.float32), v['y'].astype(np.float32), v['z'].astype(np.float32)], -1).reshape(count, 3)
+
+
+def read_mesh_any(path):
+    """-> (vertices (V,3) float32, faces (F,3) int32) of a third-party triangle-mesh PLY: `ascii`, `binary_little_endian` or
+    `binary_big_endian`; a `vertex` element with x, y, z as `float` or `double` among other scalar properties (skipped), then a
+    `face` element with one list property `vertex_indices` or `vertex_index`, its count and its indices of any integer type, among
+    other scalar properties (skipped); later elements are ignored.  A polygon with more than three corners (or fewer), any other
+    layout, a malformed header or a truncated body raises ValueError naming the file."""
+    def bad(why):
+        return ValueError('%s: %s' % (path, why))
+
+    with open(path, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise bad('not a PLY file (no "ply" magic)')
+        fmt, elements = None, []
+        while True:
+            raw = f.readline()
+            if not raw:
+                raise bad('the header has no end_header')
+            words = raw.decode('ascii', 'replace').split()
+            if not words or words[0] in ('comment', 'obj_info'):
+                continue
+            if words[0] == 'end_header':
+                break
+            if words[0] == 'format' and len(words) >= 2:
+                fmt = words[1]
+            elif words[0] == 'element' and len(words) == 3 and words[2].isdigit():
+                elements.append((words[1], int(words[2]), []))
+            elif words[0] == 'property' and elements:
+                if len(words) == 5 and words[1] == 'list' and words[2] in _PLY_TYPES and words[3] in _PLY_TYPES:
+                    elements[-1][2].append((words[4], _PLY_TYPES[words[2]], _PLY_TYPES[words[3]]))
+                elif len(words) == 3 and words[1] in _PLY_TYPES:
+                    elements[-1][2].append((words[2], _PLY_TYPES[words[1]], None))
+                else:
+                    raise bad('bad property line %r' % ' '.join(words))
+            else:
+                raise bad('bad header line %r' % ' '.join(words))
+        if fmt not in ('ascii', 'binary_little_endian', 'binary_big_endian'):
+            raise bad('unsupported format %r' % fmt)
+        if [e[0] for e in elements[:2]] != ['vertex', 'face']:
+            raise bad('expected a vertex element and then a face element, got %s' % [e[0] for e in elements])
+        (_, nv, vprops), (_, nf, fprops) = elements[:2]
+        vnames = [p[0] for p in vprops]
+        if any(p[2] is not None for p in vprops):
+            raise bad('a list property inside the vertex element is not supported')
+        for c in 'xyz':
+            if vnames.count(c) != 1 or vprops[vnames.index(c)][1] not in ('f4', 'f8'):
+                raise bad('the vertex element has no (single) float or double property %r' % c)
+        lists = [k for k, p in enumerate(fprops) if p[2] is not None]
+        if len(lists) != 1 or fprops[lists[0]][0] not in ('vertex_indices', 'vertex_index'):
+            raise bad('the face element needs exactly one list property, vertex_indices or vertex_index')
+        li = lists[0]
+        if fprops[li][1][0] not in 'iu' or fprops[li][2][0] not in 'iu':
+            raise bad('the face list\'s count and indices must be integers')
+
+        def polygon(i, n):
+            return bad('face %d is a polygon with %d corners: triangles only' % (i, n))
+        if fmt == 'ascii':
+            cols = [vnames.index(c) for c in 'xyz']
+            vertices = np.empty((nv, 3), np.float64)
+            for i in range(nv):
+                words = f.readline().split()
+                if len(words) < len(vprops):
+                    raise bad('truncated body: vertex %d of %d' % (i, nv))
+                try:
+                    vertices[i] = [float(words[c]) for c in cols]
+                except ValueError:
+                    raise bad('vertex %d: not a number' % i)
+            faces = np.empty((nf, 3), np.int64)
+            for i in range(nf):
+                words = f.readline().split()
+                try:
+                    if len(words) <= li:
+                        raise bad('truncated body: face %d of %d' % (i, nf))
+                    n = int(words[li])                          # scalars in front of the list hold one word each
+                    if n != 3:
+                        raise polygon(i, n)
+                    if len(words) < len(fprops) + 3:
+                        raise bad('truncated body: face %d of %d' % (i, nf))
+                    faces[i] = [int(w) for w in words[li + 1:li + 4]]
+                except ValueError as e:
+                    raise e if str(e).startswith(path) else bad('face %d: not an integer' % i)
+        else:
+            order = '<' if fmt == 'binary_little_endian' else '>'
+            vdtype = np.dtype([(n, order + t) for n, t, _ in vprops])
+            body = f.read(nv * vdtype.itemsize)
+            if len(body) != nv * vdtype.itemsize:
+                raise bad('truncated body: %d bytes for %d vertices of %d bytes' % (len(body), nv, vdtype.itemsize))
+            v = np.frombuffer(body, vdtype, nv)
+            vertices = np.stack([v['x'], v['y'], v['z']], -1).reshape(nv, 3)
+            fdtype = np.dtype([fld for p in fprops for fld in (
+                [('_n', order + p[1]), ('_v', order + p[2], (3,))] if p[2] is not None else [('s_' + p[0], order + p[1])])])
+            body = f.read(nf * fdtype.itemsize)                   # every face a triangle: records of one size
+            t = np.frombuffer(body[:len(body) // fdtype.itemsize * fdtype.itemsize], fdtype)
+            wrong = np.flatnonzero(t['_n'] != 3)
+            if wrong.size:                                        # the first record that is no triangle is still aligned
+                raise polygon(int(wrong[0]), int(t['_n'][wrong[0]]))
+            if len(t) != nf:
+                raise bad('truncated body: %d of %d faces' % (len(t), nf))
+            faces = t['_v'].astype(np.int64).reshape(nf, 3)
+    if nf and (faces.min() < 0 or faces.max() >= nv):
+        raise bad('a face index outside 0..%d' % (nv - 1))
+    return vertices.astype(np.float32).reshape(nv, 3), faces.astype(np.int32).reshape(nf, 3)

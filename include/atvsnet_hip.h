@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 58
+#define ATVS_ABI_VERSION 59
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1223,6 +1223,55 @@ int atvs_tsdf_mesh_count(const int* blocks, int nb, int bx, int by, int bz, cons
 int atvs_tsdf_mesh_emit(const int* blocks, int nb, int bx, int by, int bz, double voxel, const double* origin, const float* tsdf,
                         const float* color, const void* emask, const void* vstart, const void* fstart, long n_vertices,
                         long n_faces, float* vertices, void* colors, int* faces, atvs_stream_t stream);
+
+/* A triangle mesh rendered into cameras (ops/mesh.py mesh_render / depth_occlude, atvsnet/eval_depth.py, csrc/mesh_render.hip):
+ * per pixel the nearest depth of the mesh along the ray through the pixel's centre, and the face that gives it.  Pointers are
+ * device pointers.  A 64-bit integer atomic min and no float atomics: the outputs are a function of the inputs alone, bit for bit
+ * on every run.  No host synchronisation, no allocation; scratch is the caller's.  tests/mesh_render_restated.py restates the
+ * definition densely (every face against every pixel).
+ *
+ * The definition.  vertices (n_vertices,3) float32 in the cameras' frame, faces (n_faces,3) int32 indices into them, cams
+ * (n_cams,16) doubles in atvs_scan_render's layout (c = R row-major, t, fx, fy, cx, cy), maps of rows x cols pixels.  Everything
+ * in double, every operation rounded, nothing contracted, in exactly this order.
+ *   Camera-space vertices.  For a vertex (X, Y, Z) widened to double: C_k = ((c[3k] X + c[3k+1] Y) + c[3k+2] Z) + c[9+k],
+ *   k = 0, 1, 2 (atvs_scan_render's form).
+ *   Which faces take part.  A face (i0, i1, i2) with camera-space vertices A, B, D takes part in a camera when all nine
+ *   coordinates are finite and at least one of A_2, B_2, D_2 is > 0.
+ *   Cross products.  N0 = B x D, N1 = D x A, N2 = A x B, a component of a x b being a_1 b_2 - a_2 b_1 (and cyclic): two rounded
+ *   products and one subtraction.
+ *   Determinant.  det = (A_0 N0_0 + A_1 N0_1) + A_2 N0_2.
+ *   Pixel ray.  For pixel (u, v): rx = (((double)u + pixel_centre) - cx) / fx, ry = (((double)v + pixel_centre) - cy) / fy: the
+ *   centre of pixel u is the image coordinate u + pixel_centre, the convention under which atvs_scan_render sends x to
+ *   floor((x - pixel_centre) + 0.5).
+ *   Edge functions.  E_i = (Ni_0 rx + Ni_1 ry) + Ni_2, S = (E0 + E1) + E2.
+ *   Coverage.  The pixel is covered when (E0 >= 0 and E1 >= 0 and E2 >= 0 and S > 0) or (E0 <= 0 and E1 <= 0 and E2 <= 0 and
+ *   S < 0): both windings, both sides of every edge inclusive, no fill rule, no back-face culling.
+ *   Depth.  t = det / S, the camera depth of the point where the ray meets the face's plane (the ray's third component is 1).
+ *   The pixel takes part when t > 0 and z = (float)t is finite and > 0.
+ *   Per pixel.  The smallest key ((uint64)bits(z) << 32) | face index over the covered faces that take part: a positive float32
+ *   orders as its bits do, and on equal z the lower face index wins.  depth_out (n_cams, rows, cols) float32 = that z, 0 where
+ *   nothing is covered; face_out (n_cams, rows, cols) int32 = that face, -1 where nothing is covered.
+ * No near-plane clipping exists: a face with vertices behind the camera renders where it is in front.  a x b and b x a negate
+ * exactly, so the two faces of a shared edge get E and -E at every pixel centre: a closed mesh has no cracks.  Zero-area,
+ * edge-on (S = 0), repeated-index, NaN and infinite faces cover nothing.
+ *
+ * atvs_mesh_render.  A face with an index outside 0..n_vertices-1 is skipped; error_out (one int) = the number of such faces
+ * (0: none).  scratch: atvs_mesh_render_scratch_size(n_cams, rows, cols, n_faces) bytes: 8 per pixel and 12 per entry of a list
+ * of at most 2^22 (face, camera) pairs whose box holds more than ATVS_MESH_RENDER_SMALL_PIXELS pixels; the faces are walked in
+ * chunks that cannot fill the list, so no pair is dropped.  n_faces = 0: all-zero depth, all -1 faces.
+ * pixel_centre not finite: ATVS_ERR_ARG; n_cams * rows * cols >= 2^31, n_cams outside [1, ATVS_SCAN_RENDER_MAX_CAMS], rows or
+ * cols < 1, n_vertices negative or beyond 2^30, n_faces negative or 2^31 and more, a short scratch: ATVS_ERR_SHAPE.
+ *
+ * atvs_depth_occlude.  depth, occluder, out: `pixels` float32 each.  out = 0 where occluder > 0 and depth > 0 and
+ * !((double)depth <= (double)occluder * (1.0 + tol)), else out = depth: a NaN in either keeps depth.  out may be depth (in place).
+ * One launch; pixels = 0 writes nothing.  tol negative or not finite: ATVS_ERR_ARG; pixels negative or 2^31 and more:
+ * ATVS_ERR_SHAPE. */
+#define ATVS_MESH_RENDER_SMALL_PIXELS 64
+int atvs_mesh_render_scratch_size(int n_cams, int rows, int cols, long n_faces, long* bytes);
+int atvs_mesh_render(const float* vertices, long n_vertices, const int* faces, long n_faces, const double* cams, int n_cams, int rows,
+                     int cols, double pixel_centre, void* scratch, long scratch_bytes, float* depth_out, int* face_out,
+                     int* error_out, atvs_stream_t stream);
+int atvs_depth_occlude(const float* depth, const float* occluder, long pixels, double tol, float* out, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
