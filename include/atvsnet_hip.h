@@ -1196,6 +1196,13 @@ int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* e
  * p = pa + t * (pb - pa) per coordinate in double, cast to float32; colour = floor((ca + t * (cb - ca)) + 0.5) clamped to 0..255,
  * stored r, g, b.  Vertices are ordered by owning voxel (blocks ascending, x fastest inside a block), then edge type; faces by
  * cube in that order, then tetrahedron, then the two triangles.  Zero-area triangles (tsdf == 0 at a corner) are kept.
+ * Special values follow from these comparisons as written and from nothing else.  VALID is the comparison weight >= min_weight in
+ * float32: a NaN weight is never valid, a +inf weight is valid under every min_weight, min_weight = -inf makes every voxel of a
+ * present block valid (one of a missing block stays invalid).  INSIDE is the comparison tsdf < 0: +0, -0, a positive denormal, +inf
+ * and a NaN are outside, a negative denormal and -inf are inside.  t, p and the colour expression are plain IEEE double arithmetic,
+ * so a NaN or an infinite tsdf or colour goes through them as it does (inf / inf and 0 * inf are NaN; a vertex coordinate may be
+ * NaN, its sign and payload unspecified).  A colour is v = floor(x + 0.5), then 0 unless v >= 0, then 255 unless v <= 255: NaN and
+ * -inf give 0, +inf gives 255.
  *   atvs_tsdf_mesh_count: cube_ok, emask (nb 512 bytes each), vcount, fcount (nb 512 unsigned words each): per voxel whether its
  *   cube is meshed, the set of its edge types that carry a vertex, their number, its cube's triangles.
  *   atvs_tsdf_mesh_emit: vstart, fstart = vcount, fcount after atvs_tsdf_scan, n_vertices, n_faces their totals -> vertices

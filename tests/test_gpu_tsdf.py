@@ -7,6 +7,7 @@ import torch
 
 import tsdf_restated as R
 from scan_render_restated import ring_cameras
+from tsdf_cases import _mesh_equal, _volume_equal
 
 pytestmark = pytest.mark.gpu
 
@@ -23,29 +24,6 @@ def ops():
 
 def _dev(*arrays):
     return [None if a is None else torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in arrays]
-
-
-def _volume_equal(vol, want):
-    assert np.array_equal(vol.blocks.cpu().numpy(), want['blocks'])
-    f, w, c = vol.to_dense()
-    assert np.array_equal(f.view(np.uint32), want['tsdf'].view(np.uint32))
-    assert np.array_equal(w, want['weight'])
-    if want['color'] is None:
-        assert c is None
-    else:
-        assert np.array_equal(c.view(np.uint32), want['color'].view(np.uint32))
-    # exactly the blocks with a voxel of weight > 0
-    assert bool((vol.weight.reshape(vol.num_blocks, -1) > 0).any(dim=1).all())
-
-
-def _mesh_equal(got, want):
-    v, c, f = got
-    assert np.array_equal(v.cpu().numpy().view(np.uint32), want[0].view(np.uint32))
-    if want[1] is None:
-        assert c is None
-    else:
-        assert c.dtype == torch.uint8 and np.array_equal(c.cpu().numpy(), want[1])
-    assert f.dtype == torch.int32 and np.array_equal(f.cpu().numpy(), want[2])
 
 
 class Case(object):

@@ -98,7 +98,9 @@ def _tetra_triangles(corners, inside):
 
 def mesh(tsdf, weight, color, origin, voxel, min_weight=1.0, with_edges=False):
     """Dense [z][y][x] arrays -> (vertices (V,3) float32, colors (V,3) uint8 r, g, b or None, faces (F,3) int32); with_edges: and
-    every vertex's edge as (lower voxel (i, j, k), edge type)."""
+    every vertex's edge as (lower voxel (i, j, k), edge type).
+    Special values: valid is weight >= min_weight and inside is tsdf < 0 as float32 comparisons (a NaN is neither), t, p and the
+    colour expression are plain IEEE double arithmetic, and a colour is floor(x + 0.5), then 0 unless >= 0, then 255 unless <= 255."""
     f = np.asarray(tsdf, np.float32)
     w = np.asarray(weight, np.float32)
     nz, ny, nx = f.shape
@@ -145,7 +147,10 @@ def mesh(tsdf, weight, color, origin, voxel, min_weight=1.0, with_edges=False):
         if color is not None:
             for c in range(3):
                 ca, cb = float(color[a[2], a[1], a[0], c]), float(color[b[2], b[1], b[0], c])
-                colors[n, 2 - c] = int(min(max(np.floor((ca + t * (cb - ca)) + 0.5), 0.0), 255.0))
+                x = float(np.floor((ca + t * (cb - ca)) + 0.5))     # plain IEEE: inf - inf and 0 * inf are NaN
+                x = x if x >= 0.0 else 0.0                           # a NaN and -inf go to 0
+                x = x if x <= 255.0 else 255.0                       # +inf to 255
+                colors[n, 2 - c] = int(x)
     faces = np.zeros((len(tri_edges), 3), np.int32)
     for n, tri in enumerate(tri_edges):
         v = [index[e] for e in tri]
