@@ -22,6 +22,7 @@ from .. import variables
 from ..flags import FLAGS
 from ..tools.common import Notify
 from . import clean_cloud
+from . import clean_mesh
 from . import depth_fusion
 from . import eval_cloud
 from . import eval_depth
@@ -521,7 +522,8 @@ def _clean_cloud(points, colors, score, folder, device, gt_points, clean, normal
 
 
 def _write_mesh(scene_fusion, map_cams, folder, mesh):
-    """final3d_mesh.ply and mesh.json -> the face count.  After the cloud: the fusion's result bounds the volume."""
+    """final3d_mesh.ply and mesh.json -> the face count.  After the cloud: the fusion's result bounds the volume.  With clean= in
+    `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's clean=)."""
     from . import mesh_fusion
     t0 = time.time()
     scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
@@ -529,6 +531,9 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
     if mesh.get('render'):
         scene_mesh.render(os.path.join(folder, 'depths_mesh'))
     mesh_fusion.write_json(os.path.join(folder, 'mesh.json'), scene_mesh.report())
+    if mesh.get('clean'):
+        scene_mesh.write_clean_ply(os.path.join(folder, 'final3d_mesh_clean.ply'))
+        mesh_fusion.write_json(os.path.join(folder, 'mesh_clean.json'), scene_mesh.clean_report())
     TIMES['mesh'] = time.time() - t0
     return n_faces
 
@@ -566,6 +571,9 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
                        'mesh is integrated from the maps the fusion stages and bounded by its cloud'),
         (mesh.get('voxel') is None, '--mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --mesh_voxel (mesh needs voxel=)')]
+    if mesh is not None and mesh.get('clean') is not None:                 # in front of the row above: its message names what was given
+        mesh_row.insert(1, (mesh.get('voxel') is None, '--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need '
+                                                       '--mesh_voxel (mesh clean= needs voxel=): there is no mesh to clean'))
     normals_row = [] if fuse_normals is None else [
         (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
                        '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
@@ -641,7 +649,9 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     second fit).  With occlusion_mesh= (a list of triangle-mesh PLY files in the ground truth's frame) and occlusion_mesh_tol= in
     the dict, a rendered pixel that lies behind those meshes is taken out first (eval_depth.render_scan's occluders).  Every other
     output is what it is without it.
-    mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=), the arguments of mesh_fusion.SceneMesh:
+    mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=, clean=), the arguments of mesh_fusion.SceneMesh
+    (clean=dict(min_faces=, min_ratio=, keep_largest=) also writes final3d_mesh_clean.ply and mesh_clean.json, the mesh without the
+    connected components that miss a criterion; the other files keep their bytes):
     after the scene's fusion the staged depth planes and images are integrated into a TSDF volume bounded by the fused cloud and
     meshed by marching tetrahedra into <savepath>/<scene>/final3d_mesh.ply, with the report in mesh.json; with render=True the
     mesh is also rendered into the scene's map cameras as <savepath>/<scene>/depths_mesh/%08d_mesh.pfm (SceneMesh.render).  Every
@@ -735,6 +745,10 @@ def _mesh_options(flags):
     given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
     if getattr(flags, 'mesh_render', False):
         given['render'] = True
+    clean = {key: getattr(flags, 'mesh_clean_' + key) for key in ('min_faces', 'min_ratio', 'keep_largest')
+             if getattr(flags, 'mesh_clean_' + key, None) is not None}
+    if clean:
+        given['clean'] = clean
     return given or None
 
 
@@ -870,6 +884,7 @@ def cli(argv=None):
                         help='--mesh_voxel: views a voxel needs to be meshed (default 2, the fusion\'s num_consistent)')
     parser.add_argument('--mesh_max_blocks', type=int, default=None, metavar='N',
                         help='--mesh_voxel: blocks of 8^3 voxels the maps may mark (default 131072)')
+    clean_mesh.add_options(parser, 'mesh_clean_')
     parser.add_argument('--mesh_render', action='store_true',
                         help='--mesh_voxel: render the mesh into the scene\'s map cameras (ops.mesh_render) as '
                              '<savepath>/<scene>/depths_mesh/%%08d_mesh.pfm; mesh.json gains `render`')
@@ -909,6 +924,8 @@ def cli(argv=None):
         parser.error('--map_occlusion_mesh names no file')
     if args.mesh_render and args.mesh_voxel is None:
         parser.error('--mesh_render needs --mesh_voxel')
+    if clean_mesh.options(parser, args, 'mesh_clean_') and args.mesh_voxel is None:
+        parser.error('--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need --mesh_voxel')
     if not 0 <= args.map_splat <= 4:
         parser.error('--map_splat must be in 0..4')
     if not (args.map_occlusion_tol >= 0.0 and np.isfinite(args.map_occlusion_tol)) or not np.isfinite(args.map_pixel_centre):

@@ -4,16 +4,18 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
 
     mesh_maps      depth maps, cameras, images and a box -> the volume, the mesh, seconds per stage
     SceneMesh      the mesh of a depth_fusion.SceneFusion: its staged planes in fusion order, the box of its fused points
-    mesh_report    blocks, valid voxels, vertices, faces, zero-area faces, boundary edges
+    mesh_report    blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (ops.mesh_edge_census for a mesh on a GPU)
     render_views   the mesh rendered into cameras (ops.mesh_render), one %08d_mesh.pfm per map
+    clean=         SceneMesh and the tool also give the mesh without its small connected components (clean_mesh, section 10.3a)
 
 What this is not: there is no free-space carving (a view adds to a voxel only inside the narrow band around its depth), no per-view
 weight, no consistency mask on the depths beyond the probability filter, no mesh simplification, no hole filling, and the PLY
-carries no normals.  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports without a GPU.
+carries no normals.  Fragments are removed only when asked (the clean_ options have no defaults).  `trunc_voxels` and `min_weight`
+have defaults, not measurements.  This module imports without a GPU.
 
     python -m atvsnet_amd.atvsnet.mesh_fusion --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --voxel V
         [--trunc_voxels 4 --min_weight 2 --prob_threshold 0.8 --pixel_centre 0 --max_blocks N --report mesh.json] --out mesh.ply
-        [--render DIR]
+        [--render DIR] [--clean_min_faces N --clean_min_ratio R --clean_keep_largest K --clean_out clean.ply]
 """
 import argparse
 import json
@@ -22,7 +24,7 @@ import time
 
 import numpy as np
 
-from . import eval_depth
+from . import clean_mesh, eval_depth
 
 DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
 DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
@@ -31,9 +33,11 @@ DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel 
 
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
-                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False):
+                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
-    the driver also renders the mesh) has nothing to check."""
+    the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there."""
+    if clean is not None:
+        clean_mesh.check_criteria(**clean)
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
     if not (voxel > 0.0 and np.isfinite(voxel)):
         raise ValueError('mesh voxel must be positive and finite, got %r' % (voxel,))
@@ -103,8 +107,16 @@ def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_
     return volume, mesh, {'integrate': t1 - t0, 'extract': time.time() - t1}
 
 
+def host_boundary_edges(f, num_vertices):
+    """The edges that lie in exactly one face, on the host: numpy.unique over all 3F sorted pairs.  f (F,3) int64."""
+    e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
+    _, counts = np.unique(e[:, 0] * (int(num_vertices) + 1) + e[:, 1], return_counts=True)
+    return int((counts == 1).sum())
+
+
 def mesh_report(volume, mesh, min_weight, seconds=None):
-    """-> a dict: the box, blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (edges of one face), seconds."""
+    """-> a dict: the box, blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (edges of one face), seconds.
+    The boundary edges of a mesh on a GPU are counted there (ops.mesh_edge_census); host tensors are counted by numpy.unique."""
     vertices, _, faces = mesh
     v = vertices.cpu().numpy().astype(np.float64)
     f = faces.cpu().numpy().astype(np.int64)
@@ -112,9 +124,11 @@ def mesh_report(volume, mesh, min_weight, seconds=None):
     if len(f):
         normal = np.cross(v[f[:, 1]] - v[f[:, 0]], v[f[:, 2]] - v[f[:, 0]])
         zero = int((np.abs(normal).max(axis=1) == 0.0).sum())
-        e = np.sort(np.concatenate([f[:, [0, 1]], f[:, [1, 2]], f[:, [2, 0]]]), axis=1)
-        _, counts = np.unique(e[:, 0] * (len(v) + 1) + e[:, 1], return_counts=True)
-        boundary = int((counts == 1).sum())
+        if faces.device.type == 'cuda':
+            from .. import ops
+            boundary = ops.mesh_edge_census(faces.contiguous(), len(v))['boundary']
+        else:
+            boundary = host_boundary_edges(f, len(v))
     return {'origin': [float(o) for o in volume.origin], 'voxel': volume.voxel, 'trunc': volume.trunc, 'dims': list(volume.dims),
             'min_weight': float(min_weight), 'blocks': volume.num_blocks,
             'valid_voxels': int((volume.weight >= float(min_weight)).sum().item()) if volume.num_blocks else 0,
@@ -156,11 +170,18 @@ class SceneMesh(object):
     The box is the ops.cloud_bounds of the fused points of scene_fusion.run(), padded by trunc = trunc_voxels * voxel plus one
     block: the consistent points bound the volume, so a stray depth cannot inflate it.  The staged, probability-filtered depth
     planes (nd[..., 3]) and images (img) are integrated in scene_fusion.order().  run() -> (vertices (V,3) float32, colors (V,3)
-    uint8 r, g, b, faces (F,3) int32) as numpy arrays."""
+    uint8 r, g, b, faces (F,3) int32) as numpy arrays.
+
+    clean: None, or a dict of clean_mesh.clean's criteria (min_faces=, min_ratio=, keep_largest=).  With it run() also removes the
+    mesh's small connected components on the device, before anything is downloaded (clean_mesh.clean_device); run()'s result and
+    report() stay those of the whole mesh, and write_clean_ply(path), clean_result(), clean_report() and render(folder, clean=True)
+    give the cleaned one."""
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False):
-        self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
+                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None):
+        self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
+        self.clean = None if clean is None else dict(clean)
+        self._device_clean = self._clean_result = self._clean_report = None
         self.fusion = scene_fusion
         k = len(scene_fusion.index)
         if isinstance(cams, dict):
@@ -194,29 +215,58 @@ class SceneMesh(object):
             self.volume, mesh, stage = mesh_maps(depths, self.cams16[order], images, lo, hi, voxel, trunc_voxels, min_weight, max_blocks,
                                                  pixel_centre)
             seconds.update(stage)
+            if self.clean is not None:
+                vertices, colors, faces, self._clean_report = clean_mesh.clean_device(*mesh, **self.clean)
+                self._device_clean = (vertices, colors, faces)
             t0 = time.time()
             self.result = tuple(None if t is None else t.cpu().numpy() for t in mesh)
             self._device_mesh = mesh
             seconds['download'] = time.time() - t0
             t0 = time.time()
             self._report = mesh_report(self.volume, mesh, min_weight, seconds)
-            seconds['report'] = self._report['seconds']['report'] = time.time() - t0          # on the host: the edge census
+            seconds['report'] = self._report['seconds']['report'] = time.time() - t0          # zero-area faces on the host, the edge census on the device
         return self.result
 
     def report(self):
         self.run()
         return self._report
 
-    def render(self, folder):
+    def _cleaned(self):
+        self.run()
+        if self._device_clean is None:
+            raise RuntimeError('SceneMesh: no clean= criteria were given: there is no cleaned mesh')
+        return self._device_clean
+
+    def clean_result(self):
+        """run() -> the cleaned mesh (vertices, colors, faces) as numpy arrays."""
+        device = self._cleaned()
+        if self._clean_result is None:
+            self._clean_result = tuple(None if t is None else t.cpu().numpy() for t in device)
+        return self._clean_result
+
+    def clean_report(self):
+        """run() -> clean_mesh.clean_device's report: components, what was removed, the edge census before and after."""
+        self._cleaned()
+        return self._clean_report
+
+    def write_clean_ply(self, path):
+        """The cleaned mesh into a binary PLY at `path` -> the number of faces."""
+        from ..tools import ply
+        vertices, colors, faces = self.clean_result()
+        ply.write_mesh(path, vertices, colors, faces)
+        return len(faces)
+
+    def render(self, folder, clean=False):
         """run(), then the mesh -- still on the device -- rendered into the scene's map cameras as folder/%08d_mesh.pfm
-        (render_views); report() gains `render`."""
+        (render_views); report() gains `render`.  clean=True: the cleaned mesh, and clean_report() gains `render`."""
         self.run()
         fusion = self.fusion
         order = fusion.order()
-        vertices, _, faces = self._device_mesh
-        self._report['render'] = render_views(vertices, faces, self.cams16[order], fusion.rows, fusion.cols, folder,
-                                              [fusion.index[k] for k in order], self.options[4])
-        return self._report['render']
+        vertices, _, faces = self._cleaned() if clean else self._device_mesh
+        report = self._clean_report if clean else self._report
+        report['render'] = render_views(vertices.contiguous(), faces.contiguous(), self.cams16[order], fusion.rows, fusion.cols,
+                                        folder, [fusion.index[k] for k in order], self.options[4])
+        return report['render']
 
     def write_ply(self, path):
         """run() into a binary PLY at `path` (tools/ply.write_mesh) -> the number of faces."""
@@ -243,6 +293,9 @@ def make_parser():
     parser.add_argument('--render', default=None, metavar='DIR', help='render the mesh into the maps\' cameras (ops.mesh_render) as '
                                                                       'DIR/%%08d_mesh.pfm; the report gains `render`')
     parser.add_argument('--out', required=True, help='the mesh, a binary PLY')
+    clean_mesh.add_options(parser, 'clean_')
+    parser.add_argument('--clean_out', default=None, metavar='PLY', help='with a --clean_ criterion: the mesh without the connected '
+                                                                         'components that miss it (clean_mesh); the report gains `clean`')
     parser.add_argument('--gpu_id', type=int, default=0)
     return parser
 
@@ -284,6 +337,9 @@ def cli(argv=None):
         parser.error('--scene %s: no pair.txt' % args.scene)
     if args.bounds is not None and not os.path.isfile(args.bounds):
         parser.error('--bounds %s: no such file' % args.bounds)
+    criteria = clean_mesh.options(parser, args, 'clean_')
+    if bool(criteria) != (args.clean_out is not None):
+        parser.error('--clean_out needs one of --clean_min_faces, --clean_min_ratio, --clean_keep_largest, and they need --clean_out')
     from ..tools import ply
     indices, depths, cams = eval_depth.load_maps(args.maps, eval_depth.scene_indices(args.scene) if args.scene is not None else None)
     probs, images = _load_side_maps(args.maps, indices, depths.shape[1:])
@@ -310,6 +366,9 @@ def cli(argv=None):
                   probability_filtered=probs is not None)
     if args.render:
         result['render'] = render_views(mesh[0], mesh[2], cams16, depths.shape[1], depths.shape[2], args.render, indices, args.pixel_centre)
+    if criteria:
+        clean_v, clean_c, clean_f, result['clean'] = clean_mesh.clean_device(*mesh, **criteria)
+        ply.write_mesh(args.clean_out, clean_v.cpu().numpy(), None if clean_c is None else clean_c.cpu().numpy(), clean_f.cpu().numpy())
     if args.report:
         write_json(args.report, result)
     print(json.dumps({k: result[k] for k in ('blocks', 'valid_voxels', 'vertices', 'faces', 'zero_area_faces', 'boundary_edges')}))

@@ -1,4 +1,4 @@
-"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in twelve modules --
+"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in thirteen modules --
 
     base      ctypes plumbing, the dispatch switches (`cfg`, `configure`), launch timing
     packing   weights in operand order + their cache, tap lists, the chunk-planar layout
@@ -15,6 +15,7 @@
               scoring: a point's free-space excess against scanner cube maps, voxel-averaged shares
     tsdf      a surface from depth maps: a block-sparse TSDF volume integrated from them, a marching-tetrahedra mesh of it
     mesh      a triangle mesh rendered into cameras (nearest depth and face per pixel), depth maps occluded by such a rendering
+    mesh_topology  a mesh's connected components, a selection of its faces with the vertices compacted, its edge census
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -52,4 +53,6 @@ from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render     
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401
 from .tsdf import TSDF_MAX_DIRECTORY, TSDF_MAX_MESH_BLOCKS, TSDF_MAX_PIXEL_BLOCKS, TsdfVolume, tsdf_integrate, tsdf_mesh      # noqa: F401
 from .mesh import MESH_RENDER_SMALL_PIXELS, depth_occlude, mesh_render      # noqa: F401
+from .mesh_topology import (MESH_CENSUS_MIN_SLOTS, MESH_CENSUS_WORDS, MESH_TOPOLOGY_MAX_FACES, mesh_components, mesh_edge_census,
+    mesh_select)      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 59
+#define ATVS_ABI_VERSION 60
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1279,6 +1279,58 @@ int atvs_mesh_render(const float* vertices, long n_vertices, const int* faces, l
                      int cols, double pixel_centre, void* scratch, long scratch_bytes, float* depth_out, int* face_out,
                      int* error_out, atvs_stream_t stream);
 int atvs_depth_occlude(const float* depth, const float* occluder, long pixels, double tol, float* out, atvs_stream_t stream);
+
+/* The connectivity of a triangle mesh (ops/mesh_topology.py, atvsnet/clean_mesh.py, csrc/mesh_topology.hip): connected components,
+ * the selection of faces, the edge census.  Pointers are device pointers.  Integer arithmetic and integer atomics only, no float
+ * atomics: the outputs are a function of the inputs alone, bit for bit on every run.  No host synchronisation, no allocation;
+ * scratch is the caller's.  tests/mesh_topology_restated.py restates the definitions in numpy.  faces (n_faces,3) int32 index
+ * n_vertices vertices; n_vertices in 0..2^30 (the limit of atvs_mesh_render), n_faces in 0..ATVS_MESH_TOPOLOGY_MAX_FACES, anything
+ * else ATVS_ERR_SHAPE, as is a short scratch; a null pointer that is needed ATVS_ERR_NULL; both without a launch.
+ *
+ * atvs_mesh_components.  Two vertices are connected when one face names both; a component is a class of the transitive closure.  A
+ * face with repeated indices still connects what it names.  vertex_component (n_vertices,) int32: -1 for a vertex no face names,
+ * else the dense id of its component, ids 0..C-1 in ascending order of the component's smallest vertex index.  face_component
+ * (n_faces,) int32: the component of the face's first vertex.  face_count and vertex_count: max(1, min(n_vertices, n_faces)) int32
+ * each (a component has a face and a vertex of its own, so C is no more), the first C the components' faces and vertices, the
+ * rest 0.  info: two int32, info[0] = the number of faces with an index outside 0..n_vertices-1 (such a face is skipped, and no
+ * output is defined unless it is 0), info[1] = C.  scratch: atvs_mesh_components_scratch_size bytes, 12 per vertex and the scan's
+ * tile sums.  n_faces = 0: C = 0 and every vertex_component is -1.
+ *
+ * atvs_mesh_select.  vertices (n_vertices,3) float32, colors (n_vertices,3) uint8 or null, keep (n_faces,) uint8.  The faces with
+ * keep != 0 are kept in their order, the vertices they name are kept in their order, the faces are renumbered.  vertices_out
+ * (n_vertices,3), colors_out (n_vertices,3; unused with colors null), faces_out (n_faces,3): the first V' and F' rows are written;
+ * coordinates and colours are copied as bits.  vertex_map (n_vertices,) int32: the new index of an old vertex, or -1.  info: three
+ * int32, info[0] = the number of KEPT faces with an index outside 0..n_vertices-1 (no output is defined unless it is 0), info[1] =
+ * V', info[2] = F'.  scratch: atvs_mesh_select_scratch_size bytes, 4 per vertex and per face and the scan's tile sums.
+ *
+ * atvs_mesh_edge_census.  Each of the 3 n_faces pairs (f0,f1), (f1,f2), (f2,f0) sorted into (lo, hi); pairs with lo == hi count
+ * too.  A distinct pair's `faces` is the number of the 3 n_faces pairs that equal it (a face (a,a,a) gives its pair (a,a) three).
+ * census: eight int64 words --
+ *   [0] edges               the distinct pairs
+ *   [1] boundary            distinct pairs with faces == 1
+ *   [2] manifold            distinct pairs with faces == 2
+ *   [3] nonmanifold         distinct pairs with faces > 2
+ *   [4] misoriented         distinct pairs given twice or more in one direction: as (lo,hi) (a pair with lo == hi is given so), or
+ *                           as (hi,lo).  0 on a consistently oriented manifold mesh
+ *   [5] max_faces_per_edge  the largest faces of a distinct pair
+ *   [6] self_edges          distinct pairs with lo == hi
+ *   [7] error               faces with an index outside 0..n_vertices-1 (skipped; the other words are defined only when it is 0)
+ * scratch: atvs_mesh_edge_census_scratch_size bytes: an open-addressing table of the smallest power of two of slots that is at
+ * least 6 n_faces and at least ATVS_MESH_CENSUS_MIN_SLOTS, 16 bytes each (a 64-bit key (lo << 32) | hi and two 32-bit counters):
+ * the load is at most 0.5.  ATVS_MESH_TOPOLOGY_MAX_FACES keeps that size in a long.  The probe loop is bounded by the table; a pair
+ * that found no slot (impossible at that load) adds to [7].  n_faces = 0: all words 0. */
+#define ATVS_MESH_TOPOLOGY_MAX_FACES 268435456
+#define ATVS_MESH_CENSUS_MIN_SLOTS 1024
+int atvs_mesh_components_scratch_size(long n_vertices, long n_faces, long* bytes);
+int atvs_mesh_components(const int* faces, long n_faces, long n_vertices, void* scratch, long scratch_bytes, int* vertex_component,
+                         int* face_component, int* face_count, int* vertex_count, int* info, atvs_stream_t stream);
+int atvs_mesh_select_scratch_size(long n_vertices, long n_faces, long* bytes);
+int atvs_mesh_select(const float* vertices, const void* colors, long n_vertices, const int* faces, const void* keep, long n_faces,
+                     void* scratch, long scratch_bytes, float* vertices_out, void* colors_out, int* faces_out, int* vertex_map,
+                     int* info, atvs_stream_t stream);
+int atvs_mesh_edge_census_scratch_size(long n_faces, long* bytes);
+int atvs_mesh_edge_census(const int* faces, long n_faces, long n_vertices, void* scratch, long scratch_bytes, long* census,
+                          atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
