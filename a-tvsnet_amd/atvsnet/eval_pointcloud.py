@@ -571,6 +571,9 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
         (fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
                        'mesh is integrated from the maps the fusion stages and bounded by its cloud'),
         (mesh.get('voxel') is None, '--mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --mesh_voxel (mesh needs voxel=)')]
+    if mesh is not None and mesh.get('carve_weight') is not None:
+        mesh_row.insert(1, (mesh.get('voxel') is None, '--mesh_carve needs --mesh_voxel (mesh carve_weight= needs voxel=): there is no '
+                                                       'volume to carve'))
     if mesh is not None and mesh.get('clean') is not None:                 # in front of the row above: its message names what was given
         mesh_row.insert(1, (mesh.get('voxel') is None, '--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need '
                                                        '--mesh_voxel (mesh clean= needs voxel=): there is no mesh to clean'))
@@ -649,7 +652,7 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     second fit).  With occlusion_mesh= (a list of triangle-mesh PLY files in the ground truth's frame) and occlusion_mesh_tol= in
     the dict, a rendered pixel that lies behind those meshes is taken out first (eval_depth.render_scan's occluders).  Every other
     output is what it is without it.
-    mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=, clean=), the arguments of mesh_fusion.SceneMesh
+    mesh (with fuse only): None, or dict(voxel=, trunc_voxels=, min_weight=, max_blocks=, clean=, carve_weight=), the arguments of mesh_fusion.SceneMesh
     (clean=dict(min_faces=, min_ratio=, keep_largest=) also writes final3d_mesh_clean.ply and mesh_clean.json, the mesh without the
     connected components that miss a criterion; the other files keep their bytes):
     after the scene's fusion the staged depth planes and images are integrated into a TSDF volume bounded by the fused cloud and
@@ -745,6 +748,8 @@ def _mesh_options(flags):
     given = {key: getattr(flags, option) for option, key in names.items() if getattr(flags, option, None) is not None}
     if getattr(flags, 'mesh_render', False):
         given['render'] = True
+    if getattr(flags, 'mesh_carve', None) is not None:
+        given['carve_weight'] = flags.mesh_carve
     clean = {key: getattr(flags, 'mesh_clean_' + key) for key in ('min_faces', 'min_ratio', 'keep_largest')
              if getattr(flags, 'mesh_clean_' + key, None) is not None}
     if clean:
@@ -885,6 +890,10 @@ def cli(argv=None):
     parser.add_argument('--mesh_max_blocks', type=int, default=None, metavar='N',
                         help='--mesh_voxel: blocks of 8^3 voxels the maps may mark (default 131072)')
     clean_mesh.add_options(parser, 'mesh_clean_')
+    parser.add_argument('--mesh_carve', type=float, nargs='?', default=None, const=1.0, metavar='CW',
+                        help='--mesh_voxel: free-space carving (mesh_fusion --carve): a view that sees past a voxel votes it outside '
+                             'with this weight (given bare: 1.0, a default, not a measurement); mesh.json gains carve_weight, '
+                             'free_voxels and max_free')
     parser.add_argument('--mesh_render', action='store_true',
                         help='--mesh_voxel: render the mesh into the scene\'s map cameras (ops.mesh_render) as '
                              '<savepath>/<scene>/depths_mesh/%%08d_mesh.pfm; mesh.json gains `render`')
@@ -924,6 +933,8 @@ def cli(argv=None):
         parser.error('--map_occlusion_mesh names no file')
     if args.mesh_render and args.mesh_voxel is None:
         parser.error('--mesh_render needs --mesh_voxel')
+    if args.mesh_carve is not None and args.mesh_voxel is None:
+        parser.error('--mesh_carve needs --mesh_voxel')
     if clean_mesh.options(parser, args, 'mesh_clean_') and args.mesh_voxel is None:
         parser.error('--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need --mesh_voxel')
     if not 0 <= args.map_splat <= 4:

@@ -8,14 +8,17 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     render_views   the mesh rendered into cameras (ops.mesh_render), one %08d_mesh.pfm per map
     clean=         SceneMesh and the tool also give the mesh without its small connected components (clean_mesh, section 10.3a)
 
-What this is not: there is no free-space carving (a view adds to a voxel only inside the narrow band around its depth), no per-view
-weight, no consistency mask on the depths beyond the probability filter, no mesh simplification, no hole filling, and the PLY
-carries no normals.  Fragments are removed only when asked (the clean_ options have no defaults).  `trunc_voxels` and `min_weight`
+    carve_weight=  free-space carving (section 10.3b): a view that sees past a voxel pulls its value outside, so a shell that two views
+                   agree on and the others look through is not meshed; off (None) unless asked
+
+What this is not: there is no per-view weight, no consistency mask on the depths beyond the probability filter, no mesh
+simplification, no hole filling, and the PLY carries no normals.  Without carve_weight a view adds to a voxel only inside the narrow
+band around its depth.  Fragments are removed only when asked (the clean_ options have no defaults).  `trunc_voxels` and `min_weight`
 have defaults, not measurements.  This module imports without a GPU.
 
     python -m atvsnet_amd.atvsnet.mesh_fusion --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --voxel V
         [--trunc_voxels 4 --min_weight 2 --prob_threshold 0.8 --pixel_centre 0 --max_blocks N --report mesh.json] --out mesh.ply
-        [--render DIR] [--clean_min_faces N --clean_min_ratio R --clean_keep_largest K --clean_out clean.ply]
+        [--carve [CW]] [--render DIR] [--clean_min_faces N --clean_min_ratio R --clean_keep_largest K --clean_out clean.ply]
 """
 import argparse
 import json
@@ -30,14 +33,17 @@ DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reac
 DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
 DEFAULT_MAX_BLOCKS = 131072        # 64 Mi voxels: 1.3 GB of tsdf, weight and colour while the volume is built
 DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel coordinates: the convention that places the cloud
+DEFAULT_CARVE_WEIGHT = 1.0         # a default, not a measurement: what a bare --carve gives a free vote, one in-band view's worth
 
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
-                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None):
+                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
-    the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there."""
+    the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there,
+    carve_weight by check_carve_weight (it is not part of the tuple)."""
     if clean is not None:
         clean_mesh.check_criteria(**clean)
+    check_carve_weight(carve_weight)
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
     if not (voxel > 0.0 and np.isfinite(voxel)):
         raise ValueError('mesh voxel must be positive and finite, got %r' % (voxel,))
@@ -50,6 +56,21 @@ def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_M
     if not np.isfinite(pixel_centre):
         raise ValueError('mesh pixel_centre must be finite, got %r' % (pixel_centre,))
     return voxel, trunc_voxels, min_weight, int(max_blocks), pixel_centre
+
+
+def check_carve_weight(carve_weight):
+    """-> None (no carving) or the weight of a free vote as a float; anything but None or a finite number > 0 raises ValueError."""
+    if carve_weight is None:
+        return None
+    if isinstance(carve_weight, (bool, str, bytes)):
+        raise ValueError('mesh carve_weight must be a finite number > 0, got %r' % (carve_weight,))
+    try:
+        cw = float(carve_weight)
+    except (TypeError, ValueError):
+        raise ValueError('mesh carve_weight must be a finite number > 0, got %r' % (carve_weight,))
+    if not (cw > 0.0 and np.isfinite(cw)):
+        raise ValueError('mesh carve_weight must be a finite number > 0, got %r' % (carve_weight,))
+    return cw
 
 
 def box_of(lo, hi, voxel, trunc):
@@ -85,13 +106,15 @@ def depth_bounds(depths, cams16, pixel_centre=DEFAULT_PIXEL_CENTRE):
 
 
 def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-              max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE):
+              max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, carve_weight=None):
     """depths (n,rows,cols) float32 and images (n,rows,cols,C>=3) float32 (b, g, r first) or None on the device, cams16 (n,16)
     float64 host rows (eval_depth.camera_rows), lo / hi the bounds of what is to be meshed -> (volume, (vertices, colors, faces)
-    device tensors, {'integrate': s, 'extract': s}, each ended by a device synchronisation)."""
+    device tensors, {'integrate': s, 'extract': s}, each ended by a device synchronisation).  carve_weight: None, or the weight of
+    a free vote (ops.tsdf_integrate's carve_weight); the volume then carries `free`."""
     import torch
     from .. import ops
     voxel, trunc_voxels, min_weight, max_blocks, pixel_centre = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
+    carve = {} if check_carve_weight(carve_weight) is None else {'carve_weight': check_carve_weight(carve_weight)}
     trunc = trunc_voxels * voxel
     origin, dims = box_of(lo, hi, voxel, trunc)
     if dims[0] * dims[1] * dims[2] > ops.TSDF_MAX_DIRECTORY:
@@ -99,7 +122,8 @@ def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_
     cams = torch.from_numpy(np.ascontiguousarray(cams16, np.float64)).to(depths.device)
     torch.cuda.synchronize(depths.device)
     t0 = time.time()
-    volume = ops.tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=images, pixel_centre=pixel_centre, max_blocks=max_blocks)
+    volume = ops.tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=images, pixel_centre=pixel_centre, max_blocks=max_blocks,
+                                **carve)
     torch.cuda.synchronize(depths.device)
     t1 = time.time()
     mesh = ops.tsdf_mesh(volume, min_weight)
@@ -114,9 +138,10 @@ def host_boundary_edges(f, num_vertices):
     return int((counts == 1).sum())
 
 
-def mesh_report(volume, mesh, min_weight, seconds=None):
+def mesh_report(volume, mesh, min_weight, seconds=None, carve_weight=None):
     """-> a dict: the box, blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (edges of one face), seconds.
-    The boundary edges of a mesh on a GPU are counted there (ops.mesh_edge_census); host tensors are counted by numpy.unique."""
+    The boundary edges of a mesh on a GPU are counted there (ops.mesh_edge_census); host tensors are counted by numpy.unique.
+    With carve_weight (the volume was integrated with it) also carve_weight, free_voxels (valid voxels with free > 0) and max_free."""
     vertices, _, faces = mesh
     v = vertices.cpu().numpy().astype(np.float64)
     f = faces.cpu().numpy().astype(np.int64)
@@ -129,11 +154,19 @@ def mesh_report(volume, mesh, min_weight, seconds=None):
             boundary = ops.mesh_edge_census(faces.contiguous(), len(v))['boundary']
         else:
             boundary = host_boundary_edges(f, len(v))
-    return {'origin': [float(o) for o in volume.origin], 'voxel': volume.voxel, 'trunc': volume.trunc, 'dims': list(volume.dims),
-            'min_weight': float(min_weight), 'blocks': volume.num_blocks,
-            'valid_voxels': int((volume.weight >= float(min_weight)).sum().item()) if volume.num_blocks else 0,
-            'vertices': int(len(v)), 'faces': int(len(f)), 'zero_area_faces': zero, 'boundary_edges': boundary,
-            'seconds': dict(seconds or {})}
+    report = {'origin': [float(o) for o in volume.origin], 'voxel': volume.voxel, 'trunc': volume.trunc, 'dims': list(volume.dims),
+              'min_weight': float(min_weight), 'blocks': volume.num_blocks,
+              'valid_voxels': int((volume.weight >= float(min_weight)).sum().item()) if volume.num_blocks else 0,
+              'vertices': int(len(v)), 'faces': int(len(f)), 'zero_area_faces': zero, 'boundary_edges': boundary,
+              'seconds': dict(seconds or {})}
+    if carve_weight is not None:
+        if volume.free is None:
+            raise ValueError('mesh_report: carve_weight is given and the volume carries no free counts')
+        some = volume.num_blocks > 0
+        report.update(carve_weight=float(carve_weight),
+                      free_voxels=int(((volume.weight >= float(min_weight)) & (volume.free > 0)).sum().item()) if some else 0,
+                      max_free=float(volume.free.max().item()) if some else 0.0)
+    return report
 
 
 def render_views(vertices, faces, cams16, rows, cols, folder, indices, pixel_centre=DEFAULT_PIXEL_CENTRE):
@@ -175,11 +208,15 @@ class SceneMesh(object):
     clean: None, or a dict of clean_mesh.clean's criteria (min_faces=, min_ratio=, keep_largest=).  With it run() also removes the
     mesh's small connected components on the device, before anything is downloaded (clean_mesh.clean_device); run()'s result and
     report() stay those of the whole mesh, and write_clean_ply(path), clean_result(), clean_report() and render(folder, clean=True)
-    give the cleaned one."""
+    give the cleaned one.
+
+    carve_weight: None, or the weight of a free vote: the staged planes are integrated with free-space carving (section 10.3b) and
+    report() gains carve_weight, free_voxels and max_free."""
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None):
+                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
+        self.carve_weight = check_carve_weight(carve_weight)
         self.clean = None if clean is None else dict(clean)
         self._device_clean = self._clean_result = self._clean_report = None
         self.fusion = scene_fusion
@@ -213,7 +250,7 @@ class SceneMesh(object):
             depths = fusion.nd[:k, :, :, 3].index_select(0, idx).contiguous()
             images = fusion.img[:k] if np.array_equal(order, np.arange(k)) else fusion.img[:k].index_select(0, idx)
             self.volume, mesh, stage = mesh_maps(depths, self.cams16[order], images, lo, hi, voxel, trunc_voxels, min_weight, max_blocks,
-                                                 pixel_centre)
+                                                 pixel_centre, self.carve_weight)
             seconds.update(stage)
             if self.clean is not None:
                 vertices, colors, faces, self._clean_report = clean_mesh.clean_device(*mesh, **self.clean)
@@ -223,7 +260,7 @@ class SceneMesh(object):
             self._device_mesh = mesh
             seconds['download'] = time.time() - t0
             t0 = time.time()
-            self._report = mesh_report(self.volume, mesh, min_weight, seconds)
+            self._report = mesh_report(self.volume, mesh, min_weight, seconds, self.carve_weight)
             seconds['report'] = self._report['seconds']['report'] = time.time() - t0          # zero-area faces on the host, the edge census on the device
         return self.result
 
@@ -278,7 +315,7 @@ class SceneMesh(object):
 
 def make_parser():
     parser = argparse.ArgumentParser(description='mesh the written depth maps of a scene: TSDF fusion and marching tetrahedra on the GPU '
-                                                 '(no free-space carving, no simplification, no hole filling)')
+                                                 '(free-space carving with --carve; no simplification, no hole filling)')
     parser.add_argument('--scene', default=None, help='<data_root>/eth3d/<scene>: its pair.txt names the maps (default: every map under --maps)')
     parser.add_argument('--maps', required=True, help='<savepath>/<scene> of eval_pointcloud: depths_atvsnet/%%08d.pfm, _prob.pfm, .jpg, .txt')
     parser.add_argument('--voxel', type=float, required=True, help='the voxel\'s edge in the scene\'s unit')
@@ -287,6 +324,9 @@ def make_parser():
     parser.add_argument('--prob_threshold', type=float, default=0.8, help='a depth whose probability is below this is no sample (depth_fusion --prob_threshold)')
     parser.add_argument('--pixel_centre', type=float, default=DEFAULT_PIXEL_CENTRE, help='image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5')
     parser.add_argument('--max_blocks', type=int, default=DEFAULT_MAX_BLOCKS, help='blocks of 8^3 voxels the maps may mark')
+    parser.add_argument('--carve', type=float, nargs='?', default=None, const=DEFAULT_CARVE_WEIGHT, metavar='CW',
+                        help='free-space carving: a view that sees past a voxel votes it outside with this weight (given bare: %g, a '
+                             'default, not a measurement); the report gains carve_weight, free_voxels, max_free' % DEFAULT_CARVE_WEIGHT)
     parser.add_argument('--bounds', default=None, metavar='PLY', help='bound the volume by this cloud (the scene\'s final3d_model.ply) instead of '
                                                                       'by the maps\' own back-projected depths')
     parser.add_argument('--report', default=None, metavar='FILE', help='write the report as JSON here')
@@ -328,7 +368,7 @@ def cli(argv=None):
     parser = make_parser()
     args = parser.parse_args(argv)
     try:
-        check_options(args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre)
+        check_options(args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre, carve_weight=args.carve)
     except ValueError as e:
         parser.error(str(e))
     if not os.path.isdir(args.maps):
@@ -359,10 +399,10 @@ def cli(argv=None):
     torch.cuda.set_device(args.gpu_id)
     dev = torch.device('cuda', args.gpu_id)
     volume, mesh, seconds = mesh_maps(torch.from_numpy(depths).to(dev), cams16, None if images is None else torch.from_numpy(images).to(dev),
-                                      lo, hi, args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre)
+                                      lo, hi, args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre, args.carve)
     vertices, colors, faces = (None if t is None else t.cpu().numpy() for t in mesh)
     ply.write_mesh(args.out, vertices, colors, faces)
-    result = dict(mesh_report(volume, mesh, args.min_weight, seconds), maps=[int(i) for i in indices], colored=images is not None,
+    result = dict(mesh_report(volume, mesh, args.min_weight, seconds, args.carve), maps=[int(i) for i in indices], colored=images is not None,
                   probability_filtered=probs is not None)
     if args.render:
         result['render'] = render_views(mesh[0], mesh[2], cams16, depths.shape[1], depths.shape[2], args.render, indices, args.pixel_centre)

@@ -16,6 +16,9 @@
 // What bounds integrate: per (voxel, view of the mask) ~40 float64 operations with two divisions and one 4-byte gather that lands
 // in the L2 (a block's voxels look at a few neighbouring pixels of a map); which of the two dominates is what tools_dev/mesh_rate.py
 // measures.
+// FREE-SPACE CARVING (opt-in, atvs_tsdf_integrate_carve): a view whose depth lies beyond a voxel's band has seen past the voxel and
+// pulls its value outside.  Such a view is in no band mask, so atvs_tsdf_free_views gives every slot the views that can see into
+// its block at all (a ballot per mask word), and the kernel's second form loops over band | free.
 //
 // The extractor splits the cube of every voxel whose eight corners are valid into six Kuhn tetrahedra (one per permutation of the
 // axes), which tile space by translation: neighbouring cubes agree on their shared faces without a special case.  Every vertex
@@ -154,12 +157,18 @@ __global__ __launch_bounds__(kThreads) void tsdf_coords_kernel(const unsigned* _
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Integration: one workgroup per slot, one lane per voxel.
 // ---------------------------------------------------------------------------------------------------------------------------------
+// kCarve (free-space carving): the view loop runs over band mask | free mask, a view whose depth lies
+// beyond the band (sdf > trunc) adds 1 to a sixth sum Wf, and the epilogue forms (S + cw Wf) / (W + cw Wf) and writes `free`.
+// Without it every added line is compiled out: the plain form is the code it was.
+template <bool kCarve>
 __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __restrict__ depths, const float* __restrict__ images, int ch,
                                                               const double* __restrict__ cams, int rows, int cols, TsdfBox B, double trunc,
                                                               double pixel_centre, const int* __restrict__ coords,
                                                               const unsigned long long* __restrict__ masks, int words,
                                                               float* __restrict__ tsdf, float* __restrict__ weight,
-                                                              float* __restrict__ color, unsigned* __restrict__ any) {
+                                                              float* __restrict__ color, unsigned* __restrict__ any,
+                                                              const unsigned long long* __restrict__ free_masks, double cw,
+                                                              float* __restrict__ freev) {
   const size_t slot = blockIdx.x;
   const int t = threadIdx.x;
   const int gx = coords[slot * 3 + 0] * 8 + (t & 7), gy = coords[slot * 3 + 1] * 8 + ((t >> 3) & 7), gz = coords[slot * 3 + 2] * 8 + (t >> 6);
@@ -168,8 +177,10 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
   const double Z = B.oz + ((double)gz + 0.5) * B.voxel;
   const size_t plane = (size_t)rows * cols;
   double S = 0.0, W = 0.0, C0 = 0.0, C1 = 0.0, C2 = 0.0;
+  double Wf = 0.0;                                      // kCarve only: the views that saw past this voxel
   for (int w = 0; w < words; ++w) {
-    const unsigned long long m = masks[slot * words + w];
+    unsigned long long m = masks[slot * words + w];
+    if constexpr (kCarve) m |= free_masks[slot * words + w];
     for (int half = 0; half < 2; ++half) {
       unsigned mm = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(half ? m >> 32 : m));      // wave-uniform: scalar loop
       while (mm) {
@@ -181,7 +192,12 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
         const float d = depths[pix];
         if (!(d > 0.f && d < INFINITY)) continue;
         const double sdf = (double)d - P.c2;
-        if (!(sdf >= -trunc && sdf <= trunc)) continue;
+        if (!(sdf >= -trunc && sdf <= trunc)) {
+          if constexpr (kCarve) {
+            if (sdf > trunc) Wf += 1.0;                 // free: the view looks through the voxel; sdf < -trunc (occluded) adds nothing
+          }
+          continue;
+        }
         S += sdf / trunc;
         W += 1.0;
         if (images != nullptr) {
@@ -195,7 +211,13 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
   }
   const bool has = W > 0.0;
   const size_t o = slot * kVox + t;
-  tsdf[o] = has ? (float)(S / W) : 0.f;
+  if constexpr (kCarve) {
+    const double f = cw * Wf;                           // formed once
+    tsdf[o] = has ? (float)((S + f) / (W + f)) : 0.f;
+    freev[o] = has ? (float)Wf : 0.f;
+  } else {
+    tsdf[o] = has ? (float)(S / W) : 0.f;
+  }
   weight[o] = (float)W;
   if (color != nullptr) {
     color[o * 3 + 0] = has ? (float)(C0 / W) : 0.f;
@@ -210,7 +232,8 @@ __global__ __launch_bounds__(kVox) void tsdf_gather_kernel(const int* __restrict
                                                            const float* __restrict__ weight, const float* __restrict__ color,
                                                            const unsigned* __restrict__ keep, long count, unsigned kept,
                                                            int* __restrict__ coords_out, float* __restrict__ tsdf_out,
-                                                           float* __restrict__ weight_out, float* __restrict__ color_out) {
+                                                           float* __restrict__ weight_out, float* __restrict__ color_out,
+                                                           const float* __restrict__ freev, float* __restrict__ free_out) {
   const size_t slot = blockIdx.x;
   if (scanned_count(keep, (long)slot, count, kept) == 0u) return;
   const size_t dst = keep[slot];
@@ -218,8 +241,65 @@ __global__ __launch_bounds__(kVox) void tsdf_gather_kernel(const int* __restrict
   if (t < 3) coords_out[dst * 3 + t] = coords[slot * 3 + t];
   tsdf_out[dst * kVox + t] = tsdf[slot * kVox + t];
   weight_out[dst * kVox + t] = weight[slot * kVox + t];
+  if (freev != nullptr) free_out[dst * kVox + t] = freev[slot * kVox + t];
   if (color != nullptr)
     for (int c = 0; c < 3; ++c) color_out[dst * kVox * 3 + c * kVox + t] = color[slot * kVox * 3 + c * kVox + t];     // 1536 words, coalesced
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// Which views can see into a block (free-space carving): one wavefront per (slot, mask word), one lane per view; the ballot of the 64
+// lanes is the word (no atomic).  A lane projects the eight corners of the block's cube in scan_project's operation order.  No corner
+// in front of the camera: clear.  Some in front and some not, or a NaN among xs, ys: set.  All in front: the cube's image lies in the
+// hull of the corners' images, so the bit is set iff their bounding box, padded by a pixel, meets the image.  Depths are not read.
+// ---------------------------------------------------------------------------------------------------------------------------------
+constexpr int kFreeWaves = 4;                           // wavefronts of a workgroup
+constexpr long kFreeMaxGroups = 1L << 20;               // beyond this the wavefronts stride over the (slot, word) items
+
+__global__ __launch_bounds__(64 * kFreeWaves) void tsdf_free_views_kernel(const int* __restrict__ coords, long count,
+                                                                          const double* __restrict__ cams, int n, int rows, int cols,
+                                                                          TsdfBox B, double pixel_centre,
+                                                                          unsigned long long* __restrict__ masks, int words) {
+  const int lane = threadIdx.x & 63;
+  const long items = count * words;
+  const long first = (long)blockIdx.x * kFreeWaves + __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  for (long item = first; item < items; item += (long)gridDim.x * kFreeWaves) {      // wave-uniform: every lane reaches the ballot
+    const long slot = item / words;
+    const int view = (int)(item - slot * words) * 64 + lane;
+    bool set = false;
+    if (view < n) {                                     // the lanes beyond the last view vote 0
+      const double* __restrict__ c = cams + (size_t)view * kCam;
+      const int b0 = coords[slot * 3 + 0], b1 = coords[slot * 3 + 1], b2 = coords[slot * 3 + 2];
+      int pos = 0;
+      bool nan = false;
+      double lox = (double)INFINITY, hix = -(double)INFINITY, loy = (double)INFINITY, hiy = -(double)INFINITY;
+#pragma unroll
+      for (int k = 0; k < 8; ++k) {
+        const double X = B.ox + (double)(8 * (b0 + (k & 1))) * B.voxel;
+        const double Y = B.oy + (double)(8 * (b1 + ((k >> 1) & 1))) * B.voxel;
+        const double Z = B.oz + (double)(8 * (b2 + (k >> 2))) * B.voxel;
+        const double c2 = ((c[6] * X + c[7] * Y) + c[8] * Z) + c[11];
+        if (!(c2 > 0.0)) continue;                      // behind the camera, on its plane, or NaN
+        ++pos;
+        const double c0 = ((c[0] * X + c[1] * Y) + c[2] * Z) + c[9];
+        const double c1 = ((c[3] * X + c[4] * Y) + c[5] * Z) + c[10];
+        const double x = (c0 / c2) * c[12] + c[14];
+        const double y = (c1 / c2) * c[13] + c[15];
+        const double xs = (x - pixel_centre) + 0.5;
+        const double ys = (y - pixel_centre) + 0.5;
+        nan = nan || xs != xs || ys != ys;
+        lox = fmin(lox, xs);
+        hix = fmax(hix, xs);
+        loy = fmin(loy, ys);
+        hiy = fmax(hiy, ys);
+      }
+      if (pos == 8 && !nan)
+        set = hix >= -1.0 && lox < (double)cols + 1.0 && hiy >= -1.0 && loy < (double)rows + 1.0;
+      else
+        set = pos > 0;
+    }
+    const unsigned long long word = __ballot(set ? 1 : 0);
+    if (lane == 0) masks[item] = word;
+  }
 }
 
 // exclusive scan in place with its total: last = the last counter before, + the last entry after
@@ -603,21 +683,64 @@ extern "C" int atvs_tsdf_integrate(const float* depths, const float* images, int
   if ((images == nullptr) != (color == nullptr)) return ATVS_ERR_NULL;
   if (count > 0 && (!coords || !masks || !tsdf || !weight || !any)) return ATVS_ERR_NULL;
   if (count == 0) return ATVS_OK;
-  hipLaunchKernelGGL(tsdf_integrate_kernel, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels, cams, rows,
-                     cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf, weight, color,
-                     static_cast<unsigned*>(any));
+  hipLaunchKernelGGL(tsdf_integrate_kernel<false>, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels, cams,
+                     rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf, weight,
+                     color, static_cast<unsigned*>(any), (const unsigned long long*)nullptr, 0.0, (float*)nullptr);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_tsdf_free_views(const int* coords, long count, const double* cams, int n, int rows, int cols, double voxel,
+                                    const double* origin, int bx, int by, int bz, double pixel_centre, void* masks,
+                                    atvs_stream_t stream) {
+  if (check_maps(n, rows, cols) != ATVS_OK) return ATVS_ERR_SHAPE;
+  TsdfBox B;
+  const int rc = check_box(origin, voxel, bx, by, bz, &B);
+  if (rc != ATVS_OK) return rc;
+  if (!finite_d(pixel_centre)) return ATVS_ERR_ARG;
+  if (count < 0 || count > (long)bx * by * bz) return ATVS_ERR_SHAPE;
+  if (!cams || (count > 0 && (!coords || !masks))) return ATVS_ERR_NULL;
+  if (count == 0) return ATVS_OK;
+  const int words = (n + 63) / 64;
+  const long groups = (count * words + kFreeWaves - 1) / kFreeWaves;
+  hipLaunchKernelGGL(tsdf_free_views_kernel, dim3((unsigned)(groups < kFreeMaxGroups ? groups : kFreeMaxGroups)), dim3(64 * kFreeWaves), 0,
+                     as_stream(stream), coords, count, cams, n, rows, cols, B, pixel_centre, static_cast<unsigned long long*>(masks), words);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_tsdf_integrate_carve(const float* depths, const float* images, int channels, const double* cams, int n, int rows,
+                                         int cols, double voxel, double trunc, const double* origin, int bx, int by, int bz,
+                                         double pixel_centre, const int* coords, const void* masks, const void* free_masks,
+                                         double carve_weight, long count, float* tsdf, float* weight, float* color, float* free_out,
+                                         void* any, atvs_stream_t stream) {
+  TsdfBox B;
+  const int rc = tsdf_mark_args(depths, cams, n, rows, cols, voxel, trunc, origin, bx, by, bz, pixel_centre, &B);
+  if (rc != ATVS_OK) return rc;
+  if (!(carve_weight > 0.0) || !finite_d(carve_weight)) return ATVS_ERR_ARG;
+  if (count < 0 || count > (long)bx * by * bz) return ATVS_ERR_SHAPE;
+  if (images != nullptr && channels < 3) return ATVS_ERR_SHAPE;
+  if ((images == nullptr) != (color == nullptr)) return ATVS_ERR_NULL;
+  if (count > 0 && (!coords || !masks || !free_masks || !tsdf || !weight || !free_out || !any)) return ATVS_ERR_NULL;
+  if (count == 0) return ATVS_OK;
+  hipLaunchKernelGGL(tsdf_integrate_kernel<true>, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels, cams,
+                     rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf, weight,
+                     color, static_cast<unsigned*>(any), static_cast<const unsigned long long*>(free_masks), carve_weight, free_out);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }
 
 extern "C" int atvs_tsdf_gather(const int* coords, const float* tsdf, const float* weight, const float* color, const void* keep, long count,
-                                long kept, int* coords_out, float* tsdf_out, float* weight_out, float* color_out, atvs_stream_t stream) {
+                                long kept, int* coords_out, float* tsdf_out, float* weight_out, float* color_out, const float* free_in,
+                                float* free_out, atvs_stream_t stream) {
   if (count < 0 || count > kMaxDirectory || kept < 0 || kept > count) return ATVS_ERR_SHAPE;
   if ((color == nullptr) != (color_out == nullptr) && kept > 0) return ATVS_ERR_NULL;
+  if ((free_in == nullptr) != (free_out == nullptr) && kept > 0) return ATVS_ERR_NULL;
   if (kept > 0 && (!coords || !tsdf || !weight || !keep || !coords_out || !tsdf_out || !weight_out)) return ATVS_ERR_NULL;
   if (kept == 0) return ATVS_OK;
   hipLaunchKernelGGL(tsdf_gather_kernel, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), coords, tsdf, weight, color,
-                     static_cast<const unsigned*>(keep), count, (unsigned)kept, coords_out, tsdf_out, weight_out, color_out);
+                     static_cast<const unsigned*>(keep), count, (unsigned)kept, coords_out, tsdf_out, weight_out, color_out, free_in,
+                     free_out);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }

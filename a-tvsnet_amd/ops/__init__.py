@@ -51,7 +51,7 @@ from .cloud import cloud_normals, cloud_plane_moments_target      # noqa: F401
 from .cloud import cloud_feature_nearest, cloud_fpfh, cloud_ransac      # noqa: F401
 from .cloud import SCAN_RENDER_MAX_CAMS, SCAN_RENDER_MAX_SPLAT, scan_render      # noqa: F401
 from .cloud import CLOUD_SCAN_MAX_WINDOW, cloud_scan_excess, cloud_voxel_shares      # noqa: F401
-from .tsdf import TSDF_MAX_DIRECTORY, TSDF_MAX_MESH_BLOCKS, TSDF_MAX_PIXEL_BLOCKS, TsdfVolume, tsdf_integrate, tsdf_mesh      # noqa: F401
+from .tsdf import TSDF_MAX_DIRECTORY, TSDF_MAX_MESH_BLOCKS, TSDF_MAX_PIXEL_BLOCKS, TsdfVolume, tsdf_free_views, tsdf_integrate, tsdf_mesh      # noqa: F401
 from .mesh import MESH_RENDER_SMALL_PIXELS, depth_occlude, mesh_render      # noqa: F401
 from .mesh_topology import (MESH_CENSUS_MIN_SLOTS, MESH_CENSUS_WORDS, MESH_TOPOLOGY_MAX_FACES, mesh_components, mesh_edge_census,
     mesh_select)      # noqa: F401

@@ -42,23 +42,26 @@ def _trunc(trunc):
 class TsdfVolume(object):
     """A block-sparse TSDF volume.  origin: 3 host float64 (the corner of voxel (0,0,0); its centre is origin + 0.5 voxel), voxel,
     trunc: floats, dims: (bx, by, bz) blocks of 8^3 voxels; blocks (nb,3) int32 block coordinates (x, y, z), ascending in the linear
-    index (z by + y) bx + x; tsdf, weight (nb,8,8,8) float32 indexed [z][y][x]; color (nb,8,8,8,3) float32 (b, g, r) or None."""
-    __slots__ = ('origin', 'voxel', 'trunc', 'dims', 'blocks', 'tsdf', 'weight', 'color')
+    index (z by + y) bx + x; tsdf, weight (nb,8,8,8) float32 indexed [z][y][x]; color (nb,8,8,8,3) float32 (b, g, r) or None; free
+    (nb,8,8,8) float32, the views that saw past each voxel, or None (only tsdf_integrate with carve_weight gives one; from_dense,
+    to_dense and tsdf_mesh ignore it)."""
+    __slots__ = ('origin', 'voxel', 'trunc', 'dims', 'blocks', 'tsdf', 'weight', 'color', 'free')
 
-    def __init__(self, origin, voxel, trunc, dims, blocks, tsdf, weight, color=None):
+    def __init__(self, origin, voxel, trunc, dims, blocks, tsdf, weight, color=None, free=None):
         self.origin = np.array(list(_vec3(origin, 'origin')), np.float64)
         self.voxel, self.trunc, self.dims = _voxel(voxel), _trunc(trunc), _dims(dims)
         nb = int(blocks.shape[0])
         for t, name, dtype, shape in ((blocks, 'blocks', torch.int32, (nb, 3)), (tsdf, 'tsdf', torch.float32, (nb, 8, 8, 8)),
-                                      (weight, 'weight', torch.float32, (nb, 8, 8, 8)), (color, 'color', torch.float32, (nb, 8, 8, 8, 3))):
-            if t is None and name == 'color':
+                                      (weight, 'weight', torch.float32, (nb, 8, 8, 8)), (color, 'color', torch.float32, (nb, 8, 8, 8, 3)),
+                                      (free, 'free', torch.float32, (nb, 8, 8, 8))):
+            if t is None and name in ('color', 'free'):
                 continue
             if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape:
                 raise ValueError('%s: expected a %s tensor of shape %s, got %s %s' % (
                     name, dtype, shape, getattr(t, 'dtype', type(t).__name__), tuple(getattr(t, 'shape', ()))))
             if t.device != blocks.device:
                 raise RuntimeError('%s on %s, blocks on %s' % (name, t.device, blocks.device))
-        self.blocks, self.tsdf, self.weight, self.color = blocks, tsdf, weight, color
+        self.blocks, self.tsdf, self.weight, self.color, self.free = blocks, tsdf, weight, color, free
 
     @property
     def device(self):
@@ -146,14 +149,56 @@ def _launchable(t, name):
     return True
 
 
-def _empty_volume(origin, voxel, trunc, dims, device, with_color):
+def _empty_volume(origin, voxel, trunc, dims, device, with_color, with_free=False):
     return TsdfVolume(origin, voxel, trunc, dims, torch.empty((0, 3), dtype=torch.int32, device=device),
                       torch.empty((0, 8, 8, 8), dtype=torch.float32, device=device),
                       torch.empty((0, 8, 8, 8), dtype=torch.float32, device=device),
-                      torch.empty((0, 8, 8, 8, 3), dtype=torch.float32, device=device) if with_color else None)
+                      torch.empty((0, 8, 8, 8, 3), dtype=torch.float32, device=device) if with_color else None,
+                      torch.empty((0, 8, 8, 8), dtype=torch.float32, device=device) if with_free else None)
 
 
-def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_centre=0.0, max_blocks=131072):
+def _carve_weight(carve_weight):
+    """None, or the weight of a free vote as a float: finite and > 0; anything else raises ValueError."""
+    if carve_weight is None:
+        return None
+    if isinstance(carve_weight, bool) or not isinstance(carve_weight, (int, float, np.integer, np.floating)):
+        raise ValueError('carve_weight must be None or a finite number > 0, got %r' % (carve_weight,))
+    cw = float(carve_weight)
+    if not (cw > 0.0 and math.isfinite(cw)):
+        raise ValueError('carve_weight must be None or a finite number > 0, got %r' % (carve_weight,))
+    return cw
+
+
+def tsdf_free_views(blocks, cams, rows, cols, voxel, origin, dims, pixel_centre=0.0):
+    """blocks (count,3) int32 block coordinates of the box (origin, voxel, dims), cams (n,16) float64 -> (count, ceil(n/64)) int64:
+    bit v of a block's words is set unless view v provably sees no voxel centre of the block (include/atvsnet_hip.h has the rule:
+    the eight corners of the block's cube projected, their bounding box padded by a pixel against the image; depths are not
+    consulted).  A superset of the views that contribute to or carve a voxel of the block: what tsdf_integrate's carving loops over."""
+    voxel, dims = _voxel(voxel), _dims(dims)
+    org = _vec3(origin, 'origin')
+    centre = float(pixel_centre)
+    if not math.isfinite(centre):
+        raise ValueError('pixel_centre must be finite, got %r' % (pixel_centre,))
+    rows, cols = _int_in(rows, 'rows', 1), _int_in(cols, 'cols', 1)
+    _map_arg(blocks, 'blocks', torch.int32, 2, '(count,3)')
+    _map_arg(cams, 'cams', torch.float64, 2, '(n,16)')
+    count, n = int(blocks.shape[0]), int(cams.shape[0])
+    if int(blocks.shape[1]) != 3:
+        raise ValueError('blocks: expected shape (count,3), got %s' % (tuple(blocks.shape),))
+    if int(cams.shape[1]) != 16 or not 1 <= n <= SCAN_RENDER_MAX_CAMS:
+        raise ValueError('cams: expected shape (n,16) with 1 <= n <= %d, got %s' % (SCAN_RENDER_MAX_CAMS, tuple(cams.shape)))
+    if n * rows * cols >= 1 << 31:
+        raise ValueError('%d maps of %d x %d: 2^31 pixels or more' % (n, rows, cols))
+    if count > dims[0] * dims[1] * dims[2]:
+        raise ValueError('blocks: %d blocks in a box of %d' % (count, dims[0] * dims[1] * dims[2]))
+    _same_device(cams, 'cams', blocks, 'blocks')
+    masks = torch.empty((count, (n + 63) // 64), dtype=torch.int64, device=blocks.device)
+    if _launchable(blocks, 'blocks') and count:
+        _call('atvs_tsdf_free_views', _p(blocks), count, _p(cams), n, rows, cols, voxel, org, *dims, centre, _p(masks), _stream())
+    return masks
+
+
+def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_centre=0.0, max_blocks=131072, carve_weight=None):
     """depths (n,rows,cols) float32 z-depth (0 or non-finite: no sample), cams (n,16) float64 in scan_render's layout, images
     (n,rows,cols,C>=3) float32 with b, g, r in channels 0..2 or None -> TsdfVolume over the box (origin, voxel, dims).
 
@@ -162,7 +207,14 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
     of contributing views, color the mean of the pixels' b, g, r.  A view outside that band adds nothing (no free-space carving).
     The volume holds exactly the blocks with a voxel of weight > 0; the same inputs give the same bits.  Blocks are first marked
     conservatively from the maps; more than `max_blocks` marked blocks raise a ValueError that names the count, and a voxel so small
-    that one pixel's depth segment meets more than 4096 blocks raises too.  Synchronises twice (the two counts)."""
+    that one pixel's depth segment meets more than 4096 blocks raises too.  Synchronises twice (the two counts).
+
+    carve_weight: None (the above, with the launches it always made), or a finite number > 0: free-space carving.  A view whose
+    depth lies beyond a voxel's band (sdf > trunc) has seen past the voxel: it adds 1 to the voxel's `free` count Wf and no colour,
+    and tsdf = (S + cw Wf) / (W + cw Wf) over the in-band sums S, W.  weight stays the in-band count, a voxel no view has in band
+    is not carved, so blocks, weight and color keep their bits, and tsdf does wherever free == 0; the volume's `free` holds Wf.
+    One more launch (tsdf_free_views: the views that can see into each marked block) and a second form of the integrate kernel."""
+    cw = _carve_weight(carve_weight)
     voxel, trunc, dims = _voxel(voxel), _trunc(trunc), _dims(dims)
     org = _vec3(origin, 'origin')
     centre = float(pixel_centre)
@@ -188,7 +240,7 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
         channels = int(images.shape[3])
     dev = depths.device
     if not _launchable(depths, 'depths'):
-        return _empty_volume(origin, voxel, trunc, dims, dev, images is not None)
+        return _empty_volume(origin, voxel, trunc, dims, dev, images is not None, cw is not None)
     bx, by, bz = dims
     nbk = bx * by * bz
     box = (voxel, trunc, org, bx, by, bz, centre)
@@ -203,7 +255,7 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
     if count > max_blocks:
         raise ValueError('tsdf_integrate: the maps mark %d blocks of %d, max_blocks is %d: raise it, or the voxel' % (count, nbk, max_blocks))
     if count == 0:
-        return _empty_volume(origin, voxel, trunc, dims, dev, images is not None)
+        return _empty_volume(origin, voxel, trunc, dims, dev, images is not None, cw is not None)
     words = (n + 63) // 64
     coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
     masks = torch.empty((count, words), dtype=torch.int64, device=dev)
@@ -212,20 +264,28 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
     weight = torch.empty((count, 8, 8, 8), dtype=torch.float32, device=dev)
     color = torch.empty((count, 8, 8, 8, 3), dtype=torch.float32, device=dev) if images is not None else None
     keep = torch.empty(count, dtype=torch.int32, device=dev)
-    _call('atvs_tsdf_integrate', _p(depths), _p(images), channels, _p(cams), n, rows, cols, *box, _p(coords), _p(masks), count,
-          _p(tsdf), _p(weight), _p(color), _p(keep), _stream())
+    free = None
+    if cw is None:
+        _call('atvs_tsdf_integrate', _p(depths), _p(images), channels, _p(cams), n, rows, cols, *box, _p(coords), _p(masks), count,
+              _p(tsdf), _p(weight), _p(color), _p(keep), _stream())
+    else:
+        free_masks = tsdf_free_views(coords, cams, rows, cols, voxel, origin, dims, centre)
+        free = torch.empty((count, 8, 8, 8), dtype=torch.float32, device=dev)
+        _call('atvs_tsdf_integrate_carve', _p(depths), _p(images), channels, _p(cams), n, rows, cols, *box, _p(coords), _p(masks),
+              _p(free_masks), cw, count, _p(tsdf), _p(weight), _p(color), _p(free), _p(keep), _stream())
     kept = int(_scan(keep, count).item())
     if kept == count:
-        return TsdfVolume(origin, voxel, trunc, dims, coords, tsdf, weight, color)
-    out = _empty_volume(origin, voxel, trunc, dims, dev, images is not None)
+        return TsdfVolume(origin, voxel, trunc, dims, coords, tsdf, weight, color, free)
+    out = _empty_volume(origin, voxel, trunc, dims, dev, images is not None, cw is not None)
     if kept == 0:
         return out
     out.blocks = torch.empty((kept, 3), dtype=torch.int32, device=dev)
     out.tsdf = torch.empty((kept, 8, 8, 8), dtype=torch.float32, device=dev)
     out.weight = torch.empty((kept, 8, 8, 8), dtype=torch.float32, device=dev)
     out.color = torch.empty((kept, 8, 8, 8, 3), dtype=torch.float32, device=dev) if images is not None else None
+    out.free = torch.empty((kept, 8, 8, 8), dtype=torch.float32, device=dev) if cw is not None else None
     _call('atvs_tsdf_gather', _p(coords), _p(tsdf), _p(weight), _p(color), _p(keep), count, kept,
-          _p(out.blocks), _p(out.tsdf), _p(out.weight), _p(out.color), _stream())
+          _p(out.blocks), _p(out.tsdf), _p(out.weight), _p(out.color), _p(free), _p(out.free), _stream())
     return out
 
 

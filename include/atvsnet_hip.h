@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 60
+#define ATVS_ABI_VERSION 61
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1178,9 +1178,31 @@ int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* e
  *   atvs_tsdf_integrate: one workgroup per slot over the views of its mask -> tsdf, weight (count,8,8,8), color (count,8,8,8,3) or
  *   NULL with images NULL, any (count unsigned words) = 1 where the slot has a voxel of weight > 0.
  *   atvs_tsdf_gather: keep = the scanned `any`, kept its total -> the kept slots, in order, in coords_out, tsdf_out, weight_out,
- *   color_out: exactly the blocks that have a voxel of weight > 0.
+ *   color_out: exactly the blocks that have a voxel of weight > 0; free_in (count,8,8,8) or NULL is carried into free_out alike.
  * trunc <= 0 or not finite, voxel <= 0 or not finite, a non-finite origin or pixel_centre: ATVS_ERR_ARG; n rows cols >= 2^31,
  * n outside [1, ATVS_SCAN_RENDER_MAX_CAMS], a box beyond the limit, count beyond the directory, channels < 3: ATVS_ERR_SHAPE.
+ *
+ * Free-space carving (opt-in: atvs_tsdf_integrate_carve; atvs_tsdf_integrate is as above).  Per voxel and view, views ascending,
+ * in double, nothing contracted, with exactly the projection and the pixel above: d is the pixel's depth, sdf = (double)d - c_2.
+ * A view that is in view (scan_project true) with d > 0 and d finite is IN BAND when -trunc <= sdf <= trunc -- the contribution to
+ * S, W, C above, unchanged and in the same order --, FREE when sdf > trunc: Wf += 1, no colour (the view saw past the voxel), and
+ * nothing when sdf < -trunc (the voxel is occluded).  A depth that is no sample (0, negative, NaN, +-inf) carves nothing; a voxel
+ * behind the camera (c_2 <= 0) or outside the image is not carved.  At the end, with cw = carve_weight > 0 and f = cw * Wf formed
+ * once: weight = (float)W (the in-band count only: min_weight keeps its meaning), free = (float)Wf where W > 0, else 0,
+ * tsdf = (float)((S + f) / (W + f)) where W > 0, else 0, colour as above.  The volume holds exactly the blocks with a voxel of
+ * W > 0: a voxel that no view has in band is not carved, so the values still do not depend on which blocks or views an
+ * implementation visits.  Consequences: blocks, weight and color are bit for bit those of the run without carving, and so is tsdf
+ * wherever free == 0 (f = 0, and S is never -0: d - c_2 rounds an exact zero to +0).
+ *   atvs_tsdf_free_views: coords (count,3) int32 block coordinates -> masks (count, ceil(n / 64)) 64-bit words: bit v is set unless
+ *   view v provably sees no voxel centre of the block.  The rule, exactly: the eight corners of the block's cube are
+ *   origin[a] + (double)(8 * (b[a] + delta_a)) * voxel, delta in {0,1}^3; for each, c_2, then c_0, c_1, x, y, xs, ys in
+ *   scan_project's operation order.  No corner has c_2 > 0: clear.  Some corners have c_2 > 0 and some do not, or xs or ys of a
+ *   corner with c_2 > 0 is NaN: set.  All eight have c_2 > 0: set iff max xs >= -1, min xs < cols + 1, max ys >= -1 and
+ *   min ys < rows + 1.  With c_2 > 0 over the whole cube its image lies in the hull of the corners' images, so the mask is a
+ *   superset of the views that contribute to or carve a voxel of the block; the pixel of padding is far above the rounding of the
+ *   corner arithmetic.  Depths are not consulted.  The bits of the last word beyond view n - 1 are 0.
+ *   atvs_tsdf_integrate_carve: as atvs_tsdf_integrate over the views of masks | free_masks (both (count, ceil(n / 64))), with
+ *   free_out (count,8,8,8).  carve_weight <= 0 or not finite: ATVS_ERR_ARG.
  *
  * Extraction.  blocks (nb,3) int32 ascending in the linear index, each at most once, nb <= ATVS_TSDF_MAX_MESH_BLOCKS; tsdf, weight
  * (nb,8,8,8), color (nb,8,8,8,3) or NULL.  A voxel is VALID when weight >= min_weight (a voxel of a missing block or outside the
@@ -1224,7 +1246,14 @@ int atvs_tsdf_integrate(const float* depths, const float* images, int channels, 
                         const int* coords, const void* masks, long count, float* tsdf, float* weight, float* color, void* any,
                         atvs_stream_t stream);
 int atvs_tsdf_gather(const int* coords, const float* tsdf, const float* weight, const float* color, const void* keep, long count,
-                     long kept, int* coords_out, float* tsdf_out, float* weight_out, float* color_out, atvs_stream_t stream);
+                     long kept, int* coords_out, float* tsdf_out, float* weight_out, float* color_out, const float* free_in,
+                     float* free_out, atvs_stream_t stream);
+int atvs_tsdf_free_views(const int* coords, long count, const double* cams, int n, int rows, int cols, double voxel,
+                         const double* origin, int bx, int by, int bz, double pixel_centre, void* masks, atvs_stream_t stream);
+int atvs_tsdf_integrate_carve(const float* depths, const float* images, int channels, const double* cams, int n, int rows, int cols,
+                              double voxel, double trunc, const double* origin, int bx, int by, int bz, double pixel_centre,
+                              const int* coords, const void* masks, const void* free_masks, double carve_weight, long count,
+                              float* tsdf, float* weight, float* color, float* free_out, void* any, atvs_stream_t stream);
 int atvs_tsdf_mesh_count(const int* blocks, int nb, int bx, int by, int bz, const float* tsdf, const float* weight,
                          float min_weight, void* cube_ok, void* emask, void* vcount, void* fcount, atvs_stream_t stream);
 int atvs_tsdf_mesh_emit(const int* blocks, int nb, int bx, int by, int bz, double voxel, const double* origin, const float* tsdf,

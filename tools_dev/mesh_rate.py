@@ -11,9 +11,13 @@ The scene: the sphere of tests/tsdf_restated.py (radius 0.9) rendered analytical
     restatement  tests/tsdf_restated.py on the host: integrate over a sub-box of --host_blocks^3 blocks and --host_views views, mesh
                  of that sub-box, as voxel-views / s and faces / s.  The whole scene is not restated: 64 Mi voxels x 64 views.
 
+    carve        (--carve, a run of its own) free-space carving on the same scene: integrate without and with carving on the same
+                 slots, the free-view launch, the free mask's bits out of slots x views, the voxels with a free vote.
+
 Each step runs as a child process under its own time limit, one after the other; the first that fails ends the run.
 
     python tools_dev/mesh_rate.py --out profiles/tsdf_mesh.json
+    python tools_dev/mesh_rate.py --carve --out profiles/tsdf_mesh_carve.json
 """
 import argparse
 import json
@@ -36,6 +40,7 @@ from fusion_rate import measured_head  # noqa: E402
 
 RADIUS = 0.9
 STEPS = (('kernels', 300), ('scene', 300), ('restatement', 400))
+CARVE_STEPS = (('carve', 300),)
 MEASURED = ('a-tvsnet_amd/csrc/tsdf.hip', 'a-tvsnet_amd/csrc/scan_project.h', 'a-tvsnet_amd/csrc/cloud_scan.h', 'a-tvsnet_amd/ops/tsdf.py',
             'a-tvsnet_amd/atvsnet/mesh_fusion.py')
 
@@ -151,6 +156,71 @@ def step_kernels(a):
             'extract_faces_per_s': nf / ((ms['mesh_count'] + ms['mesh_copy_and_scans'] + ms['mesh_emit']) * 1e-3)}
 
 
+def step_carve(a):
+    """Integration with and without carving on the slots ops.tsdf_integrate would make, entry point by entry point."""
+    import torch
+    from atvsnet_amd import ops
+    from atvsnet_amd.ops import tsdf as T
+    from atvsnet_amd.ops.base import _call, _p, _stream
+    from atvsnet_amd.ops.cloud import _vec3
+    dev = torch.device('cuda:0')
+    torch.cuda.set_device(dev)
+    cams, depths, images, trunc, origin, dims = scene(a)
+    d, c, im = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (depths, cams, images))
+    n, rows, cols = depths.shape
+    bx, by, bz = dims
+    nbk = bx * by * bz
+    org = _vec3(origin, 'origin')
+    box = (a.voxel, trunc, org, bx, by, bz, 0.0)
+    directory = torch.empty(nbk, dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _call('atvs_tsdf_mark', _p(d), _p(c), n, rows, cols, *box, _p(directory), _p(err), _stream())
+    count = int(T._scan(directory, nbk).item())
+    assert int(err.item()) == 0 and 0 < count <= a.max_blocks, count
+    words = (n + 63) // 64
+    coords = torch.empty((count, 3), dtype=torch.int32, device=dev)
+    masks = torch.empty((count, words), dtype=torch.int64, device=dev)
+    free_masks = torch.empty((count, words), dtype=torch.int64, device=dev)
+    _call('atvs_tsdf_assign', _p(d), _p(c), n, rows, cols, *box, _p(directory), count, _p(coords), _p(masks), _p(err), _stream())
+    tsdf = torch.empty((count, 8, 8, 8), dtype=torch.float32, device=dev)
+    weight, free = torch.empty_like(tsdf), torch.empty_like(tsdf)
+    color = torch.empty((count, 8, 8, 8, 3), dtype=torch.float32, device=dev)
+    keep = torch.empty(count, dtype=torch.int32, device=dev)
+    ms, all_ms = {}, {}
+
+    def timed(name, fn):
+        out, ms[name], all_ms[name] = _median_ms(fn, a.reps)
+        return out
+
+    timed('integrate', lambda: _call('atvs_tsdf_integrate', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks), count,
+                                     _p(tsdf), _p(weight), _p(color), _p(keep), _stream()))
+    plain_tsdf, plain_weight = tsdf.clone(), weight.clone()
+    timed('free_views', lambda: _call('atvs_tsdf_free_views', _p(coords), count, _p(c), n, rows, cols, a.voxel, org, bx, by, bz, 0.0,
+                                      _p(free_masks), _stream()))
+    timed('integrate_carve', lambda: _call('atvs_tsdf_integrate_carve', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks),
+                                           _p(free_masks), a.carve_weight, count, _p(tsdf), _p(weight), _p(color), _p(free), _p(keep),
+                                           _stream()))
+    assert torch.equal(weight, plain_weight)
+
+    def popcount(m):
+        return int(sum(bin(int(w)).count('1') for w in m.cpu().numpy().view(np.uint64).reshape(-1)))
+    band_bits, loop_bits = popcount(masks), popcount(masks | free_masks)
+    free_bits = popcount(free_masks)
+    _, ms['tsdf_integrate_call'], all_ms['tsdf_integrate_call'] = _median_ms(
+        lambda: ops.tsdf_integrate(d, c, a.voxel, trunc, origin, dims, images=im, max_blocks=a.max_blocks), a.reps)
+    volume, ms['tsdf_integrate_call_carve'], all_ms['tsdf_integrate_call_carve'] = _median_ms(
+        lambda: ops.tsdf_integrate(d, c, a.voxel, trunc, origin, dims, images=im, max_blocks=a.max_blocks, carve_weight=a.carve_weight), a.reps)
+    valid = volume.weight >= a.min_weight
+    flipped = int(((tsdf < 0) != (plain_tsdf < 0))[plain_weight >= a.min_weight].sum().item())
+    return {'device': torch.cuda.get_device_name(dev), 'carve_weight': a.carve_weight, 'marked_blocks': count, 'kept_blocks': volume.num_blocks,
+            'views': n, 'band_mask_bits': band_bits, 'free_mask_bits': free_bits, 'loop_mask_bits': loop_bits,
+            'free_mask_share_of_slots_x_views': free_bits / float(count * n), 'voxel_views_plain': band_bits * 512,
+            'voxel_views_carve': loop_bits * 512, 'valid_voxels': int(valid.sum().item()),
+            'free_voxels': int((valid & (volume.free > 0)).sum().item()), 'max_free': float(volume.free.max().item()),
+            'valid_voxels_whose_sign_flipped': flipped, 'ms': ms, 'ms_all': all_ms,
+            'carve_voxel_views_per_s': loop_bits * 512 / (ms['integrate_carve'] * 1e-3)}
+
+
 def step_scene(a):
     import torch
     from atvsnet_amd.atvsnet import depth_fusion as DF, mesh_fusion
@@ -212,11 +282,13 @@ def main():
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--host_blocks', type=int, default=8)
     ap.add_argument('--host_views', type=int, default=4)
-    ap.add_argument('--step', default=None, choices=[s for s, _ in STEPS], help='run one step in this process and write its result to --out')
+    ap.add_argument('--carve_weight', type=float, default=1.0)
+    ap.add_argument('--carve', action='store_true', help='run the carve step alone (for profiles/tsdf_mesh_carve.json)')
+    ap.add_argument('--step', default=None, choices=[s for s, _ in STEPS + CARVE_STEPS], help='run one step in this process and write its result to --out')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.step is not None:
-        result = {'kernels': step_kernels, 'scene': step_scene, 'restatement': step_restatement}[a.step](a)
+        result = {'kernels': step_kernels, 'scene': step_scene, 'restatement': step_restatement, 'carve': step_carve}[a.step](a)
         print(json.dumps({k: v for k, v in result.items() if not k.endswith('_all')}), flush=True)
         if a.out:
             with open(a.out, 'w') as f:
@@ -226,10 +298,10 @@ def main():
                'scene': {'maps': a.maps, 'rows': a.rows, 'cols': a.cols, 'voxel': a.voxel, 'trunc_voxels': 4.0, 'min_weight': a.min_weight,
                          'sphere_radius': RADIUS, 'cameras': 'tests/scan_render_restated.ring_cameras'},
                'reps': a.reps}
-    passed = [k for k in ('maps', 'rows', 'cols', 'voxel', 'min_weight', 'max_blocks', 'reps', 'host_blocks', 'host_views')]
+    passed = [k for k in ('maps', 'rows', 'cols', 'voxel', 'min_weight', 'max_blocks', 'reps', 'host_blocks', 'host_views', 'carve_weight')]
     common = [x for k in passed for x in ('--' + k, str(getattr(a, k)))]
     with tempfile.TemporaryDirectory() as tmp:
-        for step, limit in STEPS:                        # one after the other: a step that fails or runs out of time ends the run
+        for step, limit in (CARVE_STEPS if a.carve else STEPS):                        # one after the other: a step that fails or runs out of time ends the run
             part = os.path.join(tmp, step + '.json')
             try:
                 rc = subprocess.run([sys.executable, os.path.abspath(__file__), '--step', step, '--out', part] + common, timeout=limit).returncode
