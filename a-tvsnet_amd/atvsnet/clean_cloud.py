@@ -32,6 +32,7 @@ import os
 import numpy as np
 
 from ..tools import ply
+from ..tools.common import write_json  # noqa: F401
 
 SOR_RADIUS_VOXELS = 8.0          # --sor without --sor_radius: the horizon is this many voxel edges.  A default, not a measurement.
 
@@ -134,15 +135,8 @@ def clean(points, colors=None, voxel=None, sor=None, radius_filter=None, device=
     return out_p, out_c, report
 
 
-def write_json(path, report):
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, 'w') as f:
-        json.dump(report, f, indent=1, sort_keys=True)
-        f.write('\n')
-
-
 def add_options(parser, prefix=''):
-    """The three steps' options, named --<prefix>voxel, --<prefix>sor, --<prefix>sor_radius, --<prefix>radius_filter."""
+    """The three steps' options --<prefix>voxel, --<prefix>sor, --<prefix>sor_radius, --<prefix>radius_filter, and --<prefix>keep_normals."""
     parser.add_argument('--%svoxel' % prefix, type=float, default=None, metavar='V',
                         help='keep one point per occupied voxel of edge V: the mean of its points, the colour of its first')
     parser.add_argument('--%ssor' % prefix, default=None, metavar='K,RATIO',
@@ -153,6 +147,18 @@ def add_options(parser, prefix=''):
                              'with --%svoxel V: %g V (a default, not a measurement); required without' % (prefix, prefix, SOR_RADIUS_VOXELS))
     parser.add_argument('--%sradius_filter' % prefix, default=None, metavar='R,N',
                         help='remove a point with fewer than N other points within the distance R')
+    parser.add_argument('--%skeep_normals' % prefix, action='store_true',
+                        help='the cloud carries normals (nx ny nz, as `depth_fusion --normals depth` writes them; the ETH3D driver: --fuse_normals '
+                             'depth): write those of the rows that stay into the cleaned cloud (a voxel keeps the normal of its first row)')
+
+
+def keep_normals_rules(clean, keep_normals, fused_normals):
+    """The ETH3D driver's rules for its clean_keep_normals, as (broken, message) rows: none unless it is asked for.  clean: the
+    driver's cleaning steps or None; fused_normals: whether its fusion estimates normals (fuse_normals normals='depth')."""
+    return [] if not keep_normals else [
+        (not clean, '--clean_keep_normals needs --clean_voxel, --clean_sor or --clean_radius_filter (clean_keep_normals needs clean)'),
+        (not fused_normals, '--clean_keep_normals needs --fuse_normals depth (clean_keep_normals needs fuse_normals normals=depth): '
+                            'there are no normals to keep')]
 
 
 def options(parser, args, prefix=''):
@@ -197,9 +203,6 @@ def make_parser():
     parser.add_argument('--in', dest='input', required=True, help='the cloud (a PLY as depth_fusion writes it)')
     parser.add_argument('--out', required=True, help='the cleaned cloud (PLY)')
     add_options(parser)
-    parser.add_argument('--keep_normals', action='store_true',
-                        help='the input carries normals (nx ny nz, as `depth_fusion --normals depth` writes them): write those of '
-                             'the rows that stay into the cleaned cloud (a voxel keeps the normal of its first row)')
     parser.add_argument('--report', default=None, metavar='FILE.json', help='write what every step did here (default: print it)')
     parser.add_argument('--gpu_id', type=int, default=0)
     return parser

@@ -32,6 +32,7 @@ from fractions import Fraction
 import numpy as np
 
 from ..tools import ply
+from ..tools.common import write_json  # noqa: F401
 
 REPORT_LARGEST = 16               # the report lists the sizes of this many largest components
 
@@ -147,13 +148,6 @@ def clean(vertices, colors, faces, min_faces=None, min_ratio=None, keep_largest=
     return out + (report,)
 
 
-def write_json(path, report):
-    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
-    with open(path, 'w') as f:
-        json.dump(report, f, indent=1, sort_keys=True)
-        f.write('\n')
-
-
 def add_options(parser, prefix=''):
     """The three criteria's options, named --<prefix>min_faces, --<prefix>min_ratio, --<prefix>keep_largest.  None has a default."""
     parser.add_argument('--%smin_faces' % prefix, type=int, default=None, metavar='N',
@@ -166,12 +160,13 @@ def add_options(parser, prefix=''):
 
 
 def options(parser, args, prefix=''):
-    """The parsed options of add_options as clean's keyword arguments ({} when none is given); a bad one is an argument error."""
+    """The parsed options of add_options as clean's keyword arguments ({} when none is given); a bad one is an argument error.
+    parser None: nothing is checked, and an option `args` lacks is not given."""
     out = {}
     for name in ('min_faces', 'min_ratio', 'keep_largest'):
-        if getattr(args, prefix + name) is not None:
+        if getattr(args, prefix + name, None) is not None:
             out[name] = getattr(args, prefix + name)
-    if out:
+    if out and parser is not None:
         try:
             check_criteria(**out)
         except ValueError as e:

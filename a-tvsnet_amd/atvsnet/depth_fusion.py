@@ -306,7 +306,7 @@ def _plane(t, what):
 
 class SceneFusion(object):
     """The point-cloud stage of a scene on the device, without the files: every depth map is staged into a scene-resident slab as
-    it is finished (`add`, atvs_fusion_stage_f32: the inverse-depth step of eval_pointcloud._write_map, probability_filter and
+    it is finished (`add`, atvs_fusion_stage_f32: the inverse-depth step of eth3d_maps._write_map, probability_filter and
     fake_colmap_normal), and `run` fuses all reference cameras in one pass (atvs_fusibile_scene) into the points and colours
     fuse_views computes on the same maps, in the same order.  The cameras are ordered by `out_index` ascending, as the sorted
     2333__%08d folders of depth_map_fusion order them.
@@ -470,28 +470,60 @@ def depth_map_fusion(point_folder, fusibile_exe_path, disp_thresh, num_consisten
     return out
 
 
-def main(argv=None):
+def add_options(parser, prefix='', defaults=True):
+    """The normal options, named --<prefix>normals, --<prefix>normal_threshold, --<prefix>normal_step, --<prefix>normal_depth_gate.
+    defaults: this tool's form, where normals, normal_step and normal_depth_gate default to check_normal_options' own; False: the
+    ETH3D driver's (prefix 'fuse_'), where every one defaults to None and only what is given is passed on."""
+    parser.add_argument('--%snormals' % prefix, choices=NORMAL_SOURCES, default='fake' if defaults else None,
+                        help='fake (the default): the constant normal of the reference; depth: estimated from each depth map on the '
+                             'GPU, tested in the fusion and written into the PLY')
+    parser.add_argument('--%snormal_threshold' % prefix, type=float, default=None, metavar='DEG',
+                        help='largest angle between the normals of two agreeing views (default: 360 with normals fake, %g with '
+                             'normals depth)' % DEPTH_NORMAL_THRESHOLD_DEG)
+    parser.add_argument('--%snormal_step' % prefix, type=int, default=1 if defaults else None, metavar='S',
+                        help='normals depth: pixel distance of the neighbours (default 1)')
+    parser.add_argument('--%snormal_depth_gate' % prefix, type=float, default=0.02 if defaults else None, metavar='G',
+                        help='normals depth: a neighbour counts when its depth is within G * depth (default 0.02)')
+
+
+def options(parser, args, prefix=''):
+    """The options of add_options that were given, as SceneFusion's / check_normal_options' keyword arguments ({} when none was); a bad
+    one is an argument error.  parser None: nothing is checked, and an option `args` lacks is not given.  This is the ETH3D driver's
+    fuse_normals (with fuse only): with normals='depth' its fusion estimates each map's normals from its depths, tests them and writes
+    them into final3d_model.ply -- what main --normals depth makes from the written files; scoring and cleaning read the points as before."""
+    out = {name: getattr(args, prefix + name) for name in ('normals', 'normal_threshold', 'normal_step', 'normal_depth_gate')
+           if getattr(args, prefix + name, None) is not None}
+    if parser is not None:
+        try:
+            check_normal_options(**out)
+        except ValueError as e:
+            parser.error(str(e))
+    return out
+
+
+def normal_rules(fuse_normals, fuse):
+    """The ETH3D driver's rule for its fuse_normals, as (broken, message) rows: listed for a caller that gives fuse_normals --
+    without it there is nothing the row could refuse."""
+    return [] if fuse_normals is None else [
+        (fuse is None, '--fuse_normals, --fuse_normal_threshold, --fuse_normal_step and --fuse_normal_depth_gate need --fuse '
+                       '(fuse_normals needs fuse): there is no fusion whose normals they could set')]
+
+
+def make_parser():
     parser = argparse.ArgumentParser()
     parser.add_argument('--dense_folder', type=str, default='../eval/pointcloud/lakeside')
     parser.add_argument('--fusibile_exe_path', type=str, default='../fusibile/build/fusibile')
     parser.add_argument('--prob_threshold', type=float, default=0.8)
     parser.add_argument('--disp_threshold', type=float, default=0.01)
     parser.add_argument('--num_consistent', type=float, default=2)
-    parser.add_argument('--normals', choices=NORMAL_SOURCES, default='fake',
-                        help='fake: the constant normal of the reference; depth: estimated from each depth map on the GPU, tested in '
-                             'the fusion and written into the PLY')
-    parser.add_argument('--normal_threshold', type=float, default=None, metavar='DEG',
-                        help='largest angle between the normals of two agreeing views (default: 360 with --normals fake, %g with '
-                             '--normals depth)' % DEPTH_NORMAL_THRESHOLD_DEG)
-    parser.add_argument('--normal_step', type=int, default=1, metavar='S', help='--normals depth: pixel distance of the neighbours')
-    parser.add_argument('--normal_depth_gate', type=float, default=0.02, metavar='G',
-                        help='--normals depth: a neighbour counts when its depth is within G * depth')
+    add_options(parser)
+    return parser
+
+
+def main(argv=None):
+    parser = make_parser()
     args = parser.parse_args(argv)
-    try:
-        normals, normal_threshold, normal_step, normal_depth_gate = check_normal_options(
-            args.normals, args.normal_threshold, args.normal_step, args.normal_depth_gate)
-    except ValueError as e:
-        parser.error(str(e))
+    normals, normal_threshold, normal_step, normal_depth_gate = check_normal_options(**options(parser, args))
     dense_folder = args.dense_folder
     point_folder = os.path.join(dense_folder, 'points_atvsnet')
     if not os.path.isdir(point_folder):

@@ -49,6 +49,7 @@ import os
 import numpy as np
 
 from ..tools import ply
+from ..tools.common import write_json  # noqa: F401
 
 DEFAULT_TOLERANCES = (0.01, 0.02, 0.05, 0.1, 0.2, 0.5)
 NO_NORMALS = ('%s carries no normals (nx ny nz): point-to-plane registration needs the reconstruction\'s own; fuse it with '
@@ -324,18 +325,29 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
     return result
 
 
-def write_json(path, result):
-    with open(path, 'w') as f:
-        json.dump(result, f, indent=1, sort_keys=True)
-        f.write('\n')
-
-
 GLOBAL_FLAGS = {'global_voxel': 'feature_voxel', 'global_hypotheses': 'hypotheses', 'global_seed': 'seed', 'global_tau': 'tau',
                 'global_no_mutual': 'mutual'}                      # command-line option -> register_cloud.global_init's argument
 
 
-def add_global_arguments(parser):
-    """--register_global and its options (eval_pointcloud's command line has the same)."""
+def add_register_arguments(parser):
+    """--register and the registration options this command line and eval_pointcloud's share."""
+    parser.add_argument('--register', action='store_true',
+                        help='align the reconstruction to the ground truth before scoring (voxel down-sampling + ICP in stages)')
+    parser.add_argument('--with_scale', action='store_true', help='--register: fit a similarity (scale too), not a rigid motion')
+    parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
+                        help='--register: point-to-point ICP (the default) or point-to-plane over the normals the reconstruction carries (nx ny nz '
+                             'in its PLY, as `depth_fusion --normals depth` writes them; eval_pointcloud: --fuse_normals depth): far fewer iterations')
+    parser.add_argument('--register_normals', default=None, choices=('source', 'target'),
+                        help='--register_icp plane: whose planes -- source (the default: the reconstruction\'s own normals) or '
+                             'target (the ground truth\'s, estimated on the GPU: the reconstruction needs none)')
+    parser.add_argument('--register_normal_k', type=int, default=None, metavar='K',
+                        help='--register_normals target: neighbours per estimated normal, 2..32 (default 16; a default, not a measurement)')
+    parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
+                        help='--register_normals target: their search radius (default: 4 edges of the registration\'s voxel, or twice '
+                             'the last distance without one; a default, not a measurement)')
+    parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
+                        help='two COLMAP sparse model folders of the same images, in the reconstruction\'s and the ground truth\'s '
+                             'frame: the similarity between their camera centres (matched by image name) is the initial matrix')
     parser.add_argument('--register_global', action='store_true',
                         help='--register: find the starting matrix from the clouds alone (FPFH descriptors matched in feature space, '
                              'RANSAC over triples of matches, on the GPU) instead of --init_transform / --init_cameras')
@@ -354,28 +366,91 @@ def add_global_arguments(parser):
                         help='--register_global: keep every source-to-target match, not only those the target matches back')
 
 
-def register_options(parser, args):
-    """The registration options of a parsed command line as evaluate_files' keyword arguments ({} when none is given);
-    contradictory ones are argument errors."""
-    if args.init_transform and args.init_cameras:
-        parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
-    for name in ('with_scale', 'register_distances', 'register_voxel', 'register_icp', 'register_normals', 'register_normal_k',
-                 'register_normal_radius', 'register_global'):
+def check_register_values(parser, args, need_register=('register_global',)):
+    """The argument errors this command line and eval_pointcloud's share: an option of `need_register` or of --register_global's without
+    its switch; --global_hypotheses, --global_seed, --register_normal_k or --register_normal_radius out of range."""
+    for name in need_register:
         if getattr(args, name) not in (None, False) and not args.register:
             parser.error('--%s needs --register' % name)
     for name in GLOBAL_FLAGS:
         if getattr(args, name) not in (None, False) and not args.register_global:
             parser.error('--%s needs --register_global' % name)
+    if args.global_hypotheses is not None and not 1 <= args.global_hypotheses <= 1 << 24:
+        parser.error('--global_hypotheses must be in 1..2^24')
+    if args.global_seed is not None and args.global_seed < 0:
+        parser.error('--global_seed must be >= 0')
+    if args.register_normal_k is not None and not 2 <= args.register_normal_k <= 32:
+        parser.error('--register_normal_k must be in 2..32')
+    if args.register_normal_radius is not None and not (args.register_normal_radius > 0.0 and np.isfinite(args.register_normal_radius)):
+        parser.error('--register_normal_radius must be positive and finite')
+
+
+def global_options(args):
+    """register_cloud.global_init's keyword arguments that a command line gives ({}: its defaults); None without --register_global.
+    An option `args` lacks is not given."""
+    if not getattr(args, 'register_global', False):
+        return None
+    chosen = {key: getattr(args, name) for name, key in GLOBAL_FLAGS.items() if getattr(args, name, None) not in (None, False)}
+    if 'mutual' in chosen:
+        chosen['mutual'] = False
+    return chosen
+
+
+def register_arguments(with_scale=False, icp=None, normal_side=None, normal_k=None, normal_radius=None, global_=None, **_others):
+    """evaluate's keyword arguments of a registration: register, with_scale, register_icp ('plane' only), register_normals ('target'
+    only, with register_normal_k and register_normal_radius when given), register_global and global_options (global_: None, or
+    global_options' dict).  The arguments are the keys of the ETH3D driver's register dict (with gt_ply only), which is None, or
+    dict(with_scale=, init_cameras=(recon_sparse, gt_sparse) or None): the cloud is aligned to the ground truth before it is scored
+    (--register [--init_cameras]); cloud_eval.json carries `registration`.  With icp='plane' (fuse_normals normals='depth' only) the
+    registration is point-to-plane over the normals the fusion returns; with normal_side='target' too (optionally normal_k,
+    normal_radius) over the ground truth's planes instead, its normals estimated on the device: no fuse_normals needed.  With global=
+    ({} or register_cloud.global_init's keyword arguments) the start is found from the clouds alone; init_cameras is then refused."""
+    out = dict(register=True, with_scale=bool(with_scale))
+    if icp == 'plane':
+        out['register_icp'] = 'plane'
+    if normal_side == 'target':
+        out['register_normals'] = 'target'
+        out.update({'register_' + key: v for key, v in (('normal_k', normal_k), ('normal_radius', normal_radius)) if v is not None})
+    if global_ is not None:
+        out['register_global'] = True
+        out.update({'global_options': dict(global_)} if global_ else {})
+    return out
+
+
+def register_rules(register, fused_normals):
+    """The ETH3D driver's rules for its register dict, as (broken, message) rows: those of the target normals, of point-to-plane over
+    the fused cloud's own normals (fused_normals: whether the fusion estimates them) and of global=, each only when the dict asks."""
+    register = register or {}
+    target = register.get('normal_side') == 'target'
+    plane_row = [] if not register.get('icp') == 'plane' or target else [
+        (not fused_normals, '--register_icp plane needs --fuse_normals depth (register icp=plane needs fuse_normals normals=depth): '
+                            'point-to-plane registration runs over the fused cloud\'s own normals; or give --register_normals target '
+                            '(register normal_side=target): the ground truth\'s planes, its normals estimated on the GPU')]
+    target_row = [] if not any(k in register for k in ('normal_side', 'normal_k', 'normal_radius')) else [
+        (target and not register.get('icp') == 'plane', '--register_normals target needs --register_icp plane (register '
+                                                        'normal_side=target needs icp=plane)'),
+        (not target and ('normal_k' in register or 'normal_radius' in register),
+         '--register_normal_k and --register_normal_radius need --register_normals target (normal_k and normal_radius need '
+         'normal_side=target)')]
+    global_row = [] if register.get('global') is None else [
+        (bool(register.get('init_cameras')), '--register_global finds the initial matrix from the clouds alone: give it or '
+                                             '--init_cameras (register global= or init_cameras=)')]
+    return target_row + plane_row + global_row
+
+
+def register_options(parser, args):
+    """The registration options of a parsed command line as evaluate_files' keyword arguments ({} when none is given);
+    contradictory ones are argument errors."""
+    if args.init_transform and args.init_cameras:
+        parser.error('--init_transform and --init_cameras both give the initial matrix: choose one')
+    check_register_values(parser, args, ('with_scale', 'register_distances', 'register_voxel', 'register_icp', 'register_normals',
+                                         'register_normal_k', 'register_normal_radius', 'register_global'))
     if args.register_global and (args.init_transform or args.init_cameras):
         parser.error('--register_global finds the initial matrix from the clouds alone: give it, --init_transform or --init_cameras')
     if args.global_voxel is not None and not (args.global_voxel > 0.0 and np.isfinite(args.global_voxel)):
         parser.error('--global_voxel must be positive and finite')
     if args.global_tau is not None and not (args.global_tau > 0.0 and np.isfinite(args.global_tau)):
         parser.error('--global_tau must be positive and finite')
-    if args.global_hypotheses is not None and not 1 <= args.global_hypotheses <= 1 << 24:
-        parser.error('--global_hypotheses must be in 1..2^24')
-    if args.global_seed is not None and args.global_seed < 0:
-        parser.error('--global_seed must be >= 0')
     if args.save_transform and not (args.register or args.init_transform or args.init_cameras):
         parser.error('--save_transform needs --register, --init_transform or --init_cameras: no matrix is applied otherwise')
     if args.voxel is not None and not args.voxel > 0.0:
@@ -385,13 +460,8 @@ def register_options(parser, args):
         parser.error('--register_normals target needs --register_icp plane')
     if not target and (args.register_normal_k is not None or args.register_normal_radius is not None):
         parser.error('--register_normal_k and --register_normal_radius need --register_normals target')
-    if args.register_normal_k is not None and not 2 <= args.register_normal_k <= 32:
-        parser.error('--register_normal_k must be in 2..32')
-    if args.register_normal_radius is not None and not (args.register_normal_radius > 0.0 and np.isfinite(args.register_normal_radius)):
-        parser.error('--register_normal_radius must be positive and finite')
     options = {}
     if args.register:
-        options.update(register=True, with_scale=bool(args.with_scale))
         if args.register_distances is not None:
             try:
                 options['register_distances'] = [float(t) for t in args.register_distances.split(',') if t.strip()]
@@ -404,27 +474,15 @@ def register_options(parser, args):
             if not args.register_voxel >= 0.0:
                 parser.error('--register_voxel must be >= 0')
             options['register_voxel'] = args.register_voxel
-        if target:
-            options.update(register_icp='plane', register_normals='target')
-            if args.register_normal_k is not None:
-                options['register_normal_k'] = args.register_normal_k
-            if args.register_normal_radius is not None:
-                options['register_normal_radius'] = args.register_normal_radius
-        elif args.register_icp == 'plane':
+        if args.register_icp == 'plane' and not target:
             try:
                 with_normals = ply.has_normals(args.recon)
             except (OSError, ValueError) as e:
                 parser.error('--register_icp plane: cannot read %s: %s' % (args.recon, e))
             if not with_normals:
                 parser.error('--register_icp plane: ' + NO_NORMALS % args.recon)
-            options['register_icp'] = 'plane'
-        if args.register_global:
-            options['register_global'] = True
-            chosen = {key: getattr(args, name) for name, key in GLOBAL_FLAGS.items() if getattr(args, name) not in (None, False)}
-            if 'mutual' in chosen:
-                chosen['mutual'] = False
-            if chosen:
-                options['global_options'] = chosen
+        options.update(register_arguments(args.with_scale, args.register_icp, args.register_normals, args.register_normal_k,
+                                          args.register_normal_radius, global_options(args)))
     if args.init_transform:
         options['init_transform_path'] = args.init_transform
     if args.init_cameras:
@@ -482,30 +540,13 @@ def make_parser():
     parser.add_argument('--distances', default=None, metavar='PREFIX',
                         help='write PREFIX_d2_recon.npy, PREFIX_idx_recon.npy, PREFIX_d2_gt.npy, PREFIX_idx_gt.npy')
     parser.add_argument('--gpu_id', type=int, default=0)
-    parser.add_argument('--register', action='store_true',
-                        help='align the reconstruction to the ground truth before scoring (voxel down-sampling + ICP in stages)')
-    parser.add_argument('--with_scale', action='store_true', help='--register: fit a similarity (scale too), not a rigid motion')
+    add_register_arguments(parser)
     parser.add_argument('--register_distances', default=None, metavar='a,b,c',
                         help='--register: the stages\' search distances, decreasing (default: 4, 2, 1 x the largest tolerance)')
     parser.add_argument('--register_voxel', type=float, default=None, metavar='V',
                         help='--register: voxel edge of the down-sampling before the fit (default: half the last distance; 0: none)')
-    parser.add_argument('--register_icp', default=None, choices=('point', 'plane'),
-                        help='--register: point-to-point ICP (the default) or point-to-plane over the normals the reconstruction\'s '
-                             'PLY carries (nx ny nz, as `depth_fusion --normals depth` writes them): far fewer iterations')
-    parser.add_argument('--register_normals', default=None, choices=('source', 'target'),
-                        help='--register_icp plane: whose planes -- source (the default: the normals in the reconstruction\'s PLY) or '
-                             'target (the ground truth\'s, estimated on the GPU: the reconstruction needs none)')
-    parser.add_argument('--register_normal_k', type=int, default=None, metavar='K',
-                        help='--register_normals target: neighbours per estimated normal, 2..32 (default 16; a default, not a measurement)')
-    parser.add_argument('--register_normal_radius', type=float, default=None, metavar='R',
-                        help='--register_normals target: their search radius (default: 4 edges of the registration\'s voxel, or twice '
-                             'the last distance without one; a default, not a measurement)')
-    add_global_arguments(parser)
     parser.add_argument('--init_transform', default=None, metavar='FILE',
                         help='text file with a 4x4 row-major matrix applied to the RECONSTRUCTION (the start of --register)')
-    parser.add_argument('--init_cameras', default=None, nargs=2, metavar=('RECON_SPARSE', 'GT_SPARSE'),
-                        help='two COLMAP sparse model folders of the same images, in the reconstruction\'s and the ground truth\'s '
-                             'frame: the similarity between their camera centres (matched by image name) is the initial matrix')
     parser.add_argument('--save_transform', default=None, metavar='FILE', help='write the matrix applied to the reconstruction here')
     parser.add_argument('--voxel', type=float, default=None, metavar='V',
                         help='score the clouds after a voxel down-sampling of edge V (both sides)')
@@ -548,7 +589,6 @@ def cli(argv=None):
         for k, v in dist.items():
             np.save('%s_%s.npy' % (args.distances, k), v)
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_json(args.out, result)
     else:
         print(json.dumps(result, indent=1, sort_keys=True))

@@ -28,6 +28,7 @@ import os
 
 import numpy as np
 
+from ..tools.common import write_json  # noqa: F401
 from . import eval_errors
 
 DEFAULT_SPLAT = 2                  # a default, not a measurement: a 5 x 5 window closes the gaps of a scan about as dense as the map
@@ -231,12 +232,6 @@ def report(pred, gt, indices=None, min_valid=DEFAULT_MIN_VALID, transform=None, 
     return out
 
 
-def write_json(path, result):
-    with open(path, 'w') as f:
-        json.dump(result, f, indent=1, sort_keys=True)
-        f.write('\n')
-
-
 def scene_indices(scene_folder):
     """The reference image indices of <scene_folder>/pair.txt, in its order."""
     with open(os.path.join(scene_folder, 'pair.txt')) as f:
@@ -278,6 +273,48 @@ def load_maps(maps_folder, indices=None):
     return indices, np.stack(depth), np.stack(cams)
 
 
+def add_options(parser, prefix=''):
+    """The rendering options --<prefix>splat, occlusion_tol, pixel_centre, occlusion_mesh, occlusion_mesh_tol ('map_': the ETH3D driver's)."""
+    parser.add_argument('--%ssplat' % prefix, type=int, default=DEFAULT_SPLAT, help='half-width of the occlusion window in pixels, 0..4')
+    parser.add_argument('--%socclusion_tol' % prefix, type=float, default=DEFAULT_OCCLUSION_TOL,
+                        help='a pixel is kept when its depth is within (1 + this) of the nearest depth in its window')
+    parser.add_argument('--%spixel_centre' % prefix, type=float, default=DEFAULT_PIXEL_CENTRE,
+                        help='image coordinate of the centre of pixel (0,0): 0 (the fusion\'s convention) or 0.5 (the plane sweep\'s)')
+    parser.add_argument('--%socclusion_mesh' % prefix, default=None, metavar='FILE[,FILE...]',
+                        help='triangle-mesh PLY file(s) in the ground truth\'s frame: a rendered ground-truth pixel that lies behind '
+                             'them is taken out')
+    parser.add_argument('--%socclusion_mesh_tol' % prefix, type=float, default=None, metavar='E' if prefix else None,      # as each tool had it
+                        help='a pixel is kept when its depth is within (1 + this) of the occlusion mesh\'s (default %g)' % DEFAULT_OCCLUDER_TOL)
+
+
+def options(parser, args, prefix=''):
+    """The options of add_options as render_scan's splat, occlusion_tol and pixel_centre, with occlusion_mesh (the list of files) and
+    occlusion_mesh_tol when given; a bad splat or occlusion mesh option is an argument error.  parser None: nothing is checked, and
+    an option `args` lacks has its default.  This is the ETH3D driver's score_maps (with gt_ply only): after the scene's fusion the
+    ground truth is rendered into the scene's cameras (in SceneFusion.order()) and the staged, probability-filtered depth planes --
+    what enters the cloud -- are scored against it (score_maps) into <savepath>/<scene>/depth_eval.json.  With register the ground
+    truth is moved by the inverse of the matrix already found (no second fit).  A rendered pixel that lies behind the meshes of
+    occlusion_mesh= (in the ground truth's frame), within occlusion_mesh_tol=, is taken out first (render_scan's occluders)."""
+    get = lambda name, default=None: getattr(args, prefix + name, default)          # noqa: E731
+    out = dict(splat=get('splat', DEFAULT_SPLAT), occlusion_tol=get('occlusion_tol', DEFAULT_OCCLUSION_TOL),
+               pixel_centre=get('pixel_centre', DEFAULT_PIXEL_CENTRE))
+    files, tol = get('occlusion_mesh'), get('occlusion_mesh_tol')
+    if parser is not None:
+        if not 0 <= out['splat'] <= 4:
+            parser.error('--%ssplat must be in 0..4' % prefix)
+        if tol is not None and files is None:
+            parser.error('--%socclusion_mesh_tol needs --%socclusion_mesh' % (prefix, prefix))
+        if tol is not None and not (tol >= 0.0 and np.isfinite(tol)):
+            parser.error('--%socclusion_mesh_tol must be >= 0 and finite' % prefix)
+    if files:
+        files = [p for p in files.split(',') if p] if isinstance(files, str) else list(files)
+    if parser is not None and files is not None and not files:
+        parser.error('--%socclusion_mesh names no file' % prefix)
+    if files:
+        out.update({'occlusion_mesh': files}, **({} if tol is None else {'occlusion_mesh_tol': tol}))
+    return out
+
+
 def make_parser():
     parser = argparse.ArgumentParser(description='score the depth maps of a scene against a scan rendered into their cameras '
                                                  '(a point splat with a depth test; not ETH3D\'s renderer)')
@@ -288,17 +325,9 @@ def make_parser():
     parser.add_argument('--gt_mesh', default=None, metavar='FILE[,FILE...]',
                         help='instead of --gt: triangle-mesh PLY file(s); the ground-truth maps are the rendered mesh itself '
                              '(--splat and --occlusion_tol do not apply)')
-    parser.add_argument('--occlusion_mesh', default=None, metavar='FILE[,FILE...]',
-                        help='triangle-mesh PLY file(s) in the ground truth\'s frame: a ground-truth pixel behind them is taken out')
-    parser.add_argument('--occlusion_mesh_tol', type=float, default=None,
-                        help='a pixel is kept when its depth is within (1 + this) of the occlusion mesh\'s (default %g)' % DEFAULT_OCCLUDER_TOL)
     parser.add_argument('--transform', default=None, metavar='FILE',
                         help='text file with the 4x4 recon -> scan matrix (eval_cloud --save_transform); the scan is moved by its inverse')
-    parser.add_argument('--splat', type=int, default=DEFAULT_SPLAT, help='half-width of the occlusion window in pixels, 0..4')
-    parser.add_argument('--occlusion_tol', type=float, default=DEFAULT_OCCLUSION_TOL,
-                        help='a pixel is kept when its depth is within (1 + this) of the nearest depth in its window')
-    parser.add_argument('--pixel_centre', type=float, default=DEFAULT_PIXEL_CENTRE,
-                        help='image coordinate of the centre of pixel (0,0): 0 (the fusion\'s convention) or 0.5 (the plane sweep\'s)')
+    add_options(parser)
     parser.add_argument('--min_valid', type=int, default=DEFAULT_MIN_VALID, help='maps with fewer jointly valid pixels are skipped')
     parser.add_argument('--out', default=None, help='write the result as JSON here (default: print it)')
     parser.add_argument('--save_gt', default=None, metavar='DIR', help='write the rendered maps as DIR/%%08d_gt.npy')
@@ -309,8 +338,8 @@ def make_parser():
 def cli(argv=None):
     parser = make_parser()
     args = parser.parse_args(argv)
-    if not 0 <= args.splat <= 4:
-        parser.error('--splat must be in 0..4')
+    render = options(parser, args)
+    occ_paths, occ_tol = render.pop('occlusion_mesh', []), render.pop('occlusion_mesh_tol', DEFAULT_OCCLUDER_TOL)
     if not (args.occlusion_tol >= 0.0 and np.isfinite(args.occlusion_tol)):
         parser.error('--occlusion_tol must be >= 0 and finite')
     if not np.isfinite(args.pixel_centre):
@@ -322,13 +351,6 @@ def cli(argv=None):
     gt_paths = [p for p in (args.gt if args.gt is not None else args.gt_mesh).split(',') if p]
     if not gt_paths:
         parser.error('%s names no file' % ('--gt' if args.gt is not None else '--gt_mesh'))
-    if args.occlusion_mesh_tol is not None and args.occlusion_mesh is None:
-        parser.error('--occlusion_mesh_tol needs --occlusion_mesh')
-    if args.occlusion_mesh_tol is not None and not (args.occlusion_mesh_tol >= 0.0 and np.isfinite(args.occlusion_mesh_tol)):
-        parser.error('--occlusion_mesh_tol must be >= 0 and finite')
-    occ_paths = [p for p in (args.occlusion_mesh or '').split(',') if p]
-    if args.occlusion_mesh is not None and not occ_paths:
-        parser.error('--occlusion_mesh names no file')
     for p in gt_paths + occ_paths + ([args.transform] if args.transform else []):
         if not os.path.isfile(p):
             parser.error('%s: no such file' % p)
@@ -352,16 +374,14 @@ def cli(argv=None):
         surface = load_meshes(gt_paths) if args.gt_mesh is not None else None
     except ValueError as e:
         parser.error(str(e))
-    occ_tol = DEFAULT_OCCLUDER_TOL if args.occlusion_mesh_tol is None else args.occlusion_mesh_tol
     if occluder is not None:
         extra.update(occlusion_mesh_tol=occ_tol, occlusion_faces=len(occluder[1]))
     import torch
     torch.cuda.set_device(args.gpu_id)
-    options = dict(pixel_centre=args.pixel_centre, splat=args.splat, occlusion_tol=args.occlusion_tol)
     if surface is None:
         scan = np.concatenate([ply.read_ply_points(p) for p in gt_paths], 0)
         gt = render_scan(scan, cams, pred.shape[1], pred.shape[2], transform=transform, occluders=occluder and [occluder],
-                         occluder_tol=occ_tol, **options).cpu().numpy()
+                         occluder_tol=occ_tol, **render).cpu().numpy()
     else:
         from .. import ops
         extra.update(gt_mesh=len(surface[1]))
@@ -375,9 +395,8 @@ def cli(argv=None):
         os.makedirs(args.save_gt, exist_ok=True)
         for i, g in zip(indices, gt):
             np.save(os.path.join(args.save_gt, '%08d_gt.npy' % i), g)
-    result = report(pred, gt, indices=indices, min_valid=args.min_valid, transform=transform, **dict(options, **extra))
+    result = report(pred, gt, indices=indices, min_valid=args.min_valid, transform=transform, **dict(render, **extra))
     if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         write_json(args.out, result)
     else:
         print(json.dumps(result, indent=1, sort_keys=True))

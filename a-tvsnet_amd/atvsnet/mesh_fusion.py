@@ -27,6 +27,7 @@ import time
 
 import numpy as np
 
+from ..tools.common import write_json  # noqa: F401
 from . import clean_mesh, eval_depth
 
 DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
@@ -187,12 +188,6 @@ def render_views(vertices, faces, cams16, rows, cols, folder, indices, pixel_cen
     return {'maps': int(len(depth)), 'covered_fraction': float((depth > 0).mean()) if depth.size else 0.0, 'seconds': seconds}
 
 
-def write_json(path, result):
-    with open(path, 'w') as f:
-        json.dump(result, f, indent=1, sort_keys=True)
-        f.write('\n')
-
-
 class SceneMesh(object):
     """The mesh of a scene whose maps a depth_fusion.SceneFusion holds.
 
@@ -313,27 +308,73 @@ class SceneMesh(object):
         return len(faces)
 
 
+def add_options(parser, prefix='', tool=True):
+    """The meshing options --<prefix>voxel, trunc_voxels, min_weight, max_blocks, carve and clean_mesh's criteria as --<prefix>clean_*.
+    tool: this command line's form, where --voxel is required and trunc_voxels, min_weight, max_blocks default to DEFAULT_*; False:
+    the ETH3D driver's (prefix 'mesh_'), where each defaults to None -- only what is given is passed on -- and shows a metavar.
+    --render is not here: it is a directory in the tool and a flag in the driver."""
+    def add(name, type, default, metavar, help):
+        parser.add_argument('--%s%s' % (prefix, name), type=type, required=tool and default is None, default=default if tool else None,
+                            metavar=None if tool else metavar, help=help)
+
+    add('voxel', float, None, 'V', 'the voxel\'s edge in the scene\'s unit (the ETH3D driver, with --fuse: also mesh each scene -- TSDF '
+                                   'fusion of the staged maps, marching tetrahedra -- into <savepath>/<scene>/final3d_mesh.ply and mesh.json)')
+    add('trunc_voxels', float, DEFAULT_TRUNC_VOXELS, 'T', 'the band either side of a depth, in voxels (default %g: a default, not a '
+                                                          'measurement)' % DEFAULT_TRUNC_VOXELS)
+    add('min_weight', float, DEFAULT_MIN_WEIGHT, 'W', 'views a voxel needs to be meshed (default %g, the fusion\'s num_consistent)'
+                                                      % DEFAULT_MIN_WEIGHT)
+    add('max_blocks', int, DEFAULT_MAX_BLOCKS, 'N', 'blocks of 8^3 voxels the maps may mark (default %d)' % DEFAULT_MAX_BLOCKS)
+    parser.add_argument('--%scarve' % prefix, type=float, nargs='?', default=None, const=DEFAULT_CARVE_WEIGHT, metavar='CW',
+                        help='free-space carving: a view that sees past a voxel votes it outside with this weight (given bare: %g, a '
+                             'default, not a measurement); the report gains carve_weight, free_voxels, max_free' % DEFAULT_CARVE_WEIGHT)
+    clean_mesh.add_options(parser, prefix + 'clean_')
+
+
+def options(parser, args, prefix=''):
+    """The options of add_options that were given, as SceneMesh's keyword arguments voxel=, trunc_voxels=, min_weight=, max_blocks=,
+    carve_weight= and clean= (clean_mesh's criteria; a bad one is an argument error) -- {} when none was.  parser None: nothing is
+    checked, and an option `args` lacks is not given.  This is the ETH3D driver's mesh (with fuse only; it adds render=True for its
+    --mesh_render): after the scene's fusion the staged depth planes and images are integrated into a TSDF volume bounded by the
+    fused cloud and meshed by marching tetrahedra into <savepath>/<scene>/final3d_mesh.ply, with the report in mesh.json; clean=
+    also writes final3d_mesh_clean.ply and mesh_clean.json, the mesh without the connected components that miss a criterion;
+    render=True also renders the mesh into the scene's map cameras as <savepath>/<scene>/depths_mesh/%08d_mesh.pfm."""
+    names = dict(voxel='voxel', trunc_voxels='trunc_voxels', min_weight='min_weight', max_blocks='max_blocks', carve='carve_weight')
+    out = {key: getattr(args, prefix + name) for name, key in names.items() if getattr(args, prefix + name, None) is not None}
+    clean = clean_mesh.options(parser, args, prefix + 'clean_')
+    return dict(out, clean=clean) if clean else out
+
+
+def rules(mesh, fuse):
+    """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight and clean only
+    when they are given."""
+    if mesh is None:
+        return []
+    rows = [(fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
+                           'mesh is integrated from the maps the fusion stages and bounded by its cloud'),
+            (mesh.get('voxel') is None, '--mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --mesh_voxel (mesh needs voxel=)')]
+    if mesh.get('carve_weight') is not None:
+        rows.insert(1, (mesh.get('voxel') is None, '--mesh_carve needs --mesh_voxel (mesh carve_weight= needs voxel=): there is no '
+                                                   'volume to carve'))
+    if mesh.get('clean') is not None:                 # in front of the row above: its message names what was given
+        rows.insert(1, (mesh.get('voxel') is None, '--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need '
+                                                   '--mesh_voxel (mesh clean= needs voxel=): there is no mesh to clean'))
+    return rows
+
+
 def make_parser():
     parser = argparse.ArgumentParser(description='mesh the written depth maps of a scene: TSDF fusion and marching tetrahedra on the GPU '
                                                  '(free-space carving with --carve; no simplification, no hole filling)')
     parser.add_argument('--scene', default=None, help='<data_root>/eth3d/<scene>: its pair.txt names the maps (default: every map under --maps)')
     parser.add_argument('--maps', required=True, help='<savepath>/<scene> of eval_pointcloud: depths_atvsnet/%%08d.pfm, _prob.pfm, .jpg, .txt')
-    parser.add_argument('--voxel', type=float, required=True, help='the voxel\'s edge in the scene\'s unit')
-    parser.add_argument('--trunc_voxels', type=float, default=DEFAULT_TRUNC_VOXELS, help='the band either side of a depth, in voxels (a default, not a measurement)')
-    parser.add_argument('--min_weight', type=float, default=DEFAULT_MIN_WEIGHT, help='views a voxel needs to be meshed (a default: the fusion\'s num_consistent)')
+    add_options(parser)
     parser.add_argument('--prob_threshold', type=float, default=0.8, help='a depth whose probability is below this is no sample (depth_fusion --prob_threshold)')
     parser.add_argument('--pixel_centre', type=float, default=DEFAULT_PIXEL_CENTRE, help='image coordinate of the centre of pixel (0,0): 0 (the fusion\'s) or 0.5')
-    parser.add_argument('--max_blocks', type=int, default=DEFAULT_MAX_BLOCKS, help='blocks of 8^3 voxels the maps may mark')
-    parser.add_argument('--carve', type=float, nargs='?', default=None, const=DEFAULT_CARVE_WEIGHT, metavar='CW',
-                        help='free-space carving: a view that sees past a voxel votes it outside with this weight (given bare: %g, a '
-                             'default, not a measurement); the report gains carve_weight, free_voxels, max_free' % DEFAULT_CARVE_WEIGHT)
     parser.add_argument('--bounds', default=None, metavar='PLY', help='bound the volume by this cloud (the scene\'s final3d_model.ply) instead of '
                                                                       'by the maps\' own back-projected depths')
     parser.add_argument('--report', default=None, metavar='FILE', help='write the report as JSON here')
     parser.add_argument('--render', default=None, metavar='DIR', help='render the mesh into the maps\' cameras (ops.mesh_render) as '
                                                                       'DIR/%%08d_mesh.pfm; the report gains `render`')
     parser.add_argument('--out', required=True, help='the mesh, a binary PLY')
-    clean_mesh.add_options(parser, 'clean_')
     parser.add_argument('--clean_out', default=None, metavar='PLY', help='with a --clean_ criterion: the mesh without the connected '
                                                                          'components that miss it (clean_mesh); the report gains `clean`')
     parser.add_argument('--gpu_id', type=int, default=0)

@@ -2,7 +2,7 @@
 cached features (eval_pointcloud --scene_cache).
 
 In an ETH3D pair.txt scene every image is the reference of one depth map and a source of about seven others.  The per-map path
-(eval_pointcloud.load_data + GraphedInference) decodes, resizes and centres each image, and runs the towers on it, once per map it
+(eth3d_inputs.load_data + GraphedInference) decodes, resizes and centres each image, and runs the towers on it, once per map it
 appears in.  Here:
 
 * the image is decoded once and uploaded as uint8; ops.prepare_view resizes it by the map's adaptive scale, crops and centres it,

@@ -1,5 +1,15 @@
-"""Console prefixes used by the entry point (reference: tools/common.py:15-51)."""
+"""Console prefixes used by the entry point (reference: tools/common.py:15-51); write_json, the tools' one report writer."""
+import json
+import os
 import time
+
+
+def write_json(path, report):
+    """A tool's report into `path` (its folder is made): keys sorted, one space of indent, a closing newline."""
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, 'w') as f:
+        json.dump(report, f, indent=1, sort_keys=True)
+        f.write('\n')
 
 
 class _Notify(object):

@@ -1,4 +1,4 @@
-"""The ETH3D driver's scene loop and option rules on the host (no GPU): eval_pointcloud._run_scene over a fake map source -- the
+"""The ETH3D driver's scene loop and option rules on the host (no GPU): eth3d_maps._run_scene over a fake map source -- the
 order of load / submit / finish, the files, writer errors, TIMES -- and _option_rules through run_eval_pc and cli."""
 import itertools
 import os
@@ -9,7 +9,7 @@ import torch
 
 import atvsnet_amd  # noqa: F401
 from atvsnet_amd import FLAGS
-from atvsnet_amd.atvsnet import eval_pointcloud as E
+from atvsnet_amd.atvsnet import eth3d_maps, eval_pointcloud as E
 
 MAPS = 3
 MAP_FILES = ['%08d%s' % (10 * (i + 1), ext) for i in range(MAPS) for ext in ('.pfm', '_prob.pfm', '.jpg', '.txt', '.png')]
@@ -136,7 +136,7 @@ def test_a_write_error_surfaces_and_the_source_is_closed(flags, tmp_path, monkey
             raise OSError('disk full at %d' % out_index)
         written.append(out_index)
 
-    monkeypatch.setattr(E, '_write_map', write_map)
+    monkeypatch.setattr(eth3d_maps, '_write_map', write_map)
     monkeypatch.setattr(E.example, '_load_weights', lambda: None)
     monkeypatch.setattr(torch.cuda, 'set_device', lambda device: None)
     monkeypatch.setattr(E, '_SceneSource' if scene_cache else '_PipelineSource', lambda *args: source)

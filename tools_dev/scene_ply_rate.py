@@ -5,7 +5,7 @@
 
 Both with --view_num 8 --max_d 128 and synthetic weights, on --views images at 940x490; each run processes the scene twice under
 two names (the first pass carries the graph captures) and the 'ring' pass is timed: its depth maps (zz_runtime.txt, files on disk
-included) plus, for two_step, depth_fusion.main, for in_run the fusion and PLY write (eval_pointcloud.TIMES['fuse']).  The two
+included) plus, for two_step, depth_fusion.main, for in_run the fusion and PLY write (eth3d_maps.TIMES['fuse']).  The two
 PLYs' point coordinates are compared byte for byte.
 
     python tools_dev/scene_ply_rate.py --out profiles/scene_ply_rate.json [--maps_in_flight cu_split]

@@ -5,7 +5,7 @@ Writes a scene of --views images at 940x490 (ETH3D low-res size) with a ring pai
 process.  Reports maps/s per mode (median, min, max), the per-map host time split (prepare, submit, wait, write) and the largest
 relative depth difference between the two modes' PFMs; --out writes the same as JSON.  Each run processes the scene twice under
 two names: the first pass carries the run's graph captures; maps/s and the per-map split are the second pass's (zz_runtime.txt,
-eval_pointcloud.TIMES).  The split: prepare, submit (scene mode: of which upload), wait, write (scene mode: the hand-off to the writer
+eth3d_maps.TIMES).  The split: prepare, submit (scene mode: of which upload), wait, write (scene mode: the hand-off to the writer
 thread), writer_busy (the writer thread's own time), and in scene mode gpu_ms (each map's GPU time on its slot's stream, median).
 
     python tools_dev/scene_rate.py --out profiles/scene_rate.json [--maps_in_flight cu_split]
