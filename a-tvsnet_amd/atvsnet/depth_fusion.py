@@ -414,6 +414,24 @@ class SceneFusion(object):
             self.result_normals = unit_normals(out[2].cpu().numpy()) if depth else None
         return self.result
 
+    def support(self, want=('count', 'depth', 'weight')):
+        """run(), then the fusion's agreement count of every staged pixel under the scene's own disp_threshold, num_consistent and
+        normal options (ops.fusion_support, one launch) -> a dict of device tensors, each (k,rows,cols) in fusion order (order()):
+        count int32, depth float32 (the staged depth where count >= num_consistent, 0 elsewhere: the plane as the fusion masks its
+        points), weight float32 ((1 + count) / (1 + num_consistent)).  It comes after run(), so with normals='depth' the slab already
+        carries the estimated normals and their threshold applies."""
+        import torch
+        from .. import ops
+        self.run()
+        k = len(self.index)
+        order = self.order()
+        nd = self.nd[:k]
+        if not np.array_equal(order, np.arange(k)):
+            nd = nd.index_select(0, torch.from_numpy(order).to(self.device))
+        cams = torch.from_numpy(np.ascontiguousarray(self.cams[:k][order])).to(self.device)
+        return ops.fusion_support(cams, nd, self.disp_threshold, normal_threshold_radians(self.normal_threshold), self.num_consistent,
+                                  want=want)
+
     def normals(self):
         """-> (M,3) float32: the unit normal of every point of run() (the fusion's average over the agreeing views, brought back to
         unit length by unit_normals; a zero normal stays zero).  normals='depth' only."""

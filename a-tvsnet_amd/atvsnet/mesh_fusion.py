@@ -11,10 +11,18 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     carve_weight=  free-space carving (section 10.3b): a view that sees past a voxel pulls its value outside, so a shell that two views
                    agree on and the others look through is not meshed; off (None) unless asked
 
-What this is not: there is no per-view weight, no consistency mask on the depths beyond the probability filter, no mesh
-simplification, no hole filling, and the PLY carries no normals.  Without carve_weight a view adds to a voxel only inside the narrow
-band around its depth.  Fragments are removed only when asked (the clean_ options have no defaults).  `trunc_voxels` and `min_weight`
-have defaults, not measurements.  This module imports without a GPU.
+    consistent=    the fusion's geometric test per pixel (section 10.3c): only the depths that num_consistent other views agree on are
+                   integrated -- the samples the point cloud is made of (ops.fusion_support); off unless asked
+    weights=       per-pixel view weights (section 10.3c): 'agree', (1 + agreeing views) / (1 + num_consistent) from the same launch,
+                   or on written maps 'prob', the probability map's value; a view then counts w where it counted 1; off unless asked
+                   (SceneMesh's arguments; on written maps the command atvsnet/mesh_consistent.py, this tool with four more options)
+
+What this is not: there are no weights from the viewing angle, the ETH3D driver has no probability weights (its staged slab does not
+keep the probabilities; mesh_consistent reads them from the files) and no command-line option for consistent= and weights= (they are
+run_eval_pc's mesh arguments), no mesh simplification, no hole filling, and the PLY carries no normals.
+Without carve_weight a view adds to a voxel only inside the narrow band around its depth.  Fragments are removed only when asked
+(the clean_ options have no defaults).  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports
+without a GPU.
 
     python -m atvsnet_amd.atvsnet.mesh_fusion --scene <data_root>/eth3d/<scene> --maps <out>/<scene> --voxel V
         [--trunc_voxels 4 --min_weight 2 --prob_threshold 0.8 --pixel_centre 0 --max_blocks N --report mesh.json] --out mesh.ply
@@ -35,16 +43,19 @@ DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's 
 DEFAULT_MAX_BLOCKS = 131072        # 64 Mi voxels: 1.3 GB of tsdf, weight and colour while the volume is built
 DEFAULT_PIXEL_CENTRE = 0.0         # fusion_pixel.h back-projects integer pixel coordinates: the convention that places the cloud
 DEFAULT_CARVE_WEIGHT = 1.0         # a default, not a measurement: what a bare --carve gives a free vote, one in-band view's worth
+WEIGHT_MODES = ('agree',)          # SceneMesh's and the ETH3D driver's: (1 + count) / (1 + num_consistent) of ops.fusion_support
+TOOL_WEIGHT_MODES = ('agree', 'prob')      # the tool also reads the probability maps that stand beside the depth maps
 
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
-                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None):
+                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None, consistent=False, weights=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
     the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there,
-    carve_weight by check_carve_weight (it is not part of the tuple)."""
+    carve_weight by check_carve_weight, consistent and weights by check_support (they are not part of the tuple)."""
     if clean is not None:
         clean_mesh.check_criteria(**clean)
     check_carve_weight(carve_weight)
+    check_support(consistent, weights)
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
     if not (voxel > 0.0 and np.isfinite(voxel)):
         raise ValueError('mesh voxel must be positive and finite, got %r' % (voxel,))
@@ -72,6 +83,15 @@ def check_carve_weight(carve_weight):
     if not (cw > 0.0 and np.isfinite(cw)):
         raise ValueError('mesh carve_weight must be a finite number > 0, got %r' % (carve_weight,))
     return cw
+
+
+def check_support(consistent=False, weights=None, modes=WEIGHT_MODES):
+    """-> (consistent as a bool, weights as None or one of `modes`); anything else raises ValueError."""
+    if not isinstance(consistent, (bool, np.bool_)):
+        raise ValueError('mesh consistent must be True or False, got %r' % (consistent,))
+    if weights is not None and (not isinstance(weights, str) or weights not in modes):
+        raise ValueError('mesh weights must be None or one of %s, got %r' % (', '.join(modes), weights))
+    return bool(consistent), weights
 
 
 def box_of(lo, hi, voxel, trunc):
@@ -107,15 +127,18 @@ def depth_bounds(depths, cams16, pixel_centre=DEFAULT_PIXEL_CENTRE):
 
 
 def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-              max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, carve_weight=None):
+              max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, carve_weight=None, weights=None):
     """depths (n,rows,cols) float32 and images (n,rows,cols,C>=3) float32 (b, g, r first) or None on the device, cams16 (n,16)
     float64 host rows (eval_depth.camera_rows), lo / hi the bounds of what is to be meshed -> (volume, (vertices, colors, faces)
     device tensors, {'integrate': s, 'extract': s}, each ended by a device synchronisation).  carve_weight: None, or the weight of
-    a free vote (ops.tsdf_integrate's carve_weight); the volume then carries `free`."""
+    a free vote (ops.tsdf_integrate's carve_weight); the volume then carries `free`.  weights: None, or (n,rows,cols) float32 on
+    the depths' device, the weight of every pixel (ops.tsdf_integrate's weights); it is passed through."""
     import torch
     from .. import ops
     voxel, trunc_voxels, min_weight, max_blocks, pixel_centre = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre)
     carve = {} if check_carve_weight(carve_weight) is None else {'carve_weight': check_carve_weight(carve_weight)}
+    if weights is not None:
+        carve['weights'] = weights
     trunc = trunc_voxels * voxel
     origin, dims = box_of(lo, hi, voxel, trunc)
     if dims[0] * dims[1] * dims[2] > ops.TSDF_MAX_DIRECTORY:
@@ -130,6 +153,27 @@ def mesh_maps(depths, cams16, images, lo, hi, voxel, trunc_voxels=DEFAULT_TRUNC_
     mesh = ops.tsdf_mesh(volume, min_weight)
     torch.cuda.synchronize(depths.device)
     return volume, mesh, {'integrate': t1 - t0, 'extract': time.time() - t1}
+
+
+def support_of_maps(depths, cams, disp_threshold=0.01, num_consistent=2, consistent=True, weights=False):
+    """The tool's consistency mask and agreement weights of written maps: depths (n,rows,cols) float32 on the device (probability
+    filtered), cams (n,2,4,4) as eval_depth.load_maps gives them, packed with depth_fusion.projection_matrix / pack_cameras; the
+    slab carries the fake normal, under which the normal test rejects nothing (depth_fusion.NORMAL_THRESHOLD).  One launch
+    (ops.fusion_support) -> (the depths to integrate: masked when `consistent`, else as given; the weight plane or None; the
+    report's `consistent` entry as a dict, {} without `consistent`)."""
+    import torch
+    from .. import ops
+    from . import depth_fusion
+    packed = torch.from_numpy(depth_fusion.pack_cameras([depth_fusion.projection_matrix(c) for c in np.asarray(cams, np.float64)])).to(depths.device)
+    fake = torch.where(depths > 0, torch.full_like(depths, float(np.float32(1.0) / np.float32(1.732050808))), torch.zeros_like(depths))
+    nd = torch.stack([fake, fake, fake, depths], dim=-1).contiguous()
+    got = ops.fusion_support(packed, nd, float(disp_threshold), depth_fusion.NORMAL_THRESHOLD, int(num_consistent),
+                             want=(('depth',) if consistent else ()) + (('weight',) if weights else ()))
+    report = {}
+    if consistent:
+        report['consistent'] = {'disp_threshold': float(disp_threshold), 'num_consistent': int(num_consistent),
+                                'samples': int((depths > 0).sum().item()), 'samples_kept': int((got['depth'] > 0).sum().item())}
+    return (got['depth'] if consistent else depths), got.get('weight'), report
 
 
 def host_boundary_edges(f, num_vertices):
@@ -206,12 +250,20 @@ class SceneMesh(object):
     give the cleaned one.
 
     carve_weight: None, or the weight of a free vote: the staged planes are integrated with free-space carving (section 10.3b) and
-    report() gains carve_weight, free_voxels and max_free."""
+    report() gains carve_weight, free_voxels and max_free.
+
+    consistent=True: scene_fusion.support()'s `depth` -- the staged depth where the fusion's num_consistent other views agree on it,
+    0 elsewhere -- is integrated in place of the staged depth planes, so the mesh rests on the samples the cloud is made of;
+    report() gains `consistent` (disp_threshold, num_consistent, samples, samples_kept).  weights='agree': support()'s `weight`,
+    (1 + agreeing views) / (1 + num_consistent), is each pixel's view weight (ops.tsdf_integrate's weights); report() gains
+    `weights`.  Both come from one launch; the thresholds are the scene_fusion's own (section 10.3c)."""
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
-                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None):
+                 max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None,
+                 consistent=False, weights=None):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
         self.carve_weight = check_carve_weight(carve_weight)
+        self.consistent, self.weights = check_support(consistent, weights)
         self.clean = None if clean is None else dict(clean)
         self._device_clean = self._clean_result = self._clean_report = None
         self.fusion = scene_fusion
@@ -244,8 +296,21 @@ class SceneMesh(object):
             idx = torch.from_numpy(order).to(dev)
             depths = fusion.nd[:k, :, :, 3].index_select(0, idx).contiguous()
             images = fusion.img[:k] if np.array_equal(order, np.arange(k)) else fusion.img[:k].index_select(0, idx)
+            weights, support = None, {}
+            if self.consistent or self.weights is not None:
+                t0 = time.time()
+                got = fusion.support(want=(('depth',) if self.consistent else ()) + (('weight',) if self.weights is not None else ()))
+                if self.consistent:
+                    support['consistent'] = {'disp_threshold': fusion.disp_threshold, 'num_consistent': fusion.num_consistent,
+                                             'samples': int((depths > 0).sum().item()), 'samples_kept': int((got['depth'] > 0).sum().item())}
+                    depths = got['depth']
+                if self.weights is not None:
+                    support['weights'] = self.weights
+                    weights = got['weight']
+                torch.cuda.synchronize(dev)
+                seconds['support'] = time.time() - t0
             self.volume, mesh, stage = mesh_maps(depths, self.cams16[order], images, lo, hi, voxel, trunc_voxels, min_weight, max_blocks,
-                                                 pixel_centre, self.carve_weight)
+                                                 pixel_centre, self.carve_weight, weights)
             seconds.update(stage)
             if self.clean is not None:
                 vertices, colors, faces, self._clean_report = clean_mesh.clean_device(*mesh, **self.clean)
@@ -255,7 +320,7 @@ class SceneMesh(object):
             self._device_mesh = mesh
             seconds['download'] = time.time() - t0
             t0 = time.time()
-            self._report = mesh_report(self.volume, mesh, min_weight, seconds, self.carve_weight)
+            self._report = dict(mesh_report(self.volume, mesh, min_weight, seconds, self.carve_weight), **support)
             seconds['report'] = self._report['seconds']['report'] = time.time() - t0          # zero-area faces on the host, the edge census on the device
         return self.result
 
@@ -330,6 +395,20 @@ def add_options(parser, prefix='', tool=True):
     clean_mesh.add_options(parser, prefix + 'clean_')
 
 
+def add_support_options(parser):
+    """The options of the consistency mask and the view weights (section 10.3c): --consistent, --disp_threshold, --num_consistent,
+    --weights.  They are not among add_options': this tool's and the ETH3D driver's command lines keep the options they had, and
+    atvsnet/mesh_consistent.py is the command that adds these to this tool's (cli reads them where the parser has them)."""
+    parser.add_argument('--consistent', action='store_true',
+                        help='integrate only the depths that --num_consistent other views agree on (the fusion\'s geometric test per '
+                             'pixel, ops.fusion_support): the samples the point cloud is made of; the report gains `consistent`')
+    parser.add_argument('--disp_threshold', type=float, default=None, help='--consistent / --weights agree: depth_fusion --disp_threshold (default 0.01)')
+    parser.add_argument('--num_consistent', type=int, default=None, help='--consistent / --weights agree: depth_fusion --num_consistent (default 2)')
+    parser.add_argument('--weights', choices=TOOL_WEIGHT_MODES, default=None,
+                        help='per-pixel view weights: agree = (1 + agreeing views) / (1 + num_consistent), a default, not a measurement; '
+                             'prob = the probability map\'s value; the report gains `weights`')
+
+
 def options(parser, args, prefix=''):
     """The options of add_options that were given, as SceneMesh's keyword arguments voxel=, trunc_voxels=, min_weight=, max_blocks=,
     carve_weight= and clean= (clean_mesh's criteria; a bad one is an argument error) -- {} when none was.  parser None: nothing is
@@ -345,8 +424,9 @@ def options(parser, args, prefix=''):
 
 
 def rules(mesh, fuse):
-    """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight and clean only
-    when they are given."""
+    """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight, consistent,
+    weights and clean only when they are given (consistent and weights reach the driver through run_eval_pc's mesh dict alone: its
+    command line has no option for them)."""
     if mesh is None:
         return []
     rows = [(fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
@@ -355,6 +435,11 @@ def rules(mesh, fuse):
     if mesh.get('carve_weight') is not None:
         rows.insert(1, (mesh.get('voxel') is None, '--mesh_carve needs --mesh_voxel (mesh carve_weight= needs voxel=): there is no '
                                                    'volume to carve'))
+    if mesh.get('weights') is not None:
+        rows.insert(1, (mesh.get('voxel') is None, 'mesh weights= needs voxel=: there is no volume whose views could be weighted'))
+    if mesh.get('consistent'):
+        rows.insert(1, (mesh.get('voxel') is None, 'mesh consistent= needs voxel=: there is no volume to integrate the consistent '
+                                                   'depths into'))
     if mesh.get('clean') is not None:                 # in front of the row above: its message names what was given
         rows.insert(1, (mesh.get('voxel') is None, '--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need '
                                                    '--mesh_voxel (mesh clean= needs voxel=): there is no mesh to clean'))
@@ -405,13 +490,26 @@ def _load_side_maps(maps_folder, indices, shape):
     return (None if probs is None else np.stack(probs)), (None if images is None else np.stack(images))
 
 
-def cli(argv=None):
-    parser = make_parser()
+def cli(argv=None, parser=None):
+    """parser: None (make_parser()), or a parser that also has add_support_options' options (atvsnet/mesh_consistent.py); without
+    them the mask and the weights are off."""
+    parser = make_parser() if parser is None else parser
     args = parser.parse_args(argv)
+    for name, off in (('consistent', False), ('weights', None), ('disp_threshold', None), ('num_consistent', None)):
+        if not hasattr(args, name):
+            setattr(args, name, off)
     try:
         check_options(args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre, carve_weight=args.carve)
+        check_support(args.consistent, args.weights, TOOL_WEIGHT_MODES)
     except ValueError as e:
         parser.error(str(e))
+    agree = args.consistent or args.weights == 'agree'
+    if not agree and (args.disp_threshold is not None or args.num_consistent is not None):
+        parser.error('--disp_threshold and --num_consistent need --consistent or --weights agree')
+    args.disp_threshold = 0.01 if args.disp_threshold is None else args.disp_threshold
+    args.num_consistent = 2 if args.num_consistent is None else args.num_consistent
+    if not (args.disp_threshold > 0.0 and np.isfinite(args.disp_threshold)) or args.num_consistent < 0:
+        parser.error('--disp_threshold must be positive and finite, --num_consistent >= 0')
     if not os.path.isdir(args.maps):
         parser.error('--maps %s: no such folder' % args.maps)
     if args.scene is not None and not os.path.isfile(os.path.join(args.scene, 'pair.txt')):
@@ -424,6 +522,8 @@ def cli(argv=None):
     from ..tools import ply
     indices, depths, cams = eval_depth.load_maps(args.maps, eval_depth.scene_indices(args.scene) if args.scene is not None else None)
     probs, images = _load_side_maps(args.maps, indices, depths.shape[1:])
+    if args.weights == 'prob' and probs is None:
+        parser.error('--weights prob needs the probability maps (%%08d_prob.pfm) beside the depth maps under %s' % args.maps)
     depths = depths.copy()
     if probs is not None:
         depths[probs < args.prob_threshold] = 0          # depth_fusion.probability_filter
@@ -439,12 +539,21 @@ def cli(argv=None):
     import torch
     torch.cuda.set_device(args.gpu_id)
     dev = torch.device('cuda', args.gpu_id)
-    volume, mesh, seconds = mesh_maps(torch.from_numpy(depths).to(dev), cams16, None if images is None else torch.from_numpy(images).to(dev),
-                                      lo, hi, args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre, args.carve)
+    depths_d, weights_d, support = torch.from_numpy(depths).to(dev), None, {}
+    if agree:
+        depths_d, weights_d, support = support_of_maps(depths_d, cams, args.disp_threshold, args.num_consistent, args.consistent,
+                                                       args.weights == 'agree')
+    if args.weights == 'prob':
+        weights_d = torch.from_numpy(np.ascontiguousarray(probs, np.float32)).to(dev)
+    if args.weights is not None:
+        support['weights'] = args.weights
+    volume, mesh, seconds = mesh_maps(depths_d, cams16, None if images is None else torch.from_numpy(images).to(dev),
+                                      lo, hi, args.voxel, args.trunc_voxels, args.min_weight, args.max_blocks, args.pixel_centre, args.carve,
+                                      weights_d)
     vertices, colors, faces = (None if t is None else t.cpu().numpy() for t in mesh)
     ply.write_mesh(args.out, vertices, colors, faces)
     result = dict(mesh_report(volume, mesh, args.min_weight, seconds, args.carve), maps=[int(i) for i in indices], colored=images is not None,
-                  probability_filtered=probs is not None)
+                  probability_filtered=probs is not None, **support)
     if args.render:
         result['render'] = render_views(mesh[0], mesh[2], cams16, depths.shape[1], depths.shape[2], args.render, indices, args.pixel_centre)
     if criteria:

@@ -1,6 +1,7 @@
 // The per-pixel body of the depth-map fusion (reference fusibile/fusibile.cu:138-277), shared by the per-camera kernel
 // (fusion.hip, atvs_fusibile) and the whole-scene kernel (fusion_scene.hip, atvs_fusibile_scene): both call fuse_pixel, so a
-// pixel's arithmetic is the same in the two by construction.  Both sources are built with -ffp-contract=off.
+// pixel's arithmetic is the same in the two by construction.  Its agreement loop is agreeing_views, which the support kernel
+// (fusion_support.hip, atvs_fusion_support) calls without the colours.  All three sources are built with -ffp-contract=off.
 //
 // Arithmetic contract (oracle/fusibile.py, bit for bit): float32, left to right; the CUDA texture fetch
 // tex2D<float4>(t, x + 0.5, y + 0.5) of an un-normalised linear texture is restated as the bilinear blend of texels floor(x),
@@ -43,12 +44,16 @@ struct FusedPixel {
   bool created;     // at least num_consistent other views agree
 };
 
-// Pixel (x, y) of reference camera `ref`: back-project it with its depth, project the 3-D point into every other view (ascending),
-// sample that view's (normal, depth) map and colour bilinearly, accept the view when the relative disparity difference and the
-// normal angle are under their thresholds, average normals and colours over the accepted views.
-__device__ __forceinline__ FusedPixel fuse_pixel(const float* __restrict__ cams, const float4* __restrict__ nd,
-                                                 const float4* __restrict__ img, int nviews, int ref, int rows, int cols, int x,
-                                                 int y, float disp_thresh, float normal_thresh, int num_consistent) {
+// The agreement loop of pixel (x, y) of reference camera `ref`, the one piece of code behind fuse_pixel and the support kernel
+// (fusion_support.hip): back-project the pixel with its depth, project the 3-D point into every other view (ascending), sample that
+// view's (normal, depth) map bilinearly, accept the view when it lands in the image, the relative disparity difference and the normal
+// angle are under their thresholds.  -> the number of accepted views; X receives the 3-D point, cn the reference normal plus the
+// accepted views' normals.  kImages: ct receives the reference colour plus the accepted views' colours; without it `img` is not
+// read (it may be nullptr), ct is left alone, and the fetches are compiled out.
+template <bool kImages>
+__device__ __forceinline__ int agreeing_views(const float* __restrict__ cams, const float4* __restrict__ nd,
+                                              const float4* __restrict__ img, int nviews, int ref, int rows, int cols, int x, int y,
+                                              float disp_thresh, float normal_thresh, float4& X, float4& cn, float4& ct) {
   const size_t center = (size_t)y * cols + x, plane = (size_t)rows * cols;
   const Cam cr = {cams + (size_t)ref * 28};
   const float4 nrm = nd[(size_t)ref * plane + center];
@@ -58,8 +63,8 @@ __device__ __forceinline__ FusedPixel fuse_pixel(const float* __restrict__ cams,
   const float Xx = cr.Mi(0) * ptx + cr.Mi(1) * pty + cr.Mi(2) * ptz;
   const float Xy = cr.Mi(3) * ptx + cr.Mi(4) * pty + cr.Mi(5) * ptz;
   const float Xz = cr.Mi(6) * ptx + cr.Mi(7) * pty + cr.Mi(8) * ptz;
-  float4 cn = nrm;
-  float4 ct = img[(size_t)ref * plane + center];
+  cn = nrm;
+  if constexpr (kImages) ct = img[(size_t)ref * plane + center];
   int count = 0;
   for (int i = 0; i < nviews; ++i) {
     if (i == ref) continue;
@@ -80,14 +85,27 @@ __device__ __forceinline__ FusedPixel fuse_pixel(const float* __restrict__ cams,
     float ang = acosf(dot);
     if (ang != ang) ang = 0.f;
     if (!(ang < normal_thresh)) continue;
-    const float4 t = tex_fetch(img + (size_t)i * plane, px, py, rows, cols);
     cn = make_float4(cn.x + other.x, cn.y + other.y, cn.z + other.z, 0.f);
-    ct = make_float4(ct.x + t.x, ct.y + t.y, ct.z + t.z, 0.f);
+    if constexpr (kImages) {
+      const float4 t = tex_fetch(img + (size_t)i * plane, px, py, rows, cols);
+      ct = make_float4(ct.x + t.x, ct.y + t.y, ct.z + t.z, 0.f);
+    }
     ++count;
   }
+  X = make_float4(Xx, Xy, Xz, 0.f);
+  return count;
+}
+
+// Pixel (x, y) of reference camera `ref`: the agreement loop above with the colours, then normals and colours averaged over the
+// reference and the accepted views.
+__device__ __forceinline__ FusedPixel fuse_pixel(const float* __restrict__ cams, const float4* __restrict__ nd,
+                                                 const float4* __restrict__ img, int nviews, int ref, int rows, int cols, int x,
+                                                 int y, float disp_thresh, float normal_thresh, int num_consistent) {
+  float4 X, cn, ct;
+  const int count = agreeing_views<true>(cams, nd, img, nviews, ref, rows, cols, x, y, disp_thresh, normal_thresh, X, cn, ct);
   const float k = (float)count + 1.0f;
   FusedPixel o;
-  o.coord = make_float4(Xx, Xy, Xz, 0.f);
+  o.coord = X;
   o.normal = make_float4(cn.x / k, cn.y / k, cn.z / k, 0.f);
   o.texture = make_float4(ct.x / k, ct.y / k, ct.z / k, 0.f);
   o.created = count >= num_consistent;

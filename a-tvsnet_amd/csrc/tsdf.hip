@@ -19,6 +19,8 @@
 // FREE-SPACE CARVING (opt-in, atvs_tsdf_integrate_carve): a view whose depth lies beyond a voxel's band has seen past the voxel and
 // pulls its value outside.  Such a view is in no band mask, so atvs_tsdf_free_views gives every slot the views that can see into
 // its block at all (a ballot per mask word), and the kernel's second form loops over band | free.
+// VIEW WEIGHTS (opt-in, atvs_tsdf_integrate_weighted): every pixel of every view carries a float32 weight that replaces the 1 a
+// sample counts for (fusion_support.hip makes one from the fusion's agreement count); the kernel's third form, with or without carving.
 //
 // The extractor splits the cube of every voxel whose eight corners are valid into six Kuhn tetrahedra (one per permutation of the
 // axes), which tile space by translation: neighbouring cubes agree on their shared faces without a special case.  Every vertex
@@ -160,7 +162,13 @@ __global__ __launch_bounds__(kThreads) void tsdf_coords_kernel(const unsigned* _
 // kCarve (free-space carving): the view loop runs over band mask | free mask, a view whose depth lies
 // beyond the band (sdf > trunc) adds 1 to a sixth sum Wf, and the epilogue forms (S + cw Wf) / (W + cw Wf) and writes `free`.
 // Without it every added line is compiled out: the plain form is the code it was.
-template <bool kCarve>
+// kWeighted (per-pixel view weights; the third form, always with kCarve): the pixel a view lands on carries a
+// float32 weight w; the view is a sample only when w > 0 and w is finite, and it adds w where the other forms add 1 -- w * (sdf /
+// trunc) to S, w to W, w * image[c] to C, w to Wf.  Whether this form carves is decided at run time (free_masks == nullptr: the view
+// loop runs over the band mask alone, the epilogue is the plain one, `free` is not written); the branch is uniform over the launch.
+// `weights` is the kernel's LAST parameter, so the two older forms keep their kernel-argument offsets, and they compile every
+// weighted line out.
+template <bool kCarve, bool kWeighted>
 __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __restrict__ depths, const float* __restrict__ images, int ch,
                                                               const double* __restrict__ cams, int rows, int cols, TsdfBox B, double trunc,
                                                               double pixel_centre, const int* __restrict__ coords,
@@ -168,7 +176,9 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
                                                               float* __restrict__ tsdf, float* __restrict__ weight,
                                                               float* __restrict__ color, unsigned* __restrict__ any,
                                                               const unsigned long long* __restrict__ free_masks, double cw,
-                                                              float* __restrict__ freev) {
+                                                              float* __restrict__ freev, const float* __restrict__ weights) {
+  static_assert(kCarve || !kWeighted, "the weighted form is built on the carving form");
+  [[maybe_unused]] const bool carving = !kWeighted || free_masks != nullptr;      // kWeighted: uniform over the launch; otherwise a constant
   const size_t slot = blockIdx.x;
   const int t = threadIdx.x;
   const int gx = coords[slot * 3 + 0] * 8 + (t & 7), gy = coords[slot * 3 + 1] * 8 + ((t >> 3) & 7), gz = coords[slot * 3 + 2] * 8 + (t >> 6);
@@ -180,7 +190,9 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
   double Wf = 0.0;                                      // kCarve only: the views that saw past this voxel
   for (int w = 0; w < words; ++w) {
     unsigned long long m = masks[slot * words + w];
-    if constexpr (kCarve) m |= free_masks[slot * words + w];
+    if constexpr (kCarve) {
+      if (carving) m |= free_masks[slot * words + w];
+    }
     for (int half = 0; half < 2; ++half) {
       unsigned mm = (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(half ? m >> 32 : m));      // wave-uniform: scalar loop
       while (mm) {
@@ -191,27 +203,57 @@ __global__ __launch_bounds__(kVox) void tsdf_integrate_kernel(const float* __res
         const size_t pix = (size_t)view * plane + (size_t)((int)floor(P.ys)) * cols + (size_t)((int)floor(P.xs));
         const float d = depths[pix];
         if (!(d > 0.f && d < INFINITY)) continue;
+        [[maybe_unused]] double wv = 1.0;               // kWeighted only: this pixel's weight
+        if constexpr (kWeighted) {
+          const float wp = weights[pix];
+          if (!(wp > 0.f && wp < INFINITY)) continue;   // 0, negative, NaN, +inf: the view is no sample here, it neither adds nor carves
+          wv = (double)wp;
+        }
         const double sdf = (double)d - P.c2;
         if (!(sdf >= -trunc && sdf <= trunc)) {
           if constexpr (kCarve) {
-            if (sdf > trunc) Wf += 1.0;                 // free: the view looks through the voxel; sdf < -trunc (occluded) adds nothing
+            // free: the view looks through the voxel; sdf < -trunc (occluded) adds nothing
+            if constexpr (kWeighted) {
+              if (carving && sdf > trunc) Wf += wv;
+            } else {
+              if (sdf > trunc) Wf += 1.0;
+            }
           }
           continue;
         }
-        S += sdf / trunc;
-        W += 1.0;
+        if constexpr (kWeighted) {
+          S += wv * (sdf / trunc);
+          W += wv;
+        } else {
+          S += sdf / trunc;
+          W += 1.0;
+        }
         if (images != nullptr) {
           const float* __restrict__ px = images + pix * ch;
-          C0 += (double)px[0];
-          C1 += (double)px[1];
-          C2 += (double)px[2];
+          if constexpr (kWeighted) {
+            C0 += wv * (double)px[0];
+            C1 += wv * (double)px[1];
+            C2 += wv * (double)px[2];
+          } else {
+            C0 += (double)px[0];
+            C1 += (double)px[1];
+            C2 += (double)px[2];
+          }
         }
       }
     }
   }
   const bool has = W > 0.0;
   const size_t o = slot * kVox + t;
-  if constexpr (kCarve) {
+  if constexpr (kWeighted) {
+    if (carving) {
+      const double f = cw * Wf;                         // formed once
+      tsdf[o] = has ? (float)((S + f) / (W + f)) : 0.f;
+      freev[o] = has ? (float)Wf : 0.f;
+    } else {
+      tsdf[o] = has ? (float)(S / W) : 0.f;
+    }
+  } else if constexpr (kCarve) {
     const double f = cw * Wf;                           // formed once
     tsdf[o] = has ? (float)((S + f) / (W + f)) : 0.f;
     freev[o] = has ? (float)Wf : 0.f;
@@ -683,9 +725,10 @@ extern "C" int atvs_tsdf_integrate(const float* depths, const float* images, int
   if ((images == nullptr) != (color == nullptr)) return ATVS_ERR_NULL;
   if (count > 0 && (!coords || !masks || !tsdf || !weight || !any)) return ATVS_ERR_NULL;
   if (count == 0) return ATVS_OK;
-  hipLaunchKernelGGL(tsdf_integrate_kernel<false>, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels, cams,
-                     rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf, weight,
-                     color, static_cast<unsigned*>(any), (const unsigned long long*)nullptr, 0.0, (float*)nullptr);
+  hipLaunchKernelGGL((tsdf_integrate_kernel<false, false>), dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels,
+                     cams, rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf,
+                     weight, color, static_cast<unsigned*>(any), (const unsigned long long*)nullptr, 0.0, (float*)nullptr,
+                     (const float*)nullptr);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }
@@ -723,9 +766,35 @@ extern "C" int atvs_tsdf_integrate_carve(const float* depths, const float* image
   if ((images == nullptr) != (color == nullptr)) return ATVS_ERR_NULL;
   if (count > 0 && (!coords || !masks || !free_masks || !tsdf || !weight || !free_out || !any)) return ATVS_ERR_NULL;
   if (count == 0) return ATVS_OK;
-  hipLaunchKernelGGL(tsdf_integrate_kernel<true>, dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels, cams,
-                     rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf, weight,
-                     color, static_cast<unsigned*>(any), static_cast<const unsigned long long*>(free_masks), carve_weight, free_out);
+  hipLaunchKernelGGL((tsdf_integrate_kernel<true, false>), dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels,
+                     cams, rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf,
+                     weight, color, static_cast<unsigned*>(any), static_cast<const unsigned long long*>(free_masks), carve_weight, free_out,
+                     (const float*)nullptr);
+  ATVS_LAUNCH_CHECK();
+  return ATVS_OK;
+}
+
+extern "C" int atvs_tsdf_integrate_weighted(const float* depths, const float* weights, const float* images, int channels,
+                                            const double* cams, int n, int rows, int cols, double voxel, double trunc,
+                                            const double* origin, int bx, int by, int bz, double pixel_centre, const int* coords,
+                                            const void* masks, const void* free_masks, double carve_weight, long count, float* tsdf,
+                                            float* weight, float* color, float* free_out, void* any, atvs_stream_t stream) {
+  TsdfBox B;
+  const int rc = tsdf_mark_args(depths, cams, n, rows, cols, voxel, trunc, origin, bx, by, bz, pixel_centre, &B);
+  if (rc != ATVS_OK) return rc;
+  if (!weights) return ATVS_ERR_NULL;
+  const bool carving = free_masks != nullptr || free_out != nullptr;      // both NULL: no carving, carve_weight is not read
+  if (carving && (!(carve_weight > 0.0) || !finite_d(carve_weight))) return ATVS_ERR_ARG;
+  if (count < 0 || count > (long)bx * by * bz) return ATVS_ERR_SHAPE;
+  if (images != nullptr && channels < 3) return ATVS_ERR_SHAPE;
+  if ((images == nullptr) != (color == nullptr)) return ATVS_ERR_NULL;
+  if ((free_masks == nullptr) != (free_out == nullptr)) return ATVS_ERR_NULL;
+  if (count > 0 && (!coords || !masks || !tsdf || !weight || !any)) return ATVS_ERR_NULL;
+  if (count == 0) return ATVS_OK;
+  hipLaunchKernelGGL((tsdf_integrate_kernel<true, true>), dim3((unsigned)count), dim3(kVox), 0, as_stream(stream), depths, images, channels,
+                     cams, rows, cols, B, trunc, pixel_centre, coords, static_cast<const unsigned long long*>(masks), (n + 63) / 64, tsdf,
+                     weight, color, static_cast<unsigned*>(any), static_cast<const unsigned long long*>(free_masks),
+                     carving ? carve_weight : 0.0, free_out, weights);
   ATVS_LAUNCH_CHECK();
   return ATVS_OK;
 }

@@ -41,7 +41,7 @@ from .convolution import (SplitVolume, _DECONV_OFFSETS, _deconv_virtual_kernel, 
     photo_pieces_ok, planar_concat_ok, refine_stems, siblings_ok)      # noqa: F401
 from .prepare import (ViewPlan, prepare_taps, prepare_view, prepare_workspace, resize_u8_host, view_plan)      # noqa: F401
 from .aanet import (aanet_combine, aanet_fused, aanet_fused_ok, aanet_partial, depth_normals, divide, fusibile,
-    fusibile_scene, fusion_stage)      # noqa: F401
+    fusibile_scene, fusion_stage, fusion_support)      # noqa: F401
 from .colmap import COVIS_MAX_IMAGES, colmap_covisibility, colmap_depth_range      # noqa: F401
 from .colmap import UNDISTORT_MAX_SIDE, UNDISTORT_MODELS, undistort_map, undistort_remap      # noqa: F401
 from .cloud import CLOUD_MAX_POINTS, CLOUD_MAX_TOLERANCES, CloudGrid, cloud_counts, cloud_grid, cloud_nearest      # noqa: F401

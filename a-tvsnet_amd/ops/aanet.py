@@ -157,3 +157,35 @@ def fusibile_scene(cams, normals_depths, images, disp_thresh, normal_thresh, num
           _p(scratch), scratch.numel(), *([_p(t) for t in outputs] + [capacity, _p(count), _stream()]))
     m = int(count.item())
     return tuple(t[:m] for t in outputs)
+
+
+FUSION_SUPPORT_OUTPUTS = ('count', 'depth', 'weight')
+
+
+def fusion_support(cams, normals_depths, disp_thresh, normal_thresh, num_consistent, want=FUSION_SUPPORT_OUTPUTS):
+    """The fusion's agreement count of every pixel of the slab, from the fusion's own loop without the images (atvs_fusion_support,
+    one launch, no synchronisation).  cams (N,28), normals_depths (N,rows,cols,4) float32 -> a dict of what `want` names, each
+    (N,rows,cols) on the slab's device:
+        count   int32: fusibile's count of the pixel -- the other views, ascending, that pass the in-image, disparity and normal test;
+        depth   float32: the pixel's own depth, bit for bit, where count >= num_consistent, +0 elsewhere (the consistency-masked plane);
+        weight  float32: float32(1 + count) / float32(1 + num_consistent), for every pixel whatever the mask says: 1 for a sample that
+                just passes the mask, more for a better supported one (a default, not a measurement).
+    `meta` tensors run the host checks alone (the outputs come back on `meta`)."""
+    if not isinstance(normals_depths, torch.Tensor) or normals_depths.dim() != 4:
+        raise ValueError('fusion_support: normals_depths must be a (N, rows, cols, 4) tensor')
+    if isinstance(num_consistent, bool) or int(num_consistent) != num_consistent or int(num_consistent) < 0:
+        raise ValueError('fusion_support: num_consistent must be an integer >= 0, got %r' % (num_consistent,))
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or len(set(want)) != len(want) or any(w not in FUSION_SUPPORT_OUTPUTS for w in want):
+        raise ValueError('fusion_support: want must name at least one of %s, each once, got %r' % (FUSION_SUPPORT_OUTPUTS, want))
+    N, rows, cols, _ = (int(s) for s in normals_depths.shape)
+    launch = _fusion_args((cams, 'cams', torch.float32, (N, 28)), (normals_depths, 'normals_depths', torch.float32, (N, rows, cols, 4)))
+    if N < 1 or rows < 1 or cols < 1 or -(-rows * cols // 256) * 256 * N > 0x7fffffff:
+        raise ValueError('fusion_support: %d maps of %d x %d: at least one pixel, and fewer than 2^31 with every map rounded up to '
+                         '256 pixels' % (N, rows, cols))
+    out = {w: torch.empty((N, rows, cols), dtype=torch.int32 if w == 'count' else torch.float32, device=normals_depths.device)
+           for w in want}
+    if launch:
+        _call('atvs_fusion_support', _p(cams), _p(normals_depths), N, rows, cols, disp_thresh, normal_thresh, int(num_consistent),
+              _p(out.get('count')), _p(out.get('depth')), _p(out.get('weight')), _stream())
+    return out

@@ -198,7 +198,8 @@ def tsdf_free_views(blocks, cams, rows, cols, voxel, origin, dims, pixel_centre=
     return masks
 
 
-def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_centre=0.0, max_blocks=131072, carve_weight=None):
+def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_centre=0.0, max_blocks=131072, carve_weight=None,
+                   weights=None):
     """depths (n,rows,cols) float32 z-depth (0 or non-finite: no sample), cams (n,16) float64 in scan_render's layout, images
     (n,rows,cols,C>=3) float32 with b, g, r in channels 0..2 or None -> TsdfVolume over the box (origin, voxel, dims).
 
@@ -213,7 +214,15 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
     depth lies beyond a voxel's band (sdf > trunc) has seen past the voxel: it adds 1 to the voxel's `free` count Wf and no colour,
     and tsdf = (S + cw Wf) / (W + cw Wf) over the in-band sums S, W.  weight stays the in-band count, a voxel no view has in band
     is not carved, so blocks, weight and color keep their bits, and tsdf does wherever free == 0; the volume's `free` holds Wf.
-    One more launch (tsdf_free_views: the views that can see into each marked block) and a second form of the integrate kernel."""
+    One more launch (tsdf_free_views: the views that can see into each marked block) and a second form of the integrate kernel.
+
+    weights: None (the above, with the launches it always made), or (n,rows,cols) float32 on the depths' device: the weight w of
+    every pixel of every view (ops.fusion_support's `weight`, a probability map, ...).  A view is a sample at the pixel it lands on
+    only when also w > 0 and w is finite -- a weight that is 0, negative, NaN or infinite neither contributes nor carves -- and it
+    then adds w where it added 1: S += w (sdf / trunc), W += w, C += w image, with carving Wf += w.  weight is the sum of the
+    weights (tsdf_mesh's min_weight is compared with it as before), free the sum of the free views' weights.  Blocks are marked
+    from the depths alone; the volume still holds exactly the blocks with a voxel of weight > 0.  All-ones weights give the bits of
+    the call without weights; a third form of the integrate kernel (atvs_tsdf_integrate_weighted), with or without carve_weight."""
     cw = _carve_weight(carve_weight)
     voxel, trunc, dims = _voxel(voxel), _trunc(trunc), _dims(dims)
     org = _vec3(origin, 'origin')
@@ -238,6 +247,11 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
             raise ValueError('images: expected shape (%d,%d,%d,C>=3), got %s' % (n, rows, cols, tuple(images.shape)))
         _same_device(images, 'images', depths, 'depths')
         channels = int(images.shape[3])
+    if weights is not None:
+        _map_arg(weights, 'weights', torch.float32, 3, '(n,rows,cols)')
+        if tuple(weights.shape) != (n, rows, cols):
+            raise ValueError('weights: expected shape (%d,%d,%d), got %s' % (n, rows, cols, tuple(weights.shape)))
+        _same_device(weights, 'weights', depths, 'depths')
     dev = depths.device
     if not _launchable(depths, 'depths'):
         return _empty_volume(origin, voxel, trunc, dims, dev, images is not None, cw is not None)
@@ -265,7 +279,12 @@ def tsdf_integrate(depths, cams, voxel, trunc, origin, dims, images=None, pixel_
     color = torch.empty((count, 8, 8, 8, 3), dtype=torch.float32, device=dev) if images is not None else None
     keep = torch.empty(count, dtype=torch.int32, device=dev)
     free = None
-    if cw is None:
+    if weights is not None:
+        free_masks = None if cw is None else tsdf_free_views(coords, cams, rows, cols, voxel, origin, dims, centre)
+        free = None if cw is None else torch.empty((count, 8, 8, 8), dtype=torch.float32, device=dev)
+        _call('atvs_tsdf_integrate_weighted', _p(depths), _p(weights), _p(images), channels, _p(cams), n, rows, cols, *box, _p(coords),
+              _p(masks), _p(free_masks), 0.0 if cw is None else cw, count, _p(tsdf), _p(weight), _p(color), _p(free), _p(keep), _stream())
+    elif cw is None:
         _call('atvs_tsdf_integrate', _p(depths), _p(images), channels, _p(cams), n, rows, cols, *box, _p(coords), _p(masks), count,
               _p(tsdf), _p(weight), _p(color), _p(keep), _stream())
     else:

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 61
+#define ATVS_ABI_VERSION 62
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -665,6 +665,26 @@ int atvs_fusibile_scene_normals(const float* cams, const float* normals_depths, 
                                 long scratch_bytes, float* points, unsigned char* colors, float* normals, long capacity,
                                 int* n_points, atvs_stream_t stream);
 
+/* The fusion's agreement count of every pixel of a scene's slab (csrc/fusion_support.hip), one launch, no images.  cams,
+ * normals_depths, disp_thresh, normal_thresh as for atvs_fusibile; num_consistent >= 0.  For pixel (x, y) of camera r, `count` is
+ * atvs_fusibile's count with ref = r: the number of views other than r, taken ascending, whose projection of the pixel's 3-D point
+ * lies in the image, whose relative disparity difference is < disp_thresh and whose normal angle is < normal_thresh -- the same
+ * float32 arithmetic, left to right, nothing contracted, the same 8-bit bilinear fetch (one function, csrc/fusion_pixel.h).
+ * Three optional outputs, each (nviews, rows, cols), each may be NULL, at least one is required:
+ *   count      int32: the count.
+ *   depth_out  float32: the pixel's own depth normals_depths[..., 3], bit for bit, where count >= num_consistent, +0 elsewhere:
+ *              the depth plane as the fusion masks its points.
+ *   weight_out float32: (float)(1 + count) / (float)(1 + num_consistent), one correctly rounded float32 division, written for
+ *              every pixel whatever the mask says.  A pixel that just passes the mask weighs exactly 1, a better supported one
+ *              more, so the weights of the views a voxel had before never sum to less than their number.  The formula is a default,
+ *              not a measurement.
+ * One workgroup per (camera, run of 256 row-major pixels); no atomics, no scratch; the same inputs give the same bits.
+ * All three outputs NULL: ATVS_ERR_NULL; nviews * rows * cols beyond int: ATVS_ERR_SHAPE (atvs_fusibile_scene's limits);
+ * num_consistent < 0: ATVS_ERR_ARG. */
+int atvs_fusion_support(const float* cams, const float* normals_depths, int nviews, int rows, int cols, float disp_thresh,
+                        float normal_thresh, int num_consistent, int* count, float* depth_out, float* weight_out,
+                        atvs_stream_t stream);
+
 /* Normals of a scene's depth maps from the maps themselves (csrc/depth_normals.hip), one launch over the fusion slab
  * normals_depths (nviews, rows, cols, 4) = (nx, ny, nz, depth), IN PLACE: only .w (the depth) is read, only the three normal
  * floats are written.  cams (nviews, 28) as for atvs_fusibile.  Per pixel (x, y) with depth d, in float64:
@@ -1204,6 +1224,24 @@ int atvs_cloud_voxel_shares(const float* points, const float* d2, const float* e
  *   atvs_tsdf_integrate_carve: as atvs_tsdf_integrate over the views of masks | free_masks (both (count, ceil(n / 64))), with
  *   free_out (count,8,8,8).  carve_weight <= 0 or not finite: ATVS_ERR_ARG.
  *
+ * Per-pixel view weights (opt-in: atvs_tsdf_integrate_weighted; the two entry points above are as they were).  weights (n, rows,
+ * cols) float32 beside depths.  Per voxel and view, views ascending, in double, nothing contracted, with exactly the projection and
+ * the pixel above: d is the pixel's depth, w the pixel's weight.  The view is a SAMPLE only when the conditions above hold (in
+ * view, d > 0, d finite) and w > 0 and w is finite; a weight that is 0, negative, NaN or infinite makes the view no sample at that
+ * pixel: it neither contributes nor carves.  A sample in band (-trunc <= sdf <= trunc) adds S += (double)w * (sdf / trunc),
+ * W += (double)w, C[c] += (double)w * (double)image[c], each product rounded before its sum; with carving a free sample
+ * (sdf > trunc) adds Wf += (double)w.  The epilogues are the ones above, unchanged: tsdf = (float)(S / W) without carving,
+ * (float)((S + f) / (W + f)) with f = cw * Wf formed once with it; weight = (float)W, now a sum of weights, which
+ * atvs_tsdf_mesh_count's min_weight is compared with as before; free = (float)Wf where W > 0; color[c] = (float)(C[c] / W); all 0
+ * where W = 0.  Marking and assignment read the depths alone and are untouched: a marked block whose samples all have a weight that
+ * is no weight ends with W = 0 everywhere and is dropped by atvs_tsdf_gather, so the volume still holds exactly the blocks with a
+ * voxel of W > 0.  Consequences: with every weight 1.0 each array is bit for bit the one of the call without weights, with and
+ * without carving (1.0 * x is exact, the sums run in the same order); with weights that are 0 where a mask is false and 1 elsewhere
+ * the volume is the one integrated from the depths zeroed by that mask.
+ *   atvs_tsdf_integrate_weighted: as atvs_tsdf_integrate_carve with weights after depths.  free_masks and free_out may both be
+ *   NULL: no carving, the views of masks alone, carve_weight is not read.  One of the two NULL: ATVS_ERR_NULL.  weights NULL:
+ *   ATVS_ERR_NULL.  With carving carve_weight <= 0 or not finite: ATVS_ERR_ARG.
+ *
  * Extraction.  blocks (nb,3) int32 ascending in the linear index, each at most once, nb <= ATVS_TSDF_MAX_MESH_BLOCKS; tsdf, weight
  * (nb,8,8,8), color (nb,8,8,8,3) or NULL.  A voxel is VALID when weight >= min_weight (a voxel of a missing block or outside the
  * box is not); INSIDE means tsdf < 0.  The cube of voxel (i, j, k) has the 8 centres (i..i+1, j..j+1, k..k+1) and is meshed when
@@ -1254,6 +1292,11 @@ int atvs_tsdf_integrate_carve(const float* depths, const float* images, int chan
                               double voxel, double trunc, const double* origin, int bx, int by, int bz, double pixel_centre,
                               const int* coords, const void* masks, const void* free_masks, double carve_weight, long count,
                               float* tsdf, float* weight, float* color, float* free_out, void* any, atvs_stream_t stream);
+int atvs_tsdf_integrate_weighted(const float* depths, const float* weights, const float* images, int channels, const double* cams,
+                                 int n, int rows, int cols, double voxel, double trunc, const double* origin, int bx, int by, int bz,
+                                 double pixel_centre, const int* coords, const void* masks, const void* free_masks,
+                                 double carve_weight, long count, float* tsdf, float* weight, float* color, float* free_out,
+                                 void* any, atvs_stream_t stream);
 int atvs_tsdf_mesh_count(const int* blocks, int nb, int bx, int by, int bz, const float* tsdf, const float* weight,
                          float min_weight, void* cube_ok, void* emask, void* vcount, void* fcount, atvs_stream_t stream);
 int atvs_tsdf_mesh_emit(const int* blocks, int nb, int bx, int by, int bz, double voxel, const double* origin, const float* tsdf,

@@ -14,10 +14,16 @@ The scene: the sphere of tests/tsdf_restated.py (radius 0.9) rendered analytical
     carve        (--carve, a run of its own) free-space carving on the same scene: integrate without and with carving on the same
                  slots, the free-view launch, the free mask's bits out of slots x views, the voxels with a free vote.
 
+    weighted     (--weights, alias --support, a run of its own) the consistency mask and the view weights on the same scene:
+                 atvs_fusion_support beside atvs_fusibile_scene (count, scan and scatter: the count pass has no entry point of its
+                 own) on the same slab, and the integrate kernel's plain, carving and weighted forms on the same slots, the old
+                 forms twice, alternating.  --baseline runs the old forms alone: the step a checkout of the parent commit can run.
+
 Each step runs as a child process under its own time limit, one after the other; the first that fails ends the run.
 
     python tools_dev/mesh_rate.py --out profiles/tsdf_mesh.json
     python tools_dev/mesh_rate.py --carve --out profiles/tsdf_mesh_carve.json
+    python tools_dev/mesh_rate.py --weights --out profiles/tsdf_mesh_weighted.json
 """
 import argparse
 import json
@@ -41,7 +47,10 @@ from fusion_rate import measured_head  # noqa: E402
 RADIUS = 0.9
 STEPS = (('kernels', 300), ('scene', 300), ('restatement', 400))
 CARVE_STEPS = (('carve', 300),)
-MEASURED = ('a-tvsnet_amd/csrc/tsdf.hip', 'a-tvsnet_amd/csrc/scan_project.h', 'a-tvsnet_amd/csrc/cloud_scan.h', 'a-tvsnet_amd/ops/tsdf.py',
+WEIGHTED_STEPS = (('weighted', 300),)
+BASELINE_STEPS = (('baseline', 300),)
+MEASURED = ('a-tvsnet_amd/csrc/tsdf.hip', 'a-tvsnet_amd/csrc/fusion_support.hip', 'a-tvsnet_amd/csrc/fusion_pixel.h',
+            'a-tvsnet_amd/csrc/scan_project.h', 'a-tvsnet_amd/csrc/cloud_scan.h', 'a-tvsnet_amd/ops/tsdf.py',
             'a-tvsnet_amd/atvsnet/mesh_fusion.py')
 
 
@@ -221,6 +230,142 @@ def step_carve(a):
             'carve_voxel_views_per_s': loop_bits * 512 / (ms['integrate_carve'] * 1e-3)}
 
 
+def step_weighted(a):
+    """The support kernel beside atvs_fusibile_scene on the same slab, and the three forms of the integrate kernel on the same slots:
+    plain, carving, weighted without and with carving (the weights are the support kernel's)."""
+    import torch
+    from atvsnet_amd.atvsnet import depth_fusion as DF
+    from atvsnet_amd.ops import tsdf as T
+    from atvsnet_amd.ops.base import _call, _p, _size, _stream
+    from atvsnet_amd.ops.cloud import _vec3
+    dev = torch.device('cuda:0')
+    torch.cuda.set_device(dev)
+    cams, depths, images, trunc, origin, dims = scene(a)
+    d, c, im = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (depths, cams, images))
+    n, rows, cols = depths.shape
+    ms, all_ms = {}, {}
+
+    def timed(name, fn):
+        out, ms[name], all_ms[name] = _median_ms(fn, a.reps)
+        return out
+
+    # the slab the fusion would hold: the fake normal where there is a depth, the images as float4
+    Ps = [np.array([[k[12], 0, k[14]], [0, k[13], k[15]], [0, 0, 1.0]]) @ np.concatenate([k[:9].reshape(3, 3), k[9:12].reshape(3, 1)], 1) for k in cams]
+    cams28 = torch.from_numpy(DF.pack_cameras(Ps)).to(dev)
+    fake = torch.where(d > 0, torch.full_like(d, float(np.float32(1.0) / np.float32(1.732050808))), torch.zeros_like(d))
+    nd = torch.stack([fake, fake, fake, d], dim=-1).contiguous()
+    img4 = torch.cat([im, torch.zeros_like(im[..., :1])], dim=-1).contiguous()
+    disp, ang, ncons = 0.01, DF.NORMAL_THRESHOLD, 2
+    count = torch.empty((n, rows, cols), dtype=torch.int32, device=dev)
+    masked, wplane = torch.empty_like(d), torch.empty_like(d)
+    timed('support_all_outputs', lambda: _call('atvs_fusion_support', _p(cams28), _p(nd), n, rows, cols, disp, ang, ncons, _p(count), _p(masked),
+                                               _p(wplane), _stream()))
+    timed('support_count_alone', lambda: _call('atvs_fusion_support', _p(cams28), _p(nd), n, rows, cols, disp, ang, ncons, _p(count), None, None,
+                                               _stream()))
+    capacity = n * rows * cols
+    scratch = torch.empty(_size('atvs_fusibile_scene_scratch_size', n, rows, cols), dtype=torch.uint8, device=dev)
+    points = torch.empty((capacity, 3), dtype=torch.float32, device=dev)
+    colors = torch.empty((capacity, 3), dtype=torch.uint8, device=dev)
+    n_points = torch.empty(1, dtype=torch.int32, device=dev)
+    timed('fusibile_scene_count_scan_scatter', lambda: _call('atvs_fusibile_scene', _p(cams28), _p(nd), _p(img4), n, rows, cols, disp, ang, ncons,
+                                                             _p(scratch), scratch.numel(), _p(points), _p(colors), capacity, _p(n_points),
+                                                             _stream()))
+    fused_points = int(n_points.item())                  # beside samples_kept: the fusion also keeps a created pixel without a depth
+
+    bx, by, bz = dims
+    nbk = bx * by * bz
+    org = _vec3(origin, 'origin')
+    box = (a.voxel, trunc, org, bx, by, bz, 0.0)
+    directory = torch.empty(nbk, dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _call('atvs_tsdf_mark', _p(d), _p(c), n, rows, cols, *box, _p(directory), _p(err), _stream())
+    slots = int(T._scan(directory, nbk).item())
+    assert int(err.item()) == 0 and 0 < slots <= a.max_blocks, slots
+    words = (n + 63) // 64
+    coords = torch.empty((slots, 3), dtype=torch.int32, device=dev)
+    masks = torch.empty((slots, words), dtype=torch.int64, device=dev)
+    free_masks = torch.empty((slots, words), dtype=torch.int64, device=dev)
+    _call('atvs_tsdf_assign', _p(d), _p(c), n, rows, cols, *box, _p(directory), slots, _p(coords), _p(masks), _p(err), _stream())
+    _call('atvs_tsdf_free_views', _p(coords), slots, _p(c), n, rows, cols, a.voxel, org, bx, by, bz, 0.0, _p(free_masks), _stream())
+    tsdf = torch.empty((slots, 8, 8, 8), dtype=torch.float32, device=dev)
+    weight, free = torch.empty_like(tsdf), torch.empty_like(tsdf)
+    color = torch.empty((slots, 8, 8, 8, 3), dtype=torch.float32, device=dev)
+    keep = torch.empty(slots, dtype=torch.int32, device=dev)
+    ones = torch.ones_like(d)
+
+    def plain():
+        _call('atvs_tsdf_integrate', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks), slots, _p(tsdf), _p(weight), _p(color),
+              _p(keep), _stream())
+
+    def carve():
+        _call('atvs_tsdf_integrate_carve', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks), _p(free_masks), a.carve_weight,
+              slots, _p(tsdf), _p(weight), _p(color), _p(free), _p(keep), _stream())
+
+    def weighted(w, carving):
+        _call('atvs_tsdf_integrate_weighted', _p(d), _p(w), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks),
+              _p(free_masks) if carving else None, a.carve_weight, slots, _p(tsdf), _p(weight), _p(color), _p(free) if carving else None,
+              _p(keep), _stream())
+
+    # the old forms twice, alternating with the new one: what a baseline at the parent commit is compared with
+    for tag in ('', '_again'):
+        timed('integrate' + tag, plain)
+        timed('integrate_carve' + tag, carve)
+        timed('integrate_weighted' + tag, lambda: weighted(wplane, False))
+        timed('integrate_weighted_carve' + tag, lambda: weighted(wplane, True))
+    plain()
+    ref = (tsdf.clone(), weight.clone(), color.clone())
+    weighted(ones, False)
+    assert all(torch.equal(x.view(torch.int32), y.view(torch.int32)) for x, y in zip(ref, (tsdf, weight, color)))      # all-ones: the same bits
+    bits = int(sum(bin(int(w)).count('1') for w in masks.cpu().numpy().view(np.uint64).reshape(-1)))
+    return {'device': torch.cuda.get_device_name(dev), 'views': n, 'pixels': capacity, 'disp_threshold': disp, 'num_consistent': ncons,
+            'samples': int((d > 0).sum().item()), 'samples_kept': int((masked > 0).sum().item()), 'fused_points': fused_points,
+            'pixels_without_depth_with_count_ge_num_consistent': int(((d <= 0) & (count >= ncons)).sum().item()), 'marked_blocks': slots,
+            'voxel_views_plain': bits * 512, 'ms': ms, 'ms_all': all_ms,
+            'support_over_fusibile_scene': ms['support_all_outputs'] / ms['fusibile_scene_count_scan_scatter'],
+            'weighted_over_plain': ms['integrate_weighted'] / ms['integrate'],
+            'weighted_carve_over_carve': ms['integrate_weighted_carve'] / ms['integrate_carve']}
+
+
+def step_baseline(a):
+    """The plain and the carving form alone, on the same slots: the step that also runs on a checkout of the parent commit."""
+    import torch
+    from atvsnet_amd.ops import tsdf as T
+    from atvsnet_amd.ops.base import _call, _p, _stream
+    from atvsnet_amd.ops.cloud import _vec3
+    dev = torch.device('cuda:0')
+    torch.cuda.set_device(dev)
+    cams, depths, images, trunc, origin, dims = scene(a)
+    d, c, im = (torch.from_numpy(np.ascontiguousarray(x)).to(dev) for x in (depths, cams, images))
+    n, rows, cols = depths.shape
+    bx, by, bz = dims
+    nbk = bx * by * bz
+    org = _vec3(origin, 'origin')
+    box = (a.voxel, trunc, org, bx, by, bz, 0.0)
+    directory = torch.empty(nbk, dtype=torch.int32, device=dev)
+    err = torch.empty(1, dtype=torch.int32, device=dev)
+    _call('atvs_tsdf_mark', _p(d), _p(c), n, rows, cols, *box, _p(directory), _p(err), _stream())
+    slots = int(T._scan(directory, nbk).item())
+    words = (n + 63) // 64
+    coords = torch.empty((slots, 3), dtype=torch.int32, device=dev)
+    masks = torch.empty((slots, words), dtype=torch.int64, device=dev)
+    free_masks = torch.empty((slots, words), dtype=torch.int64, device=dev)
+    _call('atvs_tsdf_assign', _p(d), _p(c), n, rows, cols, *box, _p(directory), slots, _p(coords), _p(masks), _p(err), _stream())
+    _call('atvs_tsdf_free_views', _p(coords), slots, _p(c), n, rows, cols, a.voxel, org, bx, by, bz, 0.0, _p(free_masks), _stream())
+    tsdf = torch.empty((slots, 8, 8, 8), dtype=torch.float32, device=dev)
+    weight, free = torch.empty_like(tsdf), torch.empty_like(tsdf)
+    color = torch.empty((slots, 8, 8, 8, 3), dtype=torch.float32, device=dev)
+    keep = torch.empty(slots, dtype=torch.int32, device=dev)
+    ms, all_ms = {}, {}
+    for tag in ('', '_again'):
+        _, ms['integrate' + tag], all_ms['integrate' + tag] = _median_ms(
+            lambda: _call('atvs_tsdf_integrate', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks), slots, _p(tsdf), _p(weight),
+                          _p(color), _p(keep), _stream()), a.reps)
+        _, ms['integrate_carve' + tag], all_ms['integrate_carve' + tag] = _median_ms(
+            lambda: _call('atvs_tsdf_integrate_carve', _p(d), _p(im), 3, _p(c), n, rows, cols, *box, _p(coords), _p(masks), _p(free_masks),
+                          a.carve_weight, slots, _p(tsdf), _p(weight), _p(color), _p(free), _p(keep), _stream()), a.reps)
+    return {'device': torch.cuda.get_device_name(dev), 'marked_blocks': slots, 'ms': ms, 'ms_all': all_ms}
+
+
 def step_scene(a):
     import torch
     from atvsnet_amd.atvsnet import depth_fusion as DF, mesh_fusion
@@ -284,11 +429,15 @@ def main():
     ap.add_argument('--host_views', type=int, default=4)
     ap.add_argument('--carve_weight', type=float, default=1.0)
     ap.add_argument('--carve', action='store_true', help='run the carve step alone (for profiles/tsdf_mesh_carve.json)')
-    ap.add_argument('--step', default=None, choices=[s for s, _ in STEPS + CARVE_STEPS], help='run one step in this process and write its result to --out')
+    ap.add_argument('--weights', '--support', dest='weights', action='store_true',
+                    help='run the weighted step alone (for profiles/tsdf_mesh_weighted.json)')
+    ap.add_argument('--baseline', action='store_true', help='run the baseline step alone: the plain and carving forms, as the parent commit has them')
+    ap.add_argument('--step', default=None, choices=[s for s, _ in STEPS + CARVE_STEPS + WEIGHTED_STEPS + BASELINE_STEPS], help='run one step in this process and write its result to --out')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     if a.step is not None:
-        result = {'kernels': step_kernels, 'scene': step_scene, 'restatement': step_restatement, 'carve': step_carve}[a.step](a)
+        result = {'kernels': step_kernels, 'scene': step_scene, 'restatement': step_restatement, 'carve': step_carve,
+                  'weighted': step_weighted, 'baseline': step_baseline}[a.step](a)
         print(json.dumps({k: v for k, v in result.items() if not k.endswith('_all')}), flush=True)
         if a.out:
             with open(a.out, 'w') as f:
@@ -301,7 +450,7 @@ def main():
     passed = [k for k in ('maps', 'rows', 'cols', 'voxel', 'min_weight', 'max_blocks', 'reps', 'host_blocks', 'host_views', 'carve_weight')]
     common = [x for k in passed for x in ('--' + k, str(getattr(a, k)))]
     with tempfile.TemporaryDirectory() as tmp:
-        for step, limit in (CARVE_STEPS if a.carve else STEPS):                        # one after the other: a step that fails or runs out of time ends the run
+        for step, limit in (CARVE_STEPS if a.carve else WEIGHTED_STEPS if a.weights else BASELINE_STEPS if a.baseline else STEPS):                        # one after the other: a step that fails or runs out of time ends the run
             part = os.path.join(tmp, step + '.json')
             try:
                 rc = subprocess.run([sys.executable, os.path.abspath(__file__), '--step', step, '--out', part] + common, timeout=limit).returncode
