@@ -18,7 +18,7 @@ No criterion has a default: which fragments are noise depends on the scene and t
 faces that stay keep their order, the vertices they name keep theirs, the faces are renumbered (ops.mesh_select); the edge census
 (ops.mesh_edge_census) is taken before and after.  Everything between the upload and the download stays on the device; the
 criteria are decided on the host from the per-component counts, one number per component.  There is no CPU fallback.  What this is
-not: components by shared edge rather than shared vertex, criteria by area, hole filling, simplification, normals.  This module
+not: components by shared edge rather than shared vertex, criteria by area, hole filling, normals (simplification is atvsnet/simplify_mesh.py).  This module
 imports without a GPU; only `clean` and `clean_device` need one.
 """
 from __future__ import print_function
@@ -176,7 +176,7 @@ def options(parser, args, prefix=''):
 
 def make_parser():
     parser = argparse.ArgumentParser(description='clean a triangle mesh on the GPU: remove the connected components that are too '
-                                                 'small (no hole filling, no simplification)')
+                                                 'small (no hole filling; simplification is atvsnet/simplify_mesh.py)')
     parser.add_argument('--in', dest='input', required=True, help='the mesh: a PLY as mesh_fusion writes it (its colours are kept) '
                                                                   'or a third-party triangle-mesh PLY')
     parser.add_argument('--out', required=True, help='the cleaned mesh (a binary PLY)')

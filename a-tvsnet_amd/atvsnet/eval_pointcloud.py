@@ -112,7 +112,8 @@ def _clean_cloud(points, colors, score, folder, opts, normals=None):
 
 def _write_mesh(scene_fusion, map_cams, folder, mesh):
     """final3d_mesh.ply and mesh.json -> the face count.  After the cloud: the fusion's result bounds the volume.  With clean= in
-    `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's clean=)."""
+    `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's clean=); with
+    simplify= also final3d_mesh_simple.ply and mesh_simple.json, the mesh (the cleaned one with clean=) after vertex clustering."""
     t0 = time.time()
     scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
     n_faces = scene_mesh.write_ply(os.path.join(folder, 'final3d_mesh.ply'))
@@ -122,6 +123,9 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
     if mesh.get('clean'):
         scene_mesh.write_clean_ply(os.path.join(folder, 'final3d_mesh_clean.ply'))
         mesh_fusion.write_json(os.path.join(folder, 'mesh_clean.json'), scene_mesh.clean_report())
+    if mesh.get('simplify'):
+        scene_mesh.write_simple_ply(os.path.join(folder, 'final3d_mesh_simple.ply'))
+        mesh_fusion.write_json(os.path.join(folder, 'mesh_simple.json'), scene_mesh.simplify_report())
     TIMES['mesh'] = time.time() - t0
     return n_faces
 
@@ -199,7 +203,8 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     final3d_model_clean.ply and cloud_clean.json; with gt_ply the cleaned cloud is scored too, into cloud_eval_clean.json (moved by the
     matrix found for the uncleaned cloud, not registered again); clean_keep_normals (with clean and fuse_normals normals='depth'
     only): the cleaned PLY carries the normals of the rows that stay -- clean_cloud.options.
-    mesh (with fuse only): mesh_fusion.SceneMesh's arguments, with render=True also depths_mesh/ -- mesh_fusion.options."""
+    mesh (with fuse only): mesh_fusion.SceneMesh's arguments, with render=True also depths_mesh/ -- mesh_fusion.options; its
+    simplify=dict(cell_voxels=R) (no command-line option) also writes final3d_mesh_simple.ply and mesh_simple.json."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
                    clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals, mesh=mesh)

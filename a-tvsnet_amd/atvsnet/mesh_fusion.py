@@ -7,6 +7,8 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     mesh_report    blocks, valid voxels, vertices, faces, zero-area faces, boundary edges (ops.mesh_edge_census for a mesh on a GPU)
     render_views   the mesh rendered into cameras (ops.mesh_render), one %08d_mesh.pfm per map
     clean=         SceneMesh and the tool also give the mesh without its small connected components (clean_mesh, section 10.3a)
+    simplify=      SceneMesh also gives the mesh -- the cleaned one with clean= -- simplified by vertex clustering on a lattice of
+                   cell_voxels voxels (simplify_mesh, section 10.3d); off unless asked
 
     carve_weight=  free-space carving (section 10.3b): a view that sees past a voxel pulls its value outside, so a shell that two views
                    agree on and the others look through is not meshed; off (None) unless asked
@@ -18,8 +20,9 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
                    (SceneMesh's arguments; on written maps the command atvsnet/mesh_consistent.py, this tool with four more options)
 
 What this is not: there are no weights from the viewing angle, the ETH3D driver has no probability weights (its staged slab does not
-keep the probabilities; mesh_consistent reads them from the files) and no command-line option for consistent= and weights= (they are
-run_eval_pc's mesh arguments), no mesh simplification, no hole filling, and the PLY carries no normals.
+keep the probabilities; mesh_consistent reads them from the files) and no command-line option for consistent=, weights= and
+simplify= (they are run_eval_pc's mesh arguments; a written mesh is simplified by the command atvsnet/simplify_mesh.py), no hole
+filling, and the PLY carries no normals.
 Without carve_weight a view adds to a voxel only inside the narrow band around its depth.  Fragments are removed only when asked
 (the clean_ options have no defaults).  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports
 without a GPU.
@@ -36,7 +39,7 @@ import time
 import numpy as np
 
 from ..tools.common import write_json  # noqa: F401
-from . import clean_mesh, eval_depth
+from . import clean_mesh, eval_depth, simplify_mesh
 
 DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
 DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
@@ -48,12 +51,15 @@ TOOL_WEIGHT_MODES = ('agree', 'prob')      # the tool also reads the probability
 
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
-                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None, consistent=False, weights=None):
+                  pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None, consistent=False, weights=None,
+                  simplify=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
     the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there,
-    carve_weight by check_carve_weight, consistent and weights by check_support (they are not part of the tuple)."""
+    carve_weight by check_carve_weight, consistent and weights by check_support, simplify by check_simplify (they are not part of
+    the tuple)."""
     if clean is not None:
         clean_mesh.check_criteria(**clean)
+    check_simplify(simplify)
     check_carve_weight(carve_weight)
     check_support(consistent, weights)
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
@@ -83,6 +89,23 @@ def check_carve_weight(carve_weight):
     if not (cw > 0.0 and np.isfinite(cw)):
         raise ValueError('mesh carve_weight must be a finite number > 0, got %r' % (carve_weight,))
     return cw
+
+
+def check_simplify(simplify):
+    """-> None (no simplification) or (cell_voxels float, placement, rank_epsilon): simplify is a dict(cell_voxels=R[, placement=,
+    rank_epsilon=]); the cell is R voxels and its origin the volume's, so the cells sit on the voxel lattice.  Anything else raises
+    ValueError."""
+    if simplify is None:
+        return None
+    if not isinstance(simplify, dict) or 'cell_voxels' not in simplify or set(simplify) - {'cell_voxels', 'placement', 'rank_epsilon'}:
+        raise ValueError('mesh simplify must be a dict(cell_voxels=R[, placement=, rank_epsilon=]), got %r' % (simplify,))
+    try:
+        cell, placement, _, rank_epsilon = simplify_mesh.check_options(
+            simplify['cell_voxels'], simplify.get('placement', simplify_mesh.DEFAULT_PLACEMENT), None,
+            simplify.get('rank_epsilon', simplify_mesh.DEFAULT_RANK_EPSILON))
+    except ValueError as e:
+        raise ValueError('mesh simplify: %s' % str(e).replace('cell must', 'cell_voxels must'))
+    return cell, placement, rank_epsilon
 
 
 def check_support(consistent=False, weights=None, modes=WEIGHT_MODES):
@@ -249,6 +272,11 @@ class SceneMesh(object):
     report() stay those of the whole mesh, and write_clean_ply(path), clean_result(), clean_report() and render(folder, clean=True)
     give the cleaned one.
 
+    simplify: None, or dict(cell_voxels=R[, placement='quadric' | 'mean', rank_epsilon=1e-3]).  With it run() also simplifies the
+    mesh -- the cleaned one when clean= is given -- on the device by vertex clustering (simplify_mesh.simplify_device) with cells of
+    R voxels whose origin is the volume's, so they sit on the voxel lattice; run()'s result, report() and the cleaned mesh stay as
+    they are, and simplify_result(), simplify_report() and write_simple_ply(path) give the simplified one (section 10.3d).
+
     carve_weight: None, or the weight of a free vote: the staged planes are integrated with free-space carving (section 10.3b) and
     report() gains carve_weight, free_voxels and max_free.
 
@@ -260,8 +288,10 @@ class SceneMesh(object):
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
                  max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None,
-                 consistent=False, weights=None):
+                 consistent=False, weights=None, simplify=None):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
+        self.simplify = check_simplify(simplify)
+        self._device_simple = self._simple_result = self._simple_report = None
         self.carve_weight = check_carve_weight(carve_weight)
         self.consistent, self.weights = check_support(consistent, weights)
         self.clean = None if clean is None else dict(clean)
@@ -315,6 +345,13 @@ class SceneMesh(object):
             if self.clean is not None:
                 vertices, colors, faces, self._clean_report = clean_mesh.clean_device(*mesh, **self.clean)
                 self._device_clean = (vertices, colors, faces)
+            if self.simplify is not None:
+                cell_voxels, placement, rank_epsilon = self.simplify
+                source = mesh if self.clean is None else self._device_clean
+                vertices, colors, faces, self._simple_report = simplify_mesh.simplify_device(
+                    *source, cell=cell_voxels * voxel, placement=placement, origin=self.volume.origin, rank_epsilon=rank_epsilon)
+                self._simple_report.update(cell_voxels=cell_voxels, source='clean' if self.clean is not None else 'mesh')
+                self._device_simple = (vertices, colors, faces)
             t0 = time.time()
             self.result = tuple(None if t is None else t.cpu().numpy() for t in mesh)
             self._device_mesh = mesh
@@ -350,6 +387,31 @@ class SceneMesh(object):
         """The cleaned mesh into a binary PLY at `path` -> the number of faces."""
         from ..tools import ply
         vertices, colors, faces = self.clean_result()
+        ply.write_mesh(path, vertices, colors, faces)
+        return len(faces)
+
+    def _simplified(self):
+        self.run()
+        if self._device_simple is None:
+            raise RuntimeError('SceneMesh: no simplify= was given: there is no simplified mesh')
+        return self._device_simple
+
+    def simplify_result(self):
+        """run() -> the simplified mesh (vertices, colors, faces) as numpy arrays."""
+        device = self._simplified()
+        if self._simple_result is None:
+            self._simple_result = tuple(None if t is None else t.cpu().numpy() for t in device)
+        return self._simple_result
+
+    def simplify_report(self):
+        """run() -> simplify_mesh.simplify_device's report, with cell_voxels and the source ('mesh' or 'clean')."""
+        self._simplified()
+        return self._simple_report
+
+    def write_simple_ply(self, path):
+        """The simplified mesh into a binary PLY at `path` -> the number of faces."""
+        from ..tools import ply
+        vertices, colors, faces = self.simplify_result()
         ply.write_mesh(path, vertices, colors, faces)
         return len(faces)
 
@@ -425,8 +487,8 @@ def options(parser, args, prefix=''):
 
 def rules(mesh, fuse):
     """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight, consistent,
-    weights and clean only when they are given (consistent and weights reach the driver through run_eval_pc's mesh dict alone: its
-    command line has no option for them)."""
+    weights, clean and simplify only when they are given (consistent, weights and simplify reach the driver through run_eval_pc's
+    mesh dict alone: its command line has no option for them)."""
     if mesh is None:
         return []
     rows = [(fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
@@ -443,12 +505,15 @@ def rules(mesh, fuse):
     if mesh.get('clean') is not None:                 # in front of the row above: its message names what was given
         rows.insert(1, (mesh.get('voxel') is None, '--mesh_clean_min_faces, --mesh_clean_min_ratio and --mesh_clean_keep_largest need '
                                                    '--mesh_voxel (mesh clean= needs voxel=): there is no mesh to clean'))
+    if mesh.get('simplify') is not None:
+        rows.insert(1, (mesh.get('voxel') is None, 'mesh simplify= needs voxel=: there is no mesh to simplify, and its cells are '
+                                                   'counted in voxels'))
     return rows
 
 
 def make_parser():
     parser = argparse.ArgumentParser(description='mesh the written depth maps of a scene: TSDF fusion and marching tetrahedra on the GPU '
-                                                 '(free-space carving with --carve; no simplification, no hole filling)')
+                                                 '(free-space carving with --carve; simplification is atvsnet/simplify_mesh.py; no hole filling)')
     parser.add_argument('--scene', default=None, help='<data_root>/eth3d/<scene>: its pair.txt names the maps (default: every map under --maps)')
     parser.add_argument('--maps', required=True, help='<savepath>/<scene> of eval_pointcloud: depths_atvsnet/%%08d.pfm, _prob.pfm, .jpg, .txt')
     add_options(parser)

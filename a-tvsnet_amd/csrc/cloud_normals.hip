@@ -7,7 +7,8 @@
 // (s, and the six sums of products) take the samples in ascending t.  The samples are differences to the query, so every term is of
 // the neighbourhood's own size and the one-pass covariance S_ab - s_a s_b / c does not cancel however far the cloud is from the origin.
 //
-// THE SOLVER: cyclic Jacobi, kSweeps = 6 sweeps of the three rotations (0,1), (0,2), (1,2), 18 rotations, always all of them.  The
+// THE SOLVER (jacobi3.h, shared with mesh_simplify.hip; the same operations in the same order as when it stood here): cyclic
+// Jacobi, kSweeps = 6 sweeps of the three rotations (0,1), (0,2), (1,2), 18 rotations, always all of them.  The
 // matrix and the accumulated rotations live in fifteen named doubles; nothing is indexed at run time, no trip count depends on the
 // data.  A rotation of the pair (p, q) with the third index r:
 //     theta = (a_qq - a_pp) / (2 a_pq);  t = sign(theta) / (|theta| + sqrt(theta theta + 1))   (t = 0 where a_pq == 0)
@@ -23,37 +24,12 @@
 
 #include "common.h"
 #include "cloud_common.h"
+#include "jacobi3.h"
 
 namespace {
 
 constexpr int kMaxK = ATVS_CLOUD_MAX_K;
-constexpr int kSweeps = 6;
 constexpr double kRankRatio = 1e-12;                     // lambda_1 <= kRankRatio lambda_2: fewer than two directions
-
-// One Jacobi rotation of the pair (p, q); r is the third index.  All arguments are named registers.
-__device__ __forceinline__ void jacobi_rotate(double& app, double& aqq, double& apq, double& apr, double& aqr, double& v0p, double& v0q,
-                                              double& v1p, double& v1q, double& v2p, double& v2q) {
-  const double theta = (aqq - app) / (2.0 * apq);
-  const double mag = fabs(theta) + sqrt(theta * theta + 1.0);
-  const double t = apq == 0.0 ? 0.0 : (theta < 0.0 ? -1.0 / mag : 1.0 / mag);
-  const double c = 1.0 / sqrt(t * t + 1.0);
-  const double s = t * c;
-  const double h = t * apq;
-  app = app - h;
-  aqq = aqq + h;
-  apq = 0.0;
-  const double pr = c * apr - s * aqr, qr = s * apr + c * aqr;
-  apr = pr;
-  aqr = qr;
-  const double a0 = c * v0p - s * v0q, b0 = s * v0p + c * v0q;
-  const double a1 = c * v1p - s * v1q, b1 = s * v1p + c * v1q;
-  const double a2 = c * v2p - s * v2q, b2 = s * v2p + c * v2q;
-  v0p = a0; v0q = b0;
-  v1p = a1; v1q = b1;
-  v2p = a2; v2q = b2;
-}
-
-__device__ __forceinline__ bool finite_d(double v) { return fabs(v) < (double)__uint_as_float(0x7f800000u); }
 
 __global__ __launch_bounds__(kThreads) void cloud_normals_kernel(const float* __restrict__ points, long n, const float* __restrict__ queries,
                                                                  long m, const int* __restrict__ idx, int k, int self_counts,
@@ -89,12 +65,7 @@ __global__ __launch_bounds__(kThreads) void cloud_normals_kernel(const float* __
   double a00 = xx - (s0 * s0) / c, a01 = xy - (s0 * s1) / c, a02 = xz - (s0 * s2) / c;
   double a11 = yy - (s1 * s1) / c, a12 = yz - (s1 * s2) / c, a22 = zz - (s2 * s2) / c;
   double v00 = 1.0, v01 = 0.0, v02 = 0.0, v10 = 0.0, v11 = 1.0, v12 = 0.0, v20 = 0.0, v21 = 0.0, v22 = 1.0;
-#pragma unroll
-  for (int sweep = 0; sweep < kSweeps; ++sweep) {
-    jacobi_rotate(a00, a11, a01, a02, a12, v00, v01, v10, v11, v20, v21);
-    jacobi_rotate(a00, a22, a02, a01, a12, v00, v02, v10, v12, v20, v22);
-    jacobi_rotate(a11, a22, a12, a01, a02, v01, v02, v11, v12, v21, v22);
-  }
+  jacobi3(a00, a01, a02, a11, a12, a22, v00, v01, v02, v10, v11, v12, v20, v21, v22);
   // the smallest eigenvalue's column, the lowest index on ties; the other two in order
   const bool first = a00 <= a11 && a00 <= a22, second = !first && a11 <= a22;
   const double l0 = first ? a00 : (second ? a11 : a22);

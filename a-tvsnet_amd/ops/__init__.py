@@ -16,6 +16,7 @@
     tsdf      a surface from depth maps: a block-sparse TSDF volume integrated from them, a marching-tetrahedra mesh of it
     mesh      a triangle mesh rendered into cameras (nearest depth and face per pixel), depth maps occluded by such a rendering
     mesh_topology  a mesh's connected components, a selection of its faces with the vertices compacted, its edge census
+    mesh_simplify  vertex clustering: the clusters' exact sums and fixed-point quadrics, the representatives, the rewritten faces
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -55,4 +56,6 @@ from .tsdf import TSDF_MAX_DIRECTORY, TSDF_MAX_MESH_BLOCKS, TSDF_MAX_PIXEL_BLOCK
 from .mesh import MESH_RENDER_SMALL_PIXELS, depth_occlude, mesh_render      # noqa: F401
 from .mesh_topology import (MESH_CENSUS_MIN_SLOTS, MESH_CENSUS_WORDS, MESH_TOPOLOGY_MAX_FACES, mesh_components, mesh_edge_census,
     mesh_select)      # noqa: F401
+from .mesh_simplify import (MESH_PLACEMENTS, MESH_RANK_EPSILON, MESH_SIMPLIFY_MIN_SLOTS, MESH_SIMPLIFY_SOLVE_UNITS, MeshClusters,
+    mesh_cluster, mesh_cluster_faces, mesh_cluster_max_move, mesh_cluster_place, mesh_cluster_quadrics)      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 62
+#define ATVS_ABI_VERSION 63
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1403,6 +1403,88 @@ int atvs_mesh_select(const float* vertices, const void* colors, long n_vertices,
 int atvs_mesh_edge_census_scratch_size(long n_faces, long* bytes);
 int atvs_mesh_edge_census(const int* faces, long n_faces, long n_vertices, void* scratch, long scratch_bytes, long* census,
                           atvs_stream_t stream);
+
+/* A triangle mesh simplified by vertex clustering (Rossignac and Borrel) with each cluster's representative placed by its quadric
+ * (Lindstrom): ops/mesh_simplify.py, atvsnet/simplify_mesh.py, csrc/mesh_simplify.hip; DESIGN.md section 10.3d.  Pointers are device
+ * pointers except origin (HOST, 3 finite doubles).  Integer atomics only, no float atomics: every output is a function of the inputs
+ * alone, bit for bit on every run.  No host synchronisation, no allocation; scratch is the caller's.
+ * tests/mesh_simplify_restated.py restates the definitions in numpy.  vertices (n_vertices,3) float32, colors (n_vertices,3) uint8 or
+ * null, faces (n_faces,3) int32, cell a double > 0 (else, or with an origin that is not finite, ATVS_ERR_ARG); n_vertices in 0..2^30,
+ * n_faces in 0..ATVS_MESH_TOPOLOGY_MAX_FACES, anything else ATVS_ERR_SHAPE, as is a short scratch; a null pointer that is needed
+ * ATVS_ERR_NULL; all without a launch.
+ *
+ * atvs_mesh_cluster.  The clusters are atvs_cloud_voxel_downsample's voxels: per axis, in double, g = ((double)x - origin) / cell,
+ * c = floor(g), u = (uint64)floor((g - c) 2^32) clamped to 2^32 - 1.  A cluster is a triple c; ids 0..C-1 in ascending order of the
+ * cluster's lowest vertex index.  vertex_cluster (n_vertices,) int32: the id, -1 for a vertex with a non-finite coordinate (it forms
+ * no cluster).  All finite vertices count, whether a face names them or not.  Per cluster, in rows of buffers of n_vertices rows of
+ * which the first C are written: cells (.,3) int32 the triple c, counts (.,) int32 the number k of its vertices, position_sums (.,3)
+ * the exact unsigned 64-bit sums of u, color_sums (.,3) the integer sums of the colours (not written with colors null).  count: one
+ * int64, C -- or -1 when a finite vertex's c leaves [0, 2^21) (no other output is defined then).  scratch:
+ * atvs_mesh_cluster_scratch_size(n_vertices) bytes: a table of the smallest power of two of slots that is at least 2 n_vertices and
+ * at least 1024, 64 bytes each, and 8 bytes per vertex.
+ *
+ * atvs_mesh_cluster_quadrics.  quadrics (n_clusters,10) int64 and incidences (n_clusters,) int32, both zeroed here.  A face
+ * contributes only if its three vertices are finite (vertex_cluster >= 0) and m = (b - a) x (c - a) has L2 = m.m > 0 and finite;
+ * differences are of (double) coordinates, products then additions, (m0 m0 + m1 m1) + m2 m2.  For such a face n = m / sqrt(L2) and
+ * w = min(1, sqrt(L2) / (cell cell)): area weighting that saturates for a triangle larger than a cell, which keeps every term in
+ * [-1, 1].  The face contributes once to each DISTINCT cluster K among its three: with the face's first vertex (in a, b, c order)
+ * that lies in K, p = (g - c) - 0.5 per axis (cell units about the cell's centre), d = -((n0 p0 + n1 p1) + n2 p2), the ten terms
+ * w n0 n0, w n0 n1, w n0 n2, w n1 n1, w n1 n2, w n2 n2, w d n0, w d n1, w d n2, w d d -- each ((w x) y) -- are rounded to integers as
+ * rint(term 2^30) and added with 64-bit integer atomics; incidences[K] += 1.  At most 3 x 2^28 incidences: no sum reaches 2^60.
+ * Zero-area faces and faces with repeated indices add nothing (L2 = 0).  info: one int32, the number of faces with an index outside
+ * 0..n_vertices-1 or a vertex_cluster outside -1..n_clusters-1 (skipped; no output is defined unless it is 0).
+ *
+ * atvs_mesh_cluster_place.  One lane per cluster, everything in double, in cell units about the cell's centre.  The sums are INPUTS
+ * (cells, counts, position_sums, color_sums or null, quadrics; quadrics may be null with placement 0).  x0_a = ((double)S_a /
+ * (double)k) / 2^32 - 0.5, the exact mean.  placement ATVS_MESH_PLACE_MEAN ends there.  ATVS_MESH_PLACE_QUADRIC: A (symmetric, from
+ * sums 0..5) and b (sums 6..8) are (double)sum x 2^-30; A is eigen-decomposed by the fixed 18-rotation Jacobi of atvs_cloud_normals
+ * (csrc/jacobi3.h), eigenvalue i on the diagonal and its vector in column i; lambda_max is the largest of the three;
+ * g_a = ((A_a0 x0_0 + A_a1 x0_1) + A_a2 x0_2) + b_a; then for i = 0, 1, 2 in turn, where lambda_i > rank_epsilon lambda_max,
+ * t = ((v_0i g_0 + v_1i g_1) + v_2i g_2) / lambda_i and x_a = x_a - v_ai t (x starts at x0).  The cluster falls back to x0 when
+ * lambda_max <= 2^-20 (a cluster of slivers only), a value is not finite, or any |x_a| > 0.5 (the minimiser leaves the cell:
+ * Lindstrom's rule).  positions (n_clusters,3) float32: origin_a + cell (((double)c_a + 0.5) + x_a), rounded once.  colors_out
+ * (n_clusters,3) uint8 (with color_sums): (2 S + k) / (2 k) in integers.  placed (n_clusters,) uint8: 1 where the quadric position
+ * was used.  rank_epsilon: a double in (0, 1) (else ATVS_ERR_ARG); 1e-3 is Lindstrom's value, a default and not a measurement.  Both
+ * placements keep a representative inside its cell, so no vertex moves farther than cell sqrt(3).
+ *     The solve's allowance: the Jacobi commits a backward error of at most 128 units of 2^-53 |A| (atvs_cloud_normals' S); on the
+ * kept eigenpairs the inverse is at most 1 / (rank_epsilon lambda_max), and |x - x0| <= sqrt(3) inside the cell, so the
+ * decomposition moves x by at most 128 sqrt(3) < 222 units of 2^-53 / rank_epsilon.  g costs 6 roundings per row on terms of at most
+ * |A| |x0| + |b| <= (0.87 + 3 x 0.87) lambda_max (|b| <= trace(A) sqrt(3) / 2): under 21 units; the three projections and updates
+ * (5 + 1 + 2 roundings each on |g| / lambda_i) add under 8 x 3 x 3.5 = 84 more.  Under 327 in all; the header states
+ * ATVS_MESH_SIMPLIFY_SOLVE_UNITS = 512 units of 2^-53 / rank_epsilon, in cell units: 5.7e-11 cells at 1e-3, against 9.3e-10 = 2^-30.
+ *
+ * atvs_mesh_cluster_max_move.  out: one uint32, zeroed here, then the integer atomic max over the finite vertices of the bits of
+ * (float)((e0 e0 + e1 e1) + e2 e2), e_a = (double)positions[vertex_cluster][a] - (double)vertices[a] (a non-negative float's bits
+ * order as its value): the largest squared move.
+ *
+ * atvs_mesh_cluster_faces.  faces_out (n_faces,3) int32: a face rewritten to its three cluster ids (-1 for a non-finite vertex;
+ * -1, -1, -1 for a face counted in info[0]).  keep (n_faces,) uint8: 0 when the face names a non-finite vertex (info[1],
+ * nonfinite_faces), else when two ids are equal (info[2], degenerate_faces), else when a face with a lower index that got this far
+ * has the same SET of three ids (info[3], duplicate_faces): the lowest index of each set stays, with its own winding; else 1.
+ * info: four int32; info[0] = faces with an index outside 0..n_vertices-1 plus faces that found no slot (impossible at the table's
+ * load); no output is defined unless it is 0.  scratch: atvs_mesh_cluster_faces_scratch_size(n_faces) bytes: an open-addressing
+ * table of the smallest power of two of slots that is at least 2 n_faces and at least ATVS_MESH_SIMPLIFY_MIN_SLOTS, 4 bytes each (a
+ * slot holds a face index; load at most 0.5; every probe loop is bounded by the table), and 4 bytes per face.  atvs_mesh_select
+ * then compacts positions and faces_out by keep: surviving faces keep their order and surviving clusters theirs. */
+#define ATVS_MESH_SIMPLIFY_MIN_SLOTS 1024
+#define ATVS_MESH_SIMPLIFY_SOLVE_UNITS 512
+#define ATVS_MESH_PLACE_MEAN 0
+#define ATVS_MESH_PLACE_QUADRIC 1
+int atvs_mesh_cluster_scratch_size(long n_vertices, long* bytes);
+int atvs_mesh_cluster(const float* vertices, const void* colors, long n_vertices, double cell, const double* origin, void* scratch,
+                      long scratch_bytes, int* vertex_cluster, int* cells, int* counts, long* position_sums, long* color_sums,
+                      long* count, atvs_stream_t stream);
+int atvs_mesh_cluster_quadrics(const float* vertices, long n_vertices, const int* faces, long n_faces, const int* vertex_cluster,
+                               long n_clusters, double cell, const double* origin, long* quadrics, int* incidences, int* info,
+                               atvs_stream_t stream);
+int atvs_mesh_cluster_place(const int* cells, const int* counts, const long* position_sums, const long* color_sums,
+                            const long* quadrics, long n_clusters, double cell, const double* origin, int placement,
+                            double rank_epsilon, float* positions, void* colors_out, void* placed, atvs_stream_t stream);
+int atvs_mesh_cluster_max_move(const float* vertices, long n_vertices, const int* vertex_cluster, const float* positions,
+                               long n_clusters, void* out, atvs_stream_t stream);
+int atvs_mesh_cluster_faces_scratch_size(long n_faces, long* bytes);
+int atvs_mesh_cluster_faces(const int* faces, long n_faces, long n_vertices, const int* vertex_cluster, void* scratch,
+                            long scratch_bytes, int* faces_out, void* keep, int* info, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
