@@ -65,7 +65,7 @@ int atvs_get_homographies(const float* left_cam, const float* right_cam, const f
  *   planar != 0 (mode 0 or 1, C in {16, 32, 64}, ld_out == C, c_off == 0): out is written chunk-planar,
  *           [C/8] planes of [D][h][w][8], `planar` floats apart (>= D*h*w*8; pad it so that the planes do not start
  *           on the same HBM channel) -- the layout atvs_conv_xw_f32 / _xb_f32 read with x_planar (dense 32-byte
- *           voxels per 8-channel chunk); same values, another place.
+ *           voxels per 8-channel chunk); same values, another place.  The pad between the planes is never written.
  *   pieces != 0 (with planar): every value is written as its two fp16 pieces, h0 = fp16(x), h1 = fp16((x - h0) * 2048) -- the
  *           operand split of the split-operand convolutions, done once by the producer: a chunk plane then holds
  *           [2 pieces][D][h][w][8 fp16] (the same D*h*w*32 bytes), which atvs_conv_xb_f32 reads with x_pieces and stages

@@ -16,6 +16,7 @@ A row holds
     outputs, scratch   pieces of the source lines that allocate them: at least one guarded allocation must match each (scratch:
                 only where the call launches, `launches(p)`)
     writable    the inputs the op rewrites in place
+    slices(p)   -> {input name: what of it the op may write, a bool mask or (lo, hi) of the last axis}: every other element is held
     excluded    what the selection leaves out, each with the line of include/atvsnet_hip.h that allows it
 
 Where the header specifies a whole buffer of which the wrapper returns a slice (the 16 tolerance counters, the component counts),
@@ -48,13 +49,16 @@ ROWS = collections.OrderedDict()
 
 class Row(object):
     def __init__(self, name, entries, sizes, build, shapes, run, select, names, outputs, scratch=(), launches=None, writable=(),
-                 excluded=(), constants=''):
+                 excluded=(), constants='', slices=None, table=None):
         self.name, self.entries, self.sizes, self.build, self.shapes, self.run, self.select = name, tuple(entries), sizes, build, shapes, run, select
-        self.names, self.outputs, self.scratch, self.writable, self.excluded = tuple(names), tuple(outputs), tuple(scratch), tuple(writable), tuple(excluded)
+        self.names, self.scratch, self.writable, self.excluded = tuple(names), tuple(scratch), tuple(writable), tuple(excluded)
+        self.outputs = outputs if callable(outputs) else tuple(outputs)      # (a function of the size's parameters in the network table)
         self.launches = launches or (lambda p: True)
         self.constants = constants
-        assert name not in ROWS
-        ROWS[name] = self
+        self.slices = slices or (lambda p: {})      # slices(p) -> {input name: bool mask | (lo, hi) of the last axis}: what the op may write
+        table = ROWS if table is None else table    # (tests/network_contract_rows.py registers in a table of its own)
+        assert name not in table
+        table[name] = self
 
     def required(self, size):
         """The entry points this size must reach."""
@@ -827,8 +831,4 @@ Row('fusion_support', ('atvs_fusion_support',), FUSION_SIZES, _fusion_inputs, _f
 
 
 # ----------------------------------------------------------------------------------------------------- what no row covers, and why
-NETWORK = 'a network-side kernel declared behind the fusion section: poisoned by its own tests, runs inside captured graphs'
-EXCLUDED_ENTRY_POINTS = {
-    'atvs_deconv_up_pack': NETWORK, 'atvs_deconv_up_f32': NETWORK, 'atvs_conv_c16_pack': NETWORK, 'atvs_conv_c16_f32': NETWORK,
-    'atvs_conv_c16b_pack': NETWORK, 'atvs_conv_c16b_f32': NETWORK, 'atvs_conv_c16b_sum_f32': NETWORK,
-}
+EXCLUDED_ENTRY_POINTS = {}           # nothing: the network side, once listed here, has its own table (tests/network_contract_rows.py)

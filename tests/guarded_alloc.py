@@ -15,6 +15,25 @@ into another allocation in between.
 
 `recording_lib()` puts a proxy in front of the loaded library that notes the name of each entry point called.
 `run_contract(...)` is the three-run comparison (plain, fill 0x00, fill 0xFF) both test files share.
+
+Three additions serve the network side (tests/network_contract_rows.py, tests/test_gpu_network_contract.py):
+
+Slice masks.  Many network ops write a channel range of a caller's wider buffer.  `place(t, writable=<bool mask | (lo, hi) of the
+last axis>)` remembers the bits of every element the op may NOT write; `check()` reports such an element that changed with its flat
+index.  The buffer must hold a position-dependent pattern (the rows' `ramp`): a kernel that copies a neighbour's value over a
+neighbour then still changes it.
+
+Arranged weights.  ops/packing.py packs on the host and uploads with `.to(device)`, which no patch of torch.empty sees.
+`weights_under(place, **switches)` is `ops.configure(clear_pack_cache=True, **switches)` in which every `_Packed.wp` / `.tab` that a
+packer assigns becomes `place(...)` of it, so the launch reads its weights from a guarded allocation whose next byte is the
+pattern: a read-ahead beyond "one zero chunk behind the last" meets pattern bytes, which differ from what the plain run's
+allocator holds there, and a store meets the guard.  The caches are cleared on entry and on exit and asserted empty afterwards.
+
+Pooled device words.  ops.nonfinite_flag, _fin_counter, _side_stream and prepare_workspace make a device buffer on first use and
+KEEP it.  Made inside a guarded block it would be a payload of that block: a 0xFF-filled flag word that the next test reads as
+"a non-finite moment was seen", and memory that is released with the block while the pool still points into it.  So
+`run_contract(warm=...)` touches the pools before the first run, and `pools=` (-> [(name, tensor)]) is asserted inside every block,
+before the guards are dropped, to hold no tensor whose address lies in one of the block's buffers (`guarded.owns`).
 """
 import collections
 import contextlib
@@ -67,7 +86,7 @@ def bits(t):
 
 
 class _Buffer(object):
-    __slots__ = ('raw', 'start', 'nbytes', 'guard', 'payload', 'record', 'kept')
+    __slots__ = ('raw', 'start', 'nbytes', 'guard', 'payload', 'record', 'kept', 'mask')
 
 
 class guarded(object):
@@ -168,22 +187,32 @@ class guarded(object):
         assert b.payload.is_contiguous() and b.payload.data_ptr() % ALIGN == 0
         name, line, function, text = site or _site()
         b.record = Allocation(name, line, function + ': ' + text, nbytes, kind, shape, dtype)
-        b.kept = None
+        b.kept = b.mask = None
         self.allocations.append(b.record)
         self._buffers.append(b)
         return b.payload
 
     def place(self, t, writable=False):
         """A copy of `t` inside a guarded allocation of this block's device.  Its bits are remembered: check() reports a placed
-        input that changed, unless `writable` (an operand the op rewrites in place: only its guards are held)."""
+        input that changed, unless `writable` is True (an operand the op rewrites in place: only its guards are held).
+        writable = a bool tensor of t's shape (True: the op may write the element), or (lo, hi): the op may write [..., lo:hi] of
+        the last axis and nothing else -- check() reports every other element that changed."""
         if not self._active:
             raise RuntimeError('place() outside the guarded block')
         src = t.detach().contiguous()
         out = self._allocate(tuple(src.shape), src.dtype, 'input', _site())
         out.copy_(src)
-        if not writable:
-            self._buffers[-1].kept = _ORIGINAL['empty'](tuple(src.shape), dtype=src.dtype, device=self.device).copy_(src)
+        b = self._buffers[-1]
+        if writable is not True:
+            b.kept = _ORIGINAL['empty'](tuple(src.shape), dtype=src.dtype, device=self.device).copy_(src)
+        if writable is not True and writable is not False:
+            b.mask = writable_mask(writable, tuple(src.shape)).to(self.device)
         return out
+
+    def owns(self, t):
+        """Does the tensor's first byte lie inside one of this block's buffers (guards included)?"""
+        a = t.data_ptr()
+        return any(b.raw.data_ptr() <= a < b.raw.data_ptr() + b.raw.numel() for b in self._buffers)
 
     # ------------------------------------------------------------------------------------------------------------ checking
     def check(self):
@@ -198,7 +227,7 @@ class guarded(object):
             lo, hi = b.start - b.guard, b.start + _round_up(b.nbytes) + b.guard
             flags.append((b.raw[lo:b.start] != pattern(lo, b.start, self.device)).any())
             flags.append((b.raw[b.start + b.nbytes:hi] != pattern(b.start + b.nbytes, hi, self.device)).any())
-            same = torch.tensor(True, device=self.device) if b.kept is None else _same_bits_device(b.payload, b.kept)
+            same = torch.tensor(True, device=self.device) if b.kept is None else _same_bits_device(b.payload, b.kept, b.mask)
             flags.append(~same)
         flags = torch.stack(flags).cpu().reshape(-1, 3).tolist()
         found = []
@@ -216,8 +245,12 @@ class guarded(object):
                 where = 'in the round-up tail' if last < _round_up(b.nbytes) else 'past the 256-byte round-up'
                 found.append('%s: %d bytes AFTER the payload changed (%s), offsets %d .. %d' % (what, len(bad), where, first, last))
             if changed:
-                diff = torch.nonzero(bits(b.payload).reshape(-1) != bits(b.kept).reshape(-1)).reshape(-1)
-                found.append('%s: the placed INPUT changed, %d elements, first %d' % (what, len(diff), int(diff[0])))
+                ne = bits(b.payload).reshape(-1) != bits(b.kept).reshape(-1)
+                if b.mask is not None:
+                    ne &= ~b.mask.reshape(-1).cpu()
+                diff = torch.nonzero(ne).reshape(-1)
+                found.append('%s: %s, %d elements, first %d' % (what, 'the placed INPUT changed' if b.mask is None else
+                                                               'elements OUTSIDE the writable slice changed', len(diff), int(diff[0])))
         if found:
             raise AssertionError('%d buffer violations:\n  %s' % (len(found), '\n  '.join(found)))
 
@@ -231,11 +264,29 @@ class guarded(object):
         return len(mine), sum(a.nbytes for a in mine)
 
 
-def _same_bits_device(a, b):
-    a, b = a.contiguous().reshape(-1), b.contiguous().reshape(-1)
+def _same_bits_device(a, b, mask=None):
+    """Do a and b hold the same bits -- with `mask` (True: writable), wherever the mask is False?"""
     if a.numel() == 0:
         return torch.tensor(True, device=a.device)
-    return (a.view(torch.uint8) == b.view(torch.uint8)).all()
+    item = a.element_size()
+    same = a.contiguous().reshape(-1).view(torch.uint8) == b.contiguous().reshape(-1).view(torch.uint8)
+    if mask is not None:
+        same = same.reshape(-1, item) | mask.reshape(-1, 1)
+    return same.all()
+
+
+def writable_mask(spec, shape):
+    """A bool tensor of `shape`, True where the op may write: spec is such a tensor, or (lo, hi) of the last axis."""
+    if isinstance(spec, torch.Tensor):
+        if spec.dtype != torch.bool or tuple(spec.shape) != tuple(shape):
+            raise ValueError('a writable mask is a bool tensor of the placed tensor\'s shape %s, got %s %s' % (shape, spec.dtype, tuple(spec.shape)))
+        return spec.contiguous()
+    lo, hi = spec
+    if not 0 <= lo <= hi <= shape[-1]:
+        raise ValueError('writable range %s of a last axis of %d' % ((lo, hi), shape[-1]))
+    m = _ORIGINAL['zeros'](shape, dtype=torch.bool)           # (the original: a mask is no allocation of the op under test)
+    m[..., lo:hi] = True
+    return m
 
 
 # ----------------------------------------------------------------------------------------------------------------- the library
@@ -306,19 +357,65 @@ def assert_same_bits(runs, names, what=''):
 Contract = collections.namedtuple('Contract', 'guards selected')
 
 
-def run_contract(run, inputs, select, device, names=(), writable=(), fills=(0x00, 0xFF), what=''):
+def _identity(t, **kw):
+    return t
+
+
+@contextlib.contextmanager
+def _no_weights(place):
+    yield
+
+
+@contextlib.contextmanager
+def weights_under(place, ops=None, **switches):
+    """`ops.configure(clear_pack_cache=True, **switches)` in which every arranged-weight tensor a packer assigns to a `_Packed`
+    (`pk.wp`, `pk.tab`) is replaced by `place(...)` of it: with the guard's place, the launch reads its weights from a guarded
+    allocation.  With place None (the plain run) only the switches and the fresh caches remain.  No arranged form may stay in the
+    four caches after the block."""
+    if ops is None:
+        from atvsnet_amd import ops
+    packed = ops._Packed
+    caches = (ops._pack_cache, ops._fold_cache, ops._virt_cache, ops._xp_cache)
+
+    def set_placed(self, name, value):
+        if name in ('wp', 'tab') and isinstance(value, torch.Tensor) and value.device.type != 'meta':
+            value = place(value)
+        object.__setattr__(self, name, value)
+    with ops.configure(clear_pack_cache=True, **switches):
+        assert not any(caches), 'the arranged-weight caches were not cleared on entry'
+        if place is not None:
+            assert '__setattr__' not in vars(packed)
+            packed.__setattr__ = set_placed
+        try:
+            yield
+        finally:
+            if place is not None:
+                del packed.__setattr__
+    left = [len(c) for c in caches]
+    assert not any(left), 'arranged weights stayed in the caches after the block (pack, fold, virt, xp): %s' % left
+
+
+def run_contract(run, inputs, select, device, names=(), writable=(), fills=(0x00, 0xFF), what='', warm=None, pools=None,
+                 around=_no_weights):
     """The contract of one op at one input.  inputs: {name: CPU tensor or anything else}; run(d, place) -> result with d = the
     inputs on `device` (tensors moved, the rest as it is) and place = the guard's place (the identity in the plain run);
     select(result) -> [tensor or None, ...], the specified part of the result.  Runs plain, then under guarded(fill) for each
-    fill with every tensor input placed (`writable`: the names the op rewrites in place).  Asserts that no guard, tail or input
-    changed and that the selections have the same bits in every run.  -> Contract(guards = {fill: the guard}, selected = the plain
-    run's selection on the CPU) for the caller's own assertions."""
-    def on_device(place, writable_place):
+    fill with every tensor input placed.  writable: the names the op rewrites in place, or {name: True | bool mask | (lo, hi) of
+    the last axis}: what of that input the op may write (`place`).  Asserts that no guard, tail, input or masked element changed
+    and that the selections have the same bits in every run.
+    warm(): called once before the first run, to make every pooled device buffer the op keeps (a flag word, a counter pool)
+    outside the blocks.  pools() -> [(name, tensor)]: asserted inside every block, before its buffers are dropped, to hold no
+    tensor of the block.  around(place): a context manager around each of the three runs (place None in the plain one), e.g.
+    `weights_under`.
+    -> Contract(guards = {fill: the guard}, selected = the plain run's selection on the CPU) for the caller's own assertions."""
+    if not isinstance(writable, dict):
+        writable = {k: True for k in writable}
+
+    def on_device(place):
         d = {}
         for k, v in inputs.items():
             if isinstance(v, torch.Tensor):
-                v = v.to(device)
-                v = writable_place(v) if k in writable else place(v)
+                v = place(v.to(device), writable=writable.get(k, False))
             d[k] = v
         return d
 
@@ -327,18 +424,25 @@ def run_contract(run, inputs, select, device, names=(), writable=(), fills=(0x00
 
     def clone(t, **kw):                   # the plain run works on a copy: `inputs` may live on `device` already
         return t.clone()
+    if warm is not None:
+        warm()
     runs = collections.OrderedDict()
-    runs['plain'] = keep(select(run(on_device(clone, clone), lambda t, **kw: t)))
+    with around(None):
+        runs['plain'] = keep(select(run(on_device(clone), _identity)))
     guards = {}
     violations = []
     for fill in fills:
         with guarded(device, fill) as g:
-            d = on_device(g.place, lambda t: g.place(t, writable=True))
-            runs['fill 0x%02X' % fill] = keep(select(run(d, g.place)))
-            try:
-                g.check()
-            except AssertionError as e:
-                violations.append('fill 0x%02X: %s' % (fill, e))
+            with around(g.place):
+                d = on_device(g.place)
+                runs['fill 0x%02X' % fill] = keep(select(run(d, g.place)))
+                try:
+                    g.check()
+                except AssertionError as e:
+                    violations.append('fill 0x%02X: %s' % (fill, e))
+            leaked = [name for name, t in (pools() if pools is not None else ()) if g.owns(t)]
+            if leaked:
+                violations.append('fill 0x%02X: pooled buffers made inside the guarded block, which outlive it: %s' % (fill, ', '.join(leaked)))
             guards[fill] = g
     if violations:
         raise AssertionError('%s: %s' % (what, '\n'.join(violations)))

@@ -1,6 +1,6 @@
 """tests/buffer_contract_rows.py is complete and its builders do what they state, without a GPU: every entry point that
-include/atvsnet_hip.h declares from atvs_fusibile onwards and that writes through a pointer or takes scratch is named by a row (or
-by the explicit exclusion list, with its reason), every *_scratch_size query sits in a row beside its partner, every row names a
+include/atvsnet_hip.h declares from atvs_fusibile onwards and that writes through a pointer or takes scratch is named by a row (the
+seven network-side kernels declared behind that line by a row of tests/network_contract_rows.py: there is no exclusion list), every *_scratch_size query sits in a row beside its partner, every row names a
 size that reaches each of its entry points, and every builder returns inputs of the stated shapes and dtypes, the same ones twice."""
 import inspect
 import re
@@ -12,6 +12,7 @@ import atvsnet_amd  # noqa: F401
 from atvsnet_amd import _lib
 
 import buffer_contract_rows as BR
+import network_contract_rows as NR
 
 FIRST = 'atvs_fusibile'
 QUERIES = ('_size', '_supported', '_grid')
@@ -49,21 +50,21 @@ def _named():
 def test_the_scope_begins_where_the_issue_says_and_is_not_empty():
     scope = [n for n, _ in _in_scope()]
     assert scope[0] == FIRST and len(scope) > 80
-    assert 'atvs_mesh_cluster_faces' in scope and 'atvs_cloud_grid_build' in scope and 'atvs_conv3d_b_f32' not in scope
+    assert 'atvs_mesh_cluster_faces' in scope and 'atvs_cloud_grid_build' in scope
+    assert any('atvs_conv3d_b_f32' in row.entries for row in NR.ROWS.values())          # is in the network table
 
 
-def test_every_entry_point_that_writes_is_in_a_row_or_excluded_with_a_reason():
+def test_every_entry_point_that_writes_is_in_a_row_and_nothing_is_excluded():
     named = _named()
+    network = set(e for row in NR.ROWS.values() for e in row.entries)
     writers = [n for n, params in _in_scope() if _writes(params) and not n.endswith(QUERIES)]
     assert len(writers) > 50
-    uncovered = [n for n in writers if n not in named and n not in BR.EXCLUDED_ENTRY_POINTS]
-    assert not uncovered, 'no row of tests/buffer_contract_rows.py names %s' % uncovered
-    for n, reason in BR.EXCLUDED_ENTRY_POINTS.items():
-        assert n in writers, '%s is excluded but is no in-scope entry point that writes' % n
-        assert n not in named, '%s is both excluded and named by a row' % n
-        assert len(reason) > 20
-    # the exclusions are the network side alone: nothing of the geometry families is excluded
-    assert all(re.match(r'atvs_(deconv_up|conv_c16b?)_', n) for n in BR.EXCLUDED_ENTRY_POINTS)
+    behind = [n for n in writers if n not in named]            # the network-side kernels declared behind atvs_fusibile, and their packers
+    assert all(re.match(r'atvs_(deconv_up|conv_c16b?)_', n) for n in behind), 'no row of tests/buffer_contract_rows.py names %s' % behind
+    uncovered = [n for n in behind if n not in network and not n.endswith('_pack')]
+    assert not uncovered, 'no row of tests/network_contract_rows.py names %s' % uncovered
+    # there are no exclusions
+    assert BR.EXCLUDED_ENTRY_POINTS == {}
 
 
 def test_every_name_a_row_uses_is_declared():

@@ -287,3 +287,164 @@ def test_the_recording_proxy_notes_entry_points_and_restores_the_module():
             assert calls == ['atvs_one', 'atvs_two', 'atvs_one']
             raise KeyError('x')
     assert module.lib is original
+
+
+# ------------------------------------------------------------------------------------------------------------- slice masks
+def _pattern_rows(rows=6, ld=8):
+    return (torch.arange(rows * ld, dtype=torch.float32) * 1.25 + 0.5).reshape(rows, ld)
+
+
+def _writes_slice(lo, hi, stray=None):
+    """A fake op that writes out[:, lo:hi] = 2 x, and then what `stray` does to the buffer."""
+    def op(d, place):
+        d['out'][:, lo:hi] = 2.0 * d['x']
+        if stray is not None:
+            stray(d['out'])
+        return d['out']
+    return op
+
+
+SLICE = {'x': torch.arange(18, dtype=torch.float32).reshape(6, 3) + 100.0, 'out': _pattern_rows()}
+
+
+def test_a_channel_slice_may_be_written_and_nothing_else():
+    done = GA.run_contract(_writes_slice(2, 5), SLICE, lambda r: [r], CPU, names=('out',), writable={'out': (2, 5)})
+    assert torch.equal(done.selected[0][:, 2:5], 2.0 * SLICE['x']) and torch.equal(done.selected[0][:, :2], SLICE['out'][:, :2])
+    mask = torch.zeros(6, 8, dtype=torch.bool)
+    mask[:, 2:5] = True
+    GA.run_contract(_writes_slice(2, 5), SLICE, lambda r: [r], CPU, writable={'out': mask})
+    with pytest.raises(AssertionError, match='placed INPUT changed'):                          # not writable at all
+        GA.run_contract(_writes_slice(2, 5), SLICE, lambda r: [r], CPU)
+    with pytest.raises(ValueError, match='writable range'):
+        GA.run_contract(_writes_slice(2, 5), SLICE, lambda r: [r], CPU, writable={'out': (2, 9)})
+    with pytest.raises(ValueError, match='bool tensor'):
+        GA.run_contract(_writes_slice(2, 5), SLICE, lambda r: [r], CPU, writable={'out': mask[:3]})
+
+
+def test_one_float_beyond_the_channel_range_is_named_with_its_flat_index():
+    def beyond(out):
+        out[3, 5] = -1.0                                             # channel 5 of row 3: flat index 29
+    with pytest.raises(AssertionError, match=r'elements OUTSIDE the writable slice changed, 1 elements, first 29') as e:
+        GA.run_contract(_writes_slice(2, 5, beyond), SLICE, lambda r: [r], CPU, writable={'out': (2, 5)}, what='beyond')
+    assert 'fill 0x00' in str(e.value) and 'fill 0xFF' in str(e.value) and str(e.value).count('buffer violations') == 2
+
+
+def test_the_last_channel_of_the_previous_pixel_is_named():
+    def previous(out):
+        out[4, 7] = out[4, 7] + 1.0                                  # an offset one too small at c_off = 0 of the next row
+    with pytest.raises(AssertionError, match=r'OUTSIDE the writable slice changed, 1 elements, first 39'):
+        GA.run_contract(_writes_slice(0, 3, previous), SLICE, lambda r: [r], CPU, writable={'out': (0, 3)})
+
+
+def test_a_neighbour_copied_over_a_neighbour_is_seen_because_the_buffer_is_no_constant():
+    def smear(out):
+        out[:, 5] = out[:, 6]                                        # the kernel stores the value next door
+    with pytest.raises(AssertionError, match='OUTSIDE the writable slice changed, 6 elements, first 5'):
+        GA.run_contract(_writes_slice(2, 5, smear), SLICE, lambda r: [r], CPU, writable={'out': (2, 5)})
+    constant = dict(SLICE, out=torch.full((6, 8), 3.0))
+    GA.run_contract(_writes_slice(2, 5, smear), constant, lambda r: [r], CPU, writable={'out': (2, 5)})     # ... which a constant buffer hides
+
+
+def test_a_masked_violation_is_listed_with_the_guards_in_one_error():
+    with GA.guarded(CPU, 0x00) as g:
+        out = g.place(_pattern_rows(), writable=(0, 4))
+        out[:, :4] = 0.0
+        g.check()
+        out[1, 4] = 9.0
+        _poke(out.data_ptr() + out.numel() * 4)
+        text = _violations(g)
+    assert '2 buffer violations' in text and 'AFTER' in text and 'OUTSIDE the writable slice changed, 1 elements, first 12' in text
+
+
+# --------------------------------------------------------------------------------------------- arranged weights under the guard
+def _fake_packer(ops, key, values):
+    """What ops/packing.py does: pack on the host, upload, cache -- with "one zero element behind the last" as the packers end."""
+    pk = ops._pack_cache.get(key)
+    if pk is None:
+        whole = torch.cat([values, torch.zeros(1)])
+        pk = ops._Packed(key=key)
+        pk.wp = whole[:len(values)]
+        ops._pack_cache[key] = pk
+    return pk
+
+
+def _conv_like(read_ahead, store=False):
+    def op(d, place):
+        from atvsnet_amd import ops
+        pk = _fake_packer(ops, 'fake', torch.arange(1.0, 5.0))
+        n = pk.wp.numel() + (1 if read_ahead else 0)
+        w = torch.tensor((ctypes.c_float * n).from_address(pk.wp.data_ptr())[:])        # the kernel's own walk over the buffer
+        if store:
+            pk.wp[0] = 7.0
+        out = torch.empty(1)
+        out[0] = float((w * w).sum()) + float(d['x'].sum())
+        return out
+    return op
+
+
+def _weights(place):
+    from atvsnet_amd import ops
+    return GA.weights_under(place, ops)
+
+
+def test_arranged_weights_are_placed_and_a_read_ahead_beyond_them_is_caught():
+    from atvsnet_amd import ops
+    done = GA.run_contract(_conv_like(False), X, lambda r: [r], CPU, names=('out',), around=_weights)
+    assert float(done.selected[0]) == 30.0 + float(X['x'].sum())
+    for g in done.guards.values():
+        placed = [a for a in g.allocations if a.kind == 'input' and '_fake_packer' in a.code]
+        assert len(placed) == 1 and placed[0].nbytes == 16 and 'pk.wp = ' in placed[0].code
+    assert not ops._pack_cache and '__setattr__' not in vars(ops._Packed)
+    # the zero behind the last weight is not part of the buffer the launch is given: under the guard the next bytes are the pattern
+    with pytest.raises(AssertionError, match=r'(?s)the runs differ.*out differs from plain'):
+        GA.run_contract(_conv_like(True), X, lambda r: [r], CPU, names=('out',), around=_weights)
+    GA.run_contract(_conv_like(True), X, lambda r: [r], CPU, names=('out',))                  # without the placement nothing is seen
+    ops.clear_pack_cache()
+    with pytest.raises(AssertionError, match='placed INPUT changed, 1 elements, first 0'):     # a kernel that stores into its weights
+        GA.run_contract(_conv_like(False, store=True), X, lambda r: [r], CPU, around=_weights)
+    assert not ops._pack_cache and '__setattr__' not in vars(ops._Packed)
+
+
+def test_each_run_starts_from_empty_caches_and_no_guarded_payload_stays_in_them():
+    from atvsnet_amd import ops
+    ops._pack_cache['stale'] = ops._Packed(key='stale')
+    ops._fold_cache['stale'] = ops._xp_cache['stale'] = ops._virt_cache['stale'] = 1
+    with GA.guarded(CPU, 0xFF) as g:
+        with GA.weights_under(g.place, ops, split16=False):
+            assert not (ops._pack_cache or ops._fold_cache or ops._xp_cache or ops._virt_cache) and not ops.cfg.split16
+            pk = _fake_packer(ops, 'k', torch.arange(3.0))
+            assert g.owns(pk.wp) and pk.wp.tolist() == [0.0, 1.0, 2.0] and ops._pack_cache['k'] is pk
+            pk.ntaps = 27                                            # any other field is stored as it is
+            kept = pk
+        assert not ops._pack_cache and ops.cfg.split16 == ops.Config._DEFAULTS['split16']
+        assert g.owns(kept.wp)                                       # only a reference the caller kept still points into the block
+        g.check()
+    with pytest.raises(AttributeError):
+        with GA.weights_under(None, ops, no_such_switch=True):
+            pass
+    assert '__setattr__' not in vars(ops._Packed)
+
+
+# ------------------------------------------------------------------------------------------------------ pooled device words
+def test_a_pooled_buffer_made_inside_a_guarded_block_is_reported_and_a_warmed_one_is_not():
+    pool = {}
+
+    def flag():
+        if 'flag' not in pool:
+            pool['flag'] = torch.zeros(1, dtype=torch.int32)
+        return pool['flag']
+
+    def op(d, place):
+        out = torch.empty_like(d['x'])
+        out.copy_(d['x'] + float(flag()))
+        return out
+    with pytest.raises(AssertionError, match=r'pooled buffers made inside the guarded block, which outlive it: flag'):
+        # (the plain run makes the flag first, so drop it: the first guarded run is the one that makes it)
+        GA.run_contract(lambda d, place: (pool.clear() if place is not GA._identity else None, op(d, place))[1], X, lambda r: [r], CPU,
+                        pools=lambda: list(pool.items()), what='pool')
+    pool.clear()
+    GA.run_contract(op, X, lambda r: [r], CPU, warm=flag, pools=lambda: list(pool.items()))
+    assert pool['flag'].tolist() == [0]
+    with GA.guarded(CPU, 0xFF) as g:
+        inside, outside = torch.empty(3), GA._ORIGINAL['empty'](3)
+        assert g.owns(inside) and g.owns(inside[1:]) and not g.owns(outside)
