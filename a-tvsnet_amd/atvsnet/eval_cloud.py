@@ -9,6 +9,7 @@ distance tolerances.
            [--init_transform T.txt | --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
            [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
             [--vis_window 1] [--free_space_margin 0]]
+           [--sample_recon S] [--sample_gt S] [--sample_seed K]
 
 The top-level keys are the PLAIN precision / recall definition (the one Tanks and Temples uses): per tolerance tau, `accuracy` is
 the share of reconstruction points with a ground-truth point within tau, `completeness` the share of ground-truth points with a
@@ -39,6 +40,14 @@ registers by point-to-plane ICP over the normals the reconstruction's PLY carrie
 --register_normals target, over the ground truth's, estimated on the GPU (the reconstruction then needs none).  --voxel scores the
 voxel-down-sampled clouds (both sides), so that point density does not weight the shares.  Without these options the result is
 what it was before they existed.
+
+A triangle mesh given as --recon scores by its VERTICES: a simplified mesh then loses completeness by construction.  --sample_recon S
+samples its surface uniformly by area at spacing S on the device first (atvsnet/sample_mesh.py: one sample per S x S, every number a
+hash of --sample_seed, the face and the sample, so the same run gives the same score) and the samples are the reconstruction for
+everything above; with --register_icp plane over the source's normals the samples' face normals serve.  --sample_gt S does the same
+for every --gt file that is a mesh (a dataset whose ground truth is a surface).  A spacing of at most half the smallest tolerance is
+what DESIGN.md section 10.3e supports.  The result gains `recon_mesh` (sample_mesh's report without `seconds`) and / or `gt_mesh`
+(a list of such reports, one per sampled file, each with its `file`).
 """
 from __future__ import print_function
 
@@ -261,9 +270,50 @@ def save_matrix(path, T):
     np.savetxt(path, np.asarray(T, np.float64).reshape(4, 4), fmt='%.17g')
 
 
+def mesh_faces(path):
+    """The number of faces the header of a PLY file declares (0 without a `face` element); a file without a PLY header raises
+    ValueError.  Only the header is read."""
+    with open(path, 'rb') as f:
+        if f.readline().strip() != b'ply':
+            raise ValueError('%s: not a PLY file (no "ply" magic)' % path)
+        for _ in range(4096):
+            raw = f.readline()
+            if not raw:
+                break
+            words = raw.decode('ascii', 'replace').split()
+            if words[:1] == ['end_header']:
+                return 0
+            if words[:2] == ['element', 'face'] and len(words) == 3 and words[2].isdigit():
+                return int(words[2])
+    raise ValueError('%s: the header has no end_header' % path)
+
+
+def _spacing(value, name):
+    if isinstance(value, (bool, str, bytes)) or not (float(value) > 0.0 and np.isfinite(float(value))):
+        raise ValueError('%s must be a positive finite spacing, got %r' % (name, value))
+    return float(value)
+
+
+def sample_file(path, spacing, seed=0, normals=False, name='sample_recon'):
+    """The triangle mesh in `path` sampled at `spacing` on the current device -> (ops.MeshSamples on the device, sample_mesh's report
+    without `seconds`).  A file without faces, or with other polygons than triangles, raises ValueError."""
+    from . import sample_mesh
+    from .clean_mesh import read_mesh
+    import torch
+    if not mesh_faces(path):
+        raise ValueError('%s: %s has no faces: the option needs a triangle mesh' % (name, path))
+    vertices, colors, faces = read_mesh(path)
+    dev = torch.device('cuda', torch.cuda.current_device())
+    v = torch.from_numpy(np.ascontiguousarray(vertices, np.float32)).to(dev)
+    f = torch.from_numpy(np.ascontiguousarray(faces, np.int32)).to(dev)
+    samples, report = sample_mesh.sample_device(v, None, f, spacing=spacing, seed=seed, normals=normals)
+    report = {k: report[k] for k in sample_mesh.REPORT_KEYS if k != 'seconds'}
+    return samples, report
+
+
 def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform_path=None, distances=None,
                    init_transform_path=None, init_cameras=None, save_transform_path=None, gt_mlp_path=None,
-                   scanner_origins_path=None, **options):
+                   scanner_origins_path=None, sample_recon=None, sample_gt=None, sample_seed=None, **options):
     """`evaluate` of PLY files (tools/ply.read_ply_points): several ground-truth files are concatenated; gt_transform_path: a text
     file of 16 numbers, the 4x4 matrix row-major.  init_transform_path: the same for evaluate's init_transform; init_cameras:
     (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
@@ -274,8 +324,38 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
 
     The ETH3D-style score (evaluate's `scans`): gt_mlp_path, a MeshLab project (eval_eth3d.read_mlp) that replaces gt_paths -- each
     scan is moved by gt_transform times its own matrix (float64, rounded once) and that product's translation is its scanner's
-    origin -- or gt_paths with scanner_origins_path, a text file of one `x y z` per scan in the frame after gt_transform."""
-    if options.get('register_icp') == 'plane' and options.get('register_normals', 'source') != 'target':
+    origin -- or gt_paths with scanner_origins_path, a text file of one `x y z` per scan in the frame after gt_transform.
+
+    sample_recon: recon_path is a triangle mesh whose surface is sampled at this spacing on the device first (sample_file), with
+    sample_seed (default 0); the samples are the reconstruction for everything else, their face normals the recon_normals of
+    register_icp='plane'; the result gains `recon_mesh`.  sample_gt: the same for every file of gt_paths that has faces (at least one
+    must); the result gains `gt_mesh`, a list.  A file that is no triangle mesh, or sample_seed without either, raises ValueError."""
+    if sample_seed is not None and sample_recon is None and sample_gt is None:
+        raise ValueError('sample_seed needs sample_recon or sample_gt')
+    seed = 0 if sample_seed is None else sample_seed
+    sampled = {}
+    plane_source = options.get('register_icp') == 'plane' and options.get('register_normals', 'source') != 'target'
+    if sample_gt is not None:
+        sample_gt = _spacing(sample_gt, 'sample_gt')
+        if gt_mlp_path is not None:
+            raise ValueError('sample_gt with gt_mlp_path: a MeshLab project names laser scans, not meshes')
+        if not any(mesh_faces(p) for p in gt_paths):
+            raise ValueError('sample_gt: none of the ground-truth files is a triangle mesh')
+        sampled['gt_mesh'] = []
+
+    def read_gt(path):
+        if sample_gt is None or not mesh_faces(path):
+            return ply.read_ply_points(path)
+        samples, report = sample_file(path, sample_gt, seed, name='sample_gt')
+        sampled['gt_mesh'].append(dict(report, file=str(path)))
+        return samples.points.cpu().numpy()
+
+    if sample_recon is not None:
+        samples, sampled['recon_mesh'] = sample_file(recon_path, _spacing(sample_recon, 'sample_recon'), seed, normals=plane_source)
+        recon = samples.points
+        if plane_source:
+            options['recon_normals'] = samples.normals.cpu().numpy()
+    elif plane_source:
         if not ply.has_normals(recon_path):
             raise ValueError(NO_NORMALS % recon_path)
         recon, _, options['recon_normals'] = ply.read_ply_normals(recon_path)
@@ -297,11 +377,11 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
             options['scanner_origins'] = np.array([M[:3, 3] for _, M in moves])
             T = None
         else:
-            options['scans'] = [ply.read_ply_points(p) for p in gt_paths]
+            options['scans'] = [read_gt(p) for p in gt_paths]
             options['scanner_origins'] = eval_eth3d.load_origins(scanner_origins_path)
         gt = None
     else:
-        gt = [ply.read_ply_points(p) for p in gt_paths]
+        gt = [read_gt(p) for p in gt_paths]
         gt = np.concatenate(gt, 0) if gt else np.zeros((0, 3), np.float32)
     init, cams = None, None
     if init_transform_path is not None and init_cameras is not None:
@@ -313,8 +393,11 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
         init, matched, rms = register_cloud.init_from_cameras(*init_cameras)
         cams = {'recon_sparse': str(init_cameras[0]), 'gt_sparse': str(init_cameras[1]), 'matched_images': matched, 'rms': rms}
     if init is None and not options and save_transform_path is None:
-        return evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances)
+        result = evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances)
+        result.update(sampled)
+        return result
     result = evaluate(recon, gt, tolerances, radius, gt_transform=T, distances=distances, init_transform=init, **options)
+    result.update(sampled)
     if cams is not None:
         result['init_cameras'] = cams
     if save_transform_path is not None:
@@ -474,7 +557,7 @@ def register_options(parser, args):
             if not args.register_voxel >= 0.0:
                 parser.error('--register_voxel must be >= 0')
             options['register_voxel'] = args.register_voxel
-        if args.register_icp == 'plane' and not target:
+        if args.register_icp == 'plane' and not target and getattr(args, 'sample_recon', None) is None:
             try:
                 with_normals = ply.has_normals(args.recon)
             except (OSError, ValueError) as e:
@@ -571,8 +654,50 @@ def make_parser():
     return parser
 
 
+def add_sample_arguments(parser):
+    """--sample_recon, --sample_gt and --sample_seed: added by `cli` to what make_parser declares (the surface make_parser shares
+    with the ETH3D driver's option groups stays as it is)."""
+    parser.add_argument('--sample_recon', type=float, default=None, metavar='S',
+                        help='--recon is a triangle mesh: score samples of its surface, one per S x S, drawn on the GPU (no default; at '
+                             'most half the smallest tolerance), instead of its vertices')
+    parser.add_argument('--sample_gt', type=float, default=None, metavar='S',
+                        help='the same for every --gt file that is a triangle mesh (ground truth given as a surface)')
+    parser.add_argument('--sample_seed', type=int, default=None, metavar='K',
+                        help='--sample_recon / --sample_gt: the seed of the samples, 0..2^63-1 (default 0)')
+    return parser
+
+
+def sample_options(parser, args):
+    """--sample_recon, --sample_gt and --sample_seed of a parsed command line as evaluate_files' keyword arguments ({} without
+    them); an option without its mesh is an argument error, as is a file that is not a triangle mesh (the headers are read here)."""
+    if args.sample_seed is not None and args.sample_recon is None and args.sample_gt is None:
+        parser.error('--sample_seed needs --sample_recon or --sample_gt')
+    if args.sample_seed is not None and not 0 <= args.sample_seed < (1 << 63):
+        parser.error('--sample_seed must be in 0..2^63-1')
+    options = {}
+    for name, paths in (('sample_recon', [args.recon]), ('sample_gt', args.gt or [])):
+        value = getattr(args, name)
+        if value is None:
+            continue
+        if not (value > 0.0 and np.isfinite(value)):
+            parser.error('--%s must be a positive finite spacing' % name)
+        if name == 'sample_gt' and args.gt_mlp:
+            parser.error('--sample_gt with --gt_mlp: a MeshLab project names laser scans, not meshes')
+        try:
+            faces = [mesh_faces(p) for p in paths]
+        except (OSError, ValueError) as e:
+            parser.error('--%s: %s' % (name, e))
+        if not any(faces):
+            parser.error('--%s: %s: the option needs a triangle mesh' % (name, ('%s has no faces' % paths[0]) if len(paths) == 1 else
+                                                                         'none of the --gt files has faces'))
+        options[name] = value
+    if options and args.sample_seed is not None:
+        options['sample_seed'] = args.sample_seed
+    return options
+
+
 def cli(argv=None):
-    parser = make_parser()
+    parser = add_sample_arguments(make_parser())
     args = parser.parse_args(argv)
     try:
         tol = [float(t) for t in args.tolerances.split(',') if t.strip()]
@@ -581,10 +706,16 @@ def cli(argv=None):
         parser.error(str(e))
     options = register_options(parser, args)
     options.update(eth3d_options(parser, args))
+    options.update(sample_options(parser, args))
     import torch
     torch.cuda.set_device(args.gpu_id)
     dist = {} if args.distances else None
-    result = evaluate_files(args.recon, args.gt or [], tol, args.radius, args.gt_transform, distances=dist, **options)
+    try:
+        result = evaluate_files(args.recon, args.gt or [], tol, args.radius, args.gt_transform, distances=dist, **options)
+    except ValueError as e:
+        if not any(k in options for k in ('sample_recon', 'sample_gt')):
+            raise
+        parser.error(str(e))             # a mesh of other polygons than triangles is only seen when its body is read
     if dist is not None:
         for k, v in dist.items():
             np.save('%s_%s.npy' % (args.distances, k), v)

@@ -111,9 +111,10 @@ def _clean_cloud(points, colors, score, folder, opts, normals=None):
 
 
 def _write_mesh(scene_fusion, map_cams, folder, mesh):
-    """final3d_mesh.ply and mesh.json -> the face count.  After the cloud: the fusion's result bounds the volume.  With clean= in
-    `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's clean=); with
-    simplify= also final3d_mesh_simple.ply and mesh_simple.json, the mesh (the cleaned one with clean=) after vertex clustering."""
+    """final3d_mesh.ply and mesh.json -> (the face count, the SceneMesh).  After the cloud: the fusion's result bounds the volume.
+    With clean= in `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's
+    clean=); with simplify= also final3d_mesh_simple.ply and mesh_simple.json, the mesh (the cleaned one with clean=) after vertex
+    clustering.  score= writes nothing here: _score_mesh does, once the cloud's score is known."""
     t0 = time.time()
     scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
     n_faces = scene_mesh.write_ply(os.path.join(folder, 'final3d_mesh.ply'))
@@ -127,15 +128,34 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
         scene_mesh.write_simple_ply(os.path.join(folder, 'final3d_mesh_simple.ply'))
         mesh_fusion.write_json(os.path.join(folder, 'mesh_simple.json'), scene_mesh.simplify_report())
     TIMES['mesh'] = time.time() - t0
-    return n_faces
+    return n_faces, scene_mesh
+
+
+def _score_mesh(scene_mesh, score, folder, opts):
+    """mesh_eval.json, with clean= also mesh_eval_clean.json, with simplify= also mesh_eval_simple.json: each mesh's surface sampled
+    on the device (mesh score=dict(spacing=, seed=)) and scored against the ground truth, moved by the matrix found for the cloud
+    (as _clean_cloud moves the cleaned cloud), not registered again."""
+    t0 = time.time()
+    moved = None
+    if score is not None and 'registration' in score:
+        moved = score['registration']['matrix']
+    elif score is not None and 'init_transform' in score:
+        moved = score['init_transform']
+    names = {'mesh': 'mesh_eval.json', 'clean': 'mesh_eval_clean.json', 'simple': 'mesh_eval_simple.json'}
+    for key, result in scene_mesh.score(opts.gt_points, moved).items():
+        eval_cloud.write_json(os.path.join(folder, names[key]), result)
+    TIMES['mesh_eval'] = time.time() - t0
 
 
 def _end_scene(name, scene_fusion, map_cams, folder, opts):
-    """A fused scene's files, each group by its own step: the PLY, the mesh, the cloud's score, the maps' score, the cleaned cloud.
+    """A fused scene's files, each group by its own step: the PLY, the mesh, the cloud's score, the maps' score, the cleaned cloud,
+    the meshes' scores.
     opts: the _SceneOptions of the run."""
     n_points = _write_cloud(scene_fusion, folder)
+    scene_mesh = None
     if opts.mesh is not None:
-        print(Notify.INFO, '%s: %d mesh faces' % (name, _write_mesh(scene_fusion, map_cams, folder, opts.mesh)), Notify.ENDC)
+        n_faces, scene_mesh = _write_mesh(scene_fusion, map_cams, folder, opts.mesh)
+        print(Notify.INFO, '%s: %d mesh faces' % (name, n_faces), Notify.ENDC)
     points, colors, score, normals = None, None, None, None
     if opts.gt_points is not None or opts.clean:
         points, colors = scene_fusion.run()
@@ -151,6 +171,8 @@ def _end_scene(name, scene_fusion, map_cams, folder, opts):
     if opts.clean:
         n_clean = _clean_cloud(points, colors, score, folder, opts, normals if opts.clean_keep_normals else None)
         print(Notify.INFO, '%s: %d points after cleaning' % (name, n_clean), Notify.ENDC)
+    if scene_mesh is not None and opts.mesh.get('score') is not None:
+        _score_mesh(scene_mesh, score, folder, opts)
     print(Notify.INFO, '%s: %d fused points' % (name, n_points), Notify.ENDC)
 
 
@@ -170,7 +192,7 @@ def _option_rules(use_graph=True, scene_cache=False, write_thread=True, fuse=Non
                                        'point cloud to clean'),
         (score_maps is not None and not gt_ply, '--score_maps needs --gt_ply (score_maps needs gt_ply): there is no scan to render')
     ] + (eval_cloud.register_rules(register, fused_normals) + clean_cloud.keep_normals_rules(clean, clean_keep_normals, fused_normals)
-         + mesh_fusion.rules(mesh, fuse))
+         + mesh_fusion.rules(mesh, fuse, gt_ply))
 
 
 def _check_options(**options):
@@ -204,7 +226,9 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     matrix found for the uncleaned cloud, not registered again); clean_keep_normals (with clean and fuse_normals normals='depth'
     only): the cleaned PLY carries the normals of the rows that stay -- clean_cloud.options.
     mesh (with fuse only): mesh_fusion.SceneMesh's arguments, with render=True also depths_mesh/ -- mesh_fusion.options; its
-    simplify=dict(cell_voxels=R) (no command-line option) also writes final3d_mesh_simple.ply and mesh_simple.json."""
+    simplify=dict(cell_voxels=R) (no command-line option) also writes final3d_mesh_simple.ply and mesh_simple.json; its
+    score=dict(spacing=S[, seed=K]) (with gt_ply only, no command-line option) samples each written mesh's surface on the device and
+    scores it into mesh_eval.json, mesh_eval_clean.json and mesh_eval_simple.json (moved by the cloud's matrix with register)."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
                    clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals, mesh=mesh)

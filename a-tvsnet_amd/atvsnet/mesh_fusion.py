@@ -9,6 +9,8 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     clean=         SceneMesh and the tool also give the mesh without its small connected components (clean_mesh, section 10.3a)
     simplify=      SceneMesh also gives the mesh -- the cleaned one with clean= -- simplified by vertex clustering on a lattice of
                    cell_voxels voxels (simplify_mesh, section 10.3d); off unless asked
+    score=         SceneMesh.score samples each of these meshes' surfaces on the device (sample_mesh, section 10.3e) and scores the
+                   samples against a ground truth (eval_cloud.evaluate); the ETH3D driver writes mesh_eval*.json; off unless asked
 
     carve_weight=  free-space carving (section 10.3b): a view that sees past a voxel pulls its value outside, so a shell that two views
                    agree on and the others look through is not meshed; off (None) unless asked
@@ -21,7 +23,7 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
 
 What this is not: there are no weights from the viewing angle, the ETH3D driver has no probability weights (its staged slab does not
 keep the probabilities; mesh_consistent reads them from the files) and no command-line option for consistent=, weights= and
-simplify= (they are run_eval_pc's mesh arguments; a written mesh is simplified by the command atvsnet/simplify_mesh.py), no hole
+simplify= and score= (they are run_eval_pc's mesh arguments; a written mesh is simplified by the command atvsnet/simplify_mesh.py), no hole
 filling, and the PLY carries no normals.
 Without carve_weight a view adds to a voxel only inside the narrow band around its depth.  Fragments are removed only when asked
 (the clean_ options have no defaults).  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports
@@ -39,7 +41,7 @@ import time
 import numpy as np
 
 from ..tools.common import write_json  # noqa: F401
-from . import clean_mesh, eval_depth, simplify_mesh
+from . import clean_mesh, eval_depth, sample_mesh, simplify_mesh
 
 DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
 DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
@@ -52,14 +54,15 @@ TOOL_WEIGHT_MODES = ('agree', 'prob')      # the tool also reads the probability
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
                   pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None, consistent=False, weights=None,
-                  simplify=None):
+                  simplify=None, score=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
     the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there,
-    carve_weight by check_carve_weight, consistent and weights by check_support, simplify by check_simplify (they are not part of
-    the tuple)."""
+    carve_weight by check_carve_weight, consistent and weights by check_support, simplify by check_simplify, score by check_score
+    (they are not part of the tuple)."""
     if clean is not None:
         clean_mesh.check_criteria(**clean)
     check_simplify(simplify)
+    check_score(score)
     check_carve_weight(carve_weight)
     check_support(consistent, weights)
     voxel, trunc_voxels, min_weight, pixel_centre = float(voxel), float(trunc_voxels), float(min_weight), float(pixel_centre)
@@ -106,6 +109,21 @@ def check_simplify(simplify):
     except ValueError as e:
         raise ValueError('mesh simplify: %s' % str(e).replace('cell must', 'cell_voxels must'))
     return cell, placement, rank_epsilon
+
+
+def check_score(score):
+    """-> None (the meshes are not scored) or (spacing float, seed int): score is a dict(spacing=S[, seed=K]), the spacing of the
+    surface samples in the scene's unit (no default: at most half the smallest tolerance, section 10.3e) and their seed (default 0).
+    Anything else raises ValueError."""
+    if score is None:
+        return None
+    if not isinstance(score, dict) or 'spacing' not in score or set(score) - {'spacing', 'seed'}:
+        raise ValueError('mesh score must be a dict(spacing=S[, seed=K]), got %r' % (score,))
+    try:
+        density, _, seed = sample_mesh.check_options(spacing=score['spacing'], seed=score.get('seed', 0))
+    except ValueError as e:
+        raise ValueError('mesh score: %s' % e)
+    return float(score['spacing']), seed
 
 
 def check_support(consistent=False, weights=None, modes=WEIGHT_MODES):
@@ -284,13 +302,18 @@ class SceneMesh(object):
     0 elsewhere -- is integrated in place of the staged depth planes, so the mesh rests on the samples the cloud is made of;
     report() gains `consistent` (disp_threshold, num_consistent, samples, samples_kept).  weights='agree': support()'s `weight`,
     (1 + agreeing views) / (1 + num_consistent), is each pixel's view weight (ops.tsdf_integrate's weights); report() gains
-    `weights`.  Both come from one launch; the thresholds are the scene_fusion's own (section 10.3c)."""
+    `weights`.  Both come from one launch; the thresholds are the scene_fusion's own (section 10.3c).
+
+    score: None, or dict(spacing=S[, seed=K]).  run() does nothing with it; score(gt_points) samples the surface of the mesh, of the
+    cleaned and of the simplified one where they exist, on the device at that spacing and scores each against the ground truth
+    (section 10.3e)."""
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
                  max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None,
-                 consistent=False, weights=None, simplify=None):
+                 consistent=False, weights=None, simplify=None, score=None):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
         self.simplify = check_simplify(simplify)
+        self.score_options = check_score(score)
         self._device_simple = self._simple_result = self._simple_report = None
         self.carve_weight = check_carve_weight(carve_weight)
         self.consistent, self.weights = check_support(consistent, weights)
@@ -415,6 +438,28 @@ class SceneMesh(object):
         ply.write_mesh(path, vertices, colors, faces)
         return len(faces)
 
+    def score(self, gt_points, transform=None):
+        """run() -> {'mesh': result[, 'clean': result][, 'simple': result]}: each mesh this object holds on the device sampled at
+        score=dict(spacing=, seed=) (sample_mesh.sample_device: the tensors stay where they are) and the samples scored against
+        gt_points by eval_cloud.evaluate at its default tolerances; transform: a 4x4 matrix applied to the samples first (the matrix
+        a registration found for the scene's cloud: the meshes are not registered again).  A result carries `recon_mesh`, the
+        sampling's report without `seconds`."""
+        from . import eval_cloud
+        self.run()
+        if self.score_options is None:
+            raise RuntimeError('SceneMesh: no score= was given: there is no spacing to sample the meshes at')
+        spacing, seed = self.score_options
+        moved = {} if transform is None else {'init_transform': transform}
+        out = {}
+        for key, mesh in (('mesh', self._device_mesh), ('clean', self._device_clean), ('simple', self._device_simple)):
+            if mesh is None:
+                continue
+            vertices, _, faces = mesh
+            samples, report = sample_mesh.sample_device(vertices.contiguous(), None, faces.contiguous(), spacing=spacing, seed=seed)
+            out[key] = eval_cloud.evaluate(samples.points, gt_points, device=vertices.device, **moved)
+            out[key]['recon_mesh'] = {k: report[k] for k in sample_mesh.REPORT_KEYS if k != 'seconds'}
+        return out
+
     def render(self, folder, clean=False):
         """run(), then the mesh -- still on the device -- rendered into the scene's map cameras as folder/%08d_mesh.pfm
         (render_views); report() gains `render`.  clean=True: the cleaned mesh, and clean_report() gains `render`."""
@@ -485,10 +530,10 @@ def options(parser, args, prefix=''):
     return dict(out, clean=clean) if clean else out
 
 
-def rules(mesh, fuse):
+def rules(mesh, fuse, gt_ply=None):
     """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight, consistent,
-    weights, clean and simplify only when they are given (consistent, weights and simplify reach the driver through run_eval_pc's
-    mesh dict alone: its command line has no option for them)."""
+    weights, clean, simplify and score only when they are given (consistent, weights, simplify and score reach the driver through
+    run_eval_pc's mesh dict alone: its command line has no option for them).  score's rows stand behind the others."""
     if mesh is None:
         return []
     rows = [(fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
@@ -508,6 +553,9 @@ def rules(mesh, fuse):
     if mesh.get('simplify') is not None:
         rows.insert(1, (mesh.get('voxel') is None, 'mesh simplify= needs voxel=: there is no mesh to simplify, and its cells are '
                                                    'counted in voxels'))
+    if mesh.get('score') is not None:
+        rows += [(mesh.get('voxel') is None, 'mesh score= needs voxel=: there is no mesh to score'),
+                 (not gt_ply, 'mesh score= needs gt_ply: there is no ground truth to score the mesh\'s samples against')]
     return rows
 
 

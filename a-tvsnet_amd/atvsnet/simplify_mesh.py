@@ -26,8 +26,8 @@ restatement's numbers).  rank_epsilon = 1e-3 is Lindstrom's value, a default and
 
 What this is not: edge-collapse decimation to a target face count, topology preservation (two sheets closer than a cell merge, a
 thin handle closes; the report's two edge censuses say what happened instead of hiding it), boundary or colour-seam constraints.
-atvsnet/eval_cloud.py --recon scores a mesh by its VERTICES, so a simplified mesh loses completeness there by construction: score
-the unsimplified mesh (sampling a mesh's surface for scoring is not built).  There is no CPU fallback.  This module imports without
+atvsnet/eval_cloud.py --recon scores a mesh by its VERTICES, so a simplified mesh loses completeness there by construction: give
+it --sample_recon, which scores samples of the surface instead (atvsnet/sample_mesh.py).  There is no CPU fallback.  This module imports without
 a GPU; only `simplify` and `simplify_device` need one.
 """
 from __future__ import print_function

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 63
+#define ATVS_ABI_VERSION 64
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1485,6 +1485,54 @@ int atvs_mesh_cluster_max_move(const float* vertices, long n_vertices, const int
 int atvs_mesh_cluster_faces_scratch_size(long n_faces, long* bytes);
 int atvs_mesh_cluster_faces(const int* faces, long n_faces, long n_vertices, const int* vertex_cluster, void* scratch,
                             long scratch_bytes, int* faces_out, void* keep, int* info, atvs_stream_t stream);
+
+/* A triangle mesh's surface sampled uniformly by area, so that a mesh scores as a surface and not as its vertices: ops/mesh_sample.py,
+ * atvsnet/sample_mesh.py, atvsnet/eval_cloud.py --sample_recon, csrc/mesh_sample.hip; DESIGN.md section 10.3e.  Pointers are device
+ * pointers.  Every output is a function of (vertices, colors, faces, density, seed) alone: the random numbers are a hash of (seed,
+ * face, sample within the face), the only atomics are integer ones (a sum, a maximum, two tallies), so neither the launch shape nor
+ * the order of arrival shows, bit for bit on every run.  No host synchronisation, no allocation; scratch is the caller's.
+ * tests/mesh_sample_restated.py restates the definitions in numpy.  vertices (n_vertices,3) float32, colors (n_vertices,3) uint8 or
+ * null, faces (n_faces,3) int32; n_vertices in 0..2^30, n_faces in 0..ATVS_MESH_TOPOLOGY_MAX_FACES, n_samples in
+ * 0..ATVS_MESH_SAMPLE_MAX, anything else ATVS_ERR_SHAPE, as is a short scratch; density a finite double > 0 (samples per unit area)
+ * and seed in 0..2^63-1, else ATVS_ERR_ARG; a null pointer that is needed ATVS_ERR_NULL; all without a launch.
+ *
+ * The hash.  All arithmetic mod 2^64.  mix(z): z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9, z = (z ^ (z >> 27)) 0x94D049BB133111EB,
+ * z ^ (z >> 31) (the finaliser of splitmix64); G = 0x9E3779B97F4A7C15; hash(base, i) = mix(base + G (i + 1)).  The key of face f is
+ * k_f = hash(seed, f); sample j of face f draws w = hash(k_f, j).
+ *
+ * atvs_mesh_sample_counts.  One lane per face, in double: a, b, c the face's vertices, e1 = b - a, e2 = c - a, n = e1 x e2 (products
+ * then one subtraction per component), area = 0.5 sqrt((nx nx + ny ny) + nz nz), x = area density,
+ * u_f = ((double)(k_f >> 11) + 0.5) 2^-53, count = floor(x) + (u_f < x - floor(x)): stochastic rounding, so a surface of faces with
+ * x < 1 still gets its share and the expected count of every face is x.  counts (n_faces,) uint32, areas (n_faces,) float64.  A face
+ * with an index outside 0..n_vertices-1 (info[1]) or, else, an area that is not finite (info[2]) is skipped: count 0, area 0.  info:
+ * four int64 words, zeroed here: [0] the total of the counts (a 64-bit integer atomic), [1] and [2] the skipped faces, [3] the
+ * largest count.  A face with x >= ATVS_MESH_SAMPLE_MAX adds floor(min(x, 2^32)) to [0] and [3] without the rounding bit and its
+ * count is not defined; the caller treats info[3] >= ATVS_MESH_SAMPLE_MAX or info[0] > ATVS_MESH_SAMPLE_MAX as a shape error that
+ * reports info[0], the samples the density needs, and reads no other output.
+ *
+ * atvs_mesh_sample_offsets.  offsets (n_faces + 1,) uint32: the exclusive prefix sum of counts (an INPUT here: anybody's counts
+ * whose total is at most ATVS_MESH_SAMPLE_MAX), by the point-cloud kernels' scan; offsets[n_faces] is the total.  scratch:
+ * atvs_mesh_sample_scratch_size(n_faces) bytes, the scan's tile sums.
+ *
+ * atvs_mesh_sample_place.  One lane per sample s in [0, n_samples).  f is the face with offsets[f] <= s < offsets[f + 1] (the last
+ * face whose offset is <= s: a face with count 0 is never chosen), j = s - offsets[f], w = hash(k_f, j),
+ * u = ((double)(w >> 32) + 0.5) 2^-32, v = ((double)(w & 0xffffffff) + 0.5) 2^-32, and where u + v > 1: u = 1 - u, v = 1 - v (all
+ * exact in double).  points (n_samples,3) float32: per axis (a + u e1) + v e2 in double, rounded once.  sample_face (n_samples,)
+ * int32: f.  colors_out (n_samples,3) uint8, written when colors is given: per channel rint(((1 - u - v) c_a + u c_b) + v c_c), ties
+ * to even, 1 - u - v formed as (1 - u) - v.  normals (n_samples,3) float32, written when the pointer is given: n / sqrt((nx nx + ny
+ * ny) + nz nz) in double, rounded once (a face of area 0 has no sample under counts of atvs_mesh_sample_counts).  info: two int64
+ * words, zeroed here: [0] = 1 when offsets[n_faces] != n_samples (nothing else is written then), [1] the samples whose face has an
+ * index outside 0..n_vertices-1 (sample_face -1, zeros elsewhere; no output is defined unless both words are 0).  A lane's face is
+ * always inside 0..n_faces-1 and every store inside the n_samples rows, whatever offsets holds.  n_samples > 0 with n_faces = 0 is
+ * ATVS_ERR_SHAPE. */
+#define ATVS_MESH_SAMPLE_MAX 268435456
+int atvs_mesh_sample_counts(const float* vertices, long n_vertices, const int* faces, long n_faces, double density, long seed,
+                            void* counts, double* areas, long* info, atvs_stream_t stream);
+int atvs_mesh_sample_scratch_size(long n_faces, long* bytes);
+int atvs_mesh_sample_offsets(const void* counts, long n_faces, void* scratch, long scratch_bytes, void* offsets, atvs_stream_t stream);
+int atvs_mesh_sample_place(const float* vertices, const void* colors, long n_vertices, const int* faces, long n_faces,
+                           const void* offsets, long n_samples, long seed, float* points, int* sample_face, void* colors_out,
+                           float* normals, long* info, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
