@@ -262,17 +262,10 @@ def refinement(init_depth_images, cams, depth_num, depth_start, depth_interval, 
     return _refine_net(bufs, prob_vol.unsqueeze(-1), chan, False)
 
 
-def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_start, depth_interval, sources,
-                     shallow, ref_id=0, shallow_index=None, hom=None, residual_base=None, cost=True, prob=True):
-    """`refinement` of several source views against one reference estimate in ONE pass of the network
-    (the reference calls it once per source, example.py:163-172): depth_ref (1,h,w,1), depth_views {source: (1,h,w,1)},
-    prob_vol (1,D,h,w) shared, shallow (N,h,w,16) features of every view (shallow_index: {view id: row of shallow} when
-    it holds a subset) -> (cost residuals (S,D,h,w,8), prob residuals (S,D,h,w)), S = len(sources), each sample with
-    its own batch statistics.  cams are indexed by the view ids themselves.  hom: the depth map's homography cache
-    (_cached_homographies), e.g. the one base_stage_batch filled.  residual_base (1,D,h,w,8): the cost volume the residuals are
-    added to (TVSNet_refine, reference :439) -- a third result, residual_base + cost residual (S,D,h,w,8), then comes out of the
-    pass that forms the residuals.  cost=False / prob=False: the caller reads no cost / prob residual (None in its place): the
-    probability head does not run, the cost residual is not written."""
+def refinement_volumes_batch(depth_ref, depth_views, cams, depth_num, depth_start, depth_interval, sources, shallow, ref_id=0,
+                             shallow_index=None, hom=None):
+    """The volumes refinement_batch's network consumes (arguments as there): the buffers of _refinement_buffers with sample b
+    filled for sources[b] -> (photo_var, photo_const, geo_var, geo_const, vis_hull)."""
     si = (lambda v: v) if shallow_index is None else (lambda v: shallow_index[v])
     D = int(depth_num)
     S = len(sources)
@@ -296,8 +289,25 @@ def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_st
         _refinement_volumes(b, bufs, depth_ref, depth_views[v], cams[:, ref_id], view_cam, hull_cam,
                             shallow[si(ref_id):si(ref_id) + 1], shallow[si(v):si(v) + 1], D, ds, di, depth_start,
                             depth_interval, hom, ((ref_id, v), (ref_id, _hull_view(ref_id))), tr)
+    return bufs
+
+
+def refinement_batch(depth_ref, depth_views, prob_vol, cams, depth_num, depth_start, depth_interval, sources,
+                     shallow, ref_id=0, shallow_index=None, hom=None, residual_base=None, cost=True, prob=True):
+    """`refinement` of several source views against one reference estimate in ONE pass of the network
+    (the reference calls it once per source, example.py:163-172): depth_ref (1,h,w,1), depth_views {source: (1,h,w,1)},
+    prob_vol (1,D,h,w) shared, shallow (N,h,w,16) features of every view (shallow_index: {view id: row of shallow} when
+    it holds a subset) -> (cost residuals (S,D,h,w,8), prob residuals (S,D,h,w)), S = len(sources), each sample with
+    its own batch statistics.  cams are indexed by the view ids themselves.  hom: the depth map's homography cache
+    (_cached_homographies), e.g. the one base_stage_batch filled.  residual_base (1,D,h,w,8): the cost volume the residuals are
+    added to (TVSNet_refine, reference :439) -- a third result, residual_base + cost residual (S,D,h,w,8), then comes out of the
+    pass that forms the residuals.  cost=False / prob=False: the caller reads no cost / prob residual (None in its place): the
+    probability head does not run, the cost residual is not written."""
+    S = len(sources)
+    bufs = refinement_volumes_batch(depth_ref, depth_views, cams, depth_num, depth_start, depth_interval, sources, shallow, ref_id,
+                                    shallow_index, hom)
     pv = ops.stack([prob_vol[0].unsqueeze(-1)] * S, 0) if S > 1 else prob_vol.unsqueeze(-1)      # the shared volume, once per sample
-    return _refine_net(bufs, pv, chan, True, residual_base, cost, prob)
+    return _refine_net(bufs, pv, shallow.shape[-1], True, residual_base, cost, prob)
 
 
 def feature_extraction_batch(images):

@@ -98,6 +98,10 @@ def test_multiview_end_to_end(cuda, weights):
         g, w = G[k].cpu(), S[k]
         assert g.shape == w.shape, k
         assert float((g - w).abs().max()) <= 2e-3 * float(w.abs().max()), k
+    assert len(G['depth_views']) == len(S['depth_views']) == 3
+    for v, (g, w) in enumerate(zip(G['depth_views'], S['depth_views']), 1):      # the reverse direction's depth of every source
+        assert g.shape == w.shape, v
+        assert float((g.cpu() - w).abs().max()) <= 2e-3 * float(w.abs().max()), v
     err = rel_l1(got, want)
     print('multi-view (N=4) rel-L1 inverse depth %.3e' % err)
     assert err <= 1e-3
