@@ -9,7 +9,7 @@ distance tolerances.
            [--init_transform T.txt | --init_cameras RECON_SPARSE GT_SPARSE] [--save_transform T.txt] [--voxel v]
            [--eth3d (--gt_mlp scan_alignment.mlp | --scanner_origins origins.txt) [--eth3d_voxel 0.01] [--cube_size 1024]
             [--vis_window 1] [--free_space_margin 0]]
-           [--sample_recon S] [--sample_gt S] [--sample_seed K]
+           [--sample_recon S [--exact_recon]] [--sample_gt S [--exact_gt]] [--sample_seed K]
 
 The top-level keys are the PLAIN precision / recall definition (the one Tanks and Temples uses): per tolerance tau, `accuracy` is
 the share of reconstruction points with a ground-truth point within tau, `completeness` the share of ground-truth points with a
@@ -45,9 +45,14 @@ A triangle mesh given as --recon scores by its VERTICES: a simplified mesh then 
 samples its surface uniformly by area at spacing S on the device first (atvsnet/sample_mesh.py: one sample per S x S, every number a
 hash of --sample_seed, the face and the sample, so the same run gives the same score) and the samples are the reconstruction for
 everything above; with --register_icp plane over the source's normals the samples' face normals serve.  --sample_gt S does the same
-for every --gt file that is a mesh (a dataset whose ground truth is a surface).  A spacing of at most half the smallest tolerance is
-what DESIGN.md section 10.3e supports.  The result gains `recon_mesh` (sample_mesh's report without `seconds`) and / or `gt_mesh`
-(a list of such reports, one per sampled file, each with its `file`).
+for every --gt file that is a mesh (a dataset whose ground truth is a surface).  The result gains `recon_mesh` (sample_mesh's report
+without `seconds`) and / or `gt_mesh` (a list of such reports, one per sampled file, each with its `file`).  Samples turn a surface
+back into points, and the half of the score measured AGAINST them inherits their spacing: a spacing of at most half the smallest
+tolerance is what DESIGN.md section 10.3e supports for it.  --exact_recon (with --sample_recon) measures completeness against the
+mesh itself instead: the exact point-to-triangle distance of every ground-truth point to the surface of --recon, on the device
+(ops.mesh_grid / mesh_nearest, csrc/mesh_distance.hip), which no spacing enters; --exact_gt (with
+--sample_gt, every --gt file a mesh) does the same for accuracy against the ground-truth surface.  The samples remain the points of
+the other direction and of the registration.  The result gains `exact`.
 """
 from __future__ import print_function
 
@@ -130,11 +135,24 @@ def _matrix(T, name):
     return T.reshape(4, 4)
 
 
+def _surface(surface, name):
+    """None, or the (vertices (V,3), faces (F,3)) of evaluate's recon_surface / gt_surface; anything else raises ValueError."""
+    if surface is None:
+        return None
+    if not isinstance(surface, (tuple, list)) or len(surface) != 2:
+        raise ValueError('%s: expected (vertices (V,3), faces (F,3)), got %s' % (name, type(surface).__name__))
+    for part, what in zip(surface, ('vertices', 'faces')):
+        shape = tuple(getattr(part, 'shape', ()))
+        if len(shape) != 2 or shape[1] != 3:
+            raise ValueError('%s: %s: expected shape (n,3), got %s' % (name, what, shape))
+    return tuple(surface)
+
+
 def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform=None, device=None, distances=None,
              register=False, with_scale=False, register_distances=None, register_voxel=None, init_transform=None, voxel=None,
              scans=None, scanner_origins=None, eth3d_voxel=0.01, cube_size=1024, vis_window=1, free_space_margin=0.0,
              register_icp='point', recon_normals=None, register_normals='source', register_normal_k=None,
-             register_normal_radius=None, register_global=False, global_options=None):
+             register_normal_radius=None, register_global=False, global_options=None, recon_surface=None, gt_surface=None):
     """recon (M,3), gt (N,3): host arrays (or device tensors) of float32 points -> the dict of `metrics`.  radius: the search
     radius, default the largest tolerance.  gt_transform: a 4x4 matrix applied to `gt` on the host (float64, rounded once).
     distances: a dict that receives d2_recon, idx_recon, d2_gt, idx_gt as numpy arrays.
@@ -160,10 +178,24 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     (2 vis_window + 1)^2 window and is unobserved when it lies more than free_space_margin behind the nearest sample there.
     eth3d_voxel = 0.01 and the default tolerances are ETH3D's published ones; cube_size, vis_window and free_space_margin are
     defaults, not measurements of ETH3D's program.  With `voxel` it is an argument error: down-sampling loses which scanner saw a
-    point.  Every other key is what it is without scans."""
+    point.  Every other key is what it is without scans.
+
+    recon_surface, gt_surface: None, or (vertices (V,3) float32, faces (F,3) int32) as host arrays or device tensors: the triangle
+    mesh that `recon` / `gt` are points of.  With gt_surface the reconstruction's distances (d2_recon, accuracy) are the EXACT
+    point-to-triangle distances to that surface (ops.mesh_grid / mesh_nearest, csrc/mesh_distance.hip) instead of the distances
+    to the nearest point of `gt`; with recon_surface the ground truth's distances (d2_gt, completeness) are those to the
+    reconstruction's surface.  recon_surface's vertices are moved by the matrix `recon` is moved by (init_transform or the
+    registration's, ops.cloud_transform), gt_surface's by gt_transform; voxel down-samples the points and leaves the surfaces
+    alone; `eth3d` receives the new distances in the form of the old.  The distances' idx_* then hold face indices.  The result
+    gains `exact`: accuracy and completeness (whether that direction ran against a surface) and gt_surface_faces,
+    recon_surface_faces (the usable faces, None without the surface)."""
     import torch
     from .. import ops
     tol, radius = _check_tolerances(tolerances, radius)
+    recon_surface, gt_surface = _surface(recon_surface, 'recon_surface'), _surface(gt_surface, 'gt_surface')
+    if gt_surface is not None and gt_transform is not None:
+        moved = gt_surface[0].cpu().numpy() if isinstance(gt_surface[0], torch.Tensor) else gt_surface[0]
+        gt_surface = (transform_points(moved, gt_transform), gt_surface[1])
     if register_icp not in ('point', 'plane'):
         raise ValueError("register_icp must be 'point' or 'plane', got %r" % (register_icp,))
     if register_icp == 'plane' and not register:
@@ -219,6 +251,11 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
             return x.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
         return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.float32).reshape(-1, 3))).to(dev)
 
+    def upload_faces(x):
+        if isinstance(x, torch.Tensor):
+            return x.to(device=dev, dtype=torch.int32).reshape(-1, 3).contiguous()
+        return torch.from_numpy(np.ascontiguousarray(np.asarray(x, np.int32).reshape(-1, 3))).to(dev)
+
     if gt_transform is not None:
         gt = transform_points(gt.cpu().numpy() if isinstance(gt, torch.Tensor) else gt, gt_transform)
     if not register and (with_scale or register_distances is not None or register_voxel is not None):
@@ -229,6 +266,7 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
     extra = {}
     with torch.cuda.device(dev):
         r, g = upload(recon), upload(gt)
+        surface_r, surface_g = (None if m is None else (upload(m[0]), upload_faces(m[1])) for m in (recon_surface, gt_surface))
         if register:
             from . import register_cloud
             dist = [4.0 * max(tol), 2.0 * max(tol), max(tol)] if register_distances is None else list(register_distances)
@@ -237,14 +275,30 @@ def evaluate(recon, gt, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform
             extra['registration'] = register_cloud.register(r, g, init='global' if register_global else init, with_scale=with_scale,
                                                             distances=dist, voxel=register_voxel, device=dev, **plane)
             r = ops.cloud_transform(r, extra['registration']['matrix'])
+            if surface_r is not None:
+                surface_r = (ops.cloud_transform(surface_r[0], extra['registration']['matrix']), surface_r[1])
         elif init is not None:
             extra['init_transform'] = init.tolist()
             r = ops.cloud_transform(r, init)
+            if surface_r is not None:
+                surface_r = (ops.cloud_transform(surface_r[0], init), surface_r[1])
         if voxel is not None:
             extra.update(voxel=float(voxel), n_recon_full=int(r.shape[0]), n_gt_full=int(g.shape[0]))
             r, g = ops.cloud_voxel_downsample(r, voxel)[0], ops.cloud_voxel_downsample(g, voxel)[0]
-        d2_r, idx_r = ops.cloud_nearest(ops.cloud_grid(g, radius), r)
-        d2_g, idx_g = ops.cloud_nearest(ops.cloud_grid(r, radius), g)
+        if surface_g is None:
+            d2_r, idx_r = ops.cloud_nearest(ops.cloud_grid(g, radius), r)
+        else:
+            grid_g = ops.mesh_grid(surface_g[0], surface_g[1], radius)
+            d2_r, idx_r = ops.mesh_nearest(grid_g, r)
+        if surface_r is None:
+            d2_g, idx_g = ops.cloud_nearest(ops.cloud_grid(r, radius), g)
+        else:
+            grid_r = ops.mesh_grid(surface_r[0], surface_r[1], radius)
+            d2_g, idx_g = ops.mesh_nearest(grid_r, g)
+        if surface_r is not None or surface_g is not None:
+            extra['exact'] = {'accuracy': surface_g is not None, 'completeness': surface_r is not None,
+                              'gt_surface_faces': None if surface_g is None else grid_g.usable_faces,
+                              'recon_surface_faces': None if surface_r is None else grid_r.usable_faces}
         counts = [ops.cloud_counts(d2, tol, radius).cpu().tolist() for d2 in (d2_r, d2_g)]
         if origins is not None:
             extra['eth3d'] = eval_eth3d.score(r, g, [len(s) for s in scans], origins, d2_r, d2_g, tol, *eth3d_args)
@@ -311,9 +365,22 @@ def sample_file(path, spacing, seed=0, normals=False, name='sample_recon'):
     return samples, report
 
 
+def read_surfaces(paths):
+    """The triangle meshes of `paths` as one (vertices (V,3) float32, faces (F,3) int32): concatenated, the indices offset."""
+    from .clean_mesh import read_mesh
+    vertices, faces, first = [], [], 0
+    for path in paths:
+        v, _, f = read_mesh(path)
+        vertices.append(np.asarray(v, np.float32).reshape(-1, 3))
+        faces.append(np.asarray(f, np.int64).reshape(-1, 3) + first)
+        first += len(vertices[-1])
+    return np.ascontiguousarray(np.concatenate(vertices)), np.ascontiguousarray(np.concatenate(faces).astype(np.int32))
+
+
 def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=None, gt_transform_path=None, distances=None,
                    init_transform_path=None, init_cameras=None, save_transform_path=None, gt_mlp_path=None,
-                   scanner_origins_path=None, sample_recon=None, sample_gt=None, sample_seed=None, **options):
+                   scanner_origins_path=None, sample_recon=None, sample_gt=None, sample_seed=None, exact_recon=False, exact_gt=False,
+                   **options):
     """`evaluate` of PLY files (tools/ply.read_ply_points): several ground-truth files are concatenated; gt_transform_path: a text
     file of 16 numbers, the 4x4 matrix row-major.  init_transform_path: the same for evaluate's init_transform; init_cameras:
     (recon_sparse_dir, gt_sparse_dir), two COLMAP models whose camera centres give it (register_cloud.init_from_cameras; the
@@ -329,9 +396,25 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
     sample_recon: recon_path is a triangle mesh whose surface is sampled at this spacing on the device first (sample_file), with
     sample_seed (default 0); the samples are the reconstruction for everything else, their face normals the recon_normals of
     register_icp='plane'; the result gains `recon_mesh`.  sample_gt: the same for every file of gt_paths that has faces (at least one
-    must); the result gains `gt_mesh`, a list.  A file that is no triangle mesh, or sample_seed without either, raises ValueError."""
+    must); the result gains `gt_mesh`, a list.  A file that is no triangle mesh, or sample_seed without either, raises ValueError.
+
+    exact_recon (needs sample_recon): the samples stay the reconstruction's points for accuracy and registration, and the mesh of
+    recon_path itself answers completeness: it is evaluate's recon_surface.  exact_gt (needs sample_gt, every file of gt_paths a
+    triangle mesh, no gt_mlp_path): the ground-truth meshes, concatenated with offset indices, are evaluate's gt_surface, which
+    answers accuracy.  The result gains `exact`."""
     if sample_seed is not None and sample_recon is None and sample_gt is None:
         raise ValueError('sample_seed needs sample_recon or sample_gt')
+    if exact_recon and sample_recon is None:
+        raise ValueError('exact_recon needs sample_recon: the samples remain the reconstruction\'s points for accuracy and registration')
+    if exact_gt:
+        if gt_mlp_path is not None:
+            raise ValueError('exact_gt with gt_mlp_path: a MeshLab project names laser scans, not meshes')
+        if sample_gt is None:
+            raise ValueError('exact_gt needs sample_gt: the samples remain the ground truth\'s points for completeness')
+        without = [str(p) for p in gt_paths if not mesh_faces(p)]
+        if without or not gt_paths:
+            raise ValueError('exact_gt: every ground-truth file must be a triangle mesh, %s' % (
+                '%s has no faces' % without[0] if without else 'none is given'))
     seed = 0 if sample_seed is None else sample_seed
     sampled = {}
     plane_source = options.get('register_icp') == 'plane' and options.get('register_normals', 'source') != 'target'
@@ -350,9 +433,13 @@ def evaluate_files(recon_path, gt_paths, tolerances=DEFAULT_TOLERANCES, radius=N
         sampled['gt_mesh'].append(dict(report, file=str(path)))
         return samples.points.cpu().numpy()
 
+    if exact_gt:
+        options['gt_surface'] = read_surfaces(gt_paths)
     if sample_recon is not None:
         samples, sampled['recon_mesh'] = sample_file(recon_path, _spacing(sample_recon, 'sample_recon'), seed, normals=plane_source)
         recon = samples.points
+        if exact_recon:
+            options['recon_surface'] = read_surfaces([recon_path])
         if plane_source:
             options['recon_normals'] = samples.normals.cpu().numpy()
     elif plane_source:
@@ -696,8 +783,42 @@ def sample_options(parser, args):
     return options
 
 
+def add_exact_arguments(parser):
+    """--exact_recon and --exact_gt: added by `cli` to what make_parser and add_sample_arguments declare."""
+    parser.add_argument('--exact_recon', action='store_true',
+                        help='--sample_recon: completeness from the exact point-to-triangle distance of every ground-truth point to '
+                             'the mesh of --recon (it no longer depends on the spacing); the samples still answer accuracy')
+    parser.add_argument('--exact_gt', action='store_true',
+                        help='--sample_gt, every --gt file a triangle mesh: accuracy from the exact distance of every reconstruction '
+                             'point to the ground-truth surface; the samples still answer completeness')
+    return parser
+
+
+def exact_options(parser, args):
+    """--exact_recon and --exact_gt of a parsed command line as evaluate_files' keyword arguments ({} without them); a flag without
+    its --sample_* option, --exact_gt with --gt_mlp or with a --gt file that has no faces are argument errors."""
+    options = {}
+    if args.exact_recon:
+        if args.sample_recon is None:
+            parser.error('--exact_recon needs --sample_recon: the samples remain the reconstruction\'s points for accuracy and registration')
+        options['exact_recon'] = True
+    if args.exact_gt:
+        if args.gt_mlp:
+            parser.error('--exact_gt with --gt_mlp: a MeshLab project names laser scans, not meshes')
+        if args.sample_gt is None:
+            parser.error('--exact_gt needs --sample_gt: the samples remain the ground truth\'s points for completeness')
+        try:
+            without = [p for p in args.gt or [] if not mesh_faces(p)]
+        except (OSError, ValueError) as e:
+            parser.error('--exact_gt: %s' % e)
+        if without:
+            parser.error('--exact_gt: every --gt file must be a triangle mesh, %s has no faces' % without[0])
+        options['exact_gt'] = True
+    return options
+
+
 def cli(argv=None):
-    parser = add_sample_arguments(make_parser())
+    parser = add_exact_arguments(add_sample_arguments(make_parser()))
     args = parser.parse_args(argv)
     try:
         tol = [float(t) for t in args.tolerances.split(',') if t.strip()]
@@ -707,6 +828,7 @@ def cli(argv=None):
     options = register_options(parser, args)
     options.update(eth3d_options(parser, args))
     options.update(sample_options(parser, args))
+    options.update(exact_options(parser, args))
     import torch
     torch.cuda.set_device(args.gpu_id)
     dist = {} if args.distances else None

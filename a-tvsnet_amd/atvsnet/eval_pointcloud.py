@@ -227,8 +227,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     only): the cleaned PLY carries the normals of the rows that stay -- clean_cloud.options.
     mesh (with fuse only): mesh_fusion.SceneMesh's arguments, with render=True also depths_mesh/ -- mesh_fusion.options; its
     simplify=dict(cell_voxels=R) (no command-line option) also writes final3d_mesh_simple.ply and mesh_simple.json; its
-    score=dict(spacing=S[, seed=K]) (with gt_ply only, no command-line option) samples each written mesh's surface on the device and
-    scores it into mesh_eval.json, mesh_eval_clean.json and mesh_eval_simple.json (moved by the cloud's matrix with register)."""
+    score=dict(spacing=S[, seed=K][, exact=True]) (with gt_ply only, no command-line option) samples each written mesh's surface on
+    the device and scores it into mesh_eval.json, mesh_eval_clean.json and mesh_eval_simple.json (moved by the cloud's matrix with
+    register); with exact=True completeness comes from the exact distance of every ground-truth point to the mesh itself
+    (ops.mesh_nearest) and the files carry `exact`."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'
     _check_options(use_graph=use_graph, scene_cache=scene_cache, fuse=fuse, map_files=map_files, gt_ply=gt_ply, register=register,
                    clean=clean, score_maps=score_maps, fuse_normals=fuse_normals, clean_keep_normals=clean_keep_normals, mesh=mesh)

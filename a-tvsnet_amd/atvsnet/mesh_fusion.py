@@ -117,13 +117,22 @@ def check_score(score):
     Anything else raises ValueError."""
     if score is None:
         return None
-    if not isinstance(score, dict) or 'spacing' not in score or set(score) - {'spacing', 'seed'}:
-        raise ValueError('mesh score must be a dict(spacing=S[, seed=K]), got %r' % (score,))
+    if not isinstance(score, dict) or 'spacing' not in score or set(score) - {'spacing', 'seed', 'exact'}:
+        raise ValueError('mesh score must be a dict(spacing=S[, seed=K]) with at most exact=True beside them, got %r' % (score,))
+    if not isinstance(score.get('exact', False), bool):
+        raise ValueError('mesh score: exact must be True or False, got %r' % (score['exact'],))
     try:
         density, _, seed = sample_mesh.check_options(spacing=score['spacing'], seed=score.get('seed', 0))
     except ValueError as e:
         raise ValueError('mesh score: %s' % e)
     return float(score['spacing']), seed
+
+
+def check_score_exact(score):
+    """Whether a score dict that check_score accepts asks for exact completeness (exact=True): the distance of every ground-truth
+    point to the mesh itself (section 10.3f) instead of to its samples.  False for None."""
+    check_score(score)
+    return bool(score is not None and score.get('exact', False))
 
 
 def check_support(consistent=False, weights=None, modes=WEIGHT_MODES):
@@ -304,7 +313,7 @@ class SceneMesh(object):
     (1 + agreeing views) / (1 + num_consistent), is each pixel's view weight (ops.tsdf_integrate's weights); report() gains
     `weights`.  Both come from one launch; the thresholds are the scene_fusion's own (section 10.3c).
 
-    score: None, or dict(spacing=S[, seed=K]).  run() does nothing with it; score(gt_points) samples the surface of the mesh, of the
+    score: None, or dict(spacing=S[, seed=K][, exact=True]).  run() does nothing with it; score(gt_points) samples the surface of the mesh, of the
     cleaned and of the simplified one where they exist, on the device at that spacing and scores each against the ground truth
     (section 10.3e)."""
 
@@ -314,6 +323,7 @@ class SceneMesh(object):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
         self.simplify = check_simplify(simplify)
         self.score_options = check_score(score)
+        self.score_exact = check_score_exact(score)
         self._device_simple = self._simple_result = self._simple_report = None
         self.carve_weight = check_carve_weight(carve_weight)
         self.consistent, self.weights = check_support(consistent, weights)
@@ -443,7 +453,9 @@ class SceneMesh(object):
         score=dict(spacing=, seed=) (sample_mesh.sample_device: the tensors stay where they are) and the samples scored against
         gt_points by eval_cloud.evaluate at its default tolerances; transform: a 4x4 matrix applied to the samples first (the matrix
         a registration found for the scene's cloud: the meshes are not registered again).  A result carries `recon_mesh`, the
-        sampling's report without `seconds`."""
+        sampling's report without `seconds`.  With score=dict(..., exact=True) completeness comes from the exact distance of every
+        ground-truth point to the mesh on the device (evaluate's recon_surface, moved by the same matrix), accuracy from the samples
+        as before, and a result carries `exact`."""
         from . import eval_cloud
         self.run()
         if self.score_options is None:
@@ -456,7 +468,8 @@ class SceneMesh(object):
                 continue
             vertices, _, faces = mesh
             samples, report = sample_mesh.sample_device(vertices.contiguous(), None, faces.contiguous(), spacing=spacing, seed=seed)
-            out[key] = eval_cloud.evaluate(samples.points, gt_points, device=vertices.device, **moved)
+            surface = {'recon_surface': (vertices.contiguous(), faces.contiguous())} if self.score_exact else {}
+            out[key] = eval_cloud.evaluate(samples.points, gt_points, device=vertices.device, **dict(moved, **surface))
             out[key]['recon_mesh'] = {k: report[k] for k in sample_mesh.REPORT_KEYS if k != 'seconds'}
         return out
 

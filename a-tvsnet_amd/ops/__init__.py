@@ -18,6 +18,7 @@
     mesh_topology  a mesh's connected components, a selection of its faces with the vertices compacted, its edge census
     mesh_simplify  vertex clustering: the clusters' exact sums and fixed-point quadrics, the representatives, the rewritten faces
     mesh_sample    a mesh's surface sampled uniformly by area: per-face counts by stochastic rounding, the samples' points, colours, normals
+    mesh_distance  exact point-to-triangle distances from a cloud to a mesh: a uniform grid of face references, the nearest face within a radius
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -60,4 +61,5 @@ from .mesh_topology import (MESH_CENSUS_MIN_SLOTS, MESH_CENSUS_WORDS, MESH_TOPOL
 from .mesh_simplify import (MESH_PLACEMENTS, MESH_RANK_EPSILON, MESH_SIMPLIFY_MIN_SLOTS, MESH_SIMPLIFY_SOLVE_UNITS, MeshClusters,
     mesh_cluster, mesh_cluster_faces, mesh_cluster_max_move, mesh_cluster_place, mesh_cluster_quadrics)      # noqa: F401
 from .mesh_sample import MESH_SAMPLE_MAX, MeshSamples, mesh_sample, mesh_sample_counts, mesh_sample_points      # noqa: F401
+from .mesh_distance import MESH_GRID_MAX_REFS, MeshGrid, mesh_grid, mesh_nearest      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

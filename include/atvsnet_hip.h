@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 64
+#define ATVS_ABI_VERSION 65
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1533,6 +1533,67 @@ int atvs_mesh_sample_offsets(const void* counts, long n_faces, void* scratch, lo
 int atvs_mesh_sample_place(const float* vertices, const void* colors, long n_vertices, const int* faces, long n_faces,
                            const void* offsets, long n_samples, long seed, float* points, int* sample_face, void* colors_out,
                            float* normals, long* info, atvs_stream_t stream);
+
+/* Exact point-to-triangle distances from a cloud to a mesh's surface, so that the half of a score that is measured against a mesh
+ * does not depend on a sample spacing: ops/mesh_distance.py, atvsnet/mesh_distance.py, atvsnet/eval_cloud.py --exact_recon /
+ * --exact_gt, csrc/mesh_distance.hip; DESIGN.md section 10.3f.  Pointers are device pointers.  tests/mesh_distance_restated.py
+ * restates the definition in numpy.  vertices (n_vertices,3) float32, faces (n_faces,3) int32, queries (m,3) float32, radius R > 0
+ * (float32).  n_vertices and m in 0..2^30, n_faces in 0..ATVS_MESH_TOPOLOGY_MAX_FACES, max_refs in 0..ATVS_MESH_GRID_MAX_REFS,
+ * anything else ATVS_ERR_SHAPE, as is a short grid or scratch; R not a positive finite float32, `cell` not a finite double >= 0, or
+ * max_refs < 8 n_faces: ATVS_ERR_ARG; a null pointer that is needed ATVS_ERR_NULL; all without a launch.  No host synchronisation,
+ * no allocation.  n_faces = 0, m = 0 and a mesh without a usable face are valid: every query is not found.
+ *
+ * THE DEFINITION.  A face is USABLE when its three indices are in 0..n_vertices-1 and its nine coordinates are finite.  For a
+ * finite query p and a usable face with corners a, b, c (all converted to double; every operation below is a double operation
+ * rounded on its own, the library is built with -ffp-contract=off; u.v means (u0 v0 + u1 v1) + u2 v2):
+ *     ab = b - a, ac = c - a, ap = p - a, bp = p - b, cp = p - c
+ *     n  = (ab1 ac2 - ab2 ac1, ab2 ac0 - ab0 ac2, ab0 ac1 - ab1 ac0)
+ *     d1 = ab.ap, d2 = ac.ap, d3 = ab.bp, d4 = ac.bp, d5 = ab.cp, d6 = ac.cp
+ *     vc = d1 d4 - d3 d2, vb = d5 d2 - d1 d6, va = d3 d6 - d5 d4, s = (va + vb) + vc
+ * If n is not exactly (0, 0, 0), the closest point x is that of the FIRST region whose test holds:
+ *     A         d1 <= 0 and d2 <= 0                         x = a
+ *     B         d3 >= 0 and d4 <= d3                        x = b
+ *     AB        vc <= 0 and d1 >= 0 and d3 <= 0             t = d1 / (d1 - d3),                     x = a + t ab
+ *     C         d6 >= 0 and d5 <= d6                        x = c
+ *     AC        vb <= 0 and d2 >= 0 and d6 <= 0             t = d2 / (d2 - d6),                     x = a + t ac
+ *     BC        va <= 0 and d4 - d3 >= 0 and d5 - d6 >= 0   t = (d4 - d3) / ((d4 - d3) + (d5 - d6)),  x = b + t (c - b)
+ *     interior  s > 0                                       v = vb / s, w = vc / s,                 x = (a + v ab) + w ac
+ * (the Voronoi-region form of the closest point on a triangle); a quotient whose denominator is not > 0 is taken as 0.  ZERO-AREA
+ * FACES.  Where n is exactly (0, 0, 0) -- a repeated vertex makes ab, ac or their difference exactly zero, axis-aligned collinear
+ * triples cancel exactly -- and where no test above holds (s <= 0: only roundings on a sliver can do that), the face is the union of
+ * its three segments and x comes from the SEGMENT RULE: for (X, Y) = (a, b), (a, c), (b, c) in this order, e = Y - X, w = p - X,
+ * t = (w.e) / (e.e) clamped to [0, 1], or 0 where e.e is not > 0 (a point), y = X + t e, and x is the y of the first smallest
+ * (p - y).(p - y).  So a face that is a point gives the distance to the point, a collinear triple the distance to the segment it
+ * spans, and no quotient is ever 0 / 0.  Every parameter is in [0, 1] (a clamp, or a ratio of a non-negative number to a sum it is
+ * part of), so x is a convex combination of the corners whatever the roundings did.  Then r = p - x, d2 = (float)(r.r): rounded ONCE.
+ *
+ * Per query: d2min = the minimum of d2 over the usable faces, face = the LOWEST face index attaining it -- the 64-bit minimum of
+ * (bits(d2) << 32) | face, as atvs_cloud_nearest does for points.  When (double)d2min > (double)R (double)R, or the query is not
+ * finite, or no face is usable: d2min = +inf, face = -1.  closest (m,3) float32, written when the pointer is given: (float)x of the
+ * attaining face, NaN where face = -1.  The result is a function of the mesh, the queries and R alone: the cell edge, the origin,
+ * `cell`, max_refs, the order of the references inside a cell, how many cells hold a face and the launch shape cannot be seen in
+ * it.  Integer atomics only.
+ *
+ * atvs_mesh_grid_build.  grid: atvs_mesh_grid_scratch_size(n_faces, max_refs) bytes; it IS the grid afterwards (a copy of the usable
+ * faces' corners included: the search does not read the mesh again).  A uniform grid over the bounding box of the usable faces'
+ * corners; cell edge h >= max(R (1 + 2^-18), cell, 2^-60), larger where the box would need more cells than the point-cloud grid's
+ * cap for n_faces points; a usable face is referenced from every cell that the box of its corners overlaps (csrc/mesh_distance.hip
+ * says why the 27 cells around a query then hold every face within R).  info: four int64 words, [0] the references that h needs,
+ * [1] 1 when [0] <= max_refs and the grid was built, else 0: the grid is then NOT searchable (atvs_mesh_nearest reports every
+ * query not found) and the caller calls again with a larger `cell`; [2] the usable faces; [3] h as the bits of a double.  Once h
+ * reaches the box's extent a face is in at most 8 cells, which is why max_refs >= 8 n_faces is required: a caller that at least
+ * doubles `cell` each time ends.
+ *
+ * atvs_mesh_nearest.  scratch: atvs_mesh_nearest_scratch_size(n_faces, m) bytes (the queries' counting sort by the grid's cells).
+ * n_faces and max_refs are those of the build.  d2 (m,) float32, face (m,) int32, closest (m,3) float32 or null: every row is
+ * written. */
+#define ATVS_MESH_GRID_MAX_REFS 2147483647
+int atvs_mesh_grid_scratch_size(long n_faces, long max_refs, long* bytes);
+int atvs_mesh_grid_build(const float* vertices, long n_vertices, const int* faces, long n_faces, float radius, double cell,
+                         long max_refs, void* grid, long grid_bytes, long* info, atvs_stream_t stream);
+int atvs_mesh_nearest_scratch_size(long n_faces, long m, long* bytes);
+int atvs_mesh_nearest(const void* grid, long grid_bytes, long n_faces, long max_refs, const float* queries, long m, void* scratch,
+                      long scratch_bytes, float* d2, int* face, float* closest, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
