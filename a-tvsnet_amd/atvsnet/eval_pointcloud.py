@@ -114,7 +114,9 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
     """final3d_mesh.ply and mesh.json -> (the face count, the SceneMesh).  After the cloud: the fusion's result bounds the volume.
     With clean= in `mesh` also final3d_mesh_clean.ply and mesh_clean.json, the mesh without its small components (SceneMesh's
     clean=); with simplify= also final3d_mesh_simple.ply and mesh_simple.json, the mesh (the cleaned one with clean=) after vertex
-    clustering.  score= writes nothing here: _score_mesh does, once the cloud's score is known."""
+    clustering; with smooth= also final3d_mesh_smooth.ply (with normals when smooth= asks for them) and mesh_smooth.json, the mesh
+    (the cleaned one with clean=) after Taubin's filter, which simplify= then takes.  score= writes nothing here: _score_mesh does,
+    once the cloud's score is known."""
     t0 = time.time()
     scene_mesh = mesh_fusion.SceneMesh(scene_fusion, map_cams, **mesh)
     n_faces = scene_mesh.write_ply(os.path.join(folder, 'final3d_mesh.ply'))
@@ -124,6 +126,9 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
     if mesh.get('clean'):
         scene_mesh.write_clean_ply(os.path.join(folder, 'final3d_mesh_clean.ply'))
         mesh_fusion.write_json(os.path.join(folder, 'mesh_clean.json'), scene_mesh.clean_report())
+    if mesh.get('smooth'):
+        scene_mesh.write_smooth_ply(os.path.join(folder, 'final3d_mesh_smooth.ply'))
+        mesh_fusion.write_json(os.path.join(folder, 'mesh_smooth.json'), scene_mesh.smooth_report())
     if mesh.get('simplify'):
         scene_mesh.write_simple_ply(os.path.join(folder, 'final3d_mesh_simple.ply'))
         mesh_fusion.write_json(os.path.join(folder, 'mesh_simple.json'), scene_mesh.simplify_report())
@@ -132,7 +137,8 @@ def _write_mesh(scene_fusion, map_cams, folder, mesh):
 
 
 def _score_mesh(scene_mesh, score, folder, opts):
-    """mesh_eval.json, with clean= also mesh_eval_clean.json, with simplify= also mesh_eval_simple.json: each mesh's surface sampled
+    """mesh_eval.json, with clean= also mesh_eval_clean.json, with smooth= also mesh_eval_smooth.json, with simplify= also
+    mesh_eval_simple.json: each mesh's surface sampled
     on the device (mesh score=dict(spacing=, seed=)) and scored against the ground truth, moved by the matrix found for the cloud
     (as _clean_cloud moves the cleaned cloud), not registered again."""
     t0 = time.time()
@@ -141,7 +147,7 @@ def _score_mesh(scene_mesh, score, folder, opts):
         moved = score['registration']['matrix']
     elif score is not None and 'init_transform' in score:
         moved = score['init_transform']
-    names = {'mesh': 'mesh_eval.json', 'clean': 'mesh_eval_clean.json', 'simple': 'mesh_eval_simple.json'}
+    names = {'mesh': 'mesh_eval.json', 'clean': 'mesh_eval_clean.json', 'smooth': 'mesh_eval_smooth.json', 'simple': 'mesh_eval_simple.json'}
     for key, result in scene_mesh.score(opts.gt_points, moved).items():
         eval_cloud.write_json(os.path.join(folder, names[key]), result)
     TIMES['mesh_eval'] = time.time() - t0
@@ -227,8 +233,10 @@ def run_eval_pc(savepath, image_infos, use_graph=True, scene_cache=False, write_
     only): the cleaned PLY carries the normals of the rows that stay -- clean_cloud.options.
     mesh (with fuse only): mesh_fusion.SceneMesh's arguments, with render=True also depths_mesh/ -- mesh_fusion.options; its
     simplify=dict(cell_voxels=R) (no command-line option) also writes final3d_mesh_simple.ply and mesh_simple.json; its
+    smooth=dict(iterations=N[, lam=, mu=, pin_boundary=, normals=]) (no command-line option) also writes final3d_mesh_smooth.ply and
+    mesh_smooth.json, and the simplification then takes the smoothed mesh; its
     score=dict(spacing=S[, seed=K][, exact=True]) (with gt_ply only, no command-line option) samples each written mesh's surface on
-    the device and scores it into mesh_eval.json, mesh_eval_clean.json and mesh_eval_simple.json (moved by the cloud's matrix with
+    the device and scores it into mesh_eval.json, mesh_eval_clean.json, mesh_eval_smooth.json and mesh_eval_simple.json (moved by the cloud's matrix with
     register); with exact=True completeness comes from the exact distance of every ground-truth point to the mesh itself
     (ops.mesh_nearest) and the files carry `exact`."""
     assert FLAGS.view_num > 2, 'the ETH3D driver runs the multi-view (AANet) pipeline'

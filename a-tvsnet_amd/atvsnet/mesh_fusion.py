@@ -9,6 +9,8 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
     clean=         SceneMesh and the tool also give the mesh without its small connected components (clean_mesh, section 10.3a)
     simplify=      SceneMesh also gives the mesh -- the cleaned one with clean= -- simplified by vertex clustering on a lattice of
                    cell_voxels voxels (simplify_mesh, section 10.3d); off unless asked
+    smooth=        SceneMesh also gives the mesh -- the cleaned one with clean= -- smoothed by Taubin's filter, with vertex normals when
+                   asked (smooth_mesh, section 10.3g); simplify= then takes the smoothed mesh; off unless asked
     score=         SceneMesh.score samples each of these meshes' surfaces on the device (sample_mesh, section 10.3e) and scores the
                    samples against a ground truth (eval_cloud.evaluate); the ETH3D driver writes mesh_eval*.json; off unless asked
 
@@ -23,8 +25,9 @@ marching tetrahedra (ops.tsdf_mesh), both csrc/tsdf.hip.
 
 What this is not: there are no weights from the viewing angle, the ETH3D driver has no probability weights (its staged slab does not
 keep the probabilities; mesh_consistent reads them from the files) and no command-line option for consistent=, weights= and
-simplify= and score= (they are run_eval_pc's mesh arguments; a written mesh is simplified by the command atvsnet/simplify_mesh.py), no hole
-filling, and the PLY carries no normals.
+simplify=, smooth= and score= (they are run_eval_pc's mesh arguments; a written mesh is simplified by the command
+atvsnet/simplify_mesh.py and smoothed by atvsnet/smooth_mesh.py), no hole filling, and only the smoothed mesh's PLY carries normals
+(smooth=dict(..., normals=True)).
 Without carve_weight a view adds to a voxel only inside the narrow band around its depth.  Fragments are removed only when asked
 (the clean_ options have no defaults).  `trunc_voxels` and `min_weight` have defaults, not measurements.  This module imports
 without a GPU.
@@ -41,7 +44,7 @@ import time
 import numpy as np
 
 from ..tools.common import write_json  # noqa: F401
-from . import clean_mesh, eval_depth, sample_mesh, simplify_mesh
+from . import clean_mesh, eval_depth, sample_mesh, simplify_mesh, smooth_mesh
 
 DEFAULT_TRUNC_VOXELS = 4.0         # a default, not a measurement: the band reaches four voxels either side of a depth
 DEFAULT_MIN_WEIGHT = 2.0           # a default, not a measurement: the fusion's num_consistent
@@ -54,14 +57,15 @@ TOOL_WEIGHT_MODES = ('agree', 'prob')      # the tool also reads the probability
 
 def check_options(voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT, max_blocks=DEFAULT_MAX_BLOCKS,
                   pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None, consistent=False, weights=None,
-                  simplify=None, score=None):
+                  simplify=None, score=None, smooth=None):
     """-> the options as (voxel, trunc_voxels, min_weight, max_blocks, pixel_centre); a bad one raises ValueError.  render (whether
     the driver also renders the mesh) has nothing to check; clean (None, or a dict of clean_mesh.clean's criteria) is checked there,
-    carve_weight by check_carve_weight, consistent and weights by check_support, simplify by check_simplify, score by check_score
-    (they are not part of the tuple)."""
+    carve_weight by check_carve_weight, consistent and weights by check_support, simplify by check_simplify, score by check_score,
+    smooth by check_smooth (they are not part of the tuple)."""
     if clean is not None:
         clean_mesh.check_criteria(**clean)
     check_simplify(simplify)
+    check_smooth(smooth)
     check_score(score)
     check_carve_weight(carve_weight)
     check_support(consistent, weights)
@@ -109,6 +113,23 @@ def check_simplify(simplify):
     except ValueError as e:
         raise ValueError('mesh simplify: %s' % str(e).replace('cell must', 'cell_voxels must'))
     return cell, placement, rank_epsilon
+
+
+def check_smooth(smooth):
+    """-> None (no smoothing) or dict(iterations=, lam=, mu=, pin_boundary=, normals=) with smooth_mesh's defaults filled in: smooth
+    is a dict(iterations=N[, lam=, mu=, pin_boundary=, normals=]); mu=None is Laplacian smoothing.  Anything else raises
+    ValueError."""
+    if smooth is None:
+        return None
+    if not isinstance(smooth, dict) or 'iterations' not in smooth or set(smooth) - {'iterations', 'lam', 'mu', 'pin_boundary', 'normals'}:
+        raise ValueError('mesh smooth must be a dict(iterations=N[, lam=, mu=, pin_boundary=, normals=]), got %r' % (smooth,))
+    try:
+        iterations, lam, mu, pin_boundary, normals, _ = smooth_mesh.check_options(
+            smooth['iterations'], smooth.get('lam', smooth_mesh.DEFAULT_LAMBDA), smooth.get('mu', smooth_mesh.DEFAULT_MU),
+            smooth.get('pin_boundary', False), smooth.get('normals', False))
+    except ValueError as e:
+        raise ValueError('mesh smooth: %s' % e)
+    return dict(iterations=iterations, lam=lam, mu=mu, pin_boundary=pin_boundary, normals=normals)
 
 
 def check_score(score):
@@ -304,6 +325,13 @@ class SceneMesh(object):
     R voxels whose origin is the volume's, so they sit on the voxel lattice; run()'s result, report() and the cleaned mesh stay as
     they are, and simplify_result(), simplify_report() and write_simple_ply(path) give the simplified one (section 10.3d).
 
+    smooth: None, or dict(iterations=N[, lam=0.5, mu=-0.53, pin_boundary=False, normals=False]).  With it run() also smooths the mesh
+    -- the cleaned one when clean= is given -- on the device by Taubin's filter (smooth_mesh.smooth_device); colours and faces stay;
+    with normals=True the smoothed mesh gets vertex normals whose area unit is voxel^2 (every face larger than a voxel's votes 1, the
+    slivers of marching tetrahedra in proportion).  run()'s result, report() and the cleaned mesh stay as they are; smooth_result(),
+    smooth_report() and write_smooth_ply(path) give the smoothed one (section 10.3g).  With simplify= also given, the simplification
+    takes the smoothed mesh and its report's source is 'smooth'.
+
     carve_weight: None, or the weight of a free vote: the staged planes are integrated with free-space carving (section 10.3b) and
     report() gains carve_weight, free_voxels and max_free.
 
@@ -319,9 +347,11 @@ class SceneMesh(object):
 
     def __init__(self, scene_fusion, cams, voxel, trunc_voxels=DEFAULT_TRUNC_VOXELS, min_weight=DEFAULT_MIN_WEIGHT,
                  max_blocks=DEFAULT_MAX_BLOCKS, pixel_centre=DEFAULT_PIXEL_CENTRE, render=False, clean=None, carve_weight=None,
-                 consistent=False, weights=None, simplify=None, score=None):
+                 consistent=False, weights=None, simplify=None, score=None, smooth=None):
         self.options = check_options(voxel, trunc_voxels, min_weight, max_blocks, pixel_centre, clean=clean)
         self.simplify = check_simplify(simplify)
+        self.smooth = check_smooth(smooth)
+        self._device_smooth = self._smooth_result = self._smooth_report = None
         self.score_options = check_score(score)
         self.score_exact = check_score_exact(score)
         self._device_simple = self._simple_result = self._simple_report = None
@@ -378,12 +408,18 @@ class SceneMesh(object):
             if self.clean is not None:
                 vertices, colors, faces, self._clean_report = clean_mesh.clean_device(*mesh, **self.clean)
                 self._device_clean = (vertices, colors, faces)
+            source, source_name = (mesh, 'mesh') if self.clean is None else (self._device_clean, 'clean')
+            if self.smooth is not None:
+                vertices, colors, faces, normals, self._smooth_report = smooth_mesh.smooth_device(
+                    *source, area_unit=voxel * voxel if self.smooth['normals'] else None, **self.smooth)
+                self._smooth_report.update(source=source_name)
+                self._device_smooth = (vertices, colors, faces, normals)
+                source, source_name = (vertices, colors, faces), 'smooth'
             if self.simplify is not None:
                 cell_voxels, placement, rank_epsilon = self.simplify
-                source = mesh if self.clean is None else self._device_clean
                 vertices, colors, faces, self._simple_report = simplify_mesh.simplify_device(
                     *source, cell=cell_voxels * voxel, placement=placement, origin=self.volume.origin, rank_epsilon=rank_epsilon)
-                self._simple_report.update(cell_voxels=cell_voxels, source='clean' if self.clean is not None else 'mesh')
+                self._simple_report.update(cell_voxels=cell_voxels, source=source_name)
                 self._device_simple = (vertices, colors, faces)
             t0 = time.time()
             self.result = tuple(None if t is None else t.cpu().numpy() for t in mesh)
@@ -437,7 +473,7 @@ class SceneMesh(object):
         return self._simple_result
 
     def simplify_report(self):
-        """run() -> simplify_mesh.simplify_device's report, with cell_voxels and the source ('mesh' or 'clean')."""
+        """run() -> simplify_mesh.simplify_device's report, with cell_voxels and the source ('mesh', 'clean' or 'smooth')."""
         self._simplified()
         return self._simple_report
 
@@ -448,8 +484,33 @@ class SceneMesh(object):
         ply.write_mesh(path, vertices, colors, faces)
         return len(faces)
 
+    def _smoothed(self):
+        self.run()
+        if self._device_smooth is None:
+            raise RuntimeError('SceneMesh: no smooth= was given: there is no smoothed mesh')
+        return self._device_smooth
+
+    def smooth_result(self):
+        """run() -> the smoothed mesh (vertices, colors, faces, normals or None) as numpy arrays."""
+        device = self._smoothed()
+        if self._smooth_result is None:
+            self._smooth_result = tuple(None if t is None else t.cpu().numpy() for t in device)
+        return self._smooth_result
+
+    def smooth_report(self):
+        """run() -> smooth_mesh.smooth_device's report, with the source ('mesh' or 'clean')."""
+        self._smoothed()
+        return self._smooth_report
+
+    def write_smooth_ply(self, path):
+        """The smoothed mesh into a binary PLY at `path`, with its normals where smooth= asked for them -> the number of faces."""
+        from ..tools import ply
+        vertices, colors, faces, normals = self.smooth_result()
+        ply.write_mesh(path, vertices, colors, faces, normals)
+        return len(faces)
+
     def score(self, gt_points, transform=None):
-        """run() -> {'mesh': result[, 'clean': result][, 'simple': result]}: each mesh this object holds on the device sampled at
+        """run() -> {'mesh': result[, 'clean': result][, 'smooth': result][, 'simple': result]}: each mesh this object holds on the device sampled at
         score=dict(spacing=, seed=) (sample_mesh.sample_device: the tensors stay where they are) and the samples scored against
         gt_points by eval_cloud.evaluate at its default tolerances; transform: a 4x4 matrix applied to the samples first (the matrix
         a registration found for the scene's cloud: the meshes are not registered again).  A result carries `recon_mesh`, the
@@ -463,10 +524,11 @@ class SceneMesh(object):
         spacing, seed = self.score_options
         moved = {} if transform is None else {'init_transform': transform}
         out = {}
-        for key, mesh in (('mesh', self._device_mesh), ('clean', self._device_clean), ('simple', self._device_simple)):
+        for key, mesh in (('mesh', self._device_mesh), ('clean', self._device_clean), ('smooth', self._device_smooth),
+                          ('simple', self._device_simple)):
             if mesh is None:
                 continue
-            vertices, _, faces = mesh
+            vertices, _, faces = mesh[:3]
             samples, report = sample_mesh.sample_device(vertices.contiguous(), None, faces.contiguous(), spacing=spacing, seed=seed)
             surface = {'recon_surface': (vertices.contiguous(), faces.contiguous())} if self.score_exact else {}
             out[key] = eval_cloud.evaluate(samples.points, gt_points, device=vertices.device, **dict(moved, **surface))
@@ -545,8 +607,8 @@ def options(parser, args, prefix=''):
 
 def rules(mesh, fuse, gt_ply=None):
     """The ETH3D driver's rules for its mesh, as (broken, message) rows: none without mesh; the rows of carve_weight, consistent,
-    weights, clean, simplify and score only when they are given (consistent, weights, simplify and score reach the driver through
-    run_eval_pc's mesh dict alone: its command line has no option for them).  score's rows stand behind the others."""
+    weights, clean, simplify, smooth and score only when they are given (consistent, weights, simplify, smooth and score reach the
+    driver through run_eval_pc's mesh dict alone: its command line has no option for them).  score's rows stand behind the others."""
     if mesh is None:
         return []
     rows = [(fuse is None, '--mesh_voxel, --mesh_trunc_voxels, --mesh_min_weight and --mesh_max_blocks need --fuse (mesh needs fuse): the '
@@ -566,6 +628,9 @@ def rules(mesh, fuse, gt_ply=None):
     if mesh.get('simplify') is not None:
         rows.insert(1, (mesh.get('voxel') is None, 'mesh simplify= needs voxel=: there is no mesh to simplify, and its cells are '
                                                    'counted in voxels'))
+    if mesh.get('smooth') is not None:
+        rows.insert(1, (mesh.get('voxel') is None, 'mesh smooth= needs voxel=: there is no mesh to smooth, and its normals\' area unit '
+                                                   'is a voxel\'s'))
     if mesh.get('score') is not None:
         rows += [(mesh.get('voxel') is None, 'mesh score= needs voxel=: there is no mesh to score'),
                  (not gt_ply, 'mesh score= needs gt_ply: there is no ground truth to score the mesh\'s samples against')]

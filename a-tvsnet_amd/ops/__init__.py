@@ -1,4 +1,4 @@
-"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in fourteen modules --
+"""Python face of the C-ABI (include/atvsnet_hip.h): one function per entry point, in these modules --
 
     base      ctypes plumbing, the dispatch switches (`cfg`, `configure`), launch timing
     packing   weights in operand order + their cache, tap lists, the chunk-planar layout
@@ -19,6 +19,8 @@
     mesh_simplify  vertex clustering: the clusters' exact sums and fixed-point quadrics, the representatives, the rewritten faces
     mesh_sample    a mesh's surface sampled uniformly by area: per-face counts by stochastic rounding, the samples' points, colours, normals
     mesh_distance  exact point-to-triangle distances from a cloud to a mesh: a uniform grid of face references, the nearest face within a radius
+    mesh_smooth    Taubin smoothing: the vertices' distinct neighbours, positions as integers, the umbrella step as an exact gather;
+              area-weighted vertex normals
 
 Every name is re-exported here (`ops.conv`, `ops.cfg`, ...): callers import this package, never a submodule.  The modules share
 ONE set of state objects (`cfg`, the pack caches, the timing watch), defined once in base / packing and imported by reference.
@@ -62,4 +64,8 @@ from .mesh_simplify import (MESH_PLACEMENTS, MESH_RANK_EPSILON, MESH_SIMPLIFY_MI
     mesh_cluster, mesh_cluster_faces, mesh_cluster_max_move, mesh_cluster_place, mesh_cluster_quadrics)      # noqa: F401
 from .mesh_sample import MESH_SAMPLE_MAX, MeshSamples, mesh_sample, mesh_sample_counts, mesh_sample_points      # noqa: F401
 from .mesh_distance import MESH_GRID_MAX_REFS, MeshGrid, mesh_grid, mesh_nearest      # noqa: F401
+from .mesh_smooth import (MESH_ADJACENCY_INFO, MESH_ADJACENCY_MIN_SLOTS, MESH_FLAG_BOUNDARY, MESH_FLAG_FINITE, MESH_FLAG_NONMANIFOLD,
+    MESH_SMOOTH_LAMBDA, MESH_SMOOTH_MAX_ITERATIONS, MESH_SMOOTH_MU, MeshAdjacency, mesh_adjacency, mesh_dequantize, mesh_face_extent,
+    mesh_normals_from_sums, mesh_quantize, mesh_smooth, mesh_smooth_lattice, mesh_smooth_pass, mesh_vertex_normal_sums,
+    mesh_vertex_normals)      # noqa: F401
 from .. import _lib      # noqa: F401  (ops._lib: tests and tools reach the loader through this package)

@@ -1,7 +1,7 @@
 """Binary PLY point clouds in the layout the reference's fusibile writes (fusibile/displayUtils.h:80-135):
 `format binary_little_endian 1.0`, vertices of (float x, y, z, uchar red, green, blue); with normals (not in the reference)
-(float x, y, z, nx, ny, nz, uchar red, green, blue).  Triangle meshes (write_mesh / read_mesh): the same vertex element followed by
-`element face` with `property list uchar int vertex_indices`."""
+(float x, y, z, nx, ny, nz, uchar red, green, blue).  Triangle meshes (write_mesh / read_mesh / read_mesh_normals): either vertex
+element followed by `element face` with `property list uchar int vertex_indices`."""
 import numpy as np
 
 _VERTEX = np.dtype([('x', '<f4'), ('y', '<f4'), ('z', '<f4'), ('red', 'u1'), ('green', 'u1'), ('blue', 'u1')])
@@ -80,10 +80,11 @@ def read_ply(path):
     return read_ply_normals(path)[:2]
 
 
-def write_mesh(path, vertices, colors, faces):
+def write_mesh(path, vertices, colors, faces, normals=None):
     """vertices (V,3) float32, colors (V,3) uint8 (r, g, b) or None (white), faces (F,3) int32 -> a binary little-endian PLY:
-    `element vertex` as write_ply writes it (x y z red green blue), then `element face` with
-    `property list uchar int vertex_indices`.  A face index outside the vertices raises."""
+    `element vertex` as write_ply writes it (x y z red green blue; with normals (V,3) float32 x y z nx ny nz red green blue, a
+    non-finite normal as (0,0,0)), then `element face` with `property list uchar int vertex_indices`.  A face index outside the
+    vertices raises."""
     vertices = np.asarray(vertices, np.float32).reshape(-1, 3)
     faces = np.asarray(faces).reshape(-1, 3)
     if colors is None:
@@ -93,9 +94,15 @@ def write_mesh(path, vertices, colors, faces):
         raise ValueError('write_mesh: %d colors for %d vertices' % (len(colors), len(vertices)))
     if len(faces) and (faces.min() < 0 or faces.max() >= len(vertices)):
         raise ValueError('write_mesh: a face index outside 0..%d' % (len(vertices) - 1))
-    v = np.empty(len(vertices), _VERTEX)
+    v = np.empty(len(vertices), _VERTEX if normals is None else _VERTEX_N)
     v['x'], v['y'], v['z'] = vertices[:, 0], vertices[:, 1], vertices[:, 2]
     v['red'], v['green'], v['blue'] = colors[:, 0], colors[:, 1], colors[:, 2]
+    if normals is not None:
+        normals = np.asarray(normals, np.float32).reshape(-1, 3).copy()
+        if len(normals) != len(vertices):
+            raise ValueError('write_mesh: %d normals for %d vertices' % (len(normals), len(vertices)))
+        normals[~np.isfinite(normals).all(axis=1)] = 0.0
+        v['nx'], v['ny'], v['nz'] = normals[:, 0], normals[:, 1], normals[:, 2]
     t = np.empty(len(faces), _FACE)
     t['n'] = 3
     t['v'] = faces
@@ -107,8 +114,9 @@ def write_mesh(path, vertices, colors, faces):
         t.tofile(f)
 
 
-def read_mesh(path):
-    """-> (vertices (V,3) float32, colors (V,3) uint8, faces (F,3) int32) of a file written by write_mesh."""
+def read_mesh_normals(path):
+    """-> (vertices (V,3) float32, colors (V,3) uint8, faces (F,3) int32, normals (V,3) float32 or None) of a file written by
+    write_mesh, by the vertex properties its header lists: with or without nx, ny, nz."""
     with open(path, 'rb') as f:
         lines = []
         while not lines or lines[-1] != 'end_header':
@@ -118,16 +126,23 @@ def read_mesh(path):
             lines.append(raw.decode('ascii').strip())
         elements = [ln.split() for ln in lines if ln.startswith('element')]
         props = [ln for ln in lines if ln.startswith('property')]
-        if ([e[1] for e in elements] != ['vertex', 'face'] or lines[1] != 'format binary_little_endian 1.0' or
-                [p.split()[-1] for p in props[:-1]] != list(_VERTEX.names) or props[-1] != 'property list uchar int vertex_indices'):
+        layout = {_VERTEX.names: _VERTEX, _VERTEX_N.names: _VERTEX_N}.get(tuple(p.split()[-1] for p in props[:-1]))
+        if ([e[1] for e in elements] != ['vertex', 'face'] or lines[1] != 'format binary_little_endian 1.0' or layout is None or
+                props[-1] != 'property list uchar int vertex_indices'):
             raise ValueError('%s: not a mesh layout write_mesh writes' % path)
         nv, nf = int(elements[0][2]), int(elements[1][2])
-        v = np.fromfile(f, _VERTEX, nv)
+        v = np.fromfile(f, layout, nv)
         t = np.fromfile(f, _FACE, nf)
     if len(v) != nv or len(t) != nf or (nf and (t['n'] != 3).any()):
         raise ValueError('%s: truncated body, or a face that is no triangle' % path)
+    normals = np.stack([v['nx'], v['ny'], v['nz']], -1).reshape(-1, 3) if layout is _VERTEX_N else None
     return (np.stack([v['x'], v['y'], v['z']], -1).reshape(-1, 3), np.stack([v['red'], v['green'], v['blue']], -1).reshape(-1, 3),
-            t['v'].astype(np.int32).reshape(-1, 3))
+            t['v'].astype(np.int32).reshape(-1, 3), normals)
+
+
+def read_mesh(path):
+    """-> (vertices (V,3) float32, colors (V,3) uint8, faces (F,3) int32) of a file written by write_mesh (with or without normals)."""
+    return read_mesh_normals(path)[:3]
 
 
 _PLY_TYPES = {'char': 'i1', 'int8': 'i1', 'uchar': 'u1', 'uint8': 'u1', 'short': 'i2', 'int16': 'i2', 'ushort': 'u2', 'uint16': 'u2',

@@ -36,7 +36,7 @@ enum {
 
 /* ABI version of this header (bumped on any signature change).  atvs_abi_version() returns the value the library
  * was compiled with; the loader (a-tvsnet_amd/_lib.py) refuses a library whose version differs from this header's. */
-#define ATVS_ABI_VERSION 65
+#define ATVS_ABI_VERSION 66
 int atvs_abi_version(void);
 /* "gfx950" -- the only code object in the library. */
 const char* atvs_target_arch(void);
@@ -1594,6 +1594,81 @@ int atvs_mesh_grid_build(const float* vertices, long n_vertices, const int* face
 int atvs_mesh_nearest_scratch_size(long n_faces, long m, long* bytes);
 int atvs_mesh_nearest(const void* grid, long grid_bytes, long n_faces, long max_refs, const float* queries, long m, void* scratch,
                       long scratch_bytes, float* d2, int* face, float* closest, atvs_stream_t stream);
+
+/* A triangle mesh smoothed by Taubin's filter (umbrella weights), and its vertex normals: ops/mesh_smooth.py, atvsnet/smooth_mesh.py,
+ * csrc/mesh_smooth.hip; DESIGN.md section 10.3g.  Pointers are device pointers except origin (HOST, 3 finite doubles).  Integer
+ * atomics only, no float atomics: every output is a function of the inputs alone, bit for bit on every run -- with ONE exception, the
+ * order inside a row of `neighbours` (below), which no result computed from it can show.  No host synchronisation, no allocation;
+ * scratch is the caller's.  The library is built with -ffp-contract=off and the definitions rely on it: every operation below is a
+ * double operation rounded on its own.  tests/mesh_smooth_restated.py restates the definitions in numpy.  vertices (n_vertices,3)
+ * float32, faces (n_faces,3) int32; n_vertices in 0..2^30, n_faces in 0..ATVS_MESH_TOPOLOGY_MAX_FACES, n_neighbours in
+ * 0..6 ATVS_MESH_TOPOLOGY_MAX_FACES, anything else ATVS_ERR_SHAPE, as is a short scratch; a bad step, factor, area_unit or origin, or
+ * aliased q buffers, ATVS_ERR_ARG; a null pointer that is needed ATVS_ERR_NULL; all without a launch.
+ *
+ * atvs_mesh_adjacency.  The distinct neighbours of every vertex.  A face is usable when its three indices are in 0..n_vertices-1;
+ * the others are counted in info[3] and skipped.  Each usable face gives its three pairs (i0,i1), (i1,i2), (i2,i0), sorted into
+ * (lo, hi).  A pair with lo == hi is dropped and counted in info[4]; else a pair that names a vertex with a non-finite coordinate is
+ * dropped and counted in info[5] (both per face and pair, not per distinct pair).  The distinct pairs that remain, with the number of
+ * faces on each, go into an open-addressing table as atvs_mesh_edge_census does it: 64-bit key (lo << 32) | hi, the smallest power of
+ * two of slots that is at least 6 n_faces and at least ATVS_MESH_ADJACENCY_MIN_SLOTS, load at most 0.5, every probe loop bounded by
+ * the table.  degree (n_vertices,) int32: the number of distinct neighbours.  flags (n_vertices,) int32: bit 0 = all three
+ * coordinates finite; bit 1 = endpoint of a pair with exactly one face (a boundary vertex); bit 2 = endpoint of a pair with more
+ * than two faces.  offsets (n_vertices+1,) int32: the exclusive prefix sum of degree, by the point-cloud kernels' scan (6 x 2^28
+ * fits).  neighbours (6 n_faces,) int32: the first offsets[n_vertices] entries are written; row v = entries offsets[v] ..
+ * offsets[v+1]-1 holds v's distinct neighbours in an ORDER THAT IS NOT DEFINED (it is the order of arrival at a per-vertex cursor).
+ * info: seven int64 words, zeroed here: [0] distinct pairs, [1] boundary pairs (one face), [2] non-manifold pairs (more than two
+ * faces), [3] faces with an index out of range, [4] self pairs dropped, [5] pairs dropped for a non-finite vertex, [6] pairs that
+ * found no slot (impossible at that load).  scratch: atvs_mesh_adjacency_scratch_size(n_vertices, n_faces) bytes: the table (12 bytes
+ * a slot), a cursor per vertex and the scan's tile sums.
+ *
+ * atvs_mesh_quantize.  Positions as integers, so that a sum of neighbours is exact and has no order.  step: a positive power of two.
+ * Per coordinate q = llrint(((double)x - origin_a) / step) (ties to even); q (n_vertices,3) int64.  A vertex with a non-finite
+ * coordinate gets the row 0, 0, 0.  info: two int64 words, zeroed here: [0] non-finite vertices, [1] coordinates with |q| > 2^31; no
+ * output is defined unless [1] is 0.
+ *
+ * atvs_mesh_smooth_pass.  One umbrella step, one lane per vertex, q_in -> q_out (both (n_vertices,3) int64; they must not alias).
+ * factor: a finite double with |factor| <= 1.  A vertex keeps its q_in when it is not finite (flags bit 0 clear), when its degree is
+ * 0, or when flags & pin_mask is non-zero.  Otherwise, per axis: S = the exact int64 sum of q_in over the degree[v] entries of
+ * neighbours from offsets[v] on; m = (double)S / (double)degree; d = m - (double)q; q_out = q + llrint(factor d), clamped to
+ * [-2^32, 2^32].  |q| <= 2^32 and degree < 2^30 keep |S| below 2^62.  info: two int32 words that the CALLER zeroes before its
+ * first pass and that every pass adds to (32-bit integer atomics): [0] clamped coordinates (non-zero: the filter has diverged), [1]
+ * lanes whose row would leave the n_neighbours entries of `neighbours` or that read an index outside 0..n_vertices-1: they keep
+ * q_in.  No load or store leaves its buffer whatever the arrays hold.  No other atomics.
+ *
+ * atvs_mesh_dequantize.  q, the q0 that atvs_mesh_quantize gave, and its input vertices -> vertices_out (n_vertices,3) float32: a
+ * coordinate whose q equals its q0 keeps the BITS of the input coordinate; any other is (float)(origin_a + step (double)q).  So
+ * pinned, isolated and non-finite vertices, and zero passes, return the input bits.
+ *
+ * atvs_mesh_face_extent.  One lane per face: m = (b - a) x (c - a) in double in atvs_mesh_sample_counts' form (differences of
+ * (double) coordinates, products then one subtraction per component), s = sqrt((m0 m0 + m1 m1) + m2 m2), twice the area.  info:
+ * four int64 words, zeroed here: [0] the maximum of the finite s as the bits of a double (a 64-bit integer atomic max: a non-negative
+ * double's bits order as its value), [1] usable faces (indices in range, s finite), [2] faces with an index out of range, [3] faces
+ * with a non-finite s.
+ *
+ * atvs_mesh_vertex_normal_sums.  area_unit: a finite double > 0.  For each face with indices in range and finite s > 0: n = m / s,
+ * w = min(1, s / area_unit), and to each of its three vertices llrint((w n_a) 2^30) per axis is added into sums (n_vertices,3) int64
+ * with 64-bit integer atomics, and 1 into incidences (n_vertices,) int32; both zeroed here.  A face with a repeated index has m
+ * exactly 0 and adds nothing.  At most 3 x 2^28 incidences of terms <= 2^30: no overflow.  With area_unit = the maximum s this is
+ * plain area weighting; with a smaller unit every face larger than it votes 1 (atvs_mesh_cluster_quadrics' saturating weight).
+ * info: one int32, zeroed here: faces with an index out of range (skipped).
+ *
+ * atvs_mesh_vertex_normals.  One lane per vertex; the sums are INPUTS.  N = (double)sum, L = sqrt((N0 N0 + N1 N1) + N2 N2); normals
+ * (n_vertices,3) float32: (float)(N_a / L) where L > 0, else 0, 0, 0.  Normals point the way the winding says. */
+#define ATVS_MESH_ADJACENCY_MIN_SLOTS 1024
+int atvs_mesh_adjacency_scratch_size(long n_vertices, long n_faces, long* bytes);
+int atvs_mesh_adjacency(const float* vertices, long n_vertices, const int* faces, long n_faces, void* scratch, long scratch_bytes,
+                        int* degree, int* flags, int* offsets, int* neighbours, long* info, atvs_stream_t stream);
+int atvs_mesh_quantize(const float* vertices, long n_vertices, const double* origin, double step, long* q, long* info,
+                       atvs_stream_t stream);
+int atvs_mesh_smooth_pass(const long* q_in, long n_vertices, const int* degree, const int* flags, const int* offsets,
+                          const int* neighbours, long n_neighbours, double factor, int pin_mask, long* q_out, int* info,
+                          atvs_stream_t stream);
+int atvs_mesh_dequantize(const long* q, const long* q0, const float* vertices, long n_vertices, const double* origin, double step,
+                         float* vertices_out, atvs_stream_t stream);
+int atvs_mesh_face_extent(const float* vertices, long n_vertices, const int* faces, long n_faces, long* info, atvs_stream_t stream);
+int atvs_mesh_vertex_normal_sums(const float* vertices, long n_vertices, const int* faces, long n_faces, double area_unit, long* sums,
+                                 int* incidences, int* info, atvs_stream_t stream);
+int atvs_mesh_vertex_normals(const long* sums, long n_vertices, float* normals, atvs_stream_t stream);
 
 #ifdef __cplusplus
 }
